@@ -20,9 +20,14 @@ items per step, one global randomness stream) is cut with rabe_amd.shard.shard_r
 timed path (weak scaling, no data-path collective); after the timed region the fixed-size result records are
 gathered with ONE all_gather_into_tensor on device (RCCL) and rank 0 checks them against the unsharded order.
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (integer-VALU bound: the path is modular
-big-integer arithmetic, neither HBM- nor MFMA-bound -- DESIGN.md section 5), measured on a launch that fills the
-chip; `cpu_baseline` times the oracle's reference-order restatement on the host CPU (rank 0, N=1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up (--warmup steps, rounded up to whole passes over the
+timed schedule's launch shapes), times ONE region of exactly --steps steps, writes the last step's outputs if
+--dump-outputs DIR is given, and prints the line (`value`, `ms_per_step`, ...).  Everything else is behind --full: the
+bit-exact round-trip check of every item (`roundtrip_bit_exact`) and, for N > 1, the gather check; `roofline` for the
+dominant kernel (integer-VALU bound: the path is modular big-integer arithmetic, neither HBM- nor MFMA-bound -- DESIGN.md
+section 5), measured on a launch that fills the chip; `cpu_baseline`, which times the oracle's reference-order
+restatement on the host CPU (rank 0, N=1 only); and the informational legs (single batch, host I/O, object-level API,
+wide tables, bounded runs of configs 3-5).
 """
 import argparse
 import ctypes
@@ -45,7 +50,8 @@ for _i, _a in enumerate(sys.argv):
     elif _a.startswith("--hw-queues="):
         os.environ["GPU_MAX_HW_QUEUES"] = _a.split("=", 1)[1]
 
-from benchkit.lib import G1_GEN, G2_GEN, MAC_PER_FPMUL, ExtBuf, cpu_model, regions_summary, same_on_all_ranks, split_steps, timed_regions  # noqa: E402
+from benchkit.lib import (G1_GEN, G2_GEN, MAC_PER_FPMUL, ExtBuf, cpu_model, device_slice, dump_outputs, regions_summary,  # noqa: E402
+                          same_on_all_ranks, split_steps, timed_regions, warmup_schedule)
 
 # Algorithmic work, in Fp multiplications (1 Fp mul = 136 32x32 multiply-adds: 8-limb CIOS), per lane:
 #   SURVEY.md 8d constants (the "algorithmic minimum" the roofline is priced against) and the
@@ -82,8 +88,17 @@ def parse_args():
     ap.add_argument("--inflight", type=int, default=0,
                     help="groups in flight on separate HIP streams; 0 = the config's default (configs 2-4: 1 -- every launch fills the chip and "
                          "two groups' kernels only disturb each other, config 2: 1.13 M vs 1.02 M ops/s; config 5: 2, its launches are smaller)")
-    ap.add_argument("--min-time", type=float, default=1.0,
-                    help="the K-step timed region is repeated until this many seconds have been timed; every region times exactly --steps steps")
+    ap.add_argument("--min-time", type=float, default=None,
+                    help="repeat the K-step timed region until this many seconds have been timed (default: ONE region of exactly --steps "
+                         "steps; the legs of --full keep their 1 s); every region times exactly --steps steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures or checks: the round-trip check of every item, the "
+                         "multi-rank gather check, single-batch and host-I/O legs, roofline, object-level API, CPU baselines, the wide-table "
+                         "leg and the bounded runs of configs 3-5.  A plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (ciphertexts and decrypted Gt) as "
+                         "DIR/<name>.npy: float64 rows of the records' 32-bit words, <= 64 MB in all (larger outputs: a fixed, seeded sample "
+                         "of records)")
     ap.add_argument("--hw-queues", type=int, default=0, help="GPU_MAX_HW_QUEUES for experiments (0 = leave the HIP default)")
     ap.add_argument("--pairing-mode", type=int, default=0, choices=[0, 1, 3, 6, 29, 58, 99],
                     help="0 auto, 1 one lane per pairing, 3 three cooperating lanes per pairing, 6 six lanes per accumulator, 29 reduced radix "
@@ -367,24 +382,24 @@ def main():
         tb = sizes[-1] * B
         tail = (e2, (e2.alloc(tb * 3 * 128), e2.alloc(sizes[-1] * rows_per_batch * 3 * 64), e2.alloc(tb * 384), ExtBuf(torch, tb * 384, dev)), st2)
 
-    def run_steps():
+    def run_steps(sched=sizes):
         launch_no[0] = 0
         if tail is not None:
             e2, b2, _ = tail
             e2.wait_for(eng)                                   # the previous region's work on the main stream is done
-            submit(sizes[-1], on=(e2, b2), part=1)
+            submit(sched[-1], on=(e2, b2), part=1)
             if args.tail_mode == "pairing":
                 e2.release_when_miller_resident(eng)           # the main stream resumes when the tail's Miller blocks own their CUs
             else:
                 e2.release_before_final_exp(eng)               # the main stream resumes when the tail's Miller loops are done
-            submit(sizes[-1], on=(e2, b2), part=2)
-            submit(sizes[0], lane=0, part=1)                   # beside the tail's pairings / final exponentiation
+            submit(sched[-1], on=(e2, b2), part=2)
+            submit(sched[0], lane=0, part=1)                   # beside the tail's pairings / final exponentiation
             eng.wait_for(e2)
-            submit(sizes[0], lane=0, part=2)
-            for g_ in sizes[1:-1]:
+            submit(sched[0], lane=0, part=2)
+            for g_ in sched[1:-1]:
                 submit(g_, lane=0)
             return
-        for g_ in sizes:
+        for g_ in sched:
             submit(g_)
 
     def sync_all():
@@ -398,17 +413,18 @@ def main():
             dist.barrier()
 
     # ---------------------------------------------------------------- timed region(s): EXACTLY --steps steps each
-    if args.warmup:
-        for _ in range((args.warmup + args.steps - 1) // args.steps):
-            run_steps()
+    warm, passes = warmup_schedule(sizes, S, args.warmup)
+    for _ in range(passes):
+        run_steps(warm)
     sync_all()
     torch.cuda.synchronize()
     prof_on = bool(os.environ.get("RABE_MILLER_PROF")) and hasattr(eng.lib, "rhip_debug_miller_prof")          # diagnostic build (tools/prof_miller.sh)
     if prof_on:
         pbuf = (ctypes.c_ulonglong * 8)()
         eng.lib.rhip_debug_miller_prof(eng.ctx, pbuf)
-    regions = timed_regions(run_steps, sync_all, args.min_time)
+    regions = timed_regions(run_steps, sync_all, args.min_time or 0.0)
     elapsed = sum(regions) / len(regions)
+    leg_min_time = 1.0 if args.min_time is None else args.min_time
     if prof_on:
         eng.lib.rhip_debug_miller_prof(eng.ctx, pbuf)
         w = max(1, pbuf[6])
@@ -417,45 +433,61 @@ def main():
         for k in range(6):
             print("   %-34s %12.0f  %5.1f %%" % (names[k], pbuf[k] / w, 100.0 * pbuf[k] / max(1, pbuf[5])), file=sys.stderr)
 
+    # ---------------------------------------------------------------- what the timed path computed in its LAST step (--dump-outputs):
+    # the last group submitted (the remainder group, when there is one, runs first) and its last step slot; one slot's items, rows and records
+    last = len(sizes) - 2 if tail is not None and len(sizes) > 1 else len(sizes) - 1
+    last_lane = 0 if tail is not None else last % S
+    if args.dump_outputs and rank == 0:
+        e_, (c0_, c_, cp_, out_) = lanes_ctx[last_lane], bufs[last_lane]
+        j = sizes[last] - 1
+        arrays = [("ac17_ct_c0", e_.download(device_slice(c0_, j * B * 3 * 128, B * 3 * 128)), 3 * 128),
+                  ("ac17_ct_c", e_.download(device_slice(c_, j * rows_per_batch * 3 * 64, rows_per_batch * 3 * 64)), 3 * 64),
+                  ("ac17_ct_cp", e_.download(device_slice(cp_, j * B * 384, B * 384)), 384)]
+        if not args.only_encrypt:
+            arrays.append(("ac17_decrypted_gt", out_.t[j * B * 384:(j + 1) * B * 384].cpu().numpy().tobytes(), 384))
+        dump_outputs(args.dump_outputs, arrays)
+
     # ---------------------------------------------------------------- size-independent correctness property on the FULL batch:
     # decrypt(encrypt(msg)) == msg, bit for bit, for every item of every group slot (oracle parity at small sizes is in tests/)
-    want = eng.download(dmsg)
-    used = {}
-    for j, g_ in enumerate(sizes):
-        used[j % S] = g_                # the LAST group a lane ran is what its buffer holds
-    if tail is not None:
-        used = {0: sizes[-2] if len(sizes) > 1 else sizes[0]}
-    ok = all(bufs[i][3].t[:g_ * B * 384].cpu().numpy().tobytes() == want[:g_ * B * 384] for i, g_ in used.items())
-    if tail is not None:
-        ok = ok and tail[1][3].t[:sizes[-1] * B * 384].cpu().numpy().tobytes() == want[:sizes[-1] * B * 384]
-    gather = None
-    if dist_on:
-        f = torch.tensor([1 if ok else 0], device="cuda" if dist.get_backend() == "nccl" else "cpu")
-        dist.all_reduce(f, op=dist.ReduceOp.MIN)
-        ok = bool(f.item())
-        # the trivial gather: every rank's first-slot result records (B x 384 B) in ONE all_gather_into_tensor on device;
-        # rank 0 recomputes the unsharded batch's messages from the global randomness stream and compares in global order
-        mine = bufs[0][3].t[:B * 384]
-        src = mine if dist.get_backend() == "nccl" else mine.cpu()
-        allrec = torch.empty(world * B * 384, dtype=torch.uint8, device=src.device)
-        torch.cuda.synchronize()
-        tg0 = time.perf_counter()
-        dist.all_gather_into_tensor(allrec, src)
-        torch.cuda.synchronize()
-        tg = time.perf_counter() - tg0
-        if rank == 0:
-            dall = eng.alloc(world * B * 384)
-            dr_all = eng.upload(b"".join(le(x) for x in rho_all))
-            eng._check(eng.lib.rhip_gt_table_pow(eng.ctx, e_tab.h, E._sz(world * B), dr_all.ptr, dall.ptr))
-            gather = {"collective": "all_gather_into_tensor", "backend": dist.get_backend(), "bytes_per_rank": B * 384,
-                      "ms": round(1e3 * tg, 3), "matches_unsharded_order": allrec.cpu().numpy().tobytes() == eng.download(dall)}
+    # (--full: a plain run only times the steps)
+    ok, gather = None, None
+    if args.full:
+        want = eng.download(dmsg)
+        used = {}
+        for j, g_ in enumerate(sizes):
+            used[j % S] = g_                # the LAST group a lane ran is what its buffer holds
+        if tail is not None:
+            used = {0: sizes[-2] if len(sizes) > 1 else sizes[0]}
+        ok = all(bufs[i][3].t[:g_ * B * 384].cpu().numpy().tobytes() == want[:g_ * B * 384] for i, g_ in used.items())
+        if tail is not None:
+            ok = ok and tail[1][3].t[:sizes[-1] * B * 384].cpu().numpy().tobytes() == want[:sizes[-1] * B * 384]
+        if dist_on:
+            f = torch.tensor([1 if ok else 0], device="cuda" if dist.get_backend() == "nccl" else "cpu")
+            dist.all_reduce(f, op=dist.ReduceOp.MIN)
+            ok = bool(f.item())
+            # the trivial gather: every rank's first-slot result records (B x 384 B) in ONE all_gather_into_tensor on device;
+            # rank 0 recomputes the unsharded batch's messages from the global randomness stream and compares in global order
+            mine = bufs[0][3].t[:B * 384]
+            src = mine if dist.get_backend() == "nccl" else mine.cpu()
+            allrec = torch.empty(world * B * 384, dtype=torch.uint8, device=src.device)
+            torch.cuda.synchronize()
+            tg0 = time.perf_counter()
+            dist.all_gather_into_tensor(allrec, src)
+            torch.cuda.synchronize()
+            tg = time.perf_counter() - tg0
+            if rank == 0:
+                dall = eng.alloc(world * B * 384)
+                dr_all = eng.upload(b"".join(le(x) for x in rho_all))
+                eng._check(eng.lib.rhip_gt_table_pow(eng.ctx, e_tab.h, E._sz(world * B), dr_all.ptr, dall.ptr))
+                gather = {"collective": "all_gather_into_tensor", "backend": dist.get_backend(), "bytes_per_rank": B * 384,
+                          "ms": round(1e3 * tg, 3), "matches_unsharded_order": allrec.cpu().numpy().tobytes() == eng.download(dall)}
 
     value = world * B * args.steps / elapsed
     result = {
         "metric": "ABE ops/sec (AC17 CP-ABE encrypt+decrypt)", "value": round(value, 2), "unit": "ops/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 4),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "dtype_note": "exact BN254 integers in 32-bit limbs (Montgomery: 8 x 32 bits; 9 signed x 29 bits in the pairing kernels of full launches)",
-        "data": "synthetic", "roundtrip_bit_exact": ok,
+        "data": "synthetic",
         "timed_regions": regions_summary(regions, args.steps),
         "config": {"workload": "AC17 CP-ABE, %d-attribute random binary AND/OR MSP policies (%d distinct), batch %d encrypt+decrypt per GPU"
                                % (args.attrs, args.policies, B),
@@ -477,13 +509,15 @@ def main():
                            "every rank builds its own replica (about as long as a broadcast of the same bytes over xGMI would take)"},
         "host_prep_ms_per_policy": round(host_prep_ms_per_policy, 3),
     }
+    if ok is not None:
+        result["roundtrip_bit_exact"] = ok
     if gather is not None:
         result["gather"] = gather
 
     # ---------------------------------------------------------------- informational: ONE batch of 4096 per launch set (BASELINE config 2
     # words the workload as "batch of 4096"): its latency alone, and the rate of a stream of single-batch submissions with up to
     # four of them in flight on separate HIP streams (what a server that receives batches one at a time sees)
-    if world == 1 and not args.no_single_batch and not args.only_encrypt:
+    if args.full and world == 1 and not args.no_single_batch and not args.only_encrypt:
         # four lanes = the four contexts / HIP streams of the pool (the main context's and the remainder group's included): HIP's default
         # of four hardware queues, one each
         extra = [(e2, (e2.alloc(B * 3 * 128), e2.alloc(rows_per_batch * 3 * 64), e2.alloc(B * 384), ExtBuf(torch, B * 384, dev)), st2)
@@ -525,7 +559,7 @@ def main():
     # ---------------------------------------------------------------- informational: the same steps with host buffers
     # (inputs s, msg uploaded; ciphertext c_0, c, c_p and the decrypted Gt downloaded; pinned memory, copies on a copy
     # stream per group in flight, ordered by events).  Never `value`.
-    if not args.no_host_io_leg and not args.only_encrypt and not os.environ.get("RABE_SHARED_DEVICE"):
+    if args.full and not args.no_host_io_leg and not args.only_encrypt and not os.environ.get("RABE_SHARED_DEVICE"):
         n_s, n_msg = 2 * GB * 32, GB * 384
         sizes_out = (GB * 3 * 128, total_rows * 3 * 64, GB * 384, GB * 384)
         io = []
@@ -581,7 +615,7 @@ def main():
         barrier()
         t0 = time.perf_counter()
         reps_io = 0
-        while same_on_all_ranks(reps_io < 1 or (time.perf_counter() - t0 < 0.5 * args.min_time and reps_io < 50)):
+        while same_on_all_ranks(reps_io < 1 or (time.perf_counter() - t0 < 0.5 * leg_min_time and reps_io < 50)):
             run_io()
             reps_io += 1
         torch.cuda.synchronize()
@@ -600,7 +634,7 @@ def main():
         for c2, _ in copy_ctx:
             c2.close()
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ------------------------------------------------------------ roofline of the dominant kernel: HIP events on the launch
         # stream around every kernel of ONE full group (G x B items, nothing else running) -- the launch fills the chip
         eng.timing(True)
@@ -711,7 +745,7 @@ def main():
                 wide_build_ms = 1e3 * (time.perf_counter() - t_w)
                 run_steps()
                 sync_all()
-                reg_w = timed_regions(run_steps, sync_all, min(0.4, args.min_time))
+                reg_w = timed_regions(run_steps, sync_all, min(0.4, leg_min_time))
                 el_w = sum(reg_w) / len(reg_w)
                 v_w = B * args.steps / el_w
                 wb = 64 * sum(E.wide_count(args.wide_window, i) for i in range(E.wide_windows(args.wide_window)))
@@ -751,6 +785,7 @@ def main():
         if isinstance(result.get("cpu_baseline"), dict) and isinstance(result.get("configs"), dict):
             result["cpu_baseline"]["configs"] = {k: (v.get("cpu_baseline") if isinstance(v, dict) else None) for k, v in result["configs"].items()
                                                  if k in ("3", "4", "5")}
+    if rank == 0:
         from benchkit.lib import emit_line
         emit_line(result)
 
@@ -780,7 +815,7 @@ def configs_leg(args):
             ("3", 3, 8, [], 5), ("3_mixed", 3, 8, ["--tree", "mixed"], 0), ("3_ragged", 3, 8, ["--ragged"], 0), ("4", 4, 8, [], 2), ("4_ragged", 4, 8, ["--ragged", "--no-object-api"], 0), ("5", 5, 8, [], 3), ("5_ragged", 5, 8, ["--ragged", "--no-object-api"], 0))
     for key, cfg, steps, extra, cpu_n in legs:
         cmd = [sys.executable, os.path.abspath(__file__), "--config", str(cfg), "--gpus", "1", "--steps", str(steps), "--warmup", str(steps),
-               "--min-time", str(args.configs_min_time), "--seed", str(args.seed), "--no-object-api"] + extra
+               "--min-time", str(args.configs_min_time), "--seed", str(args.seed), "--full", "--no-object-api"] + extra
         cmd += ["--cpu-sample", str(cpu_n)] if cpu_n and not args.no_cpu_baseline else ["--no-cpu-baseline"]
         t0 = time.perf_counter()
         try:

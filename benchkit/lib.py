@@ -32,6 +32,52 @@ def split_steps(k, gmax):
     return sizes
 
 
+def warmup_schedule(sizes, lanes, steps):
+    """--warmup W: (group sizes of one warm-up pass, passes).  A pass is the timed schedule's first `lanes` groups (one per group in flight)
+    and its remainder group, so that every launch shape, lane, buffer and the remainder's overlap have run once before the timed region;
+    passes are repeated until W steps are covered (0 passes for W = 0)."""
+    one = list(sizes[:lanes])
+    if len(sizes) > lanes and sizes[-1] != sizes[0]:
+        one.append(sizes[-1])
+    return one, (-(-steps // sum(one)) if steps > 0 else 0)
+
+
+def device_slice(buf, offset, nbytes):
+    """bytes [offset, offset + nbytes) of an engine buffer (DevBuf), as a buffer Engine.download accepts"""
+    import types
+    assert 0 <= offset and 0 <= nbytes and offset + nbytes <= buf.nbytes, (offset, nbytes, buf.nbytes)
+    return types.SimpleNamespace(ptr=ctypes.c_void_p(buf.ptr.value + offset), nbytes=nbytes)
+
+
+DUMP_BUDGET = 64 << 20          # bytes of .npy data that --dump-outputs may write in all
+DUMP_MAX_RECORDS = 16384        # records kept per array; a larger output is cut to a fixed, seeded sample of its records
+DUMP_SEED = 20251016
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs DIR: every (name, data, record_bytes) -> DIR/<name>.npy, float64 of shape (records, record_bytes / 4): the
+    little-endian 32-bit words of every record (exact in float64).  An array of more than DUMP_MAX_RECORDS records (fewer if the total
+    would pass DUMP_BUDGET) keeps the records at a fixed, seeded sample of indices, in index order; the sample depends only on the record
+    count, so two builds run with the same arguments write comparable files."""
+    import os
+    import numpy as np
+    per_record = sum(8 * (rb // 4) for _, _, rb in arrays)
+    cap = max(1, min(DUMP_MAX_RECORDS, DUMP_BUDGET // max(1, per_record)))
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, data, rb in arrays:
+        assert rb % 4 == 0 and len(data) % rb == 0, (name, len(data), rb)
+        words = np.frombuffer(data, dtype="<u4").reshape(-1, rb // 4)
+        if words.shape[0] > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(words.shape[0], cap, replace=False))
+            words = words[idx]
+        a = words.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+    assert written <= DUMP_BUDGET, written
+    return written
+
+
 def same_on_all_ranks(flag):
     """rank 0's decision, everywhere (loop control of the repeated timed regions)"""
     import torch

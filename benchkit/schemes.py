@@ -12,7 +12,8 @@ import os
 import random
 import time
 
-from benchkit.lib import G1_GEN, G2_GEN, MAC_PER_FPMUL, ExtBuf, cpu_model, regions_summary, split_steps, timed_regions
+from benchkit.lib import (G1_GEN, G2_GEN, MAC_PER_FPMUL, ExtBuf, cpu_model, device_slice, dump_outputs, regions_summary, split_steps,
+                          timed_regions, warmup_schedule)
 
 
 def run(args, world, rank, local_rank, dist_on=None):
@@ -57,9 +58,9 @@ class SchemeRunner:
         b.prepare(G, lanes)
         launch_no = [0]
 
-        def run_steps():
+        def run_steps(sched=sizes):
             launch_no[0] = 0
-            for g_ in sizes:
+            for g_ in sched:
                 b.submit(launch_no[0] % S, g_)
                 launch_no[0] += 1
 
@@ -67,24 +68,29 @@ class SchemeRunner:
             for e_ in lanes:
                 e_.sync()
 
-        if args.warmup:
-            for _ in range((args.warmup + args.steps - 1) // args.steps):
-                run_steps()
+        warm, passes = warmup_schedule(sizes, S, args.warmup)
+        for _ in range(passes):
+            run_steps(warm)
         sync_all()
         torch.cuda.synchronize()
-        regions = timed_regions(run_steps, sync_all, args.min_time)
+        regions = timed_regions(run_steps, sync_all, args.min_time or 0.0)
         elapsed = sum(regions) / len(regions)
-        used = {}
-        for j, g_ in enumerate(sizes):
-            used[j % S] = g_
-        ok = all(b.check(i, g_) for i, g_ in used.items())
-        if self.dist_on:
+        if args.dump_outputs and rank == 0:          # the last step of the last group submitted
+            dump_outputs(args.dump_outputs, b.step_outputs((len(sizes) - 1) % S, sizes[-1] - 1))
+        # (--full: the round-trip check of every item and the multi-rank gather; a plain run only times the steps)
+        ok = None
+        if args.full:
+            used = {}
+            for j, g_ in enumerate(sizes):
+                used[j % S] = g_
+            ok = all(b.check(i, g_) for i, g_ in used.items())
+        if args.full and self.dist_on:
             f = torch.tensor([1 if ok else 0], device="cuda" if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(f, op=dist.ReduceOp.MIN)
             ok = bool(f.item())
         B = b.B
         gather = None
-        if self.dist_on:
+        if args.full and self.dist_on:
             # the trivial gather: every rank's first-slot result records (B x 384 B) in ONE all_gather_into_tensor on device (RCCL);
             # rank 0 recomputes the unsharded batch's messages from the global randomness stream and compares in global order
             mine = b.out_tensor(0)[:B * 384]
@@ -102,15 +108,17 @@ class SchemeRunner:
         result = {
             "metric": b.metric, "value": round(value, 2), "unit": "ops/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u32", "dtype_note": "exact BN254 integers in 32-bit limbs (Montgomery: 8 x 32 bits; 9 signed x 29 bits in the pairing kernels of full launches)", "data": "synthetic", "roundtrip_bit_exact": ok,
+            "dtype": "u32", "dtype_note": "exact BN254 integers in 32-bit limbs (Montgomery: 8 x 32 bits; 9 signed x 29 bits in the pairing kernels of full launches)", "data": "synthetic",
             "timed_regions": regions_summary(regions, args.steps),
             "config": dict(b.describe(), batch_per_gpu=B, steps_per_launch_set=sizes, launch_sets_in_flight=S,
                            hw_queues=os.environ.get("GPU_MAX_HW_QUEUES", "default"),
                            parallelism="batch-sharded x%d (no data-path collective)" % world, device=self.dev_name),
         }
+        if ok is not None:
+            result["roundtrip_bit_exact"] = ok
         if gather is not None:
             result["gather"] = gather
-        if rank == 0:
+        if rank == 0 and args.full:
             eng.timing(True)
             eng.timing_read()
             for _ in range(2):
@@ -168,6 +176,7 @@ class SchemeRunner:
                     result["cpu_baseline"] = b.cpu_baseline()
                 except Exception as ex:
                     result["cpu_baseline"] = {"error": repr(ex)}
+        if rank == 0:
             from benchkit.lib import emit_line
             emit_line(result)
         b.close()
@@ -412,6 +421,18 @@ class BswBench:
     def out_tensor(self, lane):
         return self.bufs[lane][4].t
 
+    def step_outputs(self, lane, j):
+        """--dump-outputs: what step slot j of the lane's last group computed (c, c_p, the leaves' G1 / G2 pairs, the decrypted Gt)"""
+        e_, (c, cp, g1, g2, out) = self.lanes[lane], self.bufs[lane]
+        B, L = self.B, self.leaves_per_batch
+        arrays = [("bsw_ct_c", e_.download(device_slice(c, j * B * 64, B * 64)), 64),
+                  ("bsw_ct_cp", e_.download(device_slice(cp, j * B * 384, B * 384)), 384),
+                  ("bsw_ct_c_y_g1", e_.download(device_slice(g1, j * L * 64, L * 64)), 64),
+                  ("bsw_ct_c_y_g2", e_.download(device_slice(g2, j * L * 128, L * 128)), 128)]
+        if not self.r.args.only_encrypt:
+            arrays.append(("bsw_decrypted_gt", out.t[j * B * 384:(j + 1) * B * 384].cpu().numpy().tobytes(), 384))
+        return arrays
+
     def expected_first_slot_all_ranks(self):
         eng, E = self.r.eng, self.E
         n = len(self.rho_all)
@@ -622,6 +643,16 @@ class LswBench:
     def out_tensor(self, lane):
         return self.bufs[lane][2].t
 
+    def step_outputs(self, lane, j):
+        """--dump-outputs: what step slot j of the lane's last group computed (the fresh keys' D1 / D2 per leaf, the decrypted Gt)"""
+        e_, (d1, d2, out) = self.lanes[lane], self.bufs[lane]
+        B, L = self.B, self.leaves_per_batch
+        arrays = [("lsw_key_d1", e_.download(device_slice(d1, j * L * 64, L * 64)), 64),
+                  ("lsw_key_d2", e_.download(device_slice(d2, j * L * 128, L * 128)), 128)]
+        if not self.r.args.only_encrypt:
+            arrays.append(("lsw_decrypted_gt", out.t[j * B * 384:(j + 1) * B * 384].cpu().numpy().tobytes(), 384))
+        return arrays
+
     def expected_first_slot_all_ranks(self):
         return self.msg * (self.r.world * self.B)           # every item decrypts the one pre-made ciphertext
 
@@ -795,6 +826,18 @@ class Aw11Bench:
 
     def out_tensor(self, lane):
         return self.bufs[lane][4].t
+
+    def step_outputs(self, lane, j):
+        """--dump-outputs: what step slot j of the lane's last group computed (c_0, the rows' c_1 / c_2 / c_3, the decrypted Gt)"""
+        e_, (c0, c1, c2, c3, out) = self.lanes[lane], self.bufs[lane]
+        B, L = self.B, self.rows_per_batch
+        arrays = [("aw11_ct_c0", e_.download(device_slice(c0, j * B * 384, B * 384)), 384),
+                  ("aw11_ct_c1", e_.download(device_slice(c1, j * L * 384, L * 384)), 384),
+                  ("aw11_ct_c2", e_.download(device_slice(c2, j * L * 128, L * 128)), 128),
+                  ("aw11_ct_c3", e_.download(device_slice(c3, j * L * 128, L * 128)), 128)]
+        if not self.r.args.only_encrypt:
+            arrays.append(("aw11_decrypted_gt", out.t[j * B * 384:(j + 1) * B * 384].cpu().numpy().tobytes(), 384))
+        return arrays
 
     def expected_first_slot_all_ranks(self):
         eng, E = self.r.eng, self.E

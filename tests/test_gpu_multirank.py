@@ -17,7 +17,7 @@ def run_bench(*extra):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     env["RABE_PAIRING_MODE"] = "0"          # these tests are about sharding and the gather: the ranks run the automatic kernel selection, not the suite's cross-check
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--warmup", "1", "--min-time", "0", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--warmup", "1", "--min-time", "0", "--full", "--no-cpu-baseline",
                           "--no-object-api", "--no-host-io-leg"] + list(extra), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     return json.loads(out.stdout.decode().strip().splitlines()[-1])
@@ -43,7 +43,7 @@ def test_two_ranks_under_torch_distributed_run():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
            "29531", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--g-window", "20", "--min-time", "0",
-           "--no-cpu-baseline", "--no-object-api", "--no-host-io-leg"]
+           "--full", "--no-cpu-baseline", "--no-object-api", "--no-host-io-leg"]
     out = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-2000:]
     d = json.loads(out.stdout.decode().strip().splitlines()[-1])
@@ -56,7 +56,7 @@ def run_bench_n(n, *extra, env_extra=None, timeout=1800):
         env.pop(k, None)
     env["RABE_PAIRING_MODE"] = "0"          # (as above: several ranks share this box's one GPU; the cross-check would run every launch five times in each)
     env.update(env_extra or {})
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--warmup", "1", "--min-time", "0", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--warmup", "1", "--min-time", "0", "--full", "--no-cpu-baseline",
                           "--no-object-api", "--no-host-io-leg", "--no-single-batch", "--no-configs-leg", "--wide-window", "0"] + list(extra), env=env,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
     assert out.returncode == 0, out.stderr.decode()[-2000:]

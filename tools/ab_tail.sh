@@ -2,7 +2,7 @@
 # A/B of the remainder group's schedule in the driver's form (--steps 20 --warmup 5): tail-mode pairing / final-exp / no overlap
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
-Q="--no-single-batch --no-configs-leg --no-host-io-leg --no-cpu-baseline --no-object-api --wide-window 0"
+Q="--full --min-time 1 --no-single-batch --no-configs-leg --no-host-io-leg --no-cpu-baseline --no-object-api --wide-window 0"
 for m in pairing final-exp; do
   RABE_BENCH_FULL_LINE=1 python bench.py --steps 20 --warmup 5 --tail-mode $m $Q 2>gpurun_out/ab_tail_$m.err | tail -1 > gpurun_out/ab_tail_$m.json
 done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # variants of the other device units against the product library on ONE box: configs 2-5 (top kernels) and a lone batch
 cd "$(dirname "$0")/.."
-Q="--no-single-batch --no-configs-leg --no-host-io-leg --no-cpu-baseline --no-object-api --wide-window 0 --min-time 0.5"
+Q="--full --no-single-batch --no-configs-leg --no-host-io-leg --no-cpu-baseline --no-object-api --wide-window 0 --min-time 0.5"
 for lib in "" "$@" ""; do
   echo "== ${lib:-product}"
   RABE_BENCH_FULL_LINE=1 RABE_HIP_LIB=$lib python bench.py --steps 16 --warmup 16 $Q 2>/dev/null | tail -1 | python -c "

@@ -5,9 +5,9 @@ TAG=${1:-rXXa}
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${TAG}_driver_form.json 2> gpurun_out/${TAG}_driver_form.err
-bash tools/profile_round.sh ${TAG}
+bash tools/profile_round.sh ${TAG} --full
 for c in 3 4 5; do
-  bash tools/profile_round.sh ${TAG}_cfg$c --config $c --inflight 1
+  bash tools/profile_round.sh ${TAG}_cfg$c --full --config $c --inflight 1
 done
 bash tools/trace_tail.sh "pairing final-exp"
 cp gpurun_out/timeline_tail_pairing.txt gpurun_out/${TAG}_timeline_tail_miller_resident.txt

@@ -2,7 +2,7 @@
 # one GPU session that produces everything profiles/ holds for a round and a config: the default bench line, the same command
 # under rocprofv3 --kernel-trace --stats (per-kernel averages; must agree with roofline.kernels_ms of the line it printed),
 # SQ issue counters and HBM traffic counters (separate --pmc passes).
-# usage: profile_round.sh r02e [extra bench.py args, e.g. --config 3]
+# usage: profile_round.sh r02e [extra bench.py args, e.g. --full --config 3; without --full the line has no roofline]
 TAG=${1:-rXX}; shift
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
