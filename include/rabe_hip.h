@@ -454,6 +454,22 @@ int32_t rhip_ghw11_transform_batch(rhip_ctx* ctx, size_t n_items, size_t max_pai
                                    const uint32_t* dev_sel_ct_row, const uint32_t* dev_sel_tk_attr, const rhip_fr* dev_sel_coeff,
                                    const rhip_g1* dev_ct_c1 /*[n_items]*/, const rhip_g1* dev_ct_c /*[rows]: ci*/, const rhip_g1* dev_ct_d /*[rows]: di*/,
                                    const uint32_t* dev_ct_row_off /*[n_items+1]*/, const rhip_g2_lines* tk_lines, rhip_gt* dev_out /*[n_items]*/);
+/* GHW11 encrypt (ghw11/mod.rs:189-225) over the flattened policy trees of the BSW block above.  rhip_ghw11_pk: window tables
+ * (8-bit and 16-bit) of g1, g1_a and e_gg_alpha (Ghw11PublicKey).  Explicit randomness per item = secret, the Gt `msg` and the gate
+ * coefficients, plus one draw t per leaf row.  Outputs: c = e_gg_alpha^secret * msg, c1 = g1 * secret, and per leaf row
+ * cd[2 row] = C = g1_a * lambda + g1 * (-H(j) t), cd[2 row + 1] = D = g1 * t, with lambda the leaf's share of `secret` and
+ * H(j) = leaf_hash = Fr(SHA3(remove_index(name_col))) -- one lane per row (k_ghw11_enc_rows). */
+typedef struct rhip_ghw11_pk rhip_ghw11_pk;
+int32_t rhip_ghw11_pk_create(rhip_ctx* ctx, const rhip_g1* host_g1, const rhip_g1* host_g1_a, const rhip_gt* host_e_gg_alpha, rhip_ghw11_pk** out);
+void rhip_ghw11_pk_destroy(rhip_ghw11_pk* pk);
+int32_t rhip_ghw11_encrypt_batch(rhip_ctx* ctx, const rhip_ghw11_pk* pk, size_t n_items, size_t total_leaves,
+                                 const uint32_t* dev_item_leaf_off /*[n_items+1]*/, const uint32_t* dev_item_tree_leaf /*[n_items]*/,
+                                 const uint32_t* dev_item_tree_gate /*[n_items]*/, const uint32_t* dev_path_off, const uint32_t* dev_path_gate,
+                                 const uint32_t* dev_path_x, const uint32_t* dev_gate_k, const uint32_t* dev_gate_coef_off,
+                                 const rhip_fr* dev_leaf_hash, const rhip_fr* dev_secret /*[n_items]*/, const rhip_fr* dev_coef,
+                                 const uint32_t* dev_item_coef_off /*[n_items]*/, const rhip_fr* dev_t /*[total_leaves]*/,
+                                 const rhip_gt* dev_msg /*[n_items]*/, rhip_gt* dev_c /*[n_items]*/, rhip_g1* dev_c1 /*[n_items]*/,
+                                 rhip_g1* dev_cd /*[2 total_leaves]: C, D per row*/);
 
 /* ---- Level B: AW11 multi-authority CP-ABE (src/schemes/aw11/mod.rs) -----------------------------------------------
  * rhip_aw11_pk: gk (g1, g2), the constant e(g1, g2) and, for each of the n_attrs attributes of the authorities in play,

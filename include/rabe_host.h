@@ -280,6 +280,13 @@ int32_t rabe_ghw11_encrypt(rabe_host* h, const void* pk, const char* policy, int
 int32_t rabe_ghw11_transform(rabe_host* h, const void* ct, const void* tk, void** tct);
 /* n independent transforms in one launch set; status[i] = 0 ok / -1 (tk i does not satisfy ct i; tcts[i] = NULL) */
 int32_t rabe_ghw11_transform_batch(rabe_host* h, size_t n, const void* const* cts, const void* const* tks, int32_t* status, void** tcts);
+/* n_items calls of encrypt (ghw11/mod.rs:189-225) in the form of rabe_bsw_encrypt_packed: item i encrypts plaintext i of pt_blob under
+ * policies[item_policy[i]]; ct_buf receives the Ghw11Ciphertext records (rabe_obj_serialize's bytes), built and sealed on the device (one lane
+ * per ciphertext row: share, C on one accumulator over the tables of g1_a and g1, D).  Draw order per item: secret, msg, gate coefficients,
+ * one t per share in share order, AES nonce.  Returns 1 when ct_cap is too small; ct_off[n_items] = the size needed. */
+int32_t rabe_ghw11_encrypt_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language,
+                                  size_t n_items, const uint32_t* item_policy /*[n_items]*/, const uint8_t* pt_blob, const uint64_t* pt_off /*[n_items+1]*/,
+                                  uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off /*[n_items+1]*/);
 /* The outsourced half as a service: n_items Ghw11Ciphertext records in one blob (+ n_items + 1 offsets, ct_len; bounds and --
  * unless RABE_PACKED_TRUSTED -- group membership of every decoded element are checked, an item fails alone with status -1) transformed under
  * ONE transform key.  tct_buf + 768 i receives item i's Ghw11TransformCiphertext record (c | t; zeros where status[i] = -1); returns 1 when
@@ -290,6 +297,15 @@ int32_t rabe_ghw11_transform_packed(rabe_host* h, const void* tk, size_t n_items
 /* `data` of the reference's decrypt_out is the ciphertext's data field: pass the ciphertext object */
 int32_t rabe_ghw11_decrypt_out(rabe_host* h, const void* tct, const void* rk, const void* ct, uint8_t** plaintext, size_t* len);
 int32_t rabe_ghw11_decrypt_out_gt(rabe_host* h, const void* tct, const void* rk, uint8_t out_gt[384]);
+/* The client's half in bulk: n_items calls of decrypt_out (ghw11/mod.rs:297-305) under ONE retrieve key.  tct_buf + 768 i = item i's c | t
+ * record exactly as rabe_ghw11_transform_packed writes it; record i of ct_blob (+ offsets) is item i's ciphertext, which carries the sealed
+ * data.  msg = c * t^(-z), KDF and AES-GCM open run on the device; only plaintexts come back (pt_buf + pt_off).  Unless RABE_PACKED_TRUSTED,
+ * c and t must be members of Gt.  An all-zero tct record, a malformed ciphertext record, a non-member or a tag that does not verify (e.g. a
+ * wrong rk) fails that item alone: status -1, empty or zeroed plaintext slot, the first error in rabe_host_last_error.  Returns 1 when pt_cap
+ * is below the total size of the well-formed ciphertext records; pt_off[n_items] = that size. */
+int32_t rabe_ghw11_decrypt_out_packed(rabe_host* h, const void* rk, size_t n_items, const uint8_t* tct_buf /*768 n_items*/,
+                                      const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags,
+                                      int32_t* status /*[n_items]*/, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off /*[n_items+1]*/);
 
 /* ---- bdabe (src/schemes/bdabe/mod.rs:149-399) and mke08 (src/schemes/mke08/mod.rs:130-380): DNF policies, attributes named
  * "authority::attribute".  `request_attribute_sk` / `request_authority_sk` APPEND the new secret attribute key to the user key

@@ -700,6 +700,25 @@ __device__ __noinline__ Fr share_of_leaf(const TreeTables& tt, uint32_t leaf /* 
   }
   return s;
 }
+// the same share with the multiplications inlined (k_ghw11_enc_rows): out of line, share_of_leaf brings a stack frame into its caller
+// (k_bsw_enc_scalars: 64 bytes of scratch)
+__device__ __forceinline__ Fr share_of_leaf_inl(const TreeTables& tt, uint32_t leaf, uint32_t gate0, const rhip_fr* coef, Fr secret) {
+  Fr s = secret;
+#pragma unroll 1
+  for (uint32_t e = tt.path_off[leaf]; e < tt.path_off[leaf + 1]; e++) {
+    const uint32_t g = gate0 + tt.path_gate[e];
+    const uint32_t k = tt.gate_k[g];
+    if (k <= 1) continue;
+    uint32_t xs[8] = {tt.path_x[e], 0, 0, 0, 0, 0, 0, 0};
+    const Fr x = to_mont<FrParams>(xs);
+    const rhip_fr* a = coef + tt.gate_coef_off[g];
+    Fr acc = load_fr(a[k - 2].l);
+#pragma unroll 1
+    for (int j = (int)k - 3; j >= 0; j--) acc = add(mul_inl(acc, x), load_fr(a[j].l));
+    s = add(mul_inl(acc, x), s);
+  }
+  return s;
+}
 
 // ------------------------------------------------------------------------------------------------ BSW CP-ABE
 struct rhip_bsw_pk {
@@ -785,6 +804,128 @@ extern "C" int32_t rhip_bsw_encrypt_batch(rhip_ctx* ctx, const rhip_bsw_pk* pk, 
   const rhip_gt_table* et = pk->e;
   KLAUNCH(ctx, "k_table_pow_gt_mul", k_table_pow_gt_mul, dim3(blocks_for(n_items, 64)), dim3(64), 0, ctx->stream,
           (const GtM*)(et->dev16 ? et->dev16 : et->dev), et->dev16 ? 1 : 0, n_items, secret, msg, cp);
+  return RHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ GHW11 encrypt
+struct rhip_ghw11_pk {
+  rhip_ctx* ctx;
+  rhip_g1_table* g1;
+  rhip_g1_table* g1_a;
+  rhip_gt_table* e;
+};
+extern "C" void rhip_ghw11_pk_destroy(rhip_ghw11_pk* pk) {
+  if (!pk) return;
+  rhip_g1_table_destroy(pk->g1);
+  rhip_g1_table_destroy(pk->g1_a);
+  rhip_gt_table_destroy(pk->e);
+  delete pk;
+}
+extern "C" int32_t rhip_ghw11_pk_create(rhip_ctx* ctx, const rhip_g1* g1, const rhip_g1* g1_a, const rhip_gt* e_gg_alpha, rhip_ghw11_pk** out) {
+  if (!ctx || !g1 || !g1_a || !e_gg_alpha || !out) return RHIP_ERR_ARG;
+  *out = nullptr;
+  rhip_ghw11_pk* pk = new rhip_ghw11_pk{ctx, nullptr, nullptr, nullptr};
+  int32_t rc = rhip_g1_table_create(ctx, g1, &pk->g1);
+  if (!rc) rc = rhip_g1_table_add_w16(ctx, pk->g1);
+  if (!rc) rc = rhip_g1_table_create(ctx, g1_a, &pk->g1_a);
+  if (!rc) rc = rhip_g1_table_add_w16(ctx, pk->g1_a);
+  if (!rc) rc = rhip_gt_table_create(ctx, e_gg_alpha, &pk->e);
+  if (!rc) rc = rhip_gt_table_add_w16(ctx, pk->e);
+  if (rc) { rhip_ghw11_pk_destroy(pk); return rc; }
+  *out = pk;
+  return RHIP_OK;
+}
+// the 16-bit walk of table_mul_g1_w16_inl (engine_internal.h) onto a RUNNING accumulator: a sum of two fixed-base products costs
+// the additions of both walks and nothing else
+static __device__ __forceinline__ G1Jac table_madd_g1_w16_inl(G1Jac acc, const G1M* tbl, const uint32_t k[8]) {
+#pragma unroll 1
+  for (int w = 0; w < TBL16_WINDOWS; w++) {
+    uint32_t word;
+    switch (w >> 1) {
+      case 0: word = k[0]; break;
+      case 1: word = k[1]; break;
+      case 2: word = k[2]; break;
+      case 3: word = k[3]; break;
+      case 4: word = k[4]; break;
+      case 5: word = k[5]; break;
+      case 6: word = k[6]; break;
+      default: word = k[7]; break;
+    }
+    const uint32_t d = (w & 1) ? (word >> 16) : (word & 0xffffu);
+    if (d) acc = g1_madd_inl(acc, ld_g1_m(tbl + (size_t)w * TBL16_DIGITS + (d - 1)));
+  }
+  return acc;
+}
+// two Jacobian points -> affine canonical with ONE field inversion per block.  The first point is PARKED, as a Jacobian Montgomery
+// value, in the row's own output slots (2 x 64 B of affine output >= 96 B) by the lane that computed it; the second arrives in
+// registers.  Both are read into registers before the first affine point is stored over the parked data (store3_g1_block_parked's
+// two-point form, engine.hip).
+__device__ __forceinline__ void store2_g1_block_parked(uint32_t* lds, bool active, rhip_g1* out, Fp bx, Fp by, Fp bz) {
+  G1Jac a = jac_inf<Fp>();
+  const G1Jac b{bx, by, bz};
+  if (active) a = *(const G1Jac*)out;
+  const bool ia = !active || jac_is_inf(a), ib = !active || jac_is_inf(b);
+  const Fp za = ia ? one<FpParams>() : a.z, zb = ib ? one<FpParams>() : b.z;
+  const Fp inv_ab = block_batch_inverse_n<RB_ROWS_BLOCK>(lds, mul(za, zb));
+  if (!active) return;
+  const G1Aff ra = ia ? aff_inf<Fp>() : jac_to_aff_with_zinv(a, mul(inv_ab, zb));
+  const G1Aff rb = ib ? aff_inf<Fp>() : jac_to_aff_with_zinv(b, mul(inv_ab, za));
+  store_g1(out[0].l, ra);
+  store_g1(out[1].l, rb);
+}
+static_assert(sizeof(G1Jac) <= 2 * sizeof(rhip_g1), "a parked Jacobian point fits a row's two output records");
+// one lane per ciphertext row (ghw11/mod.rs:205-217): with lambda the leaf's share of `secret`, H = Fr(SHA3(remove_index(name_col)))
+// and t the row's draw,
+//   cd[row][0] = C = g1_a * lambda + g1 * (-H t)        both walks on ONE accumulator (no point buffer, no separate addition)
+//   cd[row][1] = D = g1 * t
+// Scalars are formed in registers one at a time, just before their walk; C is parked in the row's output while D is walked.
+__global__ void __launch_bounds__(RB_ROWS_BLOCK, 2) k_ghw11_enc_rows(const G1M* g1_tbl, const G1M* g1a_tbl, size_t n_items, size_t total_leaves,
+                                                                             const uint32_t* item_leaf_off, const uint32_t* item_tree_leaf,
+                                                                             const uint32_t* item_tree_gate, TreeTables tt, const rhip_fr* leaf_hash,
+                                                                             const rhip_fr* secret, const rhip_fr* coef, const uint32_t* item_coef_off,
+                                                                             const rhip_fr* tdraw, rhip_g1* cd) {
+  __shared__ uint32_t sh[2 * 8 * RB_ROWS_BLOCK];
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = t < total_leaves;
+  if (!active) t = total_leaves - 1;        // inactive lanes shadow the last row (no stores) and still join the block inversion
+  const size_t item = owner_of(item_leaf_off, n_items, t);
+  const uint32_t leaf = item_tree_leaf[item] + (uint32_t)(t - item_leaf_off[item]);
+  uint32_t kk[8];
+  {
+    const Fr lambda = share_of_leaf_inl(tt, leaf, item_tree_gate[item], coef + item_coef_off[item], load_fr(secret[item].l));
+    from_mont_inl<FrParams>(kk, lambda);
+  }
+  G1Jac r = table_madd_g1_w16_inl(jac_inf<Fp>(), g1a_tbl, kk);
+  {
+    const Fr e = neg(mul_inl(load_fr(leaf_hash[leaf].l), load_fr(tdraw[t].l)));
+    from_mont_inl<FrParams>(kk, e);
+  }
+  r = table_madd_g1_w16_inl(r, g1_tbl, kk);
+  if (active) *(G1Jac*)(cd + 2 * t) = r;
+  ld_scalar(kk, tdraw + t);
+  r = table_madd_g1_w16_inl(jac_inf<Fp>(), g1_tbl, kk);
+  store2_g1_block_parked(sh, active, cd + 2 * t, r.x, r.y, r.z);
+}
+extern "C" int32_t rhip_ghw11_encrypt_batch(rhip_ctx* ctx, const rhip_ghw11_pk* pk, size_t n_items, size_t total_leaves, const uint32_t* item_leaf_off,
+                                            const uint32_t* item_tree_leaf, const uint32_t* item_tree_gate, const uint32_t* path_off,
+                                            const uint32_t* path_gate, const uint32_t* path_x, const uint32_t* gate_k, const uint32_t* gate_coef_off,
+                                            const rhip_fr* leaf_hash, const rhip_fr* secret, const rhip_fr* coef, const uint32_t* item_coef_off,
+                                            const rhip_fr* t, const rhip_gt* msg, rhip_gt* c, rhip_g1* c1, rhip_g1* cd) {
+  NEED(ctx);
+  if (!pk) return RHIP_ERR_ARG;
+  if (!n_items) return RHIP_OK;
+  if (!pk->g1->dev16 || !pk->g1_a->dev16) return fail(ctx, hipErrorInvalidValue, "rhip_ghw11_encrypt_batch: the key's G1 tables have no 16-bit windows");
+  if (total_leaves) {
+    const TreeTables tt{path_off, path_gate, path_x, gate_k, gate_coef_off};
+    KLAUNCH(ctx, "k_ghw11_enc_rows", k_ghw11_enc_rows, dim3(blocks_for(total_leaves, RB_ROWS_BLOCK)), dim3(RB_ROWS_BLOCK), 0, ctx->stream,
+            (const G1M*)pk->g1->dev16, (const G1M*)pk->g1_a->dev16, n_items, total_leaves, item_leaf_off, item_tree_leaf, item_tree_gate, tt, leaf_hash,
+            secret, coef, item_coef_off, t, cd);
+  }
+  int32_t rc = rhip_g1_table_mul(ctx, pk->g1, n_items, secret, c1);
+  if (rc) return rc;
+  const rhip_gt_table* et = pk->e;
+  KLAUNCH(ctx, "k_table_pow_gt_mul", k_table_pow_gt_mul, dim3(blocks_for(n_items, 64)), dim3(64), 0, ctx->stream,
+          (const GtM*)(et->dev16 ? et->dev16 : et->dev), et->dev16 ? 1 : 0, n_items, secret, msg, c);
   return RHIP_OK;
 }
 

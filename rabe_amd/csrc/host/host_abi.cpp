@@ -82,7 +82,8 @@ static thread_local std::string g_err;
 // unchunked call, two half-size chunks on two lanes are no faster for ac17 (20 480 items 339 k -> 311 k ops/s, 65 536 458 k -> 433 k,
 // 131 072 406 k -> 402 k) and slower for the GPU-bound bsw / lsw / aw11 (-6 ... -10 %): no entry point is chunked unless
 // RABE_PACKED_CHUNK asks for it.
-static const size_t CHUNK_AC17 = (size_t)1 << 40, CHUNK_BSW = (size_t)1 << 40, CHUNK_LSW = (size_t)1 << 40, CHUNK_AW11 = (size_t)1 << 40;
+static const size_t CHUNK_AC17 = (size_t)1 << 40, CHUNK_BSW = (size_t)1 << 40, CHUNK_LSW = (size_t)1 << 40, CHUNK_AW11 = (size_t)1 << 40,
+                    CHUNK_GHW11 = (size_t)1 << 40;
 #define GUARD_BEGIN try {
 #define GUARD_END(h)                                                         \
   }                                                                          \
@@ -1782,6 +1783,29 @@ int32_t rabe_ghw11_transform_packed(rabe_host* h, const void* tk, size_t n_items
   std::vector<std::string> errors;
   if (!ghw11::transform_packed(h->eng, *(const ghw11::Ghw11TransformKey*)tk, n_items, ct_blob, ct_len, ct_off, (flags & RABE_PACKED_TRUSTED) != 0, status,
                                tct_buf, tct_cap, &errors))
+    return 1;
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
+int32_t rabe_ghw11_encrypt_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
+                                  const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off) {
+  GUARD_BEGIN
+  const auto& key = *(const ghw11::Ghw11PublicKey*)pk;
+  const auto pols = strs(policies, n_policies);
+  const auto lang = lang_of(language);
+  if (!item_policy || !pt_off || !ct_off) throw RabeError("ghw11::encrypt_packed: null input");
+  return pipeline::produce(h->engines(), h->rng(), n_items, CHUNK_GHW11, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
+    return ghw11::encrypt_packed(eng, r, key, pols, lang, hi - lo, item_policy + lo, pt_blob, pt_off + lo, out, cap, off);
+  }, ct_buf, ct_cap, ct_off) ? 0 : 1;
+  GUARD_END(h)
+}
+int32_t rabe_ghw11_decrypt_out_packed(rabe_host* h, const void* rk, size_t n_items, const uint8_t* tct_buf, const uint8_t* ct_blob, size_t ct_len,
+                                      const uint64_t* ct_off, uint32_t flags, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  if (!ghw11::decrypt_out_packed(h->eng, *(const ghw11::Ghw11RetrieveKey*)rk, n_items, tct_buf, ct_blob, ct_len, ct_off, (flags & RABE_PACKED_TRUSTED) != 0,
+                                 status, pt_buf, pt_cap, pt_off, &errors))
     return 1;
   for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
   return 0;

@@ -1781,7 +1781,187 @@ void* make_tk_lines(Engine& eng, const void* arg) {          // arg: k_z | l_z |
   return lines;
 }
 void destroy_tk_lines(void* h) { rhip_g2_lines_destroy((rhip_g2_lines*)h); }
+void* make_pk(Engine& eng, const void* arg) {
+  const Ghw11PublicKey& pk = *(const Ghw11PublicKey*)arg;
+  rhip_ghw11_pk* d = nullptr;
+  eng.check(rhip_ghw11_pk_create(eng.ctx(), (const rhip_g1*)pk.g1.data(), (const rhip_g1*)pk.g1_a.data(), (const rhip_gt*)pk.e_gg_alpha.data(), &d),
+            "rhip_ghw11_pk_create");
+  return d;
+}
+void destroy_pk(void* h) { rhip_ghw11_pk_destroy((rhip_ghw11_pk*)h); }
 }  // namespace
+
+// n calls of ghw11::encrypt (ghw11/mod.rs:189-225).  Draw order per item: secret (:199), msg (:200), the gate coefficients of
+// gen_shares_policy (secretsharing/mod.rs:128-134), one t_i per share in share order (:206), the AES nonce (aes/mod.rs:17).  Like the
+// reference (:195-197) and the object API, an empty plaintext is encrypted.  Record = Ghw11Ciphertext:
+//   policy text, language, c, c1, row count, per row (name_col, C_i = g1_a * share - (g1 * h(name)) * t_i, D_i = g1 * t_i), sealed data.
+// The rows are one lane each (k_ghw11_enc_rows): share, both walks of C on one accumulator, D, one inversion per block.
+bool encrypt_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                    const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  Timer tm("ghw11::encrypt_packed");
+  Engine::ArenaScope arena(eng);
+  std::vector<std::shared_ptr<const FlatPolicy>> pols;
+  for (const auto& p : policies) pols.push_back(flat_policy(p, language));
+  for (size_t i = 0; i < n; i++) if (item_policy[i] >= policies.size()) throw RabeError("ghw11::encrypt_packed: item_policy out of range");
+  std::vector<size_t> fixed(policies.size());
+  for (size_t p = 0; p < policies.size(); p++)
+    fixed[p] = 4 + policies[p].size() + 1 + 384 + 64 + 4 + pols[p]->leaf_name.size() * (4 + 64 + 64) + pols[p]->names_bytes + 4;
+  out_off[0] = 0;
+  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_policy[i]] + (pt_off[i + 1] - pt_off[i]) + 28;
+  if (!out_buf || out_cap < out_off[n]) return false;
+  std::vector<uint32_t> leaf_off(n + 1, 0), coef_off(n + 1, 0), tree_leaf(n), tree_gate(n);
+  for (size_t i = 0; i < n; i++) {
+    leaf_off[i + 1] = leaf_off[i] + (uint32_t)pols[item_policy[i]]->leaf_name.size();
+    coef_off[i + 1] = coef_off[i] + pols[item_policy[i]]->n_coef;
+  }
+  const size_t total = leaf_off[n], total_coef = coef_off[n];
+  tm.lap("policies");
+  const size_t in_bytes = (2 * n + total_coef + total) * 32;
+  uint8_t* h_in = eng.pinned(0, in_bytes + 32);          // secret | msg exponent | coefficients | t per leaf row
+  uint8_t* h_sec = h_in;
+  uint8_t* h_rho = h_in + n * 32;
+  uint8_t* h_coef = h_in + n * 64;
+  uint8_t* h_t = h_coef + total_coef * 32;
+  std::vector<std::array<uint8_t, 12>> nonces(n);
+  draw_items(rng, n, [&](Rng& r, size_t i) {
+    Fr s = r.next_fr(), rho = r.next_fr();
+    memcpy(h_sec + 32 * i, s.l, 32);
+    memcpy(h_rho + 32 * i, rho.l, 32);
+    for (uint32_t c = coef_off[i]; c < coef_off[i + 1]; c++) { Fr a = r.next_fr(); memcpy(h_coef + 32 * (size_t)c, a.l, 32); }
+    for (uint32_t y = leaf_off[i]; y < leaf_off[i + 1]; y++) { Fr t = r.next_fr(); memcpy(h_t + 32 * (size_t)y, t.l, 32); }
+    r.fill(nonces[i].data(), 12);
+  });
+  tm.lap("draws");
+  rhip_ctx* cx = eng.ctx();
+  std::string key((const char*)pk.g1.data(), 64);
+  key.append((const char*)pk.g1_a.data(), 64).append((const char*)pk.e_gg_alpha.data(), 384);
+  rhip_ghw11_pk* dpk = (rhip_ghw11_pk*)eng.aux("ghw11_pk", key, make_pk, &pk, destroy_pk);
+  DevTrees dt(eng, pols);
+  for (size_t i = 0; i < n; i++) { tree_leaf[i] = dt.first_leaf[item_policy[i]]; tree_gate[i] = dt.first_gate[item_policy[i]]; }
+  DBuf d_leaf_off(&eng, leaf_off.data(), (n + 1) * 4), d_tl(&eng, tree_leaf.data(), n * 4), d_tg(&eng, tree_gate.data(), n * 4),
+      d_coef_off(&eng, coef_off.data(), n * 4), d_in(&eng, in_bytes + 32), d_msg(&eng, n * 384), d_c(&eng, n * 384), d_c1(&eng, n * 64),
+      d_cd(&eng, total * 128 + 4);
+  eng.check(rhip_upload_async(cx, d_in.ptr(), h_in, in_bytes), "upload");
+  const rhip_fr* dsec = d_in.as<rhip_fr>();
+  eng.check(rhip_gt_table_pow(cx, eng.gt_generator_table(), n, dsec + n, d_msg.as<rhip_gt>()), "rhip_gt_table_pow");
+  eng.check(rhip_ghw11_encrypt_batch(cx, dpk, n, total, d_leaf_off.as<uint32_t>(), d_tl.as<uint32_t>(), d_tg.as<uint32_t>(), dt.path_off.as<uint32_t>(),
+                                     dt.path_gate.as<uint32_t>(), dt.path_x.as<uint32_t>(), dt.gate_k.as<uint32_t>(), dt.gate_coef_off.as<uint32_t>(),
+                                     dt.leaf_hash.as<rhip_fr>(), dsec, dsec + 2 * n, d_coef_off.as<uint32_t>(), dsec + 2 * n + total_coef,
+                                     d_msg.as<rhip_gt>(), d_c.as<rhip_gt>(), d_c1.as<rhip_g1>(), d_cd.as<rhip_g1>()), "rhip_ghw11_encrypt_batch");
+  // records and sealing on the device (records.h)
+  std::vector<RecordLayout> layouts(policies.size());
+  for (size_t p_ = 0; p_ < policies.size(); p_++) {
+    RecordLayout& L = layouts[p_];
+    const FlatPolicy& f = *pols[p_];
+    L.str(policies[p_]);
+    L.u8((language == PolicyLanguage::HumanPolicy) ? 1 : 0);
+    L.src(0, 0, 384);
+    L.src(1, 0, 64);
+    L.u32((uint32_t)f.leaf_name.size());
+    for (size_t y = 0; y < f.leaf_name.size(); y++) {
+      L.str(f.leaf_name_col[y]);
+      L.src(2, (uint32_t)(128 * y), 128);          // C | D, adjacent in the row kernel's output as in the record
+    }
+    if (L.bytes() + 4 != fixed[p_]) throw RabeError("ghw11::encrypt_packed: record layout and size disagree");
+  }
+  std::vector<uint64_t> src_off(3 * n);
+  for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * i; src_off[n + i] = 64ull * i; src_off[2 * n + i] = 128ull * leaf_off[i]; }
+  emit_sealed_records(eng, layouts, n, item_policy, {d_c.ptr(), d_c1.ptr(), d_cd.ptr()}, src_off, d_msg.ptr(), (const uint8_t*)nonces.data(),
+                      pt_blob, pt_off, out_off, out_buf);
+  tm.lap("device: group arithmetic, records, sealing; one copy out");
+  return true;
+}
+
+// n calls of ghw11::decrypt_out (ghw11/mod.rs:297-305) under ONE retrieve key -- the client's half after transform_packed.  Item i: the
+// Ghw11TransformCiphertext record c | t at tct + 768 i, and ciphertext record i of the blob, which carries the sealed data (the reference
+// passes it beside the transformed ciphertext).  On the device: msg = c * t^(-z), KDF and AES-GCM open (records.h); only plaintexts come back.
+// An item fails alone (status -1, empty plaintext slot): an all-zero tct record (transform_packed's failure mark), a malformed ciphertext
+// record, c or t not in Gt (unless trusted), a tag that does not verify (a wrong rk, for one).
+bool decrypt_out_packed(Engine& eng, const Ghw11RetrieveKey& rk, size_t n, const uint8_t* tct, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
+                        bool trusted, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
+  Timer tm("ghw11::decrypt_out_packed");
+  Engine::ArenaScope arena(eng);
+  errors->assign(n, "");
+  if (!ct_off || !pt_off || (n && (!ct_blob || !tct || !status))) throw RabeError("ghw11::decrypt_out_packed: null input");
+  const uint64_t span = check_offsets(n, ct_off, ct_len, errors);
+  if (!pt_buf || pt_cap < span) { pt_off[n] = span; return false; }
+  std::vector<Sealed> sealed(n);
+  parallel_for(n, [&](size_t i) {
+    if (!(*errors)[i].empty()) return;
+    const uint8_t* rec = tct + 768 * i;
+    bool zero = true;
+    for (size_t b = 0; b < 768 && zero; b++) zero = rec[b] == 0;
+    if (zero) { (*errors)[i] = "ghw11::decrypt_out_packed: no transformed ciphertext for this item (transform failed)"; return; }
+    try {
+      Cursor r{ct_blob + ct_off[i], ct_blob + ct_off[i + 1]};
+      (void)r.str();
+      (void)r.raw(1 + 384 + 64);
+      const uint32_t rows = r.u32();
+      if ((size_t)rows * 132 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
+      for (uint32_t y = 0; y < rows; y++) { (void)r.str(); (void)r.raw(128); }
+      sealed[i].len = r.u32();
+      sealed[i].p = r.raw(sealed[i].len);
+      if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
+    } catch (const std::exception& ex) {
+      (*errors)[i] = ex.what();
+      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
+    }
+  });
+  tm.lap("parse");
+  std::vector<size_t> live;
+  for (size_t i = 0; i < n; i++) if ((*errors)[i].empty()) live.push_back(i);
+  const size_t m = live.size();
+  std::vector<uint64_t> sealed_off(m);
+  std::vector<uint32_t> sealed_len(m);
+  uint64_t sealed_total = 0;
+  for (size_t j = 0; j < m; j++) { sealed_off[j] = sealed_total; sealed_len[j] = sealed[live[j]].len; sealed_total += sealed_len[j]; }
+  DBuf d_msg(&eng, m * 384 + 4), d_sealed(&eng, sealed_total + 4);
+  if (m) {
+    eng.scrub_when_done();          // -z and the messages pass through the staging buffers
+    rhip_ctx* cx = eng.ctx();
+    // c | t of the live items, -z per item, the sealed parts: one staging block, three uploads
+    uint8_t* h = eng.pinned(0, m * (768 + 32) + sealed_total + 4);
+    uint8_t* h_c = h;
+    uint8_t* h_t = h + m * 384;
+    uint8_t* h_k = h + m * 768;
+    uint8_t* h_s = h_k + m * 32;
+    const Fr nz = fr_neg(rk.z);
+    parallel_for(m, [&](size_t j) {
+      const uint8_t* rec = tct + 768 * live[j];
+      memcpy(h_c + 384 * j, rec, 384);
+      memcpy(h_t + 384 * j, rec + 384, 384);
+      memcpy(h_k + 32 * j, nz.l, 32);
+      if (sealed_len[j]) memcpy(h_s + sealed_off[j], sealed[live[j]].p, sealed_len[j]);
+    });
+    tm.lap("pack");
+    DBuf d_ct(&eng, m * 768), d_k(&eng, m * 32), d_p(&eng, m * 384);
+    eng.check(rhip_upload_async(cx, d_ct.ptr(), h_c, m * 768), "upload");
+    eng.check(rhip_upload_async(cx, d_k.ptr(), h_k, m * 32), "upload");
+    if (sealed_total) eng.check(rhip_upload_async(cx, d_sealed.ptr(), h_s, sealed_total), "upload");
+    const rhip_gt* d_c = d_ct.as<rhip_gt>();
+    const rhip_gt* d_t = d_c + m;
+    std::unique_ptr<MemberChecks> mc;
+    if (!trusted) {
+      mc.reset(new MemberChecks(eng));
+      mc->add(3, d_c, m);
+      mc->add(3, d_t, m);
+    }
+    eng.check(rhip_gt_pow(cx, m, d_t, d_k.as<rhip_fr>(), d_p.as<rhip_gt>()), "rhip_gt_pow");
+    eng.check(rhip_gt_mul(cx, m, d_c, d_p.as<rhip_gt>(), d_msg.as<rhip_gt>()), "rhip_gt_mul");
+    if (mc) {
+      mc->collect();
+      const auto &ok_c = mc->ok(0), &ok_t = mc->ok(1);
+      for (size_t j = 0; j < m; j++) {
+        if (!ok_c[j]) (*errors)[live[j]] = "deserialize: c is not a member of Gt (FieldError::NotMember)";
+        else if (!ok_t[j]) (*errors)[live[j]] = "deserialize: t is not a member of Gt (FieldError::NotMember)";
+      }
+    }
+  }
+  // KDF + AES-GCM open on the device: the message never leaves HBM; plaintext bytes come back in one copy
+  open_sealed_records(eng, n, live, d_msg.ptr(), d_sealed.as<uint8_t>(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
+  tm.lap(trusted ? "device: powers, open" : "device: powers, open; membership beside");
+  return true;
+}
 
 // n calls of ghw11::transform (ghw11/mod.rs:227-295) under ONE transform key -- the outsourced half of a decryption, what a server
 // holding users' transform keys runs.  Records in: Ghw11Ciphertext (policy, c, c1, rows (name, c_i, d_i), sealed

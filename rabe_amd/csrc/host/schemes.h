@@ -195,6 +195,13 @@ std::vector<Ghw11TransformCiphertext> transform_batch(Engine& eng, const std::ve
 // record (c | t) of item i, zeros where status[i] = -1.  The device-resident path: every Miller loop replays the key's prepared lines.
 bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                       int32_t* status, uint8_t* out_buf, size_t out_cap, std::vector<std::string>* errors);
+// n calls of encrypt (packed.cpp): records = what rabe_obj_serialize writes for a Ghw11Ciphertext, built and sealed on the device
+bool encrypt_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                    const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
+// n calls of decrypt_out under ONE retrieve key: tct + 768 i = transform_packed's record of item i, the sealed data is read from the
+// ciphertext records.  Returns false (pt_off[n] = the size needed) when pt_cap is too small.
+bool decrypt_out_packed(Engine& eng, const Ghw11RetrieveKey& rk, size_t n, const uint8_t* tct, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
+                        bool trusted, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors);
 Gt decrypt_out_gt(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11RetrieveKey& rk);
 Bytes decrypt_out(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11RetrieveKey& rk, const Bytes& data);
 }  // namespace ghw11

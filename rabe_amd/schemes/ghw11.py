@@ -71,3 +71,35 @@ def transform_packed(host, tk, ct_blob, ct_off, trusted=False):
     host.call("rabe_ghw11_transform_packed", tk.ptr, ctypes.c_size_t(n), _np_ptr(ct), ctypes.c_size_t(ct.size), _np_ptr(co),
               ctypes.c_uint32(PACKED_TRUSTED if trusted else 0), _np_ptr(status), _np_ptr(out), ctypes.c_size_t(out.size))
     return out[:n], status[:n]
+
+
+def encrypt_packed(host, pk, policies, item_policy, pt_blob, pt_off, language=JSON_POLICY, out=None):
+    """n encryptions in one call (rabe_ghw11_encrypt_packed): policies are distinct texts, item_policy[i] indexes them, plaintext
+    i = pt_blob[pt_off[i]:pt_off[i+1]] -> (ct_blob, ct_off), the serialized Ghw11Ciphertext records"""
+    import numpy as np
+    from ..hostlib import _as_u8, packed_produce
+    return packed_produce(host, "rabe_ghw11_encrypt_packed", (pk.ptr,), policies, item_policy, language,
+                          (_as_u8(pt_blob), np.ascontiguousarray(pt_off, dtype=np.uint64)), out)
+
+
+def decrypt_out_packed(host, rk, tct, ct_blob, ct_off, trusted=False):
+    """n decrypt_out calls under one retrieve key (rabe_ghw11_decrypt_out_packed).  `tct`: the [n, 768] array transform_packed returns
+    (or its bytes), `ct_blob` / `ct_off`: the ciphertext records, which carry the sealed data.  Returns (pt_blob view, pt_off uint64 [n+1],
+    status int32 [n]); a failed item has status -1 and an empty or zeroed plaintext slot."""
+    import numpy as np
+    from ..hostlib import PACKED_TRUSTED, _as_u8, _np_ptr
+    n = len(ct_off) - 1
+    t = np.ascontiguousarray(_as_u8(tct) if not isinstance(tct, np.ndarray) else tct, dtype=np.uint8).reshape(-1)
+    if t.size < 768 * n:
+        raise ValueError("decrypt_out_packed: tct holds %d bytes, %d items need %d" % (t.size, n, 768 * n))
+    ct = _as_u8(ct_blob)
+    co = np.ascontiguousarray(ct_off, dtype=np.uint64)
+    po = np.zeros(n + 1, dtype=np.uint64)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    lo, hi = co[:-1], co[1:]
+    okm = (lo <= hi) & (hi <= ct.size)
+    need = int((hi[okm] - lo[okm]).sum()) if n else 0
+    buf = np.empty(max(need, 1), dtype=np.uint8)
+    host.call("rabe_ghw11_decrypt_out_packed", rk.ptr, ctypes.c_size_t(n), _np_ptr(t), _np_ptr(ct), ctypes.c_size_t(ct.size), _np_ptr(co),
+              ctypes.c_uint32(PACKED_TRUSTED if trusted else 0), _np_ptr(status), _np_ptr(buf), ctypes.c_size_t(buf.size), _np_ptr(po))
+    return buf[:int(po[n])], po, status[:n]
