@@ -470,6 +470,32 @@ int32_t rhip_ghw11_encrypt_batch(rhip_ctx* ctx, const rhip_ghw11_pk* pk, size_t 
                                  const uint32_t* dev_item_coef_off /*[n_items]*/, const rhip_fr* dev_t /*[total_leaves]*/,
                                  const rhip_gt* dev_msg /*[n_items]*/, rhip_gt* dev_c /*[n_items]*/, rhip_g1* dev_c1 /*[n_items]*/,
                                  rhip_g1* dev_cd /*[2 total_leaves]: C, D per row*/);
+/* BDABE / MKE08 encrypt (bdabe/mod.rs:317-358, mke08/mod.rs:290-334).  Every group element of their ciphertexts is a fixed-base product
+ * with the draw r of its row (one row per (item, DNF term)):  p1 * r, p2 * r (public key) and T1 * r, T2 * r, Tgt_g^r * msg_g with the
+ * term's folded attribute keys T1 = sum a1_k (G1), T2 = sum a2_k (G2), Tgt_g = prod of the keys' Gt component g (BDABE: n_gt = 1, a3;
+ * MKE08: n_gt = 2, gt1 and gt2).
+ * rhip_dnf_pk: 8- and 16-bit window tables of p1 (G1) and p2 (G2), walked by every row.
+ * rhip_dnf_terms: 8-bit window tables of n_terms term bases -- host_t1 [n_terms], host_t2 [n_terms], host_tgt [n_gt][n_terms] -- built
+ * in three launches (G1, G2, Gt; 522 KB + 1 MB + n_gt x 3.1 MB per term), and the device array of table pointers the row kernels index
+ * by term.
+ * rhip_dnf_encrypt_batch: one launch set over the n_rows rows of a call whose items may use several policies.  The term sets
+ * sets[0 .. n_sets) are concatenated: dev_row_term[j] < (sum of their n_terms) names row j's term in that order, dev_row_item[j] its item,
+ * dev_r[j] its draw; dev_msg [n_gt][n_items] the items' Gt messages (BDABE msg; MKE08 msg1, msg2).  Outputs, laid out for the records:
+ *   dev_gt [n_rows][n_gt]:  Tgt_g^r * msg_g                         (BDABE e1; MKE08 j1, j2)      -- k_dnf_enc_gt
+ *   dev_g1 [n_rows][2]:     p1 * r, T1 * r                          (BDABE e2, e4; MKE08 j3, j5)  -- k_dnf_enc_g1
+ *   dev_g2 [n_rows][2]:     p2 * r, T2 * r                          (BDABE e3, e5; MKE08 j4, j6)  -- k_dnf_enc_g2
+ * The G1 and G2 kernels run one lane per row, park the first point in the row's output and convert both with one inversion per block. */
+typedef struct rhip_dnf_pk rhip_dnf_pk;
+int32_t rhip_dnf_pk_create(rhip_ctx* ctx, const rhip_g1* host_p1, const rhip_g2* host_p2, rhip_dnf_pk** out);
+void rhip_dnf_pk_destroy(rhip_dnf_pk* pk);
+typedef struct rhip_dnf_terms rhip_dnf_terms;
+int32_t rhip_dnf_terms_create(rhip_ctx* ctx, size_t n_terms, uint32_t n_gt, const rhip_g1* host_t1, const rhip_g2* host_t2, const rhip_gt* host_tgt,
+                              rhip_dnf_terms** out);
+void rhip_dnf_terms_destroy(rhip_dnf_terms* terms);
+int32_t rhip_dnf_encrypt_batch(rhip_ctx* ctx, const rhip_dnf_pk* pk, size_t n_sets, const rhip_dnf_terms* const* sets, size_t n_items, size_t n_rows,
+                               const uint32_t* dev_row_term /*[n_rows]*/, const uint32_t* dev_row_item /*[n_rows]*/, const rhip_fr* dev_r /*[n_rows]*/,
+                               const rhip_gt* dev_msg /*[n_gt][n_items]*/, rhip_gt* dev_gt /*[n_rows][n_gt]*/, rhip_g1* dev_g1 /*[n_rows][2]*/,
+                               rhip_g2* dev_g2 /*[n_rows][2]*/);
 
 /* ---- Level B: AW11 multi-authority CP-ABE (src/schemes/aw11/mod.rs) -----------------------------------------------
  * rhip_aw11_pk: gk (g1, g2), the constant e(g1, g2) and, for each of the n_attrs attributes of the authorities in play,

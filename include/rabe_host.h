@@ -332,6 +332,22 @@ int32_t rabe_bdabe_decrypt_packed(rabe_host* h, const void* uk, size_t n_items, 
                                   int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off);
 int32_t rabe_mke08_decrypt_packed(rabe_host* h, const void* uk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
                                   int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off);
+/* n_items calls of encrypt (bdabe/mod.rs:317-358, mke08/mod.rs:290-334) in the form of rabe_aw11_encrypt_packed: item i is
+ * encrypt(pk, attr_pks, policies[item_policy[i]], language, pt_blob[pt_off[i] .. pt_off[i+1])).  ct_buf receives the BdabeCiphertext /
+ * Mke08Ciphertext records (rabe_obj_serialize's bytes), built and sealed on the device: one row per (item, DNF term), every element a
+ * fixed-base product with the row's r_j (tables of p1, p2 and of each term's folded attribute keys, cached per engine).
+ * Draw order per item -- BDABE: a, b (msg = e(G1::one(), G2::one())^(ab)), one r_j per DNF term in json_to_dnf's order, the AES nonce;
+ * MKE08: a, b, c (msg1 = gen^(ab), msg2 = msg1^c, the data sealed under msg1 * msg2), the r_j, the AES nonce.
+ * Errors fail the whole call and write no record: a policy not in DNF or naming an attribute attr_pks lacks (the object API's messages,
+ * with the index of the policy), an item_policy out of range.  Returns 1 when ct_cap is too small; ct_off[n_items] = the size needed. */
+int32_t rabe_bdabe_encrypt_packed(rabe_host* h, const void* pk, const void* const* attr_pks, size_t n_pks,
+                                  const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
+                                  const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off,
+                                  uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off);
+int32_t rabe_mke08_encrypt_packed(rabe_host* h, const void* pk, const void* const* attr_pks, size_t n_pks,
+                                  const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
+                                  const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off,
+                                  uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off);
 int32_t rabe_mke08_setup(rabe_host* h, void** pk, void** msk);
 int32_t rabe_mke08_keygen(rabe_host* h, const void* pk, const void* msk, const char* name, void** uk);
 int32_t rabe_mke08_authgen(rabe_host* h, const char* name, void** ska);

@@ -2004,6 +2004,236 @@ extern "C" int32_t rhip_aw11_decrypt_batch(rhip_ctx* ctx, size_t n_items, size_t
   return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, (const LineM*)nullptr, (const void*)nullptr, (const rhip_gt*)lead, out);
 }
 
+// ------------------------------------------------------------------------------------------------ BDABE / MKE08 encrypt (DNF policies)
+// Every group element of a ciphertext of the two DNF schemes is a fixed-base product with the row's draw r (bdabe/mod.rs:317-358,
+// mke08/mod.rs:290-334): p1 * r and p2 * r on the public key's 16-bit tables, T1 * r, T2 * r and Tgt^r on the 8-bit tables of the
+// row's term (T1 = sum of the term's G1 attribute keys, T2 the G2 sum, Tgt the product of its Gt keys; MKE08 has two Gt bases).
+struct rhip_dnf_pk {
+  rhip_ctx* ctx;
+  rhip_g1_table* p1;
+  rhip_g2_table* p2;
+};
+extern "C" void rhip_dnf_pk_destroy(rhip_dnf_pk* pk) {
+  if (!pk) return;
+  rhip_g1_table_destroy(pk->p1);
+  rhip_g2_table_destroy(pk->p2);
+  delete pk;
+}
+extern "C" int32_t rhip_dnf_pk_create(rhip_ctx* ctx, const rhip_g1* p1, const rhip_g2* p2, rhip_dnf_pk** out) {
+  if (!ctx || !p1 || !p2 || !out) return RHIP_ERR_ARG;
+  *out = nullptr;
+  rhip_dnf_pk* pk = new rhip_dnf_pk{ctx, nullptr, nullptr};
+  int32_t rc = rhip_g1_table_create(ctx, p1, &pk->p1);
+  if (!rc) rc = rhip_g1_table_add_w16(ctx, pk->p1);
+  if (!rc) rc = rhip_g2_table_create(ctx, p2, &pk->p2);
+  if (!rc) rc = rhip_g2_table_add_w16(ctx, pk->p2);
+  if (rc) { rhip_dnf_pk_destroy(pk); return rc; }
+  *out = pk;
+  return RHIP_OK;
+}
+// The 8-bit tables of n_terms term bases, one allocation per group: term t's G1 table at g1 + t * 8160 entries, its G2 table likewise,
+// Gt base g of term t at gt + (g * n_terms + t) * 8160.  dev_ptr[t * (2 + n_gt) + j]: the tables of term t (j = 0: G1, 1: G2, 2..: Gt),
+// the array the row kernels index by term.
+struct rhip_dnf_terms {
+  rhip_ctx* ctx;
+  size_t n_terms;
+  uint32_t n_gt;
+  G1M* g1;
+  G2M* g2;
+  GtM* gt;
+  const void** dev_ptr;
+};
+extern "C" void rhip_dnf_terms_destroy(rhip_dnf_terms* t) {
+  if (!t) return;
+  if (t->g1) (void)hipFree(t->g1);
+  if (t->g2) (void)hipFree(t->g2);
+  if (t->gt) (void)hipFree(t->gt);
+  if (t->dev_ptr) (void)hipFree((void*)t->dev_ptr);
+  delete t;
+}
+// G1 tables of n bases in one launch (the G2 and Gt ones: k_attr_tables_g2 / k_attr_tables_gt above)
+__global__ void __launch_bounds__(256, RB_MIN_WAVES) k_dnf_tables_g1(size_t n, const rhip_g1* base, G1M* tbl) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * TBL_WINDOWS * TBL_DIGITS) return;
+  const size_t a = t / (TBL_WINDOWS * TBL_DIGITS), e = t % (TBL_WINDOWS * TBL_DIGITS);
+  const int w = (int)(e / TBL_DIGITS);
+  const uint32_t d = (uint32_t)(e % TBL_DIGITS) + 1;
+  uint32_t k[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) k[i] = (i == (w >> 2)) ? (d << (8 * (w & 3))) : 0u;
+  st_g1_m(tbl + t, jac_to_aff(jac_mul_binary(load_g1(base[a].l), k)));
+}
+extern "C" int32_t rhip_dnf_terms_create(rhip_ctx* ctx, size_t n_terms, uint32_t n_gt, const rhip_g1* host_t1, const rhip_g2* host_t2,
+                                         const rhip_gt* host_tgt, rhip_dnf_terms** out) {
+  if (!ctx || !n_terms || (n_gt != 1 && n_gt != 2) || !host_t1 || !host_t2 || !host_tgt || !out) return RHIP_ERR_ARG;
+  *out = nullptr;
+  const size_t per = (size_t)TBL_WINDOWS * TBL_DIGITS, stride = 2 + n_gt, n_bt = n_gt * n_terms;
+  rhip_dnf_terms* t = new rhip_dnf_terms{ctx, n_terms, n_gt, nullptr, nullptr, nullptr, nullptr};
+  uint8_t* base = nullptr;          // the bases on the device: t1 | t2 | tgt
+  const size_t b1 = n_terms * sizeof(rhip_g1), b2 = n_terms * sizeof(rhip_g2), bt = n_bt * sizeof(rhip_gt);
+  hipError_t he = hipMalloc((void**)&t->g1, n_terms * per * sizeof(G1M));
+  if (he == hipSuccess) he = hipMalloc((void**)&t->g2, n_terms * per * sizeof(G2M));
+  if (he == hipSuccess) he = hipMalloc((void**)&t->gt, n_bt * per * sizeof(GtM));
+  if (he == hipSuccess) he = hipMalloc((void**)&t->dev_ptr, n_terms * stride * sizeof(void*));
+  if (he == hipSuccess) he = hipMalloc((void**)&base, b1 + b2 + bt);
+  std::vector<const void*> ptr(n_terms * stride);
+  for (size_t k = 0; k < n_terms; k++) {
+    ptr[k * stride] = t->g1 + k * per;
+    ptr[k * stride + 1] = t->g2 + k * per;
+    for (uint32_t g = 0; g < n_gt; g++) ptr[k * stride + 2 + g] = t->gt + (g * n_terms + k) * per;
+  }
+  if (he == hipSuccess) he = hipMemcpyAsync((void*)t->dev_ptr, ptr.data(), ptr.size() * sizeof(void*), hipMemcpyHostToDevice, ctx->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(base, host_t1, b1, hipMemcpyHostToDevice, ctx->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(base + b1, host_t2, b2, hipMemcpyHostToDevice, ctx->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(base + b1 + b2, host_tgt, bt, hipMemcpyHostToDevice, ctx->stream);
+  if (he == hipSuccess) {
+    hipLaunchKernelGGL(k_dnf_tables_g1, dim3(blocks_for(n_terms * per, 256)), dim3(256), 0, ctx->stream, n_terms, (const rhip_g1*)base, t->g1);
+    hipLaunchKernelGGL(k_attr_tables_g2, dim3(blocks_for(n_terms * per, 128)), dim3(128), 0, ctx->stream, n_terms, (const rhip_g2*)(base + b1), t->g2);
+    hipLaunchKernelGGL(k_attr_tables_gt, dim3(blocks_for(n_bt * per, 64)), dim3(64), 0, ctx->stream, n_bt, (const rhip_gt*)(base + b1 + b2), t->gt);
+    he = hipGetLastError();
+  }
+  if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);          // the bases and `ptr` are read before they go
+  if (base) (void)hipFree(base);
+  if (he != hipSuccess) { rhip_dnf_terms_destroy(t); return fail(ctx, he, "rhip_dnf_terms_create"); }
+  *out = t;
+  return RHIP_OK;
+}
+// 8-bit walk of a term's G1 table onto a running accumulator, inlined like table_madd_g1_w16_inl
+static __device__ __forceinline__ G1Jac table_madd_g1_inl(G1Jac acc, const G1M* tbl, const uint32_t k[8]) {
+#pragma unroll 1
+  for (int w = 0; w < TBL_WINDOWS; w++) {
+    const uint32_t d = scalar_byte(k, w);
+    if (d) acc = g1_madd_inl(acc, ld_g1_m(tbl + w * TBL_DIGITS + (d - 1)));
+  }
+  return acc;
+}
+// the G2 walks of table_mul_g2 / table_mul_g2_w16 (engine_internal.h), inlined: their out-of-line forms return the point through a
+// stack slot
+static __device__ __forceinline__ G2Jac table_mul_g2_inl(const G2M* tbl, const uint32_t k[8]) {
+  G2Jac acc = jac_inf<Fp2>();
+#pragma unroll 1
+  for (int w = 0; w < TBL_WINDOWS; w++) {
+    const uint32_t d = scalar_byte(k, w);
+    if (d) acc = jac_add_aff(acc, ld_g2_m(tbl + w * TBL_DIGITS + (d - 1)));
+  }
+  return acc;
+}
+static __device__ __forceinline__ G2Jac table_mul_g2_w16_inl(const G2M* tbl, const uint32_t k[8]) {
+  G2Jac acc = jac_inf<Fp2>();
+#pragma unroll 1
+  for (int w = 0; w < TBL16_WINDOWS; w++) {
+    uint32_t word;
+    switch (w >> 1) {
+      case 0: word = k[0]; break;
+      case 1: word = k[1]; break;
+      case 2: word = k[2]; break;
+      case 3: word = k[3]; break;
+      case 4: word = k[4]; break;
+      case 5: word = k[5]; break;
+      case 6: word = k[6]; break;
+      default: word = k[7]; break;
+    }
+    const uint32_t d = (w & 1) ? (word >> 16) : (word & 0xffffu);
+    if (d) acc = jac_add_aff(acc, ld_g2_m(tbl + (size_t)w * TBL16_DIGITS + (d - 1)));
+  }
+  return acc;
+}
+// store2_g1_block_parked for G2 (128-thread blocks): the first point is parked as a Jacobian value in the row's two output records
+// (192 B of 256), the second arrives in registers; ONE Fp inversion per block covers both, through the norms of their z's
+// (1 / (a + b u) = (a - b u) / (a^2 + b^2), as store_g2_block128 does for one point).
+__device__ __forceinline__ void store2_g2_block_parked(uint32_t* lds, bool active, rhip_g2* out, const G2Jac& b) {
+  G2Jac a = jac_inf<Fp2>();
+  if (active) a = *(const G2Jac*)out;
+  const bool ia = !active || jac_is_inf(a), ib = !active || jac_is_inf(b);
+  const Fp na = ia ? one<FpParams>() : add(sqr(a.z.c0), sqr(a.z.c1)), nb = ib ? one<FpParams>() : add(sqr(b.z.c0), sqr(b.z.c1));
+  const Fp inv_ab = block_batch_inverse_n<128>(lds, mul(na, nb));
+  if (!active) return;
+  const Fp ia_n = mul(inv_ab, nb), ib_n = mul(inv_ab, na);
+  const G2Aff ra = ia ? aff_inf<Fp2>() : jac_to_aff_with_zinv(a, Fp2{mul(a.z.c0, ia_n), neg(mul(a.z.c1, ia_n))});
+  const G2Aff rb = ib ? aff_inf<Fp2>() : jac_to_aff_with_zinv(b, Fp2{mul(b.z.c0, ib_n), neg(mul(b.z.c1, ib_n))});
+  store_g2(out[0].l, ra);
+  store_g2(out[1].l, rb);
+}
+static_assert(sizeof(G2Jac) <= 2 * sizeof(rhip_g2), "a parked G2 Jacobian point fits a row's two output records");
+// one lane per (item, term) row: g1[2 row] = p1 * r (bdabe e2 / mke08 j3), g1[2 row + 1] = T1 * r (e4 / j5).  p1 * r is parked in the
+// row's output while T1 * r is walked; one inversion per block makes both affine.
+__global__ void __launch_bounds__(RB_ROWS_BLOCK, 2) k_dnf_enc_g1(const G1M* p1_tbl, const void* const* term_tbl, uint32_t stride, size_t n_rows,
+                                                                 const uint32_t* row_term, const rhip_fr* r, rhip_g1* g1) {
+  __shared__ uint32_t sh[2 * 8 * RB_ROWS_BLOCK];
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = t < n_rows;
+  if (!active) t = n_rows - 1;        // inactive lanes shadow the last row (no stores) and still join the block inversion
+  uint32_t kk[8];
+  ld_scalar(kk, r + t);
+  G1Jac a = table_madd_g1_w16_inl(jac_inf<Fp>(), p1_tbl, kk);
+  if (active) *(G1Jac*)(g1 + 2 * t) = a;
+  a = table_madd_g1_inl(jac_inf<Fp>(), (const G1M*)term_tbl[(size_t)row_term[t] * stride], kk);
+  store2_g1_block_parked(sh, active, g1 + 2 * t, a.x, a.y, a.z);
+}
+// the same in G2: g2[2 row] = p2 * r (e3 / j4), g2[2 row + 1] = T2 * r (e5 / j6)
+__global__ void __launch_bounds__(128, RB_G2_WAVES) k_dnf_enc_g2(const G2M* p2_tbl, const void* const* term_tbl, uint32_t stride, size_t n_rows,
+                                                                const uint32_t* row_term, const rhip_fr* r, rhip_g2* g2) {
+  __shared__ uint32_t sh[2 * 8 * 128];
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = t < n_rows;
+  if (!active) t = n_rows - 1;
+  uint32_t kk[8];
+  ld_scalar(kk, r + t);
+  G2Jac a = table_mul_g2_w16_inl(p2_tbl, kk);
+  if (active) *(G2Jac*)(g2 + 2 * t) = a;
+  a = table_mul_g2_inl((const G2M*)term_tbl[(size_t)row_term[t] * stride + 1], kk);
+  store2_g2_block_parked(sh, active, g2 + 2 * t, a);
+}
+// one lane per (row, Gt base g): gt[n_gt row + g] = Tgt_g^r * msg[g n_items + item]  (bdabe e1; mke08 j1, j2)
+__global__ void __launch_bounds__(64, RB_MIN_WAVES) k_dnf_enc_gt(const void* const* term_tbl, uint32_t stride, uint32_t n_gt, size_t n_items, size_t n_rows,
+                                                                const uint32_t* row_term, const uint32_t* row_item, const rhip_fr* r, const rhip_gt* msg,
+                                                                rhip_gt* gt) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_rows * n_gt) return;
+  const size_t row = t / n_gt;
+  const uint32_t g = (uint32_t)(t % n_gt);
+  uint32_t kk[8];
+  ld_scalar(kk, r + row);
+  home_put(load_gt(msg[(size_t)g * n_items + row_item[row]].l));
+  bool started = true;
+  home_table_pow_gt(started, (const GtM*)term_tbl[(size_t)row_term[row] * stride + 2 + g], kk);
+  store_gt(gt[t].l, home_result(true));
+}
+extern "C" int32_t rhip_dnf_encrypt_batch(rhip_ctx* ctx, const rhip_dnf_pk* pk, size_t n_sets, const rhip_dnf_terms* const* sets, size_t n_items,
+                                          size_t n_rows, const uint32_t* row_term, const uint32_t* row_item, const rhip_fr* r, const rhip_gt* msg,
+                                          rhip_gt* gt, rhip_g1* g1, rhip_g2* g2) {
+  NEED(ctx);
+  if (!pk || (n_rows && (!n_sets || !sets || !row_term || !row_item || !r || !msg || !gt || !g1 || !g2))) return RHIP_ERR_ARG;
+  if (!n_rows) return RHIP_OK;
+  if (!pk->p1->dev16 || !pk->p2->dev16) return fail(ctx, hipErrorInvalidValue, "rhip_dnf_encrypt_batch: the key's tables have no 16-bit windows");
+  const uint32_t n_gt = sets[0] ? sets[0]->n_gt : 0;
+  for (size_t s = 0; s < n_sets; s++)
+    if (!sets[s] || sets[s]->n_gt != n_gt) return fail(ctx, hipErrorInvalidValue, "rhip_dnf_encrypt_batch: term sets of different schemes");
+  const uint32_t stride = 2 + n_gt;
+  const void* const* tbl = sets[0]->dev_ptr;
+  if (n_sets > 1) {          // the sets' pointer arrays back to back: row_term indexes the concatenation
+    size_t total = 0;
+    for (size_t s = 0; s < n_sets; s++) total += sets[s]->n_terms;
+    void* w = nullptr;
+    const int32_t rc = rhip_ensure_work(ctx, 15, total * stride * sizeof(void*), &w);
+    if (rc) return rc;
+    size_t at = 0;
+    for (size_t s = 0; s < n_sets; s++) {
+      HIP_TRY(ctx, hipMemcpyAsync((const void**)w + at * stride, sets[s]->dev_ptr, sets[s]->n_terms * stride * sizeof(void*), hipMemcpyDeviceToDevice,
+                                  ctx->stream));
+      at += sets[s]->n_terms;
+    }
+    tbl = (const void* const*)w;
+  }
+  KLAUNCH(ctx, "k_dnf_enc_g1", k_dnf_enc_g1, dim3(blocks_for(n_rows, RB_ROWS_BLOCK)), dim3(RB_ROWS_BLOCK), 0, ctx->stream, (const G1M*)pk->p1->dev16, tbl,
+          stride, n_rows, row_term, r, g1);
+  KLAUNCH(ctx, "k_dnf_enc_g2", k_dnf_enc_g2, dim3(blocks_for(n_rows, 128)), dim3(128), 0, ctx->stream, (const G2M*)pk->p2->dev16, tbl, stride, n_rows,
+          row_term, r, g2);
+  KLAUNCH(ctx, "k_dnf_enc_gt", k_dnf_enc_gt, dim3(blocks_for(n_rows * n_gt, 64)), dim3(64), 0, ctx->stream, tbl, stride, n_gt, n_items, n_rows, row_term,
+          row_item, r, msg, gt);
+  return RHIP_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ membership of decoded elements
 // What a decoder has to establish before an untrusted key / ciphertext reaches the pairing kernels (rabe-bn's decoding
 // raises FieldError::NotMember, src/error.rs:66): G1 has cofactor 1 (on-curve is enough: rhip_g1_on_curve); the twist has

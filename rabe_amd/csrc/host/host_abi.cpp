@@ -83,7 +83,7 @@ static thread_local std::string g_err;
 // 131 072 406 k -> 402 k) and slower for the GPU-bound bsw / lsw / aw11 (-6 ... -10 %): no entry point is chunked unless
 // RABE_PACKED_CHUNK asks for it.
 static const size_t CHUNK_AC17 = (size_t)1 << 40, CHUNK_BSW = (size_t)1 << 40, CHUNK_LSW = (size_t)1 << 40, CHUNK_AW11 = (size_t)1 << 40,
-                    CHUNK_GHW11 = (size_t)1 << 40;
+                    CHUNK_GHW11 = (size_t)1 << 40, CHUNK_DNF = (size_t)1 << 40;
 #define GUARD_BEGIN try {
 #define GUARD_END(h)                                                         \
   }                                                                          \
@@ -1658,6 +1658,36 @@ int32_t rabe_mke08_decrypt_packed(rabe_host* h, const void* uk, size_t n_items, 
   return dnf_decrypt_packed<mke08::Mke08Ciphertext, mke08::Mke08UserKey>(
       h, RABE_MKE08_CT, uk, n_items, ct_blob, ct_len, ct_off, flags, status, pt_buf, pt_cap, pt_off,
       [&](const std::vector<const mke08::Mke08UserKey*>& s, const std::vector<const mke08::Mke08Ciphertext*>& c) { return mke08::decrypt_batch(h->eng, s, c); });
+  GUARD_END(h)
+}
+int32_t rabe_bdabe_encrypt_packed(rabe_host* h, const void* pk, const void* const* attr_pks, size_t n_pks, const char* const* policies, size_t n_policies,
+                                  int32_t language, size_t n_items, const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off,
+                                  uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off) {
+  GUARD_BEGIN
+  std::vector<const bdabe::BdabePublicAttributeKey*> v;
+  for (size_t i = 0; i < n_pks; i++) v.push_back((const bdabe::BdabePublicAttributeKey*)attr_pks[i]);
+  const auto& key = *(const bdabe::BdabePublicKey*)pk;
+  const auto pols = strs(policies, n_policies);
+  const auto lang = lang_of(language);
+  if (!item_policy || !pt_off || !ct_off) throw RabeError("bdabe::encrypt_packed: null input");
+  return pipeline::produce(h->engines(), h->rng(), n_items, CHUNK_DNF, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
+    return bdabe::encrypt_packed(eng, r, key, v, pols, lang, hi - lo, item_policy + lo, pt_blob, pt_off + lo, out, cap, off);
+  }, ct_buf, ct_cap, ct_off) ? 0 : 1;
+  GUARD_END(h)
+}
+int32_t rabe_mke08_encrypt_packed(rabe_host* h, const void* pk, const void* const* attr_pks, size_t n_pks, const char* const* policies, size_t n_policies,
+                                  int32_t language, size_t n_items, const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off,
+                                  uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off) {
+  GUARD_BEGIN
+  std::vector<const mke08::Mke08PublicAttributeKey*> v;
+  for (size_t i = 0; i < n_pks; i++) v.push_back((const mke08::Mke08PublicAttributeKey*)attr_pks[i]);
+  const auto& key = *(const mke08::Mke08PublicKey*)pk;
+  const auto pols = strs(policies, n_policies);
+  const auto lang = lang_of(language);
+  if (!item_policy || !pt_off || !ct_off) throw RabeError("mke08::encrypt_packed: null input");
+  return pipeline::produce(h->engines(), h->rng(), n_items, CHUNK_DNF, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
+    return mke08::encrypt_packed(eng, r, key, v, pols, lang, hi - lo, item_policy + lo, pt_blob, pt_off + lo, out, cap, off);
+  }, ct_buf, ct_cap, ct_off) ? 0 : 1;
   GUARD_END(h)
 }
 int32_t rabe_mke08_setup(rabe_host* h, void** pk, void** msk) {

@@ -2143,5 +2143,207 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
 }
 }  // namespace ghw11
 
+// ================================================================================================ BDABE / MKE08 packed encrypt
+namespace dnfabe {
+namespace {
+// a public attribute key as the packed encrypt reads it: name, G1 and G2 parts, the n_gt Gt parts (BDABE a3; MKE08 gt1, gt2)
+struct DnfKey { const std::string* attr; const G1* g1; const G2* g2; const Gt* gt[2]; };
+struct DnfScheme {
+  const char* timer;               // "bdabe::encrypt_packed"
+  const char* terms_kind;          // cache of the term tables (Engine::aux)
+  const char* not_dnf;             // the object API's message for a policy that is not in DNF
+  uint32_t n_gt;
+};
+// Term tables are cached per engine under the BYTES of the attribute keys each term folds (the same policy text under other keys
+// is another entry).  At most TERMS_CACHE policies of at most TERMS_CACHE_MAX_TERMS terms are kept: 16 x 32 x 7.8 MB = 4.0 GB of HBM
+// for MKE08 (2.4 GB for BDABE) per engine.  A policy with more terms gets tables for the call alone.
+const size_t TERMS_CACHE = 16, TERMS_CACHE_MAX_TERMS = 32;
+struct TermsArg {
+  const std::vector<DnfTerm>* terms;
+  const std::vector<G1>* k1;
+  const std::vector<G2>* k2;
+  const std::vector<std::vector<Gt>>* kt;
+};
+void* make_terms(Engine& eng, const void* arg) {
+  const TermsArg& a = *(const TermsArg*)arg;
+  std::vector<G1> t1;
+  std::vector<G2> t2;
+  std::vector<std::vector<Gt>> tgt;
+  fold_term_bases(eng, *a.terms, *a.k1, *a.k2, *a.kt, &t1, &t2, &tgt);
+  std::vector<Gt> flat;
+  for (const auto& v : tgt) flat.insert(flat.end(), v.begin(), v.end());
+  rhip_dnf_terms* d = nullptr;
+  eng.check(rhip_dnf_terms_create(eng.ctx(), t1.size(), (uint32_t)tgt.size(), (const rhip_g1*)t1.data(), (const rhip_g2*)t2.data(),
+                                  (const rhip_gt*)flat.data(), &d), "rhip_dnf_terms_create");
+  return d;
+}
+void destroy_terms(void* h) { rhip_dnf_terms_destroy((rhip_dnf_terms*)h); }
+struct PkArg { const G1* p1; const G2* p2; };
+void* make_pk(Engine& eng, const void* arg) {
+  const PkArg& a = *(const PkArg*)arg;
+  rhip_dnf_pk* d = nullptr;
+  eng.check(rhip_dnf_pk_create(eng.ctx(), (const rhip_g1*)a.p1->data(), (const rhip_g2*)a.p2->data(), &d), "rhip_dnf_pk_create");
+  return d;
+}
+void destroy_pk(void* h) { rhip_dnf_pk_destroy((rhip_dnf_pk*)h); }
+// rethrown with the index of the policy it is about, in the class the object API throws
+[[noreturn]] void policy_error(const std::exception& e, bool panic, size_t p) {
+  const std::string msg = std::string(e.what()) + " (policies[" + std::to_string(p) + "])";
+  if (panic) throw std::runtime_error(msg);
+  throw RabeError(msg);
+}
+
+// n calls of bdabe::encrypt (bdabe/mod.rs:317-358) or mke08::encrypt (mke08/mod.rs:290-334).  Draw order per item: the message's
+// a, b (BDABE msg = e(G1::one(), G2::one())^(ab); MKE08 also c: msg1 = gen^(ab), msg2 = gen^(abc), the data is sealed under
+// msg1 msg2 = gen^(ab(1+c))), one r_j per DNF term in json_to_dnf's order, the AES nonce.  Per distinct policy: parse, DNF check,
+// json_to_dnf against the names of attr_pks, term tables (folded once, cached).  One row per (item, term) on the device
+// (rhip_dnf_encrypt_batch); records assembled and sealed there (records.h).
+bool encrypt_packed(Engine& eng, Rng& rng, const DnfScheme& sc, const G1& p1, const G2& p2, const std::vector<DnfKey>& keys,
+                    const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
+                    const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  Timer tm(sc.timer);
+  Engine::ArenaScope arena(eng);
+  Engine::Busy working(eng);          // a term set evicted by a later policy of this call lives until the call is done
+  const size_t P = policies.size(), n_gt = sc.n_gt;
+  std::vector<std::string> names;
+  for (const auto& k : keys) names.push_back(*k.attr);
+  std::vector<std::vector<DnfTerm>> terms(P);
+  std::vector<RecordLayout> layouts(P);
+  for (size_t p = 0; p < P; p++) {
+    PolicyNode tree;
+    try {
+      tree = parse_or_error(policies[p], language);
+    } catch (const std::exception& e) {
+      policy_error(e, false, p);
+    }
+    if (!policy_in_dnf(tree)) policy_error(RabeError(sc.not_dnf), false, p);
+    if (!json_to_dnf(tree, names, &terms[p]))
+      policy_error(std::runtime_error("called `Result::unwrap()` on an `Err` value: Error in json_to_dnf: could not parse policy as DNF"), true, p);
+    // the record (host_abi.cpp: ser): policy, language, term count, per term its attribute names, Gt part(s), p1 r, p2 r, T1 r, T2 r
+    RecordLayout& L = layouts[p];
+    L.str(policies[p]);
+    L.u8((language == PolicyLanguage::HumanPolicy) ? 1 : 0);
+    L.u32((uint32_t)terms[p].size());
+    for (size_t y = 0; y < terms[p].size(); y++) {
+      L.u32((uint32_t)terms[p][y].attrs.size());
+      for (const auto& a : terms[p][y].attrs) L.str(a);
+      L.src(0, (uint32_t)(384 * n_gt * y), (uint32_t)(384 * n_gt));
+      L.src(1, (uint32_t)(128 * y), 64);
+      L.src(2, (uint32_t)(256 * y), 128);
+      L.src(1, (uint32_t)(128 * y + 64), 64);
+      L.src(2, (uint32_t)(256 * y + 128), 128);
+    }
+  }
+  for (size_t i = 0; i < n; i++) if (item_policy[i] >= P) throw RabeError(std::string(sc.timer) + ": item_policy out of range");
+  out_off[0] = 0;
+  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + layouts[item_policy[i]].bytes() + 4 + (pt_off[i + 1] - pt_off[i]) + 28;
+  if (!out_buf || out_cap < out_off[n]) return false;
+  if (!n) return true;
+  std::vector<uint32_t> row_off(n + 1, 0);
+  for (size_t i = 0; i < n; i++) row_off[i + 1] = row_off[i] + (uint32_t)terms[item_policy[i]].size();
+  const size_t rows = row_off[n], n_exp = n_gt == 1 ? 1 : 3;
+  tm.lap("policies");
+  // the tables -- the key's (cached) and one term set per policy some item uses -- before the staging block is filled: a cache miss
+  // runs the fold through the engine
+  const PkArg pka{&p1, &p2};
+  rhip_dnf_pk* dpk = (rhip_dnf_pk*)eng.aux("dnf_pk", std::string((const char*)p1.data(), 64) + std::string((const char*)p2.data(), 128), make_pk, &pka,
+                                           destroy_pk);
+  std::vector<G1> k1;
+  std::vector<G2> k2;
+  std::vector<std::vector<Gt>> kt(n_gt);
+  for (const auto& k : keys) {
+    k1.push_back(*k.g1);
+    k2.push_back(*k.g2);
+    for (size_t g = 0; g < n_gt; g++) kt[g].push_back(*k.gt[g]);
+  }
+  std::vector<bool> used(P, false);
+  for (size_t i = 0; i < n; i++) used[item_policy[i]] = true;
+  std::vector<const rhip_dnf_terms*> sets;
+  std::vector<std::unique_ptr<rhip_dnf_terms, void (*)(rhip_dnf_terms*)>> own;
+  std::vector<uint32_t> term_base(P, 0);
+  uint32_t n_terms = 0;
+  for (size_t p = 0; p < P; p++) {
+    if (!used[p] || terms[p].empty()) continue;
+    const TermsArg ta{&terms[p], &k1, &k2, &kt};
+    const rhip_dnf_terms* s;
+    if (terms[p].size() <= TERMS_CACHE_MAX_TERMS) {
+      std::string key;
+      for (const auto& t : terms[p]) {
+        key.append(4, '\0');
+        put_u32((uint8_t*)&key[key.size() - 4], (uint32_t)t.keys.size());
+        for (size_t k : t.keys) {
+          key.append((const char*)k1[k].data(), 64).append((const char*)k2[k].data(), 128);
+          for (size_t g = 0; g < n_gt; g++) key.append((const char*)kt[g][k].data(), 384);
+        }
+      }
+      s = (const rhip_dnf_terms*)eng.aux(sc.terms_kind, key, make_terms, &ta, destroy_terms, TERMS_CACHE);
+    } else {
+      own.emplace_back((rhip_dnf_terms*)make_terms(eng, &ta), rhip_dnf_terms_destroy);
+      s = own.back().get();
+    }
+    sets.push_back(s);
+    term_base[p] = n_terms;
+    n_terms += (uint32_t)terms[p].size();
+  }
+  tm.lap("tables");
+  const size_t in_bytes = (n_exp * n + rows) * 32;
+  uint8_t* h_in = eng.pinned(0, in_bytes + 32);          // message exponents [n_exp][n] | r per row
+  uint8_t* h_r = h_in + n_exp * n * 32;
+  std::vector<std::array<uint8_t, 12>> nonces(n);
+  draw_items(rng, n, [&](Rng& r, size_t i) {
+    const Fr a = r.next_fr(), b = r.next_fr(), ab = fr_mul(a, b);
+    memcpy(h_in + 32 * i, ab.l, 32);
+    if (n_gt == 2) {
+      const Fr c = r.next_fr(), abc = fr_mul(ab, c), msg = fr_mul(ab, fr_add(fr_one(), c));
+      memcpy(h_in + 32 * (n + i), abc.l, 32);
+      memcpy(h_in + 32 * (2 * n + i), msg.l, 32);
+    }
+    for (uint32_t y = row_off[i]; y < row_off[i + 1]; y++) { const Fr rj = r.next_fr(); memcpy(h_r + 32 * (size_t)y, rj.l, 32); }
+    r.fill(nonces[i].data(), 12);
+  });
+  tm.lap("draws");
+  rhip_ctx* cx = eng.ctx();
+  DBuf d_in(&eng, in_bytes + 32), d_msg(&eng, n_exp * n * 384);
+  eng.check(rhip_upload_async(cx, d_in.ptr(), h_in, in_bytes), "upload");
+  eng.check(rhip_gt_table_pow(cx, eng.gt_generator_table(), n_exp * n, d_in.as<rhip_fr>(), d_msg.as<rhip_gt>()), "rhip_gt_table_pow");
+  std::vector<uint32_t> row_term(rows), row_item(rows);
+  for (size_t i = 0; i < n; i++)
+    for (uint32_t y = row_off[i]; y < row_off[i + 1]; y++) { row_term[y] = term_base[item_policy[i]] + (y - row_off[i]); row_item[y] = (uint32_t)i; }
+  DBuf d_rt = up32(eng, row_term), d_ri = up32(eng, row_item), d_gt(&eng, rows * 384 * n_gt + 4), d_g1(&eng, rows * 128 + 4), d_g2(&eng, rows * 256 + 4);
+  eng.check(rhip_dnf_encrypt_batch(cx, dpk, sets.size(), sets.data(), n, rows, d_rt.as<uint32_t>(), d_ri.as<uint32_t>(), d_in.as<rhip_fr>() + n_exp * n,
+                                   d_msg.as<rhip_gt>(), d_gt.as<rhip_gt>(), d_g1.as<rhip_g1>(), d_g2.as<rhip_g2>()), "rhip_dnf_encrypt_batch");
+  // records and sealing on the device (records.h); the data is sealed under msg (BDABE) / msg1 msg2 (MKE08)
+  std::vector<uint64_t> src_off(3 * n);
+  for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * n_gt * row_off[i]; src_off[n + i] = 128ull * row_off[i]; src_off[2 * n + i] = 256ull * row_off[i]; }
+  emit_sealed_records(eng, layouts, n, item_policy, {d_gt.ptr(), d_g1.ptr(), d_g2.ptr()}, src_off, d_msg.as<rhip_gt>() + (n_exp - 1) * n,
+                      (const uint8_t*)nonces.data(), pt_blob, pt_off, out_off, out_buf);
+  tm.lap("device: group arithmetic, records, sealing; one copy out");
+  return true;
+}
+}  // namespace
+}  // namespace dnfabe
+
+namespace bdabe {
+bool encrypt_packed(Engine& eng, Rng& rng, const BdabePublicKey& pk, const std::vector<const BdabePublicAttributeKey*>& attr_pks,
+                    const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
+                    const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  static const dnfabe::DnfScheme sc{"bdabe::encrypt_packed", "bdabe_terms", "Error in bdabe/encrypt: Policy not in DNF.", 1};
+  std::vector<dnfabe::DnfKey> keys;
+  for (const auto* k : attr_pks) keys.push_back({&k->attr, &k->a1, &k->a2, {&k->a3, nullptr}});
+  return dnfabe::encrypt_packed(eng, rng, sc, pk.p1, pk.p2, keys, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off);
+}
+}  // namespace bdabe
+
+namespace mke08 {
+bool encrypt_packed(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const std::vector<const Mke08PublicAttributeKey*>& attr_pks,
+                    const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
+                    const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  static const dnfabe::DnfScheme sc{"mke08::encrypt_packed", "mke08_terms", "Error in mke08/encrypt: policy is not in dnf", 2};
+  std::vector<dnfabe::DnfKey> keys;
+  for (const auto* k : attr_pks) keys.push_back({&k->attr, &k->g1, &k->g2, {&k->gt1, &k->gt2}});
+  return dnfabe::encrypt_packed(eng, rng, sc, pk.p1, pk.p2, keys, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off);
+}
+}  // namespace mke08
+
 }  // namespace schemes
 }  // namespace rabe

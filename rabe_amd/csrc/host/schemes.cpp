@@ -2759,6 +2759,13 @@ static std::vector<T> fold_terms(const std::vector<DnfTerm>& terms, const std::v
   }
   return acc;
 }
+void fold_term_bases(Engine& eng, const std::vector<DnfTerm>& terms, const std::vector<G1>& k1, const std::vector<G2>& k2,
+                     const std::vector<std::vector<Gt>>& kt, std::vector<G1>* t1, std::vector<G2>* t2, std::vector<std::vector<Gt>>* tgt) {
+  *t1 = fold_terms(terms, k1, [&](const std::vector<G1>& x, const std::vector<G1>& y) { return g1_add(eng, x, y); });
+  *t2 = fold_terms(terms, k2, [&](const std::vector<G2>& x, const std::vector<G2>& y) { return g2_add(eng, x, y); });
+  tgt->clear();
+  for (const auto& k : kt) tgt->push_back(fold_terms(terms, k, [&](const std::vector<Gt>& x, const std::vector<Gt>& y) { return eng.gt_mul(x, y); }));
+}
 }  // namespace dnfabe
 
 namespace bdabe {

@@ -206,6 +206,13 @@ Gt decrypt_out_gt(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11R
 Bytes decrypt_out(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11RetrieveKey& rk, const Bytes& data);
 }  // namespace ghw11
 
+namespace dnfabe {
+// the term bases of a DNF policy with the fold of encrypt (schemes.cpp: fold_terms): t1[t] = sum of k1 over term t's keys, t2 likewise,
+// (*tgt)[g][t] = product of kt[g] over them
+void fold_term_bases(Engine& eng, const std::vector<host::DnfTerm>& terms, const std::vector<G1>& k1, const std::vector<G2>& k2,
+                     const std::vector<std::vector<Gt>>& kt, std::vector<G1>* t1, std::vector<G2>* t2, std::vector<std::vector<Gt>>* tgt);
+}  // namespace dnfabe
+
 namespace bdabe {       // src/schemes/bdabe/mod.rs (DNF policies, multi-authority)
 struct BdabePublicKey { G1 g1; G2 g2; G1 p1; G2 p2; Gt e_gg_y; };                          // :49-55
 struct BdabeMasterKey { Fr y; };                                                            // :61-63
@@ -229,6 +236,10 @@ Bytes decrypt(Engine& eng, const BdabeUserKey& sk, const BdabeCiphertext& ct);
 Gt decrypt_gt(Engine& eng, const BdabeUserKey& sk, const BdabeCiphertext& ct);
 // n independent decrypts: every item's four pairing factors on one accumulator, one launch set for the batch
 std::vector<DecryptResult> decrypt_batch(Engine& eng, const std::vector<const BdabeUserKey*>& sks, const std::vector<const BdabeCiphertext*>& cts);
+// n calls of encrypt (packed.cpp): records = what rabe_obj_serialize writes for a BdabeCiphertext, built and sealed on the device
+bool encrypt_packed(Engine& eng, Rng& rng, const BdabePublicKey& pk, const std::vector<const BdabePublicAttributeKey*>& attr_pks,
+                    const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
+                    const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
 }  // namespace bdabe
 
 namespace mke08 {       // src/schemes/mke08/mod.rs (DNF policies, multi-authority)
@@ -253,6 +264,10 @@ Mke08Ciphertext encrypt(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const s
 Bytes decrypt(Engine& eng, const Mke08UserKey& sk, const Mke08Ciphertext& ct);
 Gt decrypt_gt(Engine& eng, const Mke08UserKey& sk, const Mke08Ciphertext& ct);
 std::vector<DecryptResult> decrypt_batch(Engine& eng, const std::vector<const Mke08UserKey*>& sks, const std::vector<const Mke08Ciphertext*>& cts);
+// n calls of encrypt (packed.cpp): records = what rabe_obj_serialize writes for a Mke08Ciphertext, built and sealed on the device
+bool encrypt_packed(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const std::vector<const Mke08PublicAttributeKey*>& attr_pks,
+                    const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
+                    const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
 }  // namespace mke08
 
 }}  // namespace rabe::schemes

@@ -1,7 +1,7 @@
 """rabe::schemes::mke08 (src/schemes/mke08/mod.rs:130-380) over the host layer."""
 import ctypes
 
-from ..hostlib import Obj, batch_decrypt
+from ..hostlib import JSON_POLICY, Obj, batch_decrypt
 
 
 def setup(host):
@@ -58,3 +58,13 @@ def decrypt_packed(host, uk, ct_blob, ct_off, out=None, trusted=False):
     Returns (pt_blob view, pt_off uint64 [n+1], status int32 [n])."""
     from ..hostlib import packed_decrypt
     return packed_decrypt(host, "rabe_mke08_decrypt_packed", (uk.ptr,), ct_blob, ct_off, out, trusted)
+
+
+def encrypt_packed(host, pk, attr_pks, policies, item_policy, pt_blob, pt_off, language=JSON_POLICY, out=None):
+    """n encryptions in one call (rabe_mke08_encrypt_packed): item i encrypts pt_blob[pt_off[i]:pt_off[i+1]] under
+    policies[item_policy[i]] with the public attribute keys attr_pks -> (ct_blob, ct_off), the serialized Mke08Ciphertext records"""
+    import numpy as np
+    from ..hostlib import _as_u8, packed_produce
+    arr = (ctypes.c_void_p * max(1, len(attr_pks)))(*[p.ptr for p in attr_pks])
+    return packed_produce(host, "rabe_mke08_encrypt_packed", (pk.ptr, arr, ctypes.c_size_t(len(attr_pks))), policies, item_policy, language,
+                          (_as_u8(pt_blob), np.ascontiguousarray(pt_off, dtype=np.uint64)), out)

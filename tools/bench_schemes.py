@@ -191,6 +191,41 @@ if args.only in ("", "dnf"):
             print(json.dumps({"config": label, "batch": n_items, "decrypts_per_s": round(n_items / best[False], 1),
                               "decrypts_per_s_trusted": round(n_items / best[True], 1), "seconds": round(best[False], 4)}), flush=True)
     packed_dnf(bdabe, uk, [c.serialize() for c in cts], "8f-4: BDABE decrypt, packed records (rabe_bdabe_decrypt_packed)")
+
+    def encrypt_dnf(mod, pk, attr_pk, scheme, auth):
+        """per-call encrypt (a few hundred calls) against the packed encrypt at 4096 and 65 536 items, policies of 1, 3 and 8 terms"""
+        import numpy as np
+        names8 = ["%s::T%d" % (auth, i) for i in range(8)]
+        keys = [attr_pk(n) for n in names8]
+        pol = {t: leaf(names8[0]) if t == 1 else '{"name": "or", "children": [%s]}' % ", ".join(leaf(x) for x in names8[:t]) for t in (1, 3, 8)}
+        calls = 256
+        mod.encrypt(host, pk, keys, pol[3], hl.JSON_POLICY, PT)
+        t0_ = time.perf_counter()
+        for _ in range(calls):
+            mod.encrypt(host, pk, keys, pol[3], hl.JSON_POLICY, PT)
+        dt = time.perf_counter() - t0_
+        print(json.dumps({"config": "8f-4: %s encrypt, per call (rabe_%s_encrypt), 3 terms" % (scheme.upper(), scheme), "batch": calls,
+                          "encrypts_per_s": round(calls / dt, 1), "seconds": round(dt, 4)}), flush=True)
+        for terms in (1, 3, 8):
+            for n_items in (4096, 65536):
+                pt_off = np.arange(n_items + 1, dtype=np.uint64) * len(PT)
+                t0_ = time.perf_counter()
+                blob, off = mod.encrypt_packed(host, pk, keys, [pol[terms]], [0] * n_items, PT * n_items, pt_off)
+                first = time.perf_counter() - t0_
+                best = 9e9
+                for _ in range(2):
+                    t0_ = time.perf_counter()
+                    blob, off = mod.encrypt_packed(host, pk, keys, [pol[terms]], [0] * n_items, PT * n_items, pt_off)
+                    best = min(best, time.perf_counter() - t0_)
+                last = hl.Obj.deserialize(scheme + "_ct", bytes(blob[int(off[n_items - 1]):]))
+                assert len(hl.parse_obj(scheme + "_ct", last.serialize())["j" if scheme == "bdabe" else "e"]) == terms
+                line = {"config": "8f-4: %s encrypt, packed (rabe_%s_encrypt_packed), %d terms" % (scheme.upper(), scheme, terms), "batch": n_items,
+                        "encrypts_per_s": round(n_items / best, 1), "seconds": round(best, 4), "first_call_s": round(first, 4),
+                        "record_bytes": int(blob.size)}
+                if n_items == 4096:          # the first call of a policy also folds its terms and builds their tables
+                    line["table_build_s_per_term"] = round((first - best) / terms, 4)
+                print(json.dumps(line), flush=True)
+    encrypt_dnf(bdabe, pk, lambda n: bdabe.request_attribute_pk(host, pk, au, n), "bdabe", "aa1")
     pk, msk = mke08.setup(host)
     uk = mke08.keygen(host, pk, msk, "user1")
     au = mke08.authgen(host, "auth1")
@@ -207,4 +242,5 @@ if args.only in ("", "dnf"):
     assert pts == [PT] * B
     report("8f-4: MKE08 decrypt, 3-attribute conjunction (6 pairings/item)", B, t1 - t0, {"decrypt_s": round(t1 - t0, 3)})
     packed_dnf(mke08, uk, [c.serialize() for c in cts], "8f-4: MKE08 decrypt, packed records (rabe_mke08_decrypt_packed)")
+    encrypt_dnf(mke08, pk, lambda n: mke08.request_authority_pk(host, pk, n, au), "mke08", "auth1")
 host.close()
