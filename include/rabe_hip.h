@@ -139,6 +139,18 @@ int32_t rhip_g1_mul(rhip_ctx* ctx, size_t n, const rhip_g1* dev_p, const rhip_fr
 int32_t rhip_g2_add(rhip_ctx* ctx, size_t n, const rhip_g2* dev_a, const rhip_g2* dev_b, rhip_g2* dev_out);
 int32_t rhip_g2_neg(rhip_ctx* ctx, size_t n, const rhip_g2* dev_a, rhip_g2* dev_out);
 int32_t rhip_g2_mul(rhip_ctx* ctx, size_t n, const rhip_g2* dev_p, const rhip_fr* dev_k, rhip_g2* dev_out);
+/* Variable-base G2 multiplication of rows that share scalars: out[t] = k[i] * p[t] for the rows t in [item_row_off[i], item_row_off[i+1])
+ * of item i (n_items + 1 non-decreasing offsets, item_row_off[0] = 0, item_row_off[n_items] = n_rows; an item may own no row).  What
+ * ghw11::tkgen does to a key (every element times z^-1, src/schemes/ghw11/mod.rs:156-178), for n_items keys in one launch set.  The scalar
+ * is split four ways over the twist endomorphism once per item (k = k0 + k1 L + k2 L^2 + k3 L^3 mod r, L = p mod r, |k_i| < 2^65) and
+ * every row runs one joint chain of ~66 doublings (bn254/gls4.h) instead of rhip_g2_mul's 254.  Any 256-bit scalar word is accepted (0
+ * and multiples of r give infinity); infinity in, infinity out.  The points must be members of G2 (rhip_g2_in_subgroup): for a twist
+ * point outside the r-torsion the result is NOT k * p -- rhip_g2_mul is the entry point for those. */
+int32_t rhip_g2_mul_rows(rhip_ctx* ctx, size_t n_rows, const uint32_t* dev_item_row_off /*[n_items+1]*/, const rhip_g2* dev_p /*[n_rows]*/,
+                         size_t n_items, const rhip_fr* dev_k /*[n_items]*/, rhip_g2* dev_out /*[n_rows]*/);
+/* the split alone, on the host (no GPU, no context; the code the kernel runs): mag[4 i .. 4 i + 4) = |k_i| as little-endian words,
+ * neg[i] = 1 for a negative k_i */
+int32_t rhip_host_fr_split4(const rhip_fr* k, uint32_t mag[16], uint8_t neg[4]);
 /* per-element curve membership: dev_ok[i] = 1 if on the curve (or infinity) */
 int32_t rhip_g1_on_curve(rhip_ctx* ctx, size_t n, const rhip_g1* dev_p, uint32_t* dev_ok);
 int32_t rhip_g2_on_curve(rhip_ctx* ctx, size_t n, const rhip_g2* dev_p, uint32_t* dev_ok);
@@ -470,6 +482,17 @@ int32_t rhip_ghw11_encrypt_batch(rhip_ctx* ctx, const rhip_ghw11_pk* pk, size_t 
                                  const uint32_t* dev_item_coef_off /*[n_items]*/, const rhip_fr* dev_t /*[total_leaves]*/,
                                  const rhip_gt* dev_msg /*[n_items]*/, rhip_gt* dev_c /*[n_items]*/, rhip_g1* dev_c1 /*[n_items]*/,
                                  rhip_g1* dev_cd /*[2 total_leaves]: C, D per row*/);
+/* GHW11 keygen (ghw11/mod.rs:123-152) for n_items keys under one master key.  rhip_ghw11_keys: 8- and 16-bit window tables of g2 and g2_a
+ * (Ghw11PublicKey) and the master key's g2_alpha -- the G2 side of the key pair, beside rhip_ghw11_pk (the G1 / Gt side encrypt uses).
+ * Item i owns output rows [item_row_off[i], item_row_off[i+1]) = 2 + (its number of attributes): L = g2 * r_i, K = g2_alpha + g2_a * r_i,
+ * then K_x = g2 * (h(x) r_i) per attribute with h(x) = dev_hash[item_hash_off[i] + x] (Fr(SHA3(name)); items with the same attribute list
+ * share their hashes).  One lane per row (k_ghw11_keygen_rows), one inversion per block, canonical wire form out. */
+typedef struct rhip_ghw11_keys rhip_ghw11_keys;
+int32_t rhip_ghw11_keys_create(rhip_ctx* ctx, const rhip_g2* host_g2, const rhip_g2* host_g2_a, const rhip_g2* host_g2_alpha, rhip_ghw11_keys** out);
+void rhip_ghw11_keys_destroy(rhip_ghw11_keys* keys);
+int32_t rhip_ghw11_keygen_batch(rhip_ctx* ctx, const rhip_ghw11_keys* keys, size_t n_items, size_t n_rows, const uint32_t* dev_item_row_off /*[n_items+1]*/,
+                                const uint32_t* dev_item_hash_off /*[n_items]*/, const rhip_fr* dev_hash, const rhip_fr* dev_r /*[n_items]*/,
+                                rhip_g2* dev_out /*[n_rows]*/);
 /* BDABE / MKE08 encrypt (bdabe/mod.rs:317-358, mke08/mod.rs:290-334).  Every group element of their ciphertexts is a fixed-base product
  * with the draw r of its row (one row per (item, DNF term)):  p1 * r, p2 * r (public key) and T1 * r, T2 * r, Tgt_g^r * msg_g with the
  * term's folded attribute keys T1 = sum a1_k (G1), T2 = sum a2_k (G2), Tgt_g = prod of the keys' Gt component g (BDABE: n_gt = 1, a3;

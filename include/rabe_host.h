@@ -294,6 +294,29 @@ int32_t rabe_ghw11_encrypt_packed(rabe_host* h, const void* pk, const char* cons
  * lines (kept across calls) and the rows that share l_z collapse into one pairing of a multi-scalar sum (ghw11/mod.rs:227-295). */
 int32_t rabe_ghw11_transform_packed(rabe_host* h, const void* tk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
                                     const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* tct_buf, size_t tct_cap);
+/* Bulk key issuing (conventions of rabe_bsw_keygen_packed): n_items calls of ghw11::keygen (ghw11/mod.rs:123-152) under one master key, item i
+ * with the attribute list item_set[i]; records = Ghw11SecretKey (k, l, rows (name, k_x)), written on the device.  Draw order: one r per item, in
+ * item order.  Every element is a fixed-base multiple (L = g2 * r, K = g2_alpha + g2_a * r, K_x = g2 * (h(x) r)): one lane per element over window
+ * tables of g2 and g2_a that are built once per key pair and kept.  sk_off is always filled; returns 1, with nothing drawn, when
+ * sk_cap < sk_off[n_items].  An empty attribute list (keygen returns None) or an item_set out of range fails the call before any draw. */
+int32_t rabe_ghw11_keygen_packed(rabe_host* h, const void* pk, const void* msk, const char* const* attributes, const size_t* counts,
+                                 size_t n_sets, size_t n_items, const uint32_t* item_set /*[n_items]*/,
+                                 uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off /*[n_items+1]*/);
+/* n_items calls of ghw11::tkgen (ghw11/mod.rs:156-178), one per Ghw11SecretKey record of sk_blob.  The blob is UNTRUSTED (conventions of
+ * rabe_ac17_cp_decrypt_packed): nothing outside [0, sk_len) is read; an item with bad bounds or a malformed record fails alone -- status[i] = -1,
+ * an empty tk slot, 32 zero bytes of rk; unless RABE_PACKED_TRUSTED, every decoded G2 element goes through the batched membership pass
+ * (coordinates < p, on the twist, in the r-torsion) and a non-member fails its item only.  With the flag a non-member is not rejected and its
+ * transform key is NOT z^-1 times its elements (the multiplication relies on membership): set it only for keys this process issued.
+ * Output: item i's Ghw11TransformKey record (k_z, l_z, rows (name, k_x_z): the secret key's layout, names copied) at tk_buf + tk_off[i], its
+ * Ghw11RetrieveKey record (z, 32 bytes) at rk_buf + 32 i.  Returns 1, with nothing drawn, when tk_cap is below the total size of the well-formed
+ * records (tk_off[n_items] = that size).
+ * DRAW ORDER: one z per item whose record decodes ON THE HOST (bounds + parse), in item order; the membership verdicts arrive later and do
+ * not change what is drawn (a non-member's z is spent).  z = 0 fails the whole call, as tkgen's inverse().unwrap() does.
+ * Every element times z^-1 is a variable-base G2 multiplication: z^-1 is split four ways over the twist endomorphism once per item and each
+ * element runs one joint chain of ~66 doublings (rhip_g2_mul_rows).  The staging that held z / z^-1 is zeroed when the call ends. */
+int32_t rabe_ghw11_tkgen_packed(rabe_host* h, size_t n_items, const uint8_t* sk_blob, size_t sk_len, const uint64_t* sk_off /*[n_items+1]*/,
+                                uint32_t flags, int32_t* status /*[n_items]*/,
+                                uint8_t* tk_buf, size_t tk_cap, uint64_t* tk_off /*[n_items+1]*/, uint8_t* rk_buf /*32 n_items*/);
 /* `data` of the reference's decrypt_out is the ciphertext's data field: pass the ciphertext object */
 int32_t rabe_ghw11_decrypt_out(rabe_host* h, const void* tct, const void* rk, const void* ct, uint8_t** plaintext, size_t* len);
 int32_t rabe_ghw11_decrypt_out_gt(rabe_host* h, const void* tct, const void* rk, uint8_t out_gt[384]);
@@ -381,6 +404,9 @@ int32_t rabe_policy_coeffs(const char* policy, int32_t language, char** out);
 int32_t rabe_hash_fr(const char* label, uint8_t out_le32[32]);
 /* test hook: x mod r of a 512-bit little-endian x by the fast path and by plain long division */
 int32_t rabe_fr_reduce512(const uint8_t in_le64[64], uint8_t out_fast[32], uint8_t out_division[32]);
+/* test hook, no GPU needed: the four-way split k = k0 + k1 L + k2 L^2 + k3 L^3 (mod r), L = p mod r, that rabe_ghw11_tkgen_packed's kernel
+ * applies to z^-1 (the same routine, run on the host): mag[i] = |k_i| little-endian, neg[i] = 1 for a negative k_i */
+int32_t rabe_fr_split4(const uint8_t k[32], uint8_t mag[4][16] /*little-endian magnitudes*/, uint8_t neg[4]);
 /* KDF + AES-256-GCM of src/utils/aes/mod.rs with an explicit nonce; out = nonce || ct || tag */
 int32_t rabe_encrypt_symmetric(const uint8_t gt[384], const uint8_t* data, size_t len, const uint8_t nonce[12], uint8_t** out, size_t* out_len);
 int32_t rabe_decrypt_symmetric(const uint8_t gt[384], const uint8_t* data, size_t len, uint8_t** out, size_t* out_len);

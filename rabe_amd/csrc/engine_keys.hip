@@ -1,0 +1,185 @@
+// engine_keys.hip -- bulk key issuing: the GHW11 keygen row kernel (fixed-base) and the variable-base G2 multiplication over rows that
+// share a scalar (four-way split over the twist endomorphism, bn254/gls4.h), which serves ghw11::tkgen.
+//
+// A translation unit of its own: docs/rr29.md records that adding a kernel to a unit can move its neighbours' register allocation, and
+// engine_jobs.hip holds the kernels BASELINE configs 3 - 5 time.
+#include "engine_internal.h"
+#include "bn254/gls4.h"
+
+// Montgomery records are 128 bytes and 16-byte aligned: 128-bit accesses
+__device__ __forceinline__ Fp ld_fp_q(const uint4* p) {
+  const uint4 a = p[0], b = p[1];
+  Fp r;
+  r.v[0] = a.x; r.v[1] = a.y; r.v[2] = a.z; r.v[3] = a.w;
+  r.v[4] = b.x; r.v[5] = b.y; r.v[6] = b.z; r.v[7] = b.w;
+  return r;
+}
+__device__ __forceinline__ void st_fp_q(uint4* p, const Fp& a) {
+  p[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
+  p[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
+}
+__device__ __forceinline__ G2Aff ld_g2_q(const G2M* p) {
+  const uint4* q = (const uint4*)p;
+  return G2Aff{Fp2{ld_fp_q(q), ld_fp_q(q + 2)}, Fp2{ld_fp_q(q + 4), ld_fp_q(q + 6)}};
+}
+__device__ __forceinline__ void st_g2_q(G2M* p, const G2Aff& a) {
+  uint4* q = (uint4*)p;
+  st_fp_q(q, a.x.c0); st_fp_q(q + 2, a.x.c1); st_fp_q(q + 4, a.y.c0); st_fp_q(q + 6, a.y.c1);
+}
+// item owning flat index t: the i with off[i] <= t < off[i+1] (off non-decreasing, off[0] <= t < off[n])
+__device__ __forceinline__ size_t owner_of(const uint32_t* off, size_t n, size_t t) {
+  size_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const size_t mid = (lo + hi) >> 1;
+    if (off[mid] <= t) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// ------------------------------------------------------------------------------------------------ GHW11 keygen
+struct rhip_ghw11_keys {
+  rhip_ctx* ctx;
+  rhip_g2_table* g2;
+  rhip_g2_table* g2_a;
+  rhip_g2* g2_alpha;          // device, wire form
+};
+extern "C" void rhip_ghw11_keys_destroy(rhip_ghw11_keys* k) {
+  if (!k) return;
+  rhip_g2_table_destroy(k->g2);
+  rhip_g2_table_destroy(k->g2_a);
+  if (k->g2_alpha) (void)hipFree(k->g2_alpha);
+  delete k;
+}
+extern "C" int32_t rhip_ghw11_keys_create(rhip_ctx* ctx, const rhip_g2* g2, const rhip_g2* g2_a, const rhip_g2* g2_alpha, rhip_ghw11_keys** out) {
+  if (!ctx || !g2 || !g2_a || !g2_alpha || !out) return RHIP_ERR_ARG;
+  *out = nullptr;
+  rhip_ghw11_keys* k = new rhip_ghw11_keys{ctx, nullptr, nullptr, nullptr};
+  int32_t rc = rhip_g2_table_create(ctx, g2, &k->g2);
+  if (!rc) rc = rhip_g2_table_add_w16(ctx, k->g2);
+  if (!rc) rc = rhip_g2_table_create(ctx, g2_a, &k->g2_a);
+  if (!rc) rc = rhip_g2_table_add_w16(ctx, k->g2_a);
+  if (!rc) {
+    hipError_t he = hipMalloc((void**)&k->g2_alpha, sizeof(rhip_g2));
+    if (he == hipSuccess) he = hipMemcpy(k->g2_alpha, g2_alpha, sizeof(rhip_g2), hipMemcpyHostToDevice);
+    if (he != hipSuccess) rc = fail(ctx, he, "rhip_ghw11_keys_create");
+  }
+  if (rc) { rhip_ghw11_keys_destroy(k); return rc; }
+  *out = k;
+  return RHIP_OK;
+}
+// one lane per key element (ghw11/mod.rs:123-152); rows of item i are [item_row_off[i], item_row_off[i+1]) = L, K, then its attributes:
+//   row 0: L   = g2 * r
+//   row 1: K   = g2_alpha + g2_a * r
+//   row y: K_x = (g2 * h(x)) * r = g2 * (h(x) r),  h(x) = hash[item_hash_off[i] + y - 2]
+// Every element is one walk over the 16-bit windows of g2 or g2_a; the product h(x) r is formed in the lane.  One inversion per block.
+__global__ void __launch_bounds__(128, RB_G2_WAVES) k_ghw11_keygen_rows(const G2M* g2_tbl, const G2M* g2a_tbl, const rhip_g2* g2_alpha, size_t n_items,
+                                                                       size_t n_rows, const uint32_t* item_row_off, const uint32_t* item_hash_off,
+                                                                       const rhip_fr* hash, const rhip_fr* r, rhip_g2* out) {
+  __shared__ uint32_t sh[2 * 8 * 128];
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = t < n_rows;
+  if (!active) t = n_rows - 1;        // inactive lanes shadow the last row (no stores) and still join the block inversion
+  const size_t item = owner_of(item_row_off, n_items, t);
+  const uint32_t row = (uint32_t)(t - item_row_off[item]);
+  uint32_t kk[8];
+  if (row < 2) {
+    ld_scalar(kk, r + item);
+  } else {
+    const Fr e = mul_inl(load_fr(hash[(size_t)item_hash_off[item] + (row - 2)].l), load_fr(r[item].l));
+    from_mont_inl<FrParams>(kk, e);
+  }
+  G2Jac a = table_mul_g2_w16(row == 1 ? g2a_tbl : g2_tbl, kk);
+  if (row == 1) a = jac_add_aff(a, load_g2(g2_alpha->l));
+  store_g2_block128(sh, active, out + t, a);
+}
+extern "C" int32_t rhip_ghw11_keygen_batch(rhip_ctx* ctx, const rhip_ghw11_keys* keys, size_t n_items, size_t n_rows, const uint32_t* item_row_off,
+                                           const uint32_t* item_hash_off, const rhip_fr* hash, const rhip_fr* r, rhip_g2* out) {
+  NEED(ctx);
+  if (!keys) return RHIP_ERR_ARG;
+  if (!n_items || !n_rows) return RHIP_OK;
+  if (!item_row_off || !item_hash_off || !hash || !r || !out) return RHIP_ERR_ARG;
+  KLAUNCH(ctx, "k_ghw11_keygen_rows", k_ghw11_keygen_rows, dim3(blocks_for(n_rows, 128)), dim3(128), 0, ctx->stream, (const G2M*)keys->g2->dev16,
+          (const G2M*)keys->g2_a->dev16, (const rhip_g2*)keys->g2_alpha, n_items, n_rows, item_row_off, item_hash_off, hash, r, out);
+  return RHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ variable-base G2, rows sharing a scalar
+// the split and the NAF masks, once per item (bn254/gls4.h): masks[24 i ..]
+__global__ void __launch_bounds__(256, RB_MIN_WAVES) k_gls4_masks(size_t n, const rhip_fr* k, uint32_t* masks) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t kk[8], m[24];
+  ld_scalar(kk, k + i);
+  gls4_masks(kk, m);
+#pragma unroll
+  for (int w = 0; w < 24; w++) masks[24 * i + w] = m[w];
+}
+// psi^i(P) of a lane: img[i * stride], Montgomery
+struct Gls4Bases {
+  const G2M* img;
+  size_t stride;
+  __device__ __forceinline__ G2Aff base(int i) const { return ld_g2_q(img + (size_t)i * stride); }
+};
+// one lane per row: out[t] = k[item of t] * p[t].  The lane computes the three images of its point once and keeps all four bases in
+// global memory (img[i][lane], read back where an addition needs one -- the chain's accumulator and temporaries fill the register file);
+// the masks are read through the item index, so the digit tests are uniform wherever a wave holds rows of one item.  Rows
+// [row0, row0 + cnt) of the call; lanes past cnt shadow the last row with an image slot of their own (stride >= the launch's lanes).
+__global__ void __launch_bounds__(128, RB_G2_WAVES) k_g2_mul_rows(size_t row0, size_t cnt, size_t n_items, const uint32_t* item_row_off, const rhip_g2* p,
+                                                                 const uint32_t* masks, G2M* img, size_t stride, rhip_g2* out) {
+  __shared__ uint32_t sh[2 * 8 * 128];
+  const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = lane < cnt;
+  const size_t t = row0 + (active ? lane : cnt - 1);
+  const size_t item = owner_of(item_row_off, n_items, t);
+  {
+    const G2Aff P = load_g2(p[t].l);          // infinity (0, 0) maps to itself under psi and is skipped by every addition
+    const G2Aff P2 = g2_frob2(P);
+    st_g2_q(img + lane, P);
+    st_g2_q(img + stride + lane, g2_frob1(P));
+    st_g2_q(img + 2 * stride + lane, P2);
+    st_g2_q(img + 3 * stride + lane, g2_frob1(P2));
+  }
+  const G2Jac acc = gls4_chain(Gls4Bases{img + lane, stride}, masks + 24 * item);
+  store_g2_block128(sh, active, out + t, acc);
+}
+#define RB_G2_ROWS_CHUNK ((size_t)1 << 20)          // rows per launch: bounds the image workspace at 512 MB
+extern "C" int32_t rhip_g2_mul_rows(rhip_ctx* ctx, size_t n_rows, const uint32_t* item_row_off, const rhip_g2* p, size_t n_items, const rhip_fr* k,
+                                    rhip_g2* out) {
+  NEED(ctx);
+  if (!n_rows) return RHIP_OK;
+  if (!n_items || !item_row_off || !p || !k || !out) return RHIP_ERR_ARG;
+  void* masks = nullptr;
+  void* img = nullptr;
+  int32_t rc = rhip_ensure_work(ctx, 16, n_items * 24 * sizeof(uint32_t), &masks);
+  if (rc) return rc;
+  const size_t stride = ((n_rows < RB_G2_ROWS_CHUNK ? n_rows : RB_G2_ROWS_CHUNK) + 127) / 128 * 128;
+  rc = rhip_ensure_work(ctx, 17, stride * 4 * sizeof(G2M), &img);
+  if (rc) return rc;
+  KLAUNCH(ctx, "k_gls4_masks", k_gls4_masks, dim3(blocks_for(n_items, 256)), dim3(256), 0, ctx->stream, n_items, k, (uint32_t*)masks);
+  for (size_t row0 = 0; row0 < n_rows; row0 += RB_G2_ROWS_CHUNK) {
+    const size_t cnt = n_rows - row0 < RB_G2_ROWS_CHUNK ? n_rows - row0 : RB_G2_ROWS_CHUNK;
+    KLAUNCH(ctx, "k_g2_mul_rows", k_g2_mul_rows, dim3(blocks_for(cnt, 128)), dim3(128), 0, ctx->stream, row0, cnt, n_items, item_row_off, p,
+            (const uint32_t*)masks, (G2M*)img, stride, out);
+  }
+  return RHIP_OK;
+}
+// the split alone, on the host (the RB_HD code the kernel above runs): |k_i| as four little-endian words each, neg[i] = 1 for a negative k_i
+extern "C" int32_t rhip_host_fr_split4(const rhip_fr* k, uint32_t mag[16], uint8_t neg_[4]) {
+  if (!k || !mag || !neg_) return RHIP_ERR_ARG;
+  uint32_t kk[8];
+  for (int i = 0; i < 8; i++) kk[i] = k->l[i];
+  for (int t = 0; t < 6; t++) {          // as ld_scalar: any 256-bit word is brought below r
+    uint32_t d[8], borrow = 0;
+    for (int i = 0; i < 8; i++) d[i] = subb32(kk[i], FrParams::mod(i), borrow);
+    if (borrow) break;
+    for (int i = 0; i < 8; i++) kk[i] = d[i];
+  }
+  uint32_t m[4][4];
+  bool sg[4];
+  gls4_split(kk, m, sg);
+  for (int i = 0; i < 4; i++) {
+    for (int w = 0; w < 4; w++) mag[4 * i + w] = m[i][w];
+    neg_[i] = sg[i] ? 1 : 0;
+  }
+  return RHIP_OK;
+}

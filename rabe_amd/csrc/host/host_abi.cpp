@@ -1841,6 +1841,28 @@ int32_t rabe_ghw11_decrypt_out_packed(rabe_host* h, const void* rk, size_t n_ite
   return 0;
   GUARD_END(h)
 }
+int32_t rabe_ghw11_keygen_packed(rabe_host* h, const void* pk, const void* msk, const char* const* attributes, const size_t* counts, size_t n_sets,
+                                 size_t n_items, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off) {
+  GUARD_BEGIN
+  std::vector<std::vector<std::string>> sets(n_sets);
+  size_t at = 0;
+  for (size_t s = 0; s < n_sets; s++)
+    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
+  return ghw11::keygen_packed(h->eng, h->rng(), *(const ghw11::Ghw11PublicKey*)pk, *(const ghw11::Ghw11MasterKey*)msk, sets, n_items, item_set, sk_buf,
+                              sk_cap, sk_off) ? 0 : 1;
+  GUARD_END(h)
+}
+int32_t rabe_ghw11_tkgen_packed(rabe_host* h, size_t n_items, const uint8_t* sk_blob, size_t sk_len, const uint64_t* sk_off, uint32_t flags, int32_t* status,
+                                uint8_t* tk_buf, size_t tk_cap, uint64_t* tk_off, uint8_t* rk_buf) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  if (!ghw11::tkgen_packed(h->eng, h->rng(), n_items, sk_blob, sk_len, sk_off, (flags & RABE_PACKED_TRUSTED) != 0, status, tk_buf, tk_cap, tk_off, rk_buf,
+                           &errors))
+    return 1;
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
 int32_t rabe_ghw11_decrypt_out(rabe_host* h, const void* tct, const void* rk, const void* ct, uint8_t** plaintext, size_t* len) {
   GUARD_BEGIN
   return give_bytes(ghw11::decrypt_out(h->eng, *(const ghw11::Ghw11TransformCiphertext*)tct, *(const ghw11::Ghw11RetrieveKey*)rk,
@@ -1868,6 +1890,17 @@ int32_t rabe_fr_reduce512(const uint8_t in_le64[64], uint8_t out_fast[32], uint8
   frdetail::reduce512(b, t);
   memcpy(out_fast, a, 32);
   memcpy(out_division, b, 32);
+  return 0;
+}
+
+// the four-way split of a G2 scalar behind rabe_ghw11_tkgen_packed (bn254/gls4.h, the code the kernel runs), for the tests
+int32_t rabe_fr_split4(const uint8_t k[32], uint8_t mag[4][16], uint8_t neg[4]) {
+  rhip_fr kk;
+  uint32_t m[16];
+  memcpy(kk.l, k, 32);
+  const int32_t rc = rhip_host_fr_split4(&kk, m, neg);
+  if (rc) return rc;
+  memcpy(mag, m, 64);
   return 0;
 }
 

@@ -1789,6 +1789,15 @@ void* make_pk(Engine& eng, const void* arg) {
   return d;
 }
 void destroy_pk(void* h) { rhip_ghw11_pk_destroy((rhip_ghw11_pk*)h); }
+struct KeysArg { const Ghw11PublicKey* pk; const Ghw11MasterKey* msk; };
+void* make_keys(Engine& eng, const void* arg) {
+  const KeysArg& a = *(const KeysArg*)arg;
+  rhip_ghw11_keys* d = nullptr;
+  eng.check(rhip_ghw11_keys_create(eng.ctx(), (const rhip_g2*)a.pk->g2.data(), (const rhip_g2*)a.pk->g2_a.data(), (const rhip_g2*)a.msk->g2_alpha.data(), &d),
+            "rhip_ghw11_keys_create");
+  return d;
+}
+void destroy_keys(void* h) { rhip_ghw11_keys_destroy((rhip_ghw11_keys*)h); }
 }  // namespace
 
 // n calls of ghw11::encrypt (ghw11/mod.rs:189-225).  Draw order per item: secret (:199), msg (:200), the gate coefficients of
@@ -2138,6 +2147,192 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
     memcpy(o + 384, h_out + 384 * slot[i], 384);
     status[i] = 0;
   });
+  tm.lap("assembly");
+  return true;
+}
+// n calls of ghw11::keygen (ghw11/mod.rs:123-152) under one master key.  Item i gets the attribute list sets[item_set[i]]; draw order: one r
+// per item, in item order (:130).  Record = Ghw11SecretKey: k, l, rows (name, k_x).  Every element is a fixed-base multiple (the hash to G2
+// is g2 * h(x)): L = g2 * r, K = g2_alpha + g2_a * r, K_x = g2 * (h(x) r) -- one lane per element over the 16-bit window tables of g2 and
+// g2_a (k_ghw11_keygen_rows; tables built once per key pair and kept), records written on the device from one template per list.
+bool keygen_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw11MasterKey& msk, const std::vector<std::vector<std::string>>& sets, size_t n,
+                   const uint32_t* item_set, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  Timer tm("ghw11::keygen_packed");
+  Engine::ArenaScope arena(eng);
+  eng.scrub_when_done();          // the keys' r pass through the staging buffers
+  if (!out_off || (n && !item_set)) throw RabeError("ghw11::keygen_packed: null input");
+  for (size_t i = 0; i < n; i++) if (item_set[i] >= sets.size()) throw RabeError("ghw11::keygen_packed: item_set out of range");
+  std::vector<size_t> fixed(sets.size());
+  std::vector<uint32_t> hash_off(sets.size() + 1, 0);
+  std::vector<Fr> hashes;
+  for (size_t s = 0; s < sets.size(); s++) {
+    if (sets[s].empty()) throw RabeError("ghw11::keygen_packed: an empty attribute list (ghw11::keygen returns None for it)");
+    fixed[s] = 128 + 128 + 4;
+    for (const auto& a : sets[s]) { fixed[s] += 4 + a.size() + 128; hashes.push_back(sha3_hash_fr(a)); }
+    hash_off[s + 1] = (uint32_t)hashes.size();
+  }
+  out_off[0] = 0;
+  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_set[i]];
+  if (n && (!out_buf || out_cap < out_off[n])) return false;
+  if (!n) return true;
+  std::vector<uint32_t> row_off(n + 1, 0), item_hash(n);
+  for (size_t i = 0; i < n; i++) {
+    const uint64_t next = (uint64_t)row_off[i] + 2 + sets[item_set[i]].size();
+    if (next > 0xFFFFFFF0ull) throw RabeError("ghw11::keygen_packed: more than 2^32 key elements in one call");
+    row_off[i + 1] = (uint32_t)next;
+    item_hash[i] = hash_off[item_set[i]];
+  }
+  const size_t total = row_off[n];
+  uint8_t* h_r = eng.pinned(0, n * 32 + 32);
+  draw_items(rng, n, [&](Rng& r, size_t i) { const Fr ri = r.next_fr(); memcpy(h_r + 32 * i, ri.l, 32); });
+  tm.lap("draws");
+  std::string key((const char*)pk.g2.data(), 128);
+  key.append((const char*)pk.g2_a.data(), 128).append((const char*)msk.g2_alpha.data(), 128);
+  const KeysArg ka{&pk, &msk};
+  const rhip_ghw11_keys* keys = (const rhip_ghw11_keys*)eng.aux("ghw11_keys", key, make_keys, &ka, destroy_keys, 4);
+  rhip_ctx* cx = eng.ctx();
+  DBuf d_r(&eng, n * 32), d_row_off = up32(eng, row_off), d_item_hash = up32(eng, item_hash), d_hash = up_bytes(eng, flatten_fr(hashes)),
+      d_out(&eng, total * 128 + 4);
+  eng.check(rhip_upload_async(cx, d_r.ptr(), h_r, n * 32), "upload");
+  eng.check(rhip_ghw11_keygen_batch(cx, keys, n, total, d_row_off.as<uint32_t>(), d_item_hash.as<uint32_t>(), d_hash.as<rhip_fr>(), d_r.as<rhip_fr>(),
+                                    d_out.as<rhip_g2>()), "rhip_ghw11_keygen_batch");
+  std::vector<RecordLayout> layouts(sets.size());
+  for (size_t s = 0; s < sets.size(); s++) {
+    RecordLayout& L = layouts[s];
+    L.src(0, 128, 128);          // k: row 1
+    L.src(0, 0, 128);            // l: row 0
+    L.u32((uint32_t)sets[s].size());
+    for (size_t y = 0; y < sets[s].size(); y++) { L.str(sets[s][y]); L.src(0, (uint32_t)(128 * (2 + y)), 128); }
+    if (L.bytes() != fixed[s]) throw RabeError("ghw11::keygen_packed: record layout and size disagree");
+  }
+  std::vector<uint64_t> src_off(n);
+  for (size_t i = 0; i < n; i++) src_off[i] = 128ull * row_off[i];
+  emit_plain_records(eng, layouts, n, item_set, {d_out.ptr()}, src_off, out_off, out_buf);
+  tm.lap("device: rows, records; one copy out");
+  return true;
+}
+
+// n calls of ghw11::tkgen (ghw11/mod.rs:156-178), one per Ghw11SecretKey record of an UNTRUSTED blob.  An item whose bounds are bad or whose
+// record does not parse fails alone (status -1, empty tk slot, zero rk) and draws nothing; every other item draws one z, in item order --
+// the membership verdicts of the decoded elements (unless trusted: canonical coordinates, on the twist, in the r-torsion; one batched pass
+// beside the multiplication) arrive later and do not change what is drawn: a non-member fails its item like a malformed record, its z is
+// spent.  z = 0 fails the call as tkgen's inverse().unwrap() does.  Every element times z^-1 is one row of rhip_g2_mul_rows (a four-way
+// split of z^-1 per item, one joint chain per row); tk record = the sk record with every element replaced, rk = z.
+bool tkgen_packed(Engine& eng, Rng& rng, size_t n, const uint8_t* sk_blob, size_t sk_len, const uint64_t* sk_off, bool trusted, int32_t* status,
+                  uint8_t* tk_buf, size_t tk_cap, uint64_t* tk_off, uint8_t* rk_buf, std::vector<std::string>* errors) {
+  Timer tm("ghw11::tkgen_packed");
+  Engine::ArenaScope arena(eng);
+  eng.scrub_when_done();          // z and z^-1 (the retrieve keys) pass through the staging buffers
+  errors->assign(n, "");
+  if (!sk_off || !tk_off || (n && (!sk_blob || !status || !rk_buf))) throw RabeError("ghw11::tkgen_packed: null input");
+  (void)check_offsets(n, sk_off, sk_len, errors);
+  std::vector<uint32_t> rows(n, 0);
+  parallel_for(n, [&](size_t i) {
+    if (!(*errors)[i].empty()) return;
+    try {
+      Cursor r{sk_blob + sk_off[i], sk_blob + sk_off[i + 1]};
+      (void)r.raw(256);
+      const uint32_t cnt = r.u32();
+      if ((size_t)cnt * 132 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
+      for (uint32_t y = 0; y < cnt; y++) { (void)r.str(); (void)r.raw(128); }
+      if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
+      rows[i] = 2 + cnt;
+    } catch (const std::exception& ex) {
+      (*errors)[i] = ex.what();
+      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
+    }
+  });
+  tm.lap("parse");
+  std::vector<size_t> live;
+  std::vector<uint32_t> row_off{0};
+  uint64_t span = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (!(*errors)[i].empty()) continue;
+    live.push_back(i);
+    const uint64_t next = (uint64_t)row_off.back() + rows[i];
+    if (next > 0xFFFFFFF0ull) throw RabeError("ghw11::tkgen_packed: more than 2^32 key elements in one call");
+    row_off.push_back((uint32_t)next);
+    span += sk_off[i + 1] - sk_off[i];
+  }
+  if (span && (!tk_buf || tk_cap < span)) {          // nothing drawn
+    tk_off[0] = 0;
+    for (size_t i = 0; i < n; i++) tk_off[i + 1] = tk_off[i] + ((*errors)[i].empty() ? sk_off[i + 1] - sk_off[i] : 0);
+    return false;
+  }
+  const size_t m = live.size(), total = row_off[m];
+  std::vector<uint8_t> good(m, 1);
+  uint8_t* h_out = nullptr;
+  std::vector<Fr> zs(m);
+  if (m) {
+    uint8_t* h_k = eng.pinned(0, m * 32 + 32);
+    {
+      struct Turn { Rng& r; explicit Turn(Rng& x) : r(x) { r.begin_draws(); } ~Turn() { r.end_draws(); } } turn(rng);
+      for (size_t j = 0; j < m; j++) {
+        zs[j] = rng.next_fr();
+        Fr zi;
+        if (!fr_inv(zs[j], &zi)) throw std::runtime_error("called `Option::unwrap()` on a `None` value (Fr::inverse of zero)");
+        memcpy(h_k + 32 * j, zi.l, 32);
+      }
+    }
+    tm.lap("draws + inversions");
+    uint8_t* h_p = eng.pinned(1, total * 128 + 4);
+    parallel_for(m, [&](size_t j) {
+      const uint8_t* rec = sk_blob + sk_off[live[j]];
+      uint8_t* o = h_p + 128 * (size_t)row_off[j];
+      memcpy(o, rec, 256);
+      const uint8_t* q = rec + 260;
+      for (uint32_t y = 2; y < rows[live[j]]; y++) {
+        q += 4 + get_u32(q);
+        memcpy(o + 128 * (size_t)y, q, 128);
+        q += 128;
+      }
+    });
+    tm.lap("pack");
+    rhip_ctx* cx = eng.ctx();
+    DBuf d_p(&eng, total * 128 + 4), d_k(&eng, m * 32), d_row_off = up32(eng, row_off), d_out(&eng, total * 128 + 4);
+    eng.check(rhip_upload_async(cx, d_p.ptr(), h_p, total * 128), "upload");
+    eng.check(rhip_upload_async(cx, d_k.ptr(), h_k, m * 32), "upload");
+    std::unique_ptr<MemberChecks> mc;
+    if (!trusted) {
+      mc.reset(new MemberChecks(eng));
+      mc->add(2, d_p.ptr(), total, d_row_off.as<uint32_t>(), m);
+    }
+    eng.check(rhip_g2_mul_rows(cx, total, d_row_off.as<uint32_t>(), d_p.as<rhip_g2>(), m, d_k.as<rhip_fr>(), d_out.as<rhip_g2>()), "rhip_g2_mul_rows");
+    h_out = eng.pinned(2, total * 128 + 4);
+    eng.check(rhip_download_async(cx, h_out, d_out.ptr(), total * 128), "download");
+    eng.check(rhip_sync(cx), "rhip_sync");
+    if (mc) {
+      mc->collect();
+      const auto& ok = mc->ok(0);
+      for (size_t j = 0; j < m; j++)
+        if (!ok[j]) { good[j] = 0; (*errors)[live[j]] = "deserialize: a key element is not a member of G2 (FieldError::NotMember)"; }
+    }
+    tm.lap(trusted ? "device + copies" : "device + copies, membership beside");
+  }
+  std::vector<size_t> slot(n, (size_t)-1);
+  for (size_t j = 0; j < m; j++) if (good[j]) slot[live[j]] = j;
+  tk_off[0] = 0;
+  for (size_t i = 0; i < n; i++) tk_off[i + 1] = tk_off[i] + (slot[i] != (size_t)-1 ? sk_off[i + 1] - sk_off[i] : 0);
+  parallel_for(n, [&](size_t i) {
+    uint8_t* rk = rk_buf + 32 * i;
+    if (slot[i] == (size_t)-1) { memset(rk, 0, 32); status[i] = -1; return; }
+    const size_t j = slot[i];
+    const uint8_t* rec = sk_blob + sk_off[i];
+    const uint8_t* src = h_out + 128 * (size_t)row_off[j];
+    uint8_t* w = tk_buf + tk_off[i];
+    memcpy(w, src, 256);
+    memcpy(w + 256, rec + 256, 4);
+    size_t at = 260;
+    for (uint32_t y = 2; y < rows[i]; y++) {
+      const size_t name = 4 + (size_t)get_u32(rec + at);
+      memcpy(w + at, rec + at, name);
+      at += name;
+      memcpy(w + at, src + 128 * (size_t)y, 128);
+      at += 128;
+    }
+    memcpy(rk, zs[j].l, 32);
+    status[i] = 0;
+  });
+  for (auto& z : zs) memset(z.l, 0, sizeof(z.l));
   tm.lap("assembly");
   return true;
 }

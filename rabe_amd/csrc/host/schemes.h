@@ -202,6 +202,12 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::
 // ciphertext records.  Returns false (pt_off[n] = the size needed) when pt_cap is too small.
 bool decrypt_out_packed(Engine& eng, const Ghw11RetrieveKey& rk, size_t n, const uint8_t* tct, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
                         bool trusted, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors);
+// bulk key issuing (packed.cpp): n keygen calls under one master key (records = Ghw11SecretKey; conventions of bsw::keygen_packed), and n
+// tkgen calls, one per secret-key record of an untrusted blob (tk records + 32-byte retrieve keys; false = tk_cap too small, nothing drawn)
+bool keygen_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw11MasterKey& msk, const std::vector<std::vector<std::string>>& sets, size_t n,
+                   const uint32_t* item_set, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
+bool tkgen_packed(Engine& eng, Rng& rng, size_t n, const uint8_t* sk_blob, size_t sk_len, const uint64_t* sk_off, bool trusted, int32_t* status,
+                  uint8_t* tk_buf, size_t tk_cap, uint64_t* tk_off, uint8_t* rk_buf, std::vector<std::string>* errors);
 Gt decrypt_out_gt(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11RetrieveKey& rk);
 Bytes decrypt_out(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11RetrieveKey& rk, const Bytes& data);
 }  // namespace ghw11

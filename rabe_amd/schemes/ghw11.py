@@ -103,3 +103,45 @@ def decrypt_out_packed(host, rk, tct, ct_blob, ct_off, trusted=False):
     host.call("rabe_ghw11_decrypt_out_packed", rk.ptr, ctypes.c_size_t(n), _np_ptr(t), _np_ptr(ct), ctypes.c_size_t(ct.size), _np_ptr(co),
               ctypes.c_uint32(PACKED_TRUSTED if trusted else 0), _np_ptr(status), _np_ptr(buf), ctypes.c_size_t(buf.size), _np_ptr(po))
     return buf[:int(po[n])], po, status[:n]
+
+
+def keygen_packed(host, pk, msk, attr_sets, item_set, out=None):
+    """n keys under one master key (rabe_ghw11_keygen_packed): attr_sets = distinct attribute lists, item_set[i] indexes them.
+    Returns (sk_blob: numpy uint8 view of the Ghw11SecretKey records, sk_off: numpy uint64 [n+1])."""
+    import numpy as np
+    from ..hostlib import _check, _np_ptr
+    n = len(item_set)
+    arr, _ = _strs([a for s_ in attr_sets for a in s_])
+    counts = (ctypes.c_size_t * max(len(attr_sets), 1))(*[len(s_) for s_ in attr_sets])
+    it = np.ascontiguousarray(item_set, dtype=np.uint32)
+    so = np.zeros(n + 1, dtype=np.uint64)
+    buf = out if out is not None else np.empty(0, dtype=np.uint8)
+    for _ in range(2):
+        rc = host.lib.rabe_ghw11_keygen_packed(host.h, pk.ptr, msk.ptr, arr, counts, ctypes.c_size_t(len(attr_sets)), ctypes.c_size_t(n), _np_ptr(it),
+                                               _np_ptr(buf), ctypes.c_size_t(buf.size), _np_ptr(so))
+        if rc != 1:
+            break
+        buf = np.empty(int(so[n]), dtype=np.uint8)
+    _check(rc, host.h)
+    return buf[:int(so[n])], so
+
+
+def tkgen_packed(host, sk_blob, sk_off, trusted=False):
+    """n tkgen calls, one per Ghw11SecretKey record of sk_blob (rabe_ghw11_tkgen_packed).  Returns (tk_blob view of the Ghw11TransformKey
+    records, tk_off uint64 [n+1], rk: numpy uint8 [n, 32] -- row i = the Ghw11RetrieveKey record z --, status int32 [n]); a failed item has
+    status -1, an empty tk slot and a zero rk row."""
+    import numpy as np
+    from ..hostlib import PACKED_TRUSTED, _as_u8, _np_ptr
+    n = len(sk_off) - 1
+    sk = _as_u8(sk_blob)
+    so = np.ascontiguousarray(sk_off, dtype=np.uint64)
+    to = np.zeros(n + 1, dtype=np.uint64)
+    rk = np.zeros((max(n, 1), 32), dtype=np.uint8)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    lo, hi = so[:-1], so[1:]
+    okm = (lo <= hi) & (hi <= sk.size)
+    need = int((hi[okm] - lo[okm]).sum()) if n else 0
+    buf = np.empty(max(need, 1), dtype=np.uint8)
+    host.call("rabe_ghw11_tkgen_packed", ctypes.c_size_t(n), _np_ptr(sk), ctypes.c_size_t(sk.size), _np_ptr(so),
+              ctypes.c_uint32(PACKED_TRUSTED if trusted else 0), _np_ptr(status), _np_ptr(buf), ctypes.c_size_t(buf.size), _np_ptr(to), _np_ptr(rk))
+    return buf[:int(to[n])], to, rk[:n], status[:n]

@@ -15,6 +15,7 @@ from rabe_amd.schemes import aw11, bdabe, bsw, ghw11, lsw, mke08  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--only", default="")
+ap.add_argument("--key-items", type=int, default=65536, help="keys per call of the GHW11 key-issuing leg (--only ghw11keys)")
 ap.add_argument("--rounds", type=int, default=2, help="timed repetitions per config: the first meets cold fixed-base tables of the key elements, later ones warm ones")
 args = ap.parse_args()
 B = args.batch
@@ -150,6 +151,73 @@ if args.only in ("", "ghw11"):
                           "transforms_per_s": round(n_items / t_tr[False], 1), "transforms_per_s_trusted": round(n_items / t_tr[True], 1),
                           "decrypt_outs_per_s": round(n_items / t_do[False], 1), "decrypt_outs_per_s_trusted": round(n_items / t_do[True], 1),
                           "chain_per_s": round(n_items / t_chain, 1), "seconds": round(t_tr[False], 4), "record_bytes": int(blob.size)}), flush=True)
+
+if args.only in ("", "ghw11keys"):
+    # GHW11 bulk key issuing: keygen_packed (fixed-base rows) and tkgen_packed (variable-base G2 rows, four-way split), and beside the
+    # latter the A/B of its kernel against rhip_g2_mul (the binary chain) on the same elements and scalars -- device-level calls on one
+    # Engine of this process, warm-up then best of three, timed around call + sync
+    import ctypes
+    import random
+    import numpy as np
+    from rabe_amd import Engine
+    R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+
+    def best3(fn):
+        fn()
+        best = None
+        for _ in range(3):
+            t0 = time.perf_counter()
+            r = fn()
+            dt = time.perf_counter() - t0
+            best = dt if best is None else min(best, dt)
+        return best, r
+
+    pk, msk = ghw11.setup(host)
+    eng = Engine(0)
+    n_keys = args.key_items
+    for n_attr in (50, 100):
+        attrs = ["g%03d" % i for i in range(n_attr)]          # names of one length: the records' elements sit at a fixed stride
+        t_kg, (sk_blob, sk_off) = best3(lambda: ghw11.keygen_packed(host, pk, msk, [attrs], [0] * n_keys))
+        t_tk, t_tk_tr = [best3(lambda: ghw11.tkgen_packed(host, sk_blob, sk_off, trusted=tr)) for tr in (False, True)]
+        tkb, to, rkz, st = t_tk[1]
+        assert not st.any()
+        # the first key through the object API's transform path: the records are usable
+        tk0 = hl.Obj.deserialize("ghw11_tk", bytes(tkb[:int(to[1])]), host=host)
+        ctb, cto = ghw11.encrypt_packed(host, pk, [nest(attrs)], [0], PT, [0, len(PT)])
+        tct, s1 = ghw11.transform_packed(host, tk0, ctb, cto)
+        pt, po, s2 = ghw11.decrypt_out_packed(host, hl.Obj.deserialize("ghw11_rk", rkz[0].tobytes()), tct, ctb, cto)
+        assert not s1.any() and not s2.any() and pt.tobytes() == PT
+        # kernel A/B on the elements of these keys: rows = every G2 element, item scalar = a random Fr (as z^-1 is)
+        rows = 2 + n_attr
+        rec = int(sk_off[1])
+        view = np.ascontiguousarray(sk_blob).reshape(n_keys, rec)
+        name = (rec - 260) // n_attr - 128
+        cols = [np.arange(0, 256)] + [260 + y * (name + 128) + name + np.arange(128) for y in range(n_attr)]
+        pts = np.ascontiguousarray(view[:, np.concatenate(cols)]).reshape(-1)
+        n_rows = n_keys * rows
+        ks = np.frombuffer(b"".join(random.randrange(1, R_ORDER).to_bytes(32, "little") for _ in range(n_keys)), dtype=np.uint8).reshape(n_keys, 32)
+        d_p, d_k = eng.upload(pts.tobytes()), eng.upload(ks.tobytes())
+        d_kk = eng.upload(np.repeat(ks, rows, axis=0).tobytes())
+        d_off = eng.upload((np.arange(n_keys + 1, dtype=np.uint32) * rows).tobytes())
+        d_a, d_b = eng.alloc(n_rows * 128), eng.alloc(n_rows * 128)
+
+        def run_rows():
+            eng._check(eng.lib.rhip_g2_mul_rows(eng.ctx, ctypes.c_size_t(n_rows), d_off.ptr, d_p.ptr, ctypes.c_size_t(n_keys), d_k.ptr, d_a.ptr))
+            eng.sync()
+
+        def run_binary():
+            eng._check(eng.lib.rhip_g2_mul(eng.ctx, ctypes.c_size_t(n_rows), d_p.ptr, d_kk.ptr, d_b.ptr))
+            eng.sync()
+        t_rows, _ = best3(run_rows)
+        t_bin, _ = best3(run_binary)
+        assert eng.download(d_a) == eng.download(d_b)
+        print(json.dumps({"config": "GHW11 key issuing, %d attributes: keygen_packed, tkgen_packed; k_g2_mul_rows against k_g2_mul on the same %d elements "
+                                    "and scalars" % (n_attr, n_rows), "batch": n_keys, "keygen_keys_per_s": round(n_keys / t_kg, 1),
+                          "tkgen_keys_per_s": round(n_keys / t_tk[0], 1), "tkgen_keys_per_s_trusted": round(n_keys / t_tk_tr[0], 1),
+                          "g2_mul_rows_elements_per_s": round(n_rows / t_rows, 1), "g2_mul_elements_per_s": round(n_rows / t_bin, 1),
+                          "g2_mul_rows_s": round(t_rows, 4), "g2_mul_s": round(t_bin, 4), "kernel_ratio": round(t_bin / t_rows, 3),
+                          "seconds": round(t_tk[0], 4), "record_bytes": int(sk_blob.size)}), flush=True)
+    eng.close()
 
 if args.only in ("", "dnf"):
     # 8f-4: the DNF schemes' decrypt (m + 3 pairings per item on one accumulator): a 3-conjunction policy, the key satisfies the last one
