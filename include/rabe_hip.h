@@ -148,6 +148,23 @@ int32_t rhip_g2_mul(rhip_ctx* ctx, size_t n, const rhip_g2* dev_p, const rhip_fr
  * point outside the r-torsion the result is NOT k * p -- rhip_g2_mul is the entry point for those. */
 int32_t rhip_g2_mul_rows(rhip_ctx* ctx, size_t n_rows, const uint32_t* dev_item_row_off /*[n_items+1]*/, const rhip_g2* dev_p /*[n_rows]*/,
                          size_t n_items, const rhip_fr* dev_k /*[n_items]*/, rhip_g2* dev_out /*[n_rows]*/);
+/* The same with a row index on both sides: out[row_dst[t]] = k[i] * p[row_src[t]].  A caller whose rows are ordered by scalar keeps each
+ * point once (row_src[t] < the number of points) and has the results written where its records want them (row_dst: a permutation of
+ * [0, n_rows); nothing is checked).  rhip_g2_mul_rows itself is unchanged. */
+int32_t rhip_g2_mul_rows_at(rhip_ctx* ctx, size_t n_rows, const uint32_t* dev_item_row_off /*[n_items+1]*/, const rhip_g2* dev_p,
+                            const uint32_t* dev_row_src /*[n_rows]*/, size_t n_items, const rhip_fr* dev_k /*[n_items]*/,
+                            const uint32_t* dev_row_dst /*[n_rows]*/, rhip_g2* dev_out /*[n_rows]*/);
+/* Variable-base G1 multiplication of rows that share scalars, the shape of rhip_g2_mul_rows: out[t] = k[i] * p[t] for the rows t of item i.
+ * What bdabe::request_attribute_sk / mke08::request_authority_sk do to a user's u1 (bdabe/mod.rs:275-305), one scalar per attribute against
+ * many users.  The GLV decomposition k = k1 + k2 lambda and the NAF masks of both halves are made once per item (k_glv_masks); every row
+ * runs one joint chain over P and phi(P) = (beta x, y) of ~130 doublings, and a block shares one field inversion (rhip_g1_mul: one
+ * decomposition and one inversion per element).  Any 256-bit scalar word is accepted (0 and multiples of r give infinity); infinity in,
+ * infinity out; the points must be on the curve.  Same bytes as rhip_g1_mul.  _at: out[row_dst[t]] = k[i] * p[row_src[t]], as above. */
+int32_t rhip_g1_mul_rows(rhip_ctx* ctx, size_t n_rows, const uint32_t* dev_item_row_off /*[n_items+1]*/, const rhip_g1* dev_p /*[n_rows]*/,
+                         size_t n_items, const rhip_fr* dev_k /*[n_items]*/, rhip_g1* dev_out /*[n_rows]*/);
+int32_t rhip_g1_mul_rows_at(rhip_ctx* ctx, size_t n_rows, const uint32_t* dev_item_row_off /*[n_items+1]*/, const rhip_g1* dev_p,
+                            const uint32_t* dev_row_src /*[n_rows]*/, size_t n_items, const rhip_fr* dev_k /*[n_items]*/,
+                            const uint32_t* dev_row_dst /*[n_rows]*/, rhip_g1* dev_out /*[n_rows]*/);
 /* the split alone, on the host (no GPU, no context; the code the kernel runs): mag[4 i .. 4 i + 4) = |k_i| as little-endian words,
  * neg[i] = 1 for a negative k_i */
 int32_t rhip_host_fr_split4(const rhip_fr* k, uint32_t mag[16], uint8_t neg[4]);
@@ -493,6 +510,16 @@ void rhip_ghw11_keys_destroy(rhip_ghw11_keys* keys);
 int32_t rhip_ghw11_keygen_batch(rhip_ctx* ctx, const rhip_ghw11_keys* keys, size_t n_items, size_t n_rows, const uint32_t* dev_item_row_off /*[n_items+1]*/,
                                 const uint32_t* dev_item_hash_off /*[n_items]*/, const rhip_fr* dev_hash, const rhip_fr* dev_r /*[n_items]*/,
                                 rhip_g2* dev_out /*[n_rows]*/);
+/* BDABE / MKE08 keygen (bdabe/mod.rs:201-222, mke08/mod.rs:185-206) for n_items users under one authority key (MKE08: the master key).
+ * rhip_dnf_keys: 8- and 16-bit window tables of p1, g1, p2, g2 and the authority's a1 / a2 (MKE08: msk.g1 / msk.g2).  Item i owns rows
+ * 2 i, 2 i + 1 of both outputs: out_g1 = sk.u1 = a1 + p1 * r_i, pk.u1 = g1 * r_i; out_g2 = sk.u2 = a2 + p2 * r_i, pk.u2 = g2 * r_i.
+ * One lane per element (k_dnf_keygen_g1, k_dnf_keygen_g2), one inversion per block, canonical wire form out. */
+typedef struct rhip_dnf_keys rhip_dnf_keys;
+int32_t rhip_dnf_keys_create(rhip_ctx* ctx, const rhip_g1* host_p1, const rhip_g1* host_g1, const rhip_g2* host_p2, const rhip_g2* host_g2,
+                             const rhip_g1* host_a1, const rhip_g2* host_a2, rhip_dnf_keys** out);
+void rhip_dnf_keys_destroy(rhip_dnf_keys* keys);
+int32_t rhip_dnf_keygen_batch(rhip_ctx* ctx, const rhip_dnf_keys* keys, size_t n_items, const rhip_fr* dev_r /*[n_items]*/,
+                              rhip_g1* dev_out_g1 /*[2 n_items]*/, rhip_g2* dev_out_g2 /*[2 n_items]*/);
 /* BDABE / MKE08 encrypt (bdabe/mod.rs:317-358, mke08/mod.rs:290-334).  Every group element of their ciphertexts is a fixed-base product
  * with the draw r of its row (one row per (item, DNF term)):  p1 * r, p2 * r (public key) and T1 * r, T2 * r, Tgt_g^r * msg_g with the
  * term's folded attribute keys T1 = sum a1_k (G1), T2 = sum a2_k (G2), Tgt_g = prod of the keys' Gt component g (BDABE: n_gt = 1, a3;

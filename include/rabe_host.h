@@ -371,6 +371,38 @@ int32_t rabe_mke08_encrypt_packed(rabe_host* h, const void* pk, const void* cons
                                   const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
                                   const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off,
                                   uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off);
+/* Bulk key issuing of the two schemes (conventions of rabe_ghw11_keygen_packed / rabe_ghw11_tkgen_packed).
+ * keygen_packed: n_items calls of keygen (bdabe/mod.rs:201-222, mke08/mod.rs:185-206) under one authority key (MKE08: the master key), item i
+ * for the user names[i].  Record i = rabe_obj_serialize's bytes of the user key with an empty sk_a: sk.u1 | sk.u2 | name | pk.u1 | pk.u2 | u32 0.
+ * Draw order: one r_u (mk_u) per item, in item order.  Every element is a fixed-base multiple (a1 + p1 r, a2 + p2 r, g1 r, g2 r): one lane per
+ * element over window tables of p1, g1, p2, g2 that are built once per key and kept; records are written on the device.  uk_off is always
+ * filled; returns 1, with nothing drawn, when uk_cap < uk_off[n_items]. */
+int32_t rabe_bdabe_keygen_packed(rabe_host* h, const void* pk, const void* ska, const char* const* names /*[n_items]*/, size_t n_items,
+                                 uint8_t* uk_buf, size_t uk_cap, uint64_t* uk_off /*[n_items+1]*/);
+int32_t rabe_mke08_keygen_packed(rabe_host* h, const void* pk, const void* msk, const char* const* names /*[n_items]*/, size_t n_items,
+                                 uint8_t* uk_buf, size_t uk_cap, uint64_t* uk_off /*[n_items+1]*/);
+/* Secret attribute keys in bulk: what n_items x (attributes of a list) calls of request_attribute_sk (bdabe/mod.rs:275-305) /
+ * request_authority_sk (mke08/mod.rs:248-278) give under one authority key.  Item i is a user's PUBLIC key record, name | u1 (64) | u2 (128) --
+ * the bytes of BdabePublicUserKey / Mke08PublicUserKey inside a user-key record -- and receives every attribute of the list item_set[i] (lists
+ * as in rabe_ghw11_keygen_packed: flat attributes, counts, n_sets; an empty list is allowed).  Output record i: u32 count, then count rows
+ * (attribute, au1 (64), au2 (128)) in list order -- byte for byte the sk_a tail of the user-key record, so keygen record[:-4] + this record
+ * is the object API's user key after the same calls.  Nothing is drawn.
+ * The blob is UNTRUSTED: an item with bad bounds, a malformed record or trailing bytes fails alone -- status[i] = -1, an empty output slot, the
+ * first error in rabe_host_last_error; unless RABE_PACKED_TRUSTED, u1 must be on the curve with canonical coordinates and u2 a member of G2
+ * (one batched pass beside the multiplications), and a non-member fails its item only.  With the flag a non-member is not rejected and its
+ * keys are unspecified.  Call-level errors, before any work and with no output: an attribute that is not from_authority() for this key (the
+ * object API's message and the index of its list), an item_set out of range, more than 2^32 rows.  Returns 1 when out_cap is below the total
+ * size of the well-formed items' records (out_off[n_items] = that size).
+ * exp = h(attribute) h(authority) a3 (MKE08: r) is formed once per (list, position) on the host; its rows -- the users of that list -- are
+ * adjacent in the launch (rhip_g1_mul_rows_at, rhip_g2_mul_rows_at), results land item-major and the records are written on the device. */
+int32_t rabe_bdabe_request_attribute_sk_packed(rabe_host* h, const void* ska, const char* const* attributes, const size_t* counts, size_t n_sets,
+                                               size_t n_items, const uint32_t* item_set /*[n_items]*/, const uint8_t* upk_blob, size_t upk_len,
+                                               const uint64_t* upk_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/,
+                                               uint8_t* out_buf, size_t out_cap, uint64_t* out_off /*[n_items+1]*/);
+int32_t rabe_mke08_request_authority_sk_packed(rabe_host* h, const void* ska, const char* const* attributes, const size_t* counts, size_t n_sets,
+                                               size_t n_items, const uint32_t* item_set /*[n_items]*/, const uint8_t* upk_blob, size_t upk_len,
+                                               const uint64_t* upk_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/,
+                                               uint8_t* out_buf, size_t out_cap, uint64_t* out_off /*[n_items+1]*/);
 int32_t rabe_mke08_setup(rabe_host* h, void** pk, void** msk);
 int32_t rabe_mke08_keygen(rabe_host* h, const void* pk, const void* msk, const char* name, void** uk);
 int32_t rabe_mke08_authgen(rabe_host* h, const char* name, void** ska);

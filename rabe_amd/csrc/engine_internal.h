@@ -47,7 +47,7 @@ struct rhip_ctx {
   void* fe_ws = nullptr;
   size_t fe_ws_bytes = 0;
   // grow-only work arenas of the job kernels (engine_jobs.hip: pair lists, running G2 points, scalars)
-  enum { N_WORK = 18 };          // 16, 17: the masks and the point images of rhip_g2_mul_rows (engine_keys.hip); 15: the table pointers of a DNF encrypt that spans several term sets (engine_jobs.hip: rhip_dnf_encrypt_batch); 12, 13: the cross-check mode's second result buffer and its snapshot of an in-place factor (engine_jobs.hip); 14: the two-lane Miller kernel's workspace (its own slot: in the cross-check mode it alternates with the one-lane kernel's, and a grow-only slot shared by two sizes would be re-allocated -- a device-wide hipFree -- on every launch)
+  enum { N_WORK = 19 };          // 18: the masks of rhip_g1_mul_rows (engine_keys.hip); 16, 17: the masks and the point images of rhip_g2_mul_rows (engine_keys.hip); 15: the table pointers of a DNF encrypt that spans several term sets (engine_jobs.hip: rhip_dnf_encrypt_batch); 12, 13: the cross-check mode's second result buffer and its snapshot of an in-place factor (engine_jobs.hip); 14: the two-lane Miller kernel's workspace (its own slot: in the cross-check mode it alternates with the one-lane kernel's, and a grow-only slot shared by two sizes would be re-allocated -- a device-wide hipFree -- on every launch)
   void* work[N_WORK] = {};
   size_t work_bytes[N_WORK] = {};
   // optional per-kernel timing (HIP events on the launch stream), for bench.py's roofline leg

@@ -1,5 +1,7 @@
 // engine_keys.hip -- bulk key issuing: the GHW11 keygen row kernel (fixed-base) and the variable-base G2 multiplication over rows that
-// share a scalar (four-way split over the twist endomorphism, bn254/gls4.h), which serves ghw11::tkgen.
+// share a scalar (four-way split over the twist endomorphism, bn254/gls4.h), which serves ghw11::tkgen; the user-key row kernels of
+// BDABE / MKE08 (fixed-base) and the variable-base G1 multiplication over rows that share a scalar (GLV, bn254/curve.h), which with the G2
+// one serves their secret attribute keys.
 //
 // A translation unit of its own: docs/rr29.md records that adding a kernel to a unit can move its neighbours' register allocation, and
 // engine_jobs.hip holds the kernels BASELINE configs 3 - 5 time.
@@ -181,5 +183,230 @@ extern "C" int32_t rhip_host_fr_split4(const rhip_fr* k, uint32_t mag[16], uint8
     for (int w = 0; w < 4; w++) mag[4 * i + w] = m[i][w];
     neg_[i] = sg[i] ? 1 : 0;
   }
+  return RHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ the same with a row index on both sides
+// out[row_dst[t]] = k[item of t] * p[row_src[t]]: the rows of a call are ordered by scalar (the digit tests of a wave stay uniform) while
+// the points are stored once per owner and the results land where the record writer wants them (each owner's rows adjacent).  The body of
+// k_g2_mul_rows, repeated so that kernel's code object does not change.
+__global__ void __launch_bounds__(128, RB_G2_WAVES) k_g2_mul_rows_at(size_t row0, size_t cnt, size_t n_items, const uint32_t* item_row_off, const rhip_g2* p,
+                                                                    const uint32_t* row_src, const uint32_t* masks, G2M* img, size_t stride,
+                                                                    const uint32_t* row_dst, rhip_g2* out) {
+  __shared__ uint32_t sh[2 * 8 * 128];
+  const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = lane < cnt;
+  const size_t t = row0 + (active ? lane : cnt - 1);
+  const size_t item = owner_of(item_row_off, n_items, t);
+  {
+    const G2Aff P = load_g2(p[row_src[t]].l);
+    const G2Aff P2 = g2_frob2(P);
+    st_g2_q(img + lane, P);
+    st_g2_q(img + stride + lane, g2_frob1(P));
+    st_g2_q(img + 2 * stride + lane, P2);
+    st_g2_q(img + 3 * stride + lane, g2_frob1(P2));
+  }
+  const G2Jac acc = gls4_chain(Gls4Bases{img + lane, stride}, masks + 24 * item);
+  store_g2_block128(sh, active, out + row_dst[t], acc);
+}
+extern "C" int32_t rhip_g2_mul_rows_at(rhip_ctx* ctx, size_t n_rows, const uint32_t* item_row_off, const rhip_g2* p, const uint32_t* row_src, size_t n_items,
+                                       const rhip_fr* k, const uint32_t* row_dst, rhip_g2* out) {
+  NEED(ctx);
+  if (!n_rows) return RHIP_OK;
+  if (!n_items || !item_row_off || !p || !row_src || !k || !row_dst || !out) return RHIP_ERR_ARG;
+  void* masks = nullptr;
+  void* img = nullptr;
+  int32_t rc = rhip_ensure_work(ctx, 16, n_items * 24 * sizeof(uint32_t), &masks);
+  if (rc) return rc;
+  const size_t stride = ((n_rows < RB_G2_ROWS_CHUNK ? n_rows : RB_G2_ROWS_CHUNK) + 127) / 128 * 128;
+  rc = rhip_ensure_work(ctx, 17, stride * 4 * sizeof(G2M), &img);
+  if (rc) return rc;
+  KLAUNCH(ctx, "k_gls4_masks", k_gls4_masks, dim3(blocks_for(n_items, 256)), dim3(256), 0, ctx->stream, n_items, k, (uint32_t*)masks);
+  for (size_t row0 = 0; row0 < n_rows; row0 += RB_G2_ROWS_CHUNK) {
+    const size_t cnt = n_rows - row0 < RB_G2_ROWS_CHUNK ? n_rows - row0 : RB_G2_ROWS_CHUNK;
+    KLAUNCH(ctx, "k_g2_mul_rows_at", k_g2_mul_rows_at, dim3(blocks_for(cnt, 128)), dim3(128), 0, ctx->stream, row0, cnt, n_items, item_row_off, p, row_src,
+            (const uint32_t*)masks, (G2M*)img, stride, row_dst, out);
+  }
+  return RHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ variable-base G1, rows sharing a scalar
+// GLV (bn254/curve.h: k = k1 + k2 lambda, |k1|, |k2| < 2^130) with the decomposition and the NAF masks made once per scalar:
+// masks[20 i ..] = pos1[5], neg1[5], pos2[5], neg2[5], the signs of k1 / k2 folded in (a negative half swaps its two masks).
+#define RB_GLV_MASK_WORDS 20
+__global__ void __launch_bounds__(256, RB_MIN_WAVES) k_glv_masks(size_t n, const rhip_fr* k, uint32_t* masks) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t kk[8], k1[8], k2[8], p1[8], n1[8], p2[8], n2[8];
+  bool neg1, neg2;
+  ld_scalar(kk, k + i);
+  glv_decompose(kk, k1, neg1, k2, neg2);
+  naf_masks(k1, p1, n1);
+  naf_masks(k2, p2, n2);
+  uint32_t* m = masks + RB_GLV_MASK_WORDS * i;
+#pragma unroll
+  for (int w = 0; w < 5; w++) {
+    m[w] = neg1 ? n1[w] : p1[w];
+    m[5 + w] = neg1 ? p1[w] : n1[w];
+    m[10 + w] = neg2 ? n2[w] : p2[w];
+    m[15 + w] = neg2 ? p2[w] : n2[w];
+  }
+}
+// the joint chain of jac_mul_glv_g1 over P and phi(P) = (beta x, y), digits read from the scalar's masks: ~130 doublings + ~86 mixed additions.
+// g1_madd_inl handles an infinite accumulator and the doubling / cancelling cases (k = 1, 2, lambda +- 1, ...); infinity in, infinity out.
+__device__ __forceinline__ G1Jac glv_chain_rows(const G1Aff& base, const uint32_t* m) {
+  G1Jac acc = jac_inf<Fp>();
+  if (aff_is_inf(base)) return acc;
+  constexpr uint32_t BETA[8] = RB_GLV_BETA;
+  Fp beta;
+#pragma unroll
+  for (int i = 0; i < 8; i++) beta.v[i] = BETA[i];
+  const Fp bx = mul(base.x, beta);
+  bool started = false;
+#pragma unroll 1
+  for (int w = 4; w >= 0; w--) {
+    const uint32_t pw1 = m[w], nw1 = m[5 + w], pw2 = m[10 + w], nw2 = m[15 + w];
+    if (!started && !(pw1 | nw1 | pw2 | nw2)) continue;
+#pragma unroll 1
+    for (int b = 31; b >= 0; b--) {
+      if (started) acc = g1_dbl_inl(acc);
+      const uint32_t d1p = (pw1 >> b) & 1u, d1n = (nw1 >> b) & 1u, d2p = (pw2 >> b) & 1u, d2n = (nw2 >> b) & 1u;
+      if (d1p | d1n) {
+        acc = g1_madd_inl(acc, G1Aff{base.x, d1n ? neg(base.y) : base.y});
+        started = true;
+      }
+      if (d2p | d2n) {
+        acc = g1_madd_inl(acc, G1Aff{bx, d2n ? neg(base.y) : base.y});
+        started = true;
+      }
+    }
+  }
+  return acc;
+}
+// one lane per row: out[row_dst ? row_dst[t] : t] = k[item of t] * p[row_src ? row_src[t] : t].  The masks are read through the item index,
+// so the digit tests are uniform wherever a wave holds rows of one item.  One inversion per block; lanes past n_rows shadow the last row.
+__global__ void __launch_bounds__(256, RB_G1_WAVES) k_g1_mul_rows(size_t n_rows, size_t n_items, const uint32_t* item_row_off, const rhip_g1* p,
+                                                                 const uint32_t* row_src, const uint32_t* masks, const uint32_t* row_dst, rhip_g1* out) {
+  __shared__ uint32_t lds[2 * 8 * 256];
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = t < n_rows;
+  if (!active) t = n_rows - 1;
+  const size_t item = owner_of(item_row_off, n_items, t);
+  const G1Jac r = glv_chain_rows(load_g1(p[row_src ? row_src[t] : t].l), masks + RB_GLV_MASK_WORDS * item);
+  const bool inf = !active || jac_is_inf(r);
+  const Fp zinv = block_batch_inverse_n<256>(lds, inf ? one<FpParams>() : r.z);
+  if (!active) return;
+  store_g1(out[row_dst ? row_dst[t] : t].l, inf ? aff_inf<Fp>() : jac_to_aff_with_zinv(r, zinv));
+}
+static int32_t g1_mul_rows(rhip_ctx* ctx, size_t n_rows, const uint32_t* item_row_off, const rhip_g1* p, const uint32_t* row_src, size_t n_items,
+                           const rhip_fr* k, const uint32_t* row_dst, rhip_g1* out) {
+  void* masks = nullptr;
+  const int32_t rc = rhip_ensure_work(ctx, 18, n_items * RB_GLV_MASK_WORDS * sizeof(uint32_t), &masks);
+  if (rc) return rc;
+  KLAUNCH(ctx, "k_glv_masks", k_glv_masks, dim3(blocks_for(n_items, 256)), dim3(256), 0, ctx->stream, n_items, k, (uint32_t*)masks);
+  KLAUNCH(ctx, "k_g1_mul_rows", k_g1_mul_rows, dim3(blocks_for(n_rows, 256)), dim3(256), 0, ctx->stream, n_rows, n_items, item_row_off, p, row_src,
+          (const uint32_t*)masks, row_dst, out);
+  return RHIP_OK;
+}
+extern "C" int32_t rhip_g1_mul_rows(rhip_ctx* ctx, size_t n_rows, const uint32_t* item_row_off, const rhip_g1* p, size_t n_items, const rhip_fr* k,
+                                    rhip_g1* out) {
+  NEED(ctx);
+  if (!n_rows) return RHIP_OK;
+  if (!n_items || !item_row_off || !p || !k || !out) return RHIP_ERR_ARG;
+  return g1_mul_rows(ctx, n_rows, item_row_off, p, nullptr, n_items, k, nullptr, out);
+}
+extern "C" int32_t rhip_g1_mul_rows_at(rhip_ctx* ctx, size_t n_rows, const uint32_t* item_row_off, const rhip_g1* p, const uint32_t* row_src, size_t n_items,
+                                       const rhip_fr* k, const uint32_t* row_dst, rhip_g1* out) {
+  NEED(ctx);
+  if (!n_rows) return RHIP_OK;
+  if (!n_items || !item_row_off || !p || !row_src || !k || !row_dst || !out) return RHIP_ERR_ARG;
+  return g1_mul_rows(ctx, n_rows, item_row_off, p, row_src, n_items, k, row_dst, out);
+}
+
+// ------------------------------------------------------------------------------------------------ BDABE / MKE08 user keys
+struct rhip_dnf_keys {
+  rhip_ctx* ctx;
+  rhip_g1_table* p1;
+  rhip_g1_table* g1;
+  rhip_g2_table* p2;
+  rhip_g2_table* g2;
+  rhip_g1* a1;          // device, wire form: the authority's a1 (MKE08: msk.g1)
+  rhip_g2* a2;
+};
+extern "C" void rhip_dnf_keys_destroy(rhip_dnf_keys* k) {
+  if (!k) return;
+  rhip_g1_table_destroy(k->p1);
+  rhip_g1_table_destroy(k->g1);
+  rhip_g2_table_destroy(k->p2);
+  rhip_g2_table_destroy(k->g2);
+  if (k->a1) (void)hipFree(k->a1);
+  if (k->a2) (void)hipFree(k->a2);
+  delete k;
+}
+extern "C" int32_t rhip_dnf_keys_create(rhip_ctx* ctx, const rhip_g1* p1, const rhip_g1* g1, const rhip_g2* p2, const rhip_g2* g2, const rhip_g1* a1,
+                                        const rhip_g2* a2, rhip_dnf_keys** out) {
+  if (!ctx || !p1 || !g1 || !p2 || !g2 || !a1 || !a2 || !out) return RHIP_ERR_ARG;
+  *out = nullptr;
+  rhip_dnf_keys* k = new rhip_dnf_keys{ctx, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int32_t rc = rhip_g1_table_create(ctx, p1, &k->p1);
+  if (!rc) rc = rhip_g1_table_add_w16(ctx, k->p1);
+  if (!rc) rc = rhip_g1_table_create(ctx, g1, &k->g1);
+  if (!rc) rc = rhip_g1_table_add_w16(ctx, k->g1);
+  if (!rc) rc = rhip_g2_table_create(ctx, p2, &k->p2);
+  if (!rc) rc = rhip_g2_table_add_w16(ctx, k->p2);
+  if (!rc) rc = rhip_g2_table_create(ctx, g2, &k->g2);
+  if (!rc) rc = rhip_g2_table_add_w16(ctx, k->g2);
+  if (!rc) {
+    hipError_t he = hipMalloc((void**)&k->a1, sizeof(rhip_g1));
+    if (he == hipSuccess) he = hipMemcpy(k->a1, a1, sizeof(rhip_g1), hipMemcpyHostToDevice);
+    if (he == hipSuccess) he = hipMalloc((void**)&k->a2, sizeof(rhip_g2));
+    if (he == hipSuccess) he = hipMemcpy(k->a2, a2, sizeof(rhip_g2), hipMemcpyHostToDevice);
+    if (he != hipSuccess) rc = fail(ctx, he, "rhip_dnf_keys_create");
+  }
+  if (rc) { rhip_dnf_keys_destroy(k); return rc; }
+  *out = k;
+  return RHIP_OK;
+}
+// one lane per key element (bdabe/mod.rs:201-222, mke08/mod.rs:185-206); item i owns rows 2 i, 2 i + 1 of each group:
+//   row 2 i:     sk.u1 = a1 + p1 * r_i     (G2: sk.u2 = a2 + p2 * r_i)
+//   row 2 i + 1: pk.u1 = g1 * r_i          (G2: pk.u2 = g2 * r_i)
+// Every element is one walk over the 16-bit windows of its base; one inversion per block.
+__global__ void __launch_bounds__(256, RB_G1_WAVES) k_dnf_keygen_g1(const G1M* p1_tbl, const G1M* g1_tbl, const rhip_g1* a1, size_t n_rows, const rhip_fr* r,
+                                                                   rhip_g1* out) {
+  __shared__ uint32_t lds[2 * 8 * 256];
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = t < n_rows;
+  if (!active) t = n_rows - 1;
+  uint32_t kk[8];
+  ld_scalar(kk, r + (t >> 1));
+  G1Jac acc = table_mul_g1_w16((t & 1) ? g1_tbl : p1_tbl, kk);
+  if (!(t & 1)) acc = g1_madd_inl(acc, load_g1(a1->l));
+  const bool inf = !active || jac_is_inf(acc);
+  const Fp zinv = block_batch_inverse_n<256>(lds, inf ? one<FpParams>() : acc.z);
+  if (!active) return;
+  store_g1(out[t].l, inf ? aff_inf<Fp>() : jac_to_aff_with_zinv(acc, zinv));
+}
+__global__ void __launch_bounds__(128, RB_G2_WAVES) k_dnf_keygen_g2(const G2M* p2_tbl, const G2M* g2_tbl, const rhip_g2* a2, size_t n_rows, const rhip_fr* r,
+                                                                   rhip_g2* out) {
+  __shared__ uint32_t sh[2 * 8 * 128];
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = t < n_rows;
+  if (!active) t = n_rows - 1;
+  uint32_t kk[8];
+  ld_scalar(kk, r + (t >> 1));
+  G2Jac a = table_mul_g2_w16((t & 1) ? g2_tbl : p2_tbl, kk);
+  if (!(t & 1)) a = jac_add_aff(a, load_g2(a2->l));
+  store_g2_block128(sh, active, out + t, a);
+}
+extern "C" int32_t rhip_dnf_keygen_batch(rhip_ctx* ctx, const rhip_dnf_keys* keys, size_t n_items, const rhip_fr* r, rhip_g1* out_g1, rhip_g2* out_g2) {
+  NEED(ctx);
+  if (!keys) return RHIP_ERR_ARG;
+  if (!n_items) return RHIP_OK;
+  if (!r || !out_g1 || !out_g2) return RHIP_ERR_ARG;
+  const size_t n_rows = 2 * n_items;
+  KLAUNCH(ctx, "k_dnf_keygen_g1", k_dnf_keygen_g1, dim3(blocks_for(n_rows, 256)), dim3(256), 0, ctx->stream, (const G1M*)keys->p1->dev16,
+          (const G1M*)keys->g1->dev16, (const rhip_g1*)keys->a1, n_rows, r, out_g1);
+  KLAUNCH(ctx, "k_dnf_keygen_g2", k_dnf_keygen_g2, dim3(blocks_for(n_rows, 128)), dim3(128), 0, ctx->stream, (const G2M*)keys->p2->dev16,
+          (const G2M*)keys->g2->dev16, (const rhip_g2*)keys->a2, n_rows, r, out_g2);
   return RHIP_OK;
 }

@@ -1690,6 +1690,52 @@ int32_t rabe_mke08_encrypt_packed(rabe_host* h, const void* pk, const void* cons
   }, ct_buf, ct_cap, ct_off) ? 0 : 1;
   GUARD_END(h)
 }
+// attribute lists of a bulk call: flat names + per-list counts (as rabe_ghw11_keygen_packed)
+static std::vector<std::vector<std::string>> attr_sets(const char* const* attributes, const size_t* counts, size_t n_sets) {
+  std::vector<std::vector<std::string>> sets(n_sets);
+  size_t at = 0;
+  for (size_t s = 0; s < n_sets; s++)
+    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
+  return sets;
+}
+int32_t rabe_bdabe_keygen_packed(rabe_host* h, const void* pk, const void* ska, const char* const* names, size_t n_items, uint8_t* uk_buf, size_t uk_cap,
+                                 uint64_t* uk_off) {
+  GUARD_BEGIN
+  return bdabe::keygen_packed(h->eng, h->rng(), *(const bdabe::BdabePublicKey*)pk, *(const bdabe::BdabeSecretAuthorityKey*)ska, strs(names, n_items), uk_buf,
+                              uk_cap, uk_off) ? 0 : 1;
+  GUARD_END(h)
+}
+int32_t rabe_mke08_keygen_packed(rabe_host* h, const void* pk, const void* msk, const char* const* names, size_t n_items, uint8_t* uk_buf, size_t uk_cap,
+                                 uint64_t* uk_off) {
+  GUARD_BEGIN
+  return mke08::keygen_packed(h->eng, h->rng(), *(const mke08::Mke08PublicKey*)pk, *(const mke08::Mke08MasterKey*)msk, strs(names, n_items), uk_buf, uk_cap,
+                              uk_off) ? 0 : 1;
+  GUARD_END(h)
+}
+int32_t rabe_bdabe_request_attribute_sk_packed(rabe_host* h, const void* ska, const char* const* attributes, const size_t* counts, size_t n_sets,
+                                               size_t n_items, const uint32_t* item_set, const uint8_t* upk_blob, size_t upk_len, const uint64_t* upk_off,
+                                               uint32_t flags, int32_t* status, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  if (!bdabe::request_attribute_sk_packed(h->eng, *(const bdabe::BdabeSecretAuthorityKey*)ska, attr_sets(attributes, counts, n_sets), n_items, item_set,
+                                          upk_blob, upk_len, upk_off, (flags & RABE_PACKED_TRUSTED) != 0, status, out_buf, out_cap, out_off, &errors))
+    return 1;
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
+int32_t rabe_mke08_request_authority_sk_packed(rabe_host* h, const void* ska, const char* const* attributes, const size_t* counts, size_t n_sets,
+                                               size_t n_items, const uint32_t* item_set, const uint8_t* upk_blob, size_t upk_len, const uint64_t* upk_off,
+                                               uint32_t flags, int32_t* status, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  if (!mke08::request_authority_sk_packed(h->eng, *(const mke08::Mke08SecretAuthorityKey*)ska, attr_sets(attributes, counts, n_sets), n_items, item_set,
+                                          upk_blob, upk_len, upk_off, (flags & RABE_PACKED_TRUSTED) != 0, status, out_buf, out_cap, out_off, &errors))
+    return 1;
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
 int32_t rabe_mke08_setup(rabe_host* h, void** pk, void** msk) {
   GUARD_BEGIN
   auto r = mke08::setup(h->eng, h->rng());

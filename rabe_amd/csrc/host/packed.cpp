@@ -2515,6 +2515,232 @@ bool encrypt_packed(Engine& eng, Rng& rng, const DnfScheme& sc, const G1& p1, co
   tm.lap("device: group arithmetic, records, sealing; one copy out");
   return true;
 }
+
+// ------------------------------------------------------------------------------------------------ BDABE / MKE08 bulk key issuing
+struct KeysArg { const G1* p1; const G1* g1; const G2* p2; const G2* g2; const G1* a1; const G2* a2; };
+void* make_keys(Engine& eng, const void* arg) {
+  const KeysArg& a = *(const KeysArg*)arg;
+  rhip_dnf_keys* d = nullptr;
+  eng.check(rhip_dnf_keys_create(eng.ctx(), (const rhip_g1*)a.p1->data(), (const rhip_g1*)a.g1->data(), (const rhip_g2*)a.p2->data(),
+                                 (const rhip_g2*)a.g2->data(), (const rhip_g1*)a.a1->data(), (const rhip_g2*)a.a2->data(), &d), "rhip_dnf_keys_create");
+  return d;
+}
+void destroy_keys(void* h) { rhip_dnf_keys_destroy((rhip_dnf_keys*)h); }
+
+// n calls of bdabe::keygen (bdabe/mod.rs:201-222) or mke08::keygen (mke08/mod.rs:185-206) under one authority key (a1, a2; MKE08: the master
+// key's g1, g2).  Draw order: one r_u per item, in item order.  Record = the user key with an empty sk_a: sk.u1 | sk.u2 | name | pk.u1 | pk.u2 |
+// u32 0.  Every element is a fixed-base multiple (a1 + p1 r, a2 + p2 r, g1 r, g2 r): one lane per element over the 16-bit window tables of
+// p1, g1, p2, g2 (k_dnf_keygen_g1 / _g2; tables built once per key and kept), records written on the device -- the names are a device
+// source of their own, one layout per distinct name length.
+bool keygen_packed(Engine& eng, Rng& rng, const char* what, const G1& p1, const G1& g1, const G2& p2, const G2& g2, const G1& a1, const G2& a2,
+                   const std::vector<std::string>& names, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  Timer tm(what);
+  Engine::ArenaScope arena(eng);
+  eng.scrub_when_done();          // the keys' r_u pass through the staging buffers
+  const size_t n = names.size();
+  if (!out_off) throw RabeError(std::string(what) + ": null input");
+  std::map<size_t, uint32_t> layout_of;          // name length -> layout
+  std::vector<uint32_t> item_layout(n);
+  std::vector<uint64_t> name_off(n);
+  std::vector<uint8_t> name_bytes;
+  out_off[0] = 0;
+  for (size_t i = 0; i < n; i++) {
+    const size_t len = names[i].size();
+    if (len >= ((size_t)1 << 24)) throw RabeError(std::string(what) + ": a user name of 2^24 bytes or more");
+    auto it = layout_of.find(len);
+    if (it == layout_of.end()) it = layout_of.emplace(len, (uint32_t)layout_of.size()).first;
+    item_layout[i] = it->second;
+    name_off[i] = name_bytes.size();
+    name_bytes.insert(name_bytes.end(), names[i].begin(), names[i].end());
+    out_off[i + 1] = out_off[i] + 64 + 128 + 4 + len + 64 + 128 + 4;
+  }
+  if (n && (!out_buf || out_cap < out_off[n])) return false;
+  if (!n) return true;
+  std::vector<RecordLayout> layouts(layout_of.size());
+  for (const auto& kv : layout_of) {
+    RecordLayout& L = layouts[kv.second];
+    L.src(0, 0, 64);             // sk.u1: G1 row 0
+    L.src(1, 0, 128);            // sk.u2: G2 row 0
+    L.u32((uint32_t)kv.first);
+    if (kv.first) L.src(2, 0, (uint32_t)kv.first);
+    L.src(0, 64, 64);            // pk.u1: G1 row 1
+    L.src(1, 128, 128);          // pk.u2: G2 row 1
+    L.u32(0);                    // sk_a: empty
+  }
+  uint8_t* h_r = eng.pinned(0, n * 32 + 32);
+  draw_items(rng, n, [&](Rng& r, size_t i) { const Fr ri = r.next_fr(); memcpy(h_r + 32 * i, ri.l, 32); });
+  tm.lap("draws");
+  std::string key((const char*)p1.data(), 64);
+  key.append((const char*)g1.data(), 64).append((const char*)p2.data(), 128).append((const char*)g2.data(), 128).append((const char*)a1.data(), 64)
+      .append((const char*)a2.data(), 128);
+  const KeysArg ka{&p1, &g1, &p2, &g2, &a1, &a2};
+  const rhip_dnf_keys* keys = (const rhip_dnf_keys*)eng.aux("dnf_keys", key, make_keys, &ka, destroy_keys, 4);
+  tm.lap("tables");
+  rhip_ctx* cx = eng.ctx();
+  DBuf d_r(&eng, n * 32), d_g1(&eng, n * 128 + 4), d_g2(&eng, n * 256 + 4), d_names = up_bytes(eng, name_bytes);
+  eng.check(rhip_upload_async(cx, d_r.ptr(), h_r, n * 32), "upload");
+  eng.check(rhip_dnf_keygen_batch(cx, keys, n, d_r.as<rhip_fr>(), d_g1.as<rhip_g1>(), d_g2.as<rhip_g2>()), "rhip_dnf_keygen_batch");
+  std::vector<uint64_t> src_off(3 * n);
+  for (size_t i = 0; i < n; i++) { src_off[i] = 128ull * i; src_off[n + i] = 256ull * i; src_off[2 * n + i] = name_off[i]; }
+  emit_plain_records(eng, layouts, n, item_layout.data(), {d_g1.ptr(), d_g2.ptr(), d_names.ptr()}, src_off, out_off, out_buf);
+  tm.lap("device: rows, records; one copy out");
+  return true;
+}
+
+// For every public user key record (name | u1 | u2) of an UNTRUSTED blob the secret attribute keys (attribute, u1 * exp, u2 * exp) of the list
+// sets[item_set[i]], exp = h(attribute) h(authority) secret (bdabe/mod.rs:275-305, mke08/mod.rs:248-278).  Nothing is drawn.  An attribute
+// that is not this authority's fails the call before any work, as does an item_set out of range; an item with bad bounds, a malformed
+// record or (unless trusted) a u1 off the curve / a u2 outside G2 fails alone.  Record = u32 count + rows (attribute, au1, au2): the sk_a
+// tail of the user-key record.  The multiplications run scalar-major -- one scalar per (list, position), its rows = the users of that
+// list (rhip_g1_mul_rows_at, rhip_g2_mul_rows_at) -- and write item-major through the row index, where the record writer reads them.
+bool request_sk_packed(Engine& eng, const char* what, const std::string& authority, const Fr& secret, const std::vector<std::vector<std::string>>& sets,
+                       size_t n, const uint32_t* item_set, const uint8_t* blob, size_t blob_len, const uint64_t* in_off, bool trusted, int32_t* status,
+                       uint8_t* out_buf, size_t out_cap, uint64_t* out_off, std::vector<std::string>* errors) {
+  Timer tm(what);
+  Engine::ArenaScope arena(eng);
+  eng.scrub_when_done();          // the attribute exponents pass through the staging buffers
+  errors->assign(n, "");
+  if (!in_off || !out_off || (n && (!item_set || !status || !blob))) throw RabeError(std::string(what) + ": null input");
+  for (size_t s = 0; s < sets.size(); s++)
+    for (const auto& a : sets[s])
+      if (!from_authority(a, authority))
+        throw RabeError("attribute " + a + " is not from_authority() or !is_eligible() (attribute list " + std::to_string(s) + ")");
+  uint64_t all_rows = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (item_set[i] >= sets.size()) throw RabeError(std::string(what) + ": item_set out of range");
+    all_rows += sets[item_set[i]].size();
+    if (all_rows > 0xFFFFFFF0ull) throw RabeError(std::string(what) + ": more than 2^32 key elements in one call");
+  }
+  std::vector<size_t> fixed(sets.size());
+  std::vector<uint32_t> scal_base(sets.size() + 1, 0);
+  for (size_t s = 0; s < sets.size(); s++) {
+    fixed[s] = 4;
+    for (const auto& a : sets[s]) fixed[s] += 4 + a.size() + 64 + 128;
+    scal_base[s + 1] = scal_base[s] + (uint32_t)sets[s].size();
+  }
+  (void)check_offsets(n, in_off, blob_len, errors);
+  parallel_for(n, [&](size_t i) {
+    if (!(*errors)[i].empty()) return;
+    try {
+      Cursor r{blob + in_off[i], blob + in_off[i + 1]};
+      (void)r.str();
+      (void)r.raw(64 + 128);
+      if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
+    } catch (const std::exception& ex) {
+      (*errors)[i] = ex.what();
+      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
+    }
+  });
+  tm.lap("parse");
+  std::vector<size_t> live;
+  out_off[0] = 0;
+  for (size_t i = 0; i < n; i++) {
+    const bool ok = (*errors)[i].empty();
+    if (ok) live.push_back(i);
+    out_off[i + 1] = out_off[i] + (ok ? fixed[item_set[i]] : 0);
+  }
+  if (out_off[n] && (!out_buf || out_cap < out_off[n])) return false;
+  const size_t m = live.size();
+  std::vector<uint8_t> good(m, 1);
+  if (m) {
+    // rows, scalar-major: scalar j = (list s, position y) owns the live items of list s, in item order
+    std::vector<std::vector<uint32_t>> users(sets.size());
+    std::vector<uint32_t> item_row(m + 1, 0);
+    for (size_t j = 0; j < m; j++) {
+      const uint32_t s = item_set[live[j]];
+      users[s].push_back((uint32_t)j);
+      item_row[j + 1] = item_row[j] + (uint32_t)sets[s].size();
+    }
+    const size_t total = item_row[m], n_scal = scal_base[sets.size()];
+    std::vector<uint32_t> scal_row(n_scal + 1, 0), row_src(total), row_dst(total);
+    for (size_t s = 0; s < sets.size(); s++)
+      for (size_t y = 0; y < sets[s].size(); y++) {
+        const size_t k = scal_base[s] + y;
+        uint32_t t = scal_row[k];
+        for (uint32_t j : users[s]) { row_src[t] = j; row_dst[t] = item_row[j] + (uint32_t)y; t++; }
+        scal_row[k + 1] = t;
+      }
+    uint8_t* h_k = eng.pinned(0, n_scal * 32 + 32);
+    {
+      const Fr ha = sha3_hash_fr(authority);
+      for (size_t s = 0; s < sets.size(); s++)
+        for (size_t y = 0; y < sets[s].size(); y++) {
+          Fr e = fr_mul(fr_mul(sha3_hash_fr(sets[s][y]), ha), secret);
+          memcpy(h_k + 32 * (size_t)(scal_base[s] + y), e.l, 32);
+          memset(e.l, 0, sizeof(e.l));
+        }
+    }
+    tm.lap("rows + exponents");
+    uint8_t* h_u1 = eng.pinned(1, m * 64 + 4);
+    uint8_t* h_u2 = eng.pinned(2, m * 128 + 4);
+    parallel_for(m, [&](size_t j) {
+      const uint8_t* end = blob + in_off[live[j] + 1];
+      memcpy(h_u1 + 64 * j, end - 192, 64);
+      memcpy(h_u2 + 128 * j, end - 128, 128);
+    });
+    tm.lap("pack");
+    rhip_ctx* cx = eng.ctx();
+    DBuf d_u1(&eng, m * 64 + 4), d_u2(&eng, m * 128 + 4), d_a1(&eng, total * 64 + 4), d_a2(&eng, total * 128 + 4);
+    eng.check(rhip_upload_async(cx, d_u1.ptr(), h_u1, m * 64), "upload");
+    eng.check(rhip_upload_async(cx, d_u2.ptr(), h_u2, m * 128), "upload");
+    std::unique_ptr<MemberChecks> mc;
+    if (!trusted) {
+      mc.reset(new MemberChecks(eng));
+      mc->add(1, d_u1.ptr(), m);
+      mc->add(2, d_u2.ptr(), m);
+    }
+    if (total) {
+      DBuf d_k(&eng, n_scal * 32), d_scal_row = up32(eng, scal_row), d_src = up32(eng, row_src), d_dst = up32(eng, row_dst);
+      eng.check(rhip_upload_async(cx, d_k.ptr(), h_k, n_scal * 32), "upload");
+      eng.check(rhip_g1_mul_rows_at(cx, total, d_scal_row.as<uint32_t>(), d_u1.as<rhip_g1>(), d_src.as<uint32_t>(), n_scal, d_k.as<rhip_fr>(),
+                                    d_dst.as<uint32_t>(), d_a1.as<rhip_g1>()), "rhip_g1_mul_rows_at");
+      eng.check(rhip_g2_mul_rows_at(cx, total, d_scal_row.as<uint32_t>(), d_u2.as<rhip_g2>(), d_src.as<uint32_t>(), n_scal, d_k.as<rhip_fr>(),
+                                    d_dst.as<uint32_t>(), d_a2.as<rhip_g2>()), "rhip_g2_mul_rows_at");
+    }
+    if (mc) {
+      mc->collect();
+      const auto &ok1 = mc->ok(0), &ok2 = mc->ok(1);
+      for (size_t j = 0; j < m; j++) {
+        if (ok1[j] && ok2[j]) continue;
+        good[j] = 0;
+        (*errors)[live[j]] = !ok1[j] ? "deserialize: u1 is not a point of G1 with canonical coordinates (FieldError::NotMember)"
+                                     : "deserialize: u2 is not a member of G2 (FieldError::NotMember)";
+      }
+    }
+    // the records of the items that passed: a failed item's slot is empty, so the live records stay back to back
+    std::vector<RecordLayout> layouts(sets.size());
+    for (size_t s = 0; s < sets.size(); s++) {
+      RecordLayout& L = layouts[s];
+      L.u32((uint32_t)sets[s].size());
+      for (size_t y = 0; y < sets[s].size(); y++) { L.str(sets[s][y]); L.src(0, (uint32_t)(64 * y), 64); L.src(1, (uint32_t)(128 * y), 128); }
+      if (L.bytes() != fixed[s]) throw RabeError(std::string(what) + ": record layout and size disagree");
+    }
+    std::vector<uint32_t> lay;
+    std::vector<uint64_t> off1, off2, rec_off;
+    size_t at = 0;
+    for (size_t i = 0, j = 0; i < n; i++) {
+      const bool is_live = j < m && live[j] == i;
+      const bool ok = is_live && good[j];
+      out_off[i] = at;
+      if (ok) {
+        lay.push_back(item_set[i]);
+        off1.push_back(64ull * item_row[j]);
+        off2.push_back(128ull * item_row[j]);
+        rec_off.push_back(at);
+        at += fixed[item_set[i]];
+      }
+      if (is_live) j++;
+    }
+    out_off[n] = at;
+    rec_off.push_back(at);
+    off1.insert(off1.end(), off2.begin(), off2.end());
+    emit_plain_records(eng, layouts, lay.size(), lay.data(), {d_a1.ptr(), d_a2.ptr()}, off1, rec_off.data(), out_buf);
+    if (lay.empty()) eng.check(rhip_sync(cx), "rhip_sync");
+    tm.lap(trusted ? "device: rows, records; one copy out" : "device: rows, records, membership beside; one copy out");
+  }
+  for (size_t i = 0; i < n; i++) status[i] = (*errors)[i].empty() ? 0 : -1;
+  return true;
+}
 }  // namespace
 }  // namespace dnfabe
 
@@ -2527,6 +2753,16 @@ bool encrypt_packed(Engine& eng, Rng& rng, const BdabePublicKey& pk, const std::
   for (const auto* k : attr_pks) keys.push_back({&k->attr, &k->a1, &k->a2, {&k->a3, nullptr}});
   return dnfabe::encrypt_packed(eng, rng, sc, pk.p1, pk.p2, keys, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off);
 }
+bool keygen_packed(Engine& eng, Rng& rng, const BdabePublicKey& pk, const BdabeSecretAuthorityKey& ska, const std::vector<std::string>& names,
+                   uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  return dnfabe::keygen_packed(eng, rng, "bdabe::keygen_packed", pk.p1, pk.g1, pk.p2, pk.g2, ska.a1, ska.a2, names, out_buf, out_cap, out_off);
+}
+bool request_attribute_sk_packed(Engine& eng, const BdabeSecretAuthorityKey& ska, const std::vector<std::vector<std::string>>& sets, size_t n,
+                                 const uint32_t* item_set, const uint8_t* upk_blob, size_t upk_len, const uint64_t* upk_off, bool trusted, int32_t* status,
+                                 uint8_t* out_buf, size_t out_cap, uint64_t* out_off, std::vector<std::string>* errors) {
+  return dnfabe::request_sk_packed(eng, "bdabe::request_attribute_sk_packed", ska.name, ska.a3, sets, n, item_set, upk_blob, upk_len, upk_off, trusted,
+                                   status, out_buf, out_cap, out_off, errors);
+}
 }  // namespace bdabe
 
 namespace mke08 {
@@ -2537,6 +2773,16 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const std::
   std::vector<dnfabe::DnfKey> keys;
   for (const auto* k : attr_pks) keys.push_back({&k->attr, &k->g1, &k->g2, {&k->gt1, &k->gt2}});
   return dnfabe::encrypt_packed(eng, rng, sc, pk.p1, pk.p2, keys, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off);
+}
+bool keygen_packed(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const Mke08MasterKey& msk, const std::vector<std::string>& names, uint8_t* out_buf,
+                   size_t out_cap, uint64_t* out_off) {
+  return dnfabe::keygen_packed(eng, rng, "mke08::keygen_packed", pk.p1, pk.g1, pk.p2, pk.g2, msk.g1, msk.g2, names, out_buf, out_cap, out_off);
+}
+bool request_authority_sk_packed(Engine& eng, const Mke08SecretAuthorityKey& ska, const std::vector<std::vector<std::string>>& sets, size_t n,
+                                 const uint32_t* item_set, const uint8_t* upk_blob, size_t upk_len, const uint64_t* upk_off, bool trusted, int32_t* status,
+                                 uint8_t* out_buf, size_t out_cap, uint64_t* out_off, std::vector<std::string>* errors) {
+  return dnfabe::request_sk_packed(eng, "mke08::request_authority_sk_packed", ska.name, ska.r, sets, n, item_set, upk_blob, upk_len, upk_off, trusted,
+                                   status, out_buf, out_cap, out_off, errors);
 }
 }  // namespace mke08
 

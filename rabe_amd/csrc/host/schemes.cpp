@@ -2711,12 +2711,12 @@ Bytes decrypt_out(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11R
 //   msg = lead * e(c_a, sum S2) * e(sum S1, c_b) / (e(c_c, u2) * e(u1, c_d))
 // which is ONE pairing job: m pairs (c_a, S2_i), one pair with the summed G1 argument (sum S1_i, c_b), two pairs with exponent -1.
 namespace dnfabe {
-static bool from_authority(const std::string& attr, const std::string& authority) {
+bool from_authority(const std::string& attr, const std::string& authority) {
   size_t count = 0, first = std::string::npos;
   for (size_t pos = attr.find("::"); pos != std::string::npos; pos = attr.find("::", pos + 2)) { if (!count) first = pos; count++; }   // match_indices: non-overlapping
   return count == 1 && attr.substr(0, first) == authority;
 }
-static Fr attr_exponent(const std::string& attribute, const std::string& authority, const Fr& secret) {
+Fr attr_exponent(const std::string& attribute, const std::string& authority, const Fr& secret) {
   return fr_mul(fr_mul(sha3_hash_fr(attribute), sha3_hash_fr(authority)), secret);
 }
 struct AttrKey { const std::string* attr; const G1* g1; const G2* g2; };

@@ -217,6 +217,9 @@ namespace dnfabe {
 // (*tgt)[g][t] = product of kt[g] over them
 void fold_term_bases(Engine& eng, const std::vector<host::DnfTerm>& terms, const std::vector<G1>& k1, const std::vector<G2>& k2,
                      const std::vector<std::vector<Gt>>& kt, std::vector<G1>* t1, std::vector<G2>* t2, std::vector<std::vector<Gt>>* tgt);
+// "authority::attribute" with exactly one "::" (bdabe/mod.rs:401-420); the exponent h(attribute) h(authority) secret of an attribute's keys
+bool from_authority(const std::string& attr, const std::string& authority);
+Fr attr_exponent(const std::string& attribute, const std::string& authority, const Fr& secret);
 }  // namespace dnfabe
 
 namespace bdabe {       // src/schemes/bdabe/mod.rs (DNF policies, multi-authority)
@@ -246,6 +249,14 @@ std::vector<DecryptResult> decrypt_batch(Engine& eng, const std::vector<const Bd
 bool encrypt_packed(Engine& eng, Rng& rng, const BdabePublicKey& pk, const std::vector<const BdabePublicAttributeKey*>& attr_pks,
                     const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
                     const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
+// bulk key issuing (packed.cpp).  keygen_packed: n calls of keygen under one authority key, records = BdabeUserKey with an empty sk_a (false =
+// out_cap too small, nothing drawn).  request_attribute_sk_packed: for every BdabePublicUserKey record (name | u1 | u2) of an untrusted blob the
+// secret attribute keys of the list sets[item_set[i]]; records = u32 count + rows (attribute, au1, au2), the sk_a tail of the user-key record
+bool keygen_packed(Engine& eng, Rng& rng, const BdabePublicKey& pk, const BdabeSecretAuthorityKey& ska, const std::vector<std::string>& names,
+                   uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
+bool request_attribute_sk_packed(Engine& eng, const BdabeSecretAuthorityKey& ska, const std::vector<std::vector<std::string>>& sets, size_t n,
+                                 const uint32_t* item_set, const uint8_t* upk_blob, size_t upk_len, const uint64_t* upk_off, bool trusted, int32_t* status,
+                                 uint8_t* out_buf, size_t out_cap, uint64_t* out_off, std::vector<std::string>* errors);
 }  // namespace bdabe
 
 namespace mke08 {       // src/schemes/mke08/mod.rs (DNF policies, multi-authority)
@@ -274,6 +285,12 @@ std::vector<DecryptResult> decrypt_batch(Engine& eng, const std::vector<const Mk
 bool encrypt_packed(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const std::vector<const Mke08PublicAttributeKey*>& attr_pks,
                     const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
                     const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
+// bulk key issuing (packed.cpp): as bdabe's, under the master key (keygen) and an authority's r (request_authority_sk)
+bool keygen_packed(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const Mke08MasterKey& msk, const std::vector<std::string>& names, uint8_t* out_buf,
+                   size_t out_cap, uint64_t* out_off);
+bool request_authority_sk_packed(Engine& eng, const Mke08SecretAuthorityKey& ska, const std::vector<std::vector<std::string>>& sets, size_t n,
+                                 const uint32_t* item_set, const uint8_t* upk_blob, size_t upk_len, const uint64_t* upk_off, bool trusted, int32_t* status,
+                                 uint8_t* out_buf, size_t out_cap, uint64_t* out_off, std::vector<std::string>* errors);
 }  // namespace mke08
 
 }}  // namespace rabe::schemes

@@ -193,6 +193,22 @@ class Engine:
         self._check(self.lib.rhip_g2_mul_rows(self.ctx, ctypes.c_size_t(n_rows), doff.ptr, dp.ptr, ctypes.c_size_t(n_items), dk.ptr, out.ptr))
         raw = self.download(out, n_rows * G2)
         return [raw[i * G2:(i + 1) * G2] for i in range(n_rows)]
+
+    def g1_mul_rows(self, points, item_row_off, scalars):
+        """out[t] = scalars[i] * points[t] for the rows t of item i (rhip_g1_mul_rows: one GLV decomposition per scalar, one joint chain per
+        row, one inversion per block); item_row_off: len(scalars) + 1 non-decreasing offsets ending at len(points).  Same bytes as g1_mul."""
+        n_rows, n_items = len(points), len(scalars)
+        if len(item_row_off) != n_items + 1 or item_row_off[0] != 0 or item_row_off[-1] != n_rows:
+            raise ValueError("g1_mul_rows: item_row_off must run from 0 to len(points) in len(scalars) + 1 entries")
+        if any(item_row_off[i] > item_row_off[i + 1] for i in range(n_items)):
+            raise ValueError("g1_mul_rows: item_row_off must not decrease")
+        if not n_rows:
+            return []
+        dp, dk, doff = self.upload(b"".join(points)), self.upload(b"".join(scalars)), self.upload_u32(item_row_off)
+        out = self.alloc(n_rows * G1)
+        self._check(self.lib.rhip_g1_mul_rows(self.ctx, ctypes.c_size_t(n_rows), doff.ptr, dp.ptr, ctypes.c_size_t(n_items), dk.ptr, out.ptr))
+        raw = self.download(out, n_rows * G1)
+        return [raw[i * G1:(i + 1) * G1] for i in range(n_rows)]
     def gt_mul(self, a, b): return self._elem("rhip_gt_mul", len(a), [a, b], GT)
     def gt_inv(self, a): return self._elem("rhip_gt_inv", len(a), [a], GT)
     def gt_pow(self, a, k): return self._elem("rhip_gt_pow", len(a), [a, k], GT)

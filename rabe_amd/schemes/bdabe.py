@@ -68,3 +68,58 @@ def encrypt_packed(host, pk, attr_pks, policies, item_policy, pt_blob, pt_off, l
     arr = (ctypes.c_void_p * max(1, len(attr_pks)))(*[p.ptr for p in attr_pks])
     return packed_produce(host, "rabe_bdabe_encrypt_packed", (pk.ptr, arr, ctypes.c_size_t(len(attr_pks))), policies, item_policy, language,
                           (_as_u8(pt_blob), np.ascontiguousarray(pt_off, dtype=np.uint64)), out)
+
+
+def keygen_packed(host, pk, ska, names, out=None):
+    """one user key per name under one authority key (rabe_bdabe_keygen_packed).  Returns (uk_blob: numpy uint8 view of the BdabeUserKey
+    records with an empty sk_a, uk_off: numpy uint64 [n+1])."""
+    import numpy as np
+    from ..hostlib import _check, _np_ptr, _strs
+    n = len(names)
+    arr, _ = _strs(list(names))
+    off = np.zeros(n + 1, dtype=np.uint64)
+    buf = out if out is not None else np.empty(0, dtype=np.uint8)
+    for _ in range(2):
+        rc = host.lib.rabe_bdabe_keygen_packed(host.h, pk.ptr, ska.ptr, arr, ctypes.c_size_t(n), _np_ptr(buf), ctypes.c_size_t(buf.size), _np_ptr(off))
+        if rc != 1:
+            break
+        buf = np.empty(int(off[n]), dtype=np.uint8)
+    _check(rc, host.h)
+    return buf[:int(off[n])], off
+
+
+def public_user_key_record(uk_record):
+    """the BdabePublicUserKey record (name | u1 | u2) inside a serialized user key: what a user hands to an authority"""
+    rec = bytes(uk_record)
+    end = 192 + 4 + int.from_bytes(rec[192:196], "little") + 192
+    if len(rec) < 196 or len(rec) < end:
+        raise ValueError("not a serialized user key")
+    return rec[192:end]
+
+
+def request_attribute_sk_packed(host, ska, attr_sets, item_set, upk_blob, upk_off, trusted=False):
+    """the secret attribute keys of attr_sets[item_set[i]] for the public user key record i of upk_blob (rabe_bdabe_request_attribute_sk_packed).
+    Returns (blob view of the records -- u32 count + rows (attribute, au1, au2), the sk_a tail of a user-key record --, off uint64 [n+1],
+    status int32 [n]); a failed item has status -1 and an empty slot."""
+    import numpy as np
+    from ..hostlib import PACKED_TRUSTED, _as_u8, _check, _np_ptr, _strs
+    n = len(upk_off) - 1
+    arr, _ = _strs([a for s_ in attr_sets for a in s_])
+    counts = (ctypes.c_size_t * max(len(attr_sets), 1))(*[len(s_) for s_ in attr_sets])
+    it = np.ascontiguousarray(item_set, dtype=np.uint32)
+    if len(it) != n:
+        raise ValueError("request_attribute_sk_packed: one item_set entry per record")
+    blob = _as_u8(upk_blob)
+    uo = np.ascontiguousarray(upk_off, dtype=np.uint64)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    buf = np.empty(0, dtype=np.uint8)
+    for _ in range(2):
+        rc = host.lib.rabe_bdabe_request_attribute_sk_packed(host.h, ska.ptr, arr, counts, ctypes.c_size_t(len(attr_sets)), ctypes.c_size_t(n), _np_ptr(it), _np_ptr(blob),
+                            ctypes.c_size_t(blob.size), _np_ptr(uo), ctypes.c_uint32(PACKED_TRUSTED if trusted else 0), _np_ptr(status),
+                            _np_ptr(buf), ctypes.c_size_t(buf.size), _np_ptr(off))
+        if rc != 1:
+            break
+        buf = np.empty(int(off[n]), dtype=np.uint8)
+    _check(rc, host.h)
+    return buf[:int(off[n])], off, status[:n]

@@ -15,7 +15,7 @@ from rabe_amd.schemes import aw11, bdabe, bsw, ghw11, lsw, mke08  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=256)
 ap.add_argument("--only", default="")
-ap.add_argument("--key-items", type=int, default=65536, help="keys per call of the GHW11 key-issuing leg (--only ghw11keys)")
+ap.add_argument("--key-items", type=int, default=65536, help="keys per call of the key-issuing legs (--only ghw11keys, --only dnfkeys)")
 ap.add_argument("--rounds", type=int, default=2, help="timed repetitions per config: the first meets cold fixed-base tables of the key elements, later ones warm ones")
 args = ap.parse_args()
 B = args.batch
@@ -217,6 +217,89 @@ if args.only in ("", "ghw11keys"):
                           "g2_mul_rows_elements_per_s": round(n_rows / t_rows, 1), "g2_mul_elements_per_s": round(n_rows / t_bin, 1),
                           "g2_mul_rows_s": round(t_rows, 4), "g2_mul_s": round(t_bin, 4), "kernel_ratio": round(t_bin / t_rows, 3),
                           "seconds": round(t_tk[0], 4), "record_bytes": int(sk_blob.size)}), flush=True)
+    eng.close()
+
+if args.only in ("", "dnfkeys"):
+    # BDABE / MKE08 bulk key issuing: keygen_packed (fixed-base rows) and request_*_sk_packed (variable-base G1 and G2 rows, 8 attributes per
+    # user) at --key-items users, the object API on 256 users of the same inputs, and the A/B of k_g1_mul_rows against k_g1_mul on the same
+    # elements and scalars -- one process, warm-up then best of three, timed around call (+ sync for the device-level calls)
+    import ctypes
+    import random
+    import numpy as np
+    from rabe_amd import Engine
+    R_ORDER = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+
+    def best3(fn):
+        fn()
+        best = None
+        for _ in range(3):
+            t0 = time.perf_counter()
+            r = fn()
+            dt = time.perf_counter() - t0
+            best = dt if best is None else min(best, dt)
+        return best, r
+
+    eng = Engine(0)
+    n_users, n_obj = args.key_items, 256
+    attrs = ["aa1::b%d" % i for i in range(8)]
+    names = ["user%05d" % (i % 100000) for i in range(n_users)]          # names of one length: the records sit at a fixed stride
+    for scheme, mod in (("bdabe", bdabe), ("mke08", mke08)):
+        pk, msk = mod.setup(host)
+        if scheme == "bdabe":
+            au = bdabe.authgen(host, pk, msk, "aa1")
+            issuer, req_obj, req_packed = au, (lambda uk, a: bdabe.request_attribute_sk(host, uk, au, a)), bdabe.request_attribute_sk_packed
+        else:
+            au = mke08.authgen(host, "aa1")
+            issuer, req_obj, req_packed = msk, (lambda uk, a: mke08.request_authority_sk(host, uk, a, au)), mke08.request_authority_sk_packed
+        t_kg, (uk_blob, uk_off) = best3(lambda: mod.keygen_packed(host, pk, issuer, names))
+        rec = int(uk_off[1])
+        view = np.ascontiguousarray(uk_blob).reshape(n_users, rec)
+        upk = np.ascontiguousarray(view[:, 192:rec - 4])
+        upk_off = np.arange(n_users + 1, dtype=np.uint64) * (rec - 196)
+        assert bytes(upk[0]) == mod.public_user_key_record(bytes(view[0]))
+        t_rq, t_rq_tr = [best3(lambda: req_packed(host, au, [attrs], [0] * n_users, upk.reshape(-1), upk_off, trusted=tr)) for tr in (False, True)]
+        ob, oo, st = t_rq[1]
+        assert not st.any()
+        # the object API on the first 256 users: one keygen call and eight request calls per user
+        mod.keygen(host, pk, issuer, "warm")
+        t0 = time.perf_counter()
+        uks = [mod.keygen(host, pk, issuer, names[i]) for i in range(n_obj)]
+        t_kg_obj = time.perf_counter() - t0
+        uks = [hl.Obj.deserialize(scheme + "_uk", bytes(view[i]), host=host) for i in range(n_obj)]          # the packed call's users
+        t0 = time.perf_counter()
+        for uk in uks:
+            for a in attrs:
+                req_obj(uk, a)
+        t_rq_obj = time.perf_counter() - t0
+        for i in (0, n_obj - 1):
+            assert uks[i].serialize() == bytes(view[i, :rec - 4]) + bytes(ob[int(oo[i]):int(oo[i + 1])])
+        # kernel A/B on these users' u1: one scalar per attribute, its rows = every user
+        n_rows = n_users * len(attrs)
+        u1 = np.ascontiguousarray(upk[:, -192:-128])
+        ks = np.frombuffer(b"".join(random.randrange(1, R_ORDER).to_bytes(32, "little") for _ in attrs), dtype=np.uint8).reshape(len(attrs), 32)
+        d_p = eng.upload(np.tile(u1, (len(attrs), 1)).tobytes())
+        d_k, d_kk = eng.upload(ks.tobytes()), eng.upload(np.repeat(ks, n_users, axis=0).tobytes())
+        d_off = eng.upload((np.arange(len(attrs) + 1, dtype=np.uint32) * n_users).tobytes())
+        d_a, d_b = eng.alloc(n_rows * 64), eng.alloc(n_rows * 64)
+
+        def run_rows():
+            eng._check(eng.lib.rhip_g1_mul_rows(eng.ctx, ctypes.c_size_t(n_rows), d_off.ptr, d_p.ptr, ctypes.c_size_t(len(attrs)), d_k.ptr, d_a.ptr))
+            eng.sync()
+
+        def run_glv():
+            eng._check(eng.lib.rhip_g1_mul(eng.ctx, ctypes.c_size_t(n_rows), d_p.ptr, d_kk.ptr, d_b.ptr))
+            eng.sync()
+        t_rows, _ = best3(run_rows)
+        t_glv, _ = best3(run_glv)
+        assert eng.download(d_a) == eng.download(d_b)
+        print(json.dumps({"config": "%s key issuing, %d attributes per user: keygen_packed, request_sk_packed; the object API on %d users; k_g1_mul_rows "
+                                    "against k_g1_mul on the same %d elements and scalars" % (scheme.upper(), len(attrs), n_obj, n_rows), "batch": n_users,
+                          "keygen_keys_per_s": round(n_users / t_kg, 1), "keygen_keys_per_s_object": round(n_obj / t_kg_obj, 1),
+                          "request_sk_users_per_s": round(n_users / t_rq[0], 1), "request_sk_users_per_s_trusted": round(n_users / t_rq_tr[0], 1),
+                          "request_sk_users_per_s_object": round(n_obj / t_rq_obj, 1),
+                          "g1_mul_rows_elements_per_s": round(n_rows / t_rows, 1), "g1_mul_elements_per_s": round(n_rows / t_glv, 1),
+                          "g1_mul_rows_s": round(t_rows, 4), "g1_mul_s": round(t_glv, 4), "kernel_ratio": round(t_glv / t_rows, 3),
+                          "seconds": round(t_rq[0], 4), "record_bytes": int(uk_blob.size) + int(ob.size)}), flush=True)
     eng.close()
 
 if args.only in ("", "dnf"):
