@@ -471,6 +471,22 @@ int32_t rhip_lsw_decrypt_batch_one_ct(rhip_ctx* ctx, size_t n_items, size_t max_
                                       const uint32_t* dev_sk_leaf_off /*[n_sk+1]*/, const uint32_t* dev_sk_idx /*[n_items] or NULL*/,
                                       const rhip_g2_lines* ct_e2_lines /* or NULL */, rhip_gt* dev_out /*[n_items]*/);
 
+/* The same with ONE secret key for every item and a ciphertext of its own per item (ciphertext i = item i: dev_ct_e2 [n_items], attribute rows
+ * [ct_attr_off[i], ct_attr_off[i+1]) of dev_ct_e1j) -- what a KP-ABE key holder does and rabe_lsw_decrypt_one_sk_packed runs.  Every D2 is the
+ * key's: sk_d2_lines = rhip_g2_lines_prepare over the key's D2 rows (block = leaf row, what sel_sk_leaf names), so the m_i key-side Miller loops
+ * of an item replay prepared lines and the only walked G2 argument is the item's own e2 (whose walk verdict rhip_ctx_collect_walk_verdicts
+ * hands out).  sum_e -c_e D1_e depends on the selection alone and is computed once per selection GROUP, stated by the caller: the n_sel entries
+ * are the concatenation of the groups' entries, group g owning [group_off[g], group_off[g+1]); item i belongs to group item_group[i], i.e.
+ * sel_start[i] = group_off[item_group[i]] and m_i = the group's entry count.  Without sharing: one group per item (n_groups = n_items).  What
+ * stays per pair is the scaling c_e * E1_{i,e}.  Results are those of rhip_lsw_decrypt_batch with dev_sk_idx = all zero. */
+int32_t rhip_lsw_decrypt_batch_one_sk(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel,
+                                      const uint32_t* dev_pair_off /*[n_items+1]*/, const uint32_t* dev_sel_start /*[n_items]*/,
+                                      const uint32_t* dev_sel_sk_leaf, const uint32_t* dev_sel_ct_attr, const rhip_fr* dev_sel_coeff,
+                                      size_t n_groups, const uint32_t* dev_group_off /*[n_groups+1]*/, const uint32_t* dev_item_group /*[n_items]*/,
+                                      const rhip_gt* dev_ct_e1 /*[n_items]*/, const rhip_g2* dev_ct_e2 /*[n_items]*/,
+                                      const rhip_g1* dev_ct_e1j /*[ct attribute rows]: ej.1*/, const uint32_t* dev_ct_attr_off /*[n_items+1]*/,
+                                      const rhip_g1* dev_sk_d1 /*[the key's leaf rows]*/, const rhip_g2_lines* sk_d2_lines, rhip_gt* dev_out /*[n_items]*/);
+
 /* ---- Level B: GHW11 outsourced decryption (src/schemes/ghw11/mod.rs:227-295) ----------------------
  * Group arithmetic of n_items calls of ghw11::transform under ONE transform key.  tk_lines = rhip_g2_lines_prepare over the key's G2
  * elements in the order k_z, l_z, k_x[0], k_x[1], ... : every Miller loop of the batch replays prepared lines (no G2 arithmetic).

@@ -42,7 +42,7 @@ int32_t rabe_host_create(int32_t device, rabe_host** out);
 /* ---- device group: ONE host over several GPUs of a node ----------------------------------------------------------------------
  * Every encrypt / keygen / decrypt call is independent (the reference's schemes are pure functions of their arguments and fresh
  * randomness), so a batch shards by item: the packed entry points of the four BASELINE schemes -- rabe_ac17_cp_{encrypt,decrypt}_packed,
- * rabe_bsw_{encrypt,decrypt}_packed, rabe_lsw_{keygen,decrypt}_packed, rabe_aw11_{encrypt,decrypt}_packed -- cut their n_items into one
+ * rabe_bsw_{encrypt,decrypt}_packed, rabe_lsw_{keygen,decrypt,decrypt_one_sk}_packed, rabe_aw11_{encrypt,decrypt}_packed -- cut their n_items into one
  * contiguous block per device (sizes differ by at most one, blocks in device order), run every block on its own host thread and engine
  * (each device builds its replica of a key's window tables / prepared lines on first use and keeps it), and the records / plaintexts /
  * status entries land in the caller's buffers exactly where the single-device call puts them.  Randomness is drawn block after block
@@ -240,6 +240,20 @@ int32_t rabe_lsw_keygen_packed(rabe_host* h, const void* pk, const void* msk, co
 int32_t rabe_lsw_decrypt_packed(rabe_host* h, const void* ct, size_t n_items, const uint8_t* sk_blob, size_t sk_len,
                                 const uint64_t* sk_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* pt_buf, size_t pt_cap,
                                 uint64_t* pt_off /*[n_items+1]*/);
+/* The shape of a KP-ABE key holder: ONE key of the holder's own against n_items ciphertexts from outside -- KpAbeCiphertext records as
+ * rabe_obj_serialize writes them and rabe_lsw_encrypt_packed emits them (conventions of rabe_bsw_decrypt_packed: nothing outside
+ * [0, ct_len) is read; bad bounds, a malformed record, attributes that do not satisfy the key's policy, a tag that does not verify fail
+ * that item alone: status -1, an empty plaintext slot, the first error in rabe_host_last_error).  Over rhip_lsw_decrypt_batch_one_sk: the
+ * key-side Miller loops replay the key's prepared lines (built once per key and engine), sum_e -c_e D1_e is computed once per distinct
+ * list of row names, the sealed parts are opened on the device.  Records that list the same names in the same order share one plan
+ * (calc_pruned + coefficients, the reference's FIRST-row lookups :249-263); another order or a duplicated name is a list of its own.
+ * Unless RABE_PACKED_TRUSTED is set every decoded element is checked: e1 in Gt, the row elements on the G1 curve with canonical
+ * coordinates, e2 in G2 (out of its own Miller loop, or the stand-alone test).  A selected negative attribute fails the item as in
+ * rabe_lsw_decrypt_packed.  No randomness is drawn.  Returns 1 when pt_cap is below the total of the well-formed records' sealed
+ * lengths (a device group that cuts the batch: below their total record size); pt_off[n_items] then holds the size to come back with. */
+int32_t rabe_lsw_decrypt_one_sk_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
+                                       const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/,
+                                       uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off /*[n_items+1]*/);
 
 /* ---- aw11 (src/schemes/aw11/mod.rs:100-390) */
 int32_t rabe_aw11_setup(rabe_host* h, void** gk);

@@ -1498,6 +1498,99 @@ static int32_t lsw_decrypt_impl(rhip_ctx* ctx, size_t n_items, size_t max_pairs,
   return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, ct_e2_lines ? (const LineM*)ct_e2_lines->lines : (const LineM*)nullptr, ct_e2_lines ? ct_e2_lines->lines29 : nullptr, ct_e1, out);
 }
 
+// decrypt of many ciphertexts under ONE key (the mirror image of the one-ciphertext form): every D2 is the key's, so the m key-side
+// Miller loops of an item replay the key's prepared lines (block = key leaf row) and the only walked G2 argument is the item's own e2;
+// sum_e -c_e D1_e depends on the selection alone and is computed once per selection GROUP.  Item i owns pairs [pair_off[i], pair_off[i+1]) = m_i + 1:
+//   s < m : P = c_e * E1[ct attr of item i],      lines of D2[key leaf]        (e = sel_start[i] + s)
+//   m     : P = the sum of the item's group,      Q = e2[i]  (walked)
+// the MSM's bases, once per selection entry: terms[e] = D1[sel_sk_leaf[e]] (Montgomery)
+__global__ void __launch_bounds__(256, RB_MIN_WAVES) k_lsw_entry_terms(size_t n_sel, const uint32_t* sel_sk_leaf, const rhip_g1* sk_d1, G1M* terms) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < n_sel) st_g1_q(terms + e, load_g1(sk_d1[sel_sk_leaf[e]].l));
+}
+// lane = group: sum of its L partial sums -> gsum[g] (affine Montgomery; one inversion per block), gsum_inf[g] = 1 for the identity
+__global__ void __launch_bounds__(RB_PAIRS_BLOCK, 2) k_msm_finish_groups_g1(size_t n_groups, uint32_t L, const G1JM* part, G1M* gsum, uint8_t* gsum_inf) {
+  __shared__ uint32_t lds[2 * 8 * RB_PAIRS_BLOCK];
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = g < n_groups;
+  if (!active) g = n_groups - 1;
+  G1Jac acc = ld_jac_q(part + g * L);
+  for (uint32_t c = 1; c < L; c++) acc = jac_add(acc, ld_jac_q(part + g * L + c));
+  const bool inf = !active || jac_is_inf(acc);
+  const Fp zinv = block_batch_inverse_n<RB_PAIRS_BLOCK>(lds, inf ? one<FpParams>() : acc.z);
+  if (!active) return;
+  gsum_inf[g] = inf ? 1 : 0;
+  if (!inf) st_g1_q(gsum + g, jac_to_aff_with_zinv(acc, zinv));
+}
+__global__ void __launch_bounds__(RB_PAIRS_BLOCK, 2) k_lsw_dec_pairs_one_sk(size_t n_items, size_t total_pairs, const uint32_t* pair_off, uint32_t ppi, const uint32_t* tile_off,
+                                                                           const uint32_t* sel_start, const uint32_t* sel_sk_leaf, const uint32_t* sel_ct_attr,
+                                                                           const rhip_fr* sel_coeff, const uint32_t* item_group, const G1M* gsum, const uint8_t* gsum_inf,
+                                                                           const rhip_g2* ct_e2, const rhip_g1* ct_e1j, const uint32_t* ct_attr_off, const uint8_t* line_inf,
+                                                                           G1M* P, G2M* Q, uint32_t* qref) {
+  __shared__ uint32_t lds[2 * 8 * RB_PAIRS_BLOCK];
+  size_t t, item;
+  bool active;
+  pair_lane((size_t)blockIdx.x * blockDim.x + threadIdx.x, n_items, total_pairs, pair_off, ppi, tile_off, &t, &item, &active);
+  const uint32_t j = (uint32_t)(t - pair_off[item]);
+  const uint32_t m = pair_off[item + 1] - pair_off[item] - 1;
+  const bool last = (j == m);
+  G1Aff base = aff_inf<Fp>();
+  uint32_t k[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t line = 0;
+  if (!last) {
+    const uint32_t e = sel_start[item] + j;
+    base = load_g1(ct_e1j[ct_attr_off[item] + sel_ct_attr[e]].l);
+    ld_scalar(k, sel_coeff + e);
+    line = sel_sk_leaf[e];
+  }
+  bool p_inf;
+  scale_and_store(lds, active && !last, base, k, false, P + t, &p_inf);
+  if (!active) return;
+  if (!last) { qref[t] = (p_inf || line_inf[line]) ? RHIP_Q_SKIP : line; return; }
+  const uint32_t g = item_group[item];
+  const G2Aff q = load_g2(ct_e2[item].l);
+  const bool skip = gsum_inf[g] != 0 || aff_is_inf(q);
+  if (!skip) { st_g1_q(P + t, ld_g1_q(gsum + g)); st_g2_q(Q + t, q); }
+  qref[t] = skip ? RHIP_Q_SKIP : RHIP_Q_WALK;
+}
+extern "C" int32_t rhip_lsw_decrypt_batch_one_sk(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
+                                                 const uint32_t* sel_start, const uint32_t* sel_sk_leaf, const uint32_t* sel_ct_attr, const rhip_fr* sel_coeff,
+                                                 size_t n_groups, const uint32_t* group_off, const uint32_t* item_group, const rhip_gt* ct_e1, const rhip_g2* ct_e2,
+                                                 const rhip_g1* ct_e1j, const uint32_t* ct_attr_off, const rhip_g1* sk_d1, const rhip_g2_lines* sk_d2_lines,
+                                                 rhip_gt* out) {
+  NEED(ctx);
+  if (!n_items) return RHIP_OK;
+  if (!total_pairs || !pair_off || !n_sel || !n_groups || !group_off || !item_group || !sk_d2_lines || !max_pairs || total_pairs < n_items) return RHIP_ERR_ARG;
+  PairLists pl;
+  int32_t rc = alloc_pair_lists(ctx, total_pairs, &pl);
+  if (rc) return rc;
+  void *w_terms = nullptr, *w_masks = nullptr, *w_part = nullptr, *w_sum = nullptr;
+  rc = rhip_ensure_work(ctx, 4, n_sel * sizeof(G1M), &w_terms);
+  if (!rc) rc = rhip_ensure_work(ctx, 5, n_sel * 16 * sizeof(uint32_t), &w_masks);
+  uint32_t L, C;
+  choose_msm_chunks(ctx, n_groups, max_pairs - 1, &L, &C);
+  if (!rc) rc = rhip_ensure_work(ctx, 6, n_groups * L * sizeof(G1JM), &w_part);
+  if (!rc) rc = rhip_ensure_work(ctx, 8, n_groups * (sizeof(G1M) + 1) + 64, &w_sum);
+  if (rc) return rc;
+  G1M* gsum = (G1M*)w_sum;
+  uint8_t* gsum_inf = (uint8_t*)(gsum + n_groups);
+  // the sums, over the groups as the MSM's "items": group g's terms and masks are its entries [group_off[g], group_off[g+1])
+  KLAUNCH(ctx, "k_naf_masks", k_naf_masks, dim3(blocks_for(n_sel, 256)), dim3(256), 0, ctx->stream, n_sel, sel_coeff, (uint32_t*)w_masks);
+  KLAUNCH(ctx, "k_lsw_entry_terms", k_lsw_entry_terms, dim3(blocks_for(n_sel, 256)), dim3(256), 0, ctx->stream, n_sel, sel_sk_leaf, sk_d1, (G1M*)w_terms);
+  KLAUNCH(ctx, "k_msm_partial_g1", (k_msm_partial<Fp, G1M, G1JM>), dim3(blocks_for(n_groups * L, 64)), dim3(64), 0, ctx->stream, n_groups, L, C, group_off, group_off,
+          (const G1M*)w_terms, (const uint32_t*)w_masks, 1, (G1JM*)w_part);
+  KLAUNCH(ctx, "k_msm_finish_groups_g1", k_msm_finish_groups_g1, dim3(blocks_for(n_groups, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_groups, L,
+          (const G1JM*)w_part, gsum, gsum_inf);
+  const uint32_t ppi = uniform_ppi(n_items, max_pairs, total_pairs);
+  size_t g_lanes = 0;
+  const uint32_t* tile_off = nullptr;
+  if ((rc = gather_lanes(ctx, n_items, max_pairs, total_pairs, pair_off, ppi, &tile_off, &g_lanes)) != RHIP_OK) return rc;
+  KLAUNCH(ctx, "k_lsw_dec_pairs_one_sk", k_lsw_dec_pairs_one_sk, dim3(blocks_for(g_lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items, total_pairs,
+          pair_off, ppi, tile_off, sel_start, sel_sk_leaf, sel_ct_attr, sel_coeff, item_group, (const G1M*)gsum, (const uint8_t*)gsum_inf, ct_e2, ct_e1j, ct_attr_off,
+          (const uint8_t*)sk_d2_lines->q_inf, pl.P, pl.Q, pl.qref);
+  return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, (const LineM*)sk_d2_lines->lines, sk_d2_lines->lines29, ct_e1, out);
+}
+
 // ------------------------------------------------------------------------------------------------ GHW11 outsourced decryption
 // transform (ghw11/mod.rs:227-295; SURVEY.md 8f-1: "decrypt-as-a-service"): every G2 argument is one of the TRANSFORM KEY's
 // (k_z, l_z, k_x per attribute) -- fixed for a batch served under one key, so all m + 2 Miller loops of an item replay prepared

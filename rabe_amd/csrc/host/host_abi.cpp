@@ -1258,6 +1258,26 @@ int32_t rabe_lsw_decrypt_packed(rabe_host* h, const void* ct, size_t n_items, co
   return 0;
   GUARD_END(h)
 }
+int32_t rabe_lsw_decrypt_one_sk_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
+                                       int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  const auto& key = *(const lsw::KpAbeSecretKey*)sk;
+  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
+  if (!ct_off || !pt_off) throw RabeError("lsw::decrypt_one_sk_packed: null input");
+  // what a batch cut over a device group asks of the plaintext buffer (pipeline.cpp: consume); the one-engine call states its own, smaller, size
+  uint64_t span = 0;
+  for (size_t i = 0; i < n_items; i++) if (ct_off[i] <= ct_off[i + 1] && ct_off[i + 1] <= ct_len) span += ct_off[i + 1] - ct_off[i];
+  pt_off[n_items] = span;
+  if (!pipeline::consume(h->engines(), n_items, CHUNK_LSW, ct_off, ct_len, [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off,
+                                                                          std::vector<std::string>* errs) {
+        return lsw::decrypt_one_sk_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
+      }, status, pt_buf, pt_cap, pt_off, &errors))
+    return 1;
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
 int32_t rabe_aw11_keygen_packed(rabe_host* h, const void* gk, const void* msk, const char* const* gids, const char* const* attributes, const size_t* counts,
                                 size_t n_sets, size_t n_items, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off) {
   GUARD_BEGIN

@@ -1360,6 +1360,214 @@ bool decrypt_packed(Engine& eng, const KpAbeCiphertext& ct, size_t n, const uint
   tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
   return true;
 }
+
+namespace {
+void* make_sk_d2_lines(Engine& eng, const void* arg) {          // arg: d2 of every key row (128 B each)
+  const std::string& pts = *(const std::string*)arg;
+  DBuf d(&eng, pts.data(), pts.size());
+  rhip_g2_lines* lines = nullptr;
+  eng.check(rhip_g2_lines_prepare(eng.ctx(), pts.size() / 128, d.as<rhip_g2>(), &lines), "rhip_g2_lines_prepare");
+  return lines;
+}
+}  // namespace
+
+// n calls of lsw::decrypt (lsw/mod.rs:228-290) with ONE key: n ciphertexts (a blob of KpAbeCiphertext records) from outside, the shape of a
+// KP-ABE key holder.  The key's policy is parsed once; per distinct list of row names (the bytes of the names, in the record's order):
+// calc_pruned over those names and, for every pruned (name, name_col), the FIRST key row and the FIRST ciphertext row named `name` and the
+// FIRST coefficient named name_col (:249-263).  Records with the same list share their selection entries -- one selection GROUP of
+// rhip_lsw_decrypt_batch_one_sk; the same names in another order, or a duplicated name, are another list with entries of its own.  A
+// pruned negative attribute fails the item as in decrypt_packed.  Every D2 is the key's (prepared lines, kept per engine); the one walked
+// G2 argument of an item is its own e2, whose walk gives its membership verdict.  The whole rows (e1, e2, e3 of every attribute) are gathered
+// and checked as a decoder would; row r's E1 is element 3 r of that array.  pt_cap below the sealed lengths of the well-formed records:
+// returns false with that size in pt_off[n].
+bool decrypt_one_sk_packed(Engine& eng, const KpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                           int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
+  Timer tm("lsw::decrypt_one_sk_packed");
+  Engine::ArenaScope arena(eng);
+  errors->assign(n, "");
+  if (!ct_off || !pt_off || (n && !ct_blob)) throw RabeError("lsw::decrypt_one_sk_packed: null input");
+  (void)check_offsets(n, ct_off, ct_len, errors);
+  BlobGather gather(eng, ct_blob, ct_len);          // the blob starts for the device now, beside the parsing below (records.h)
+  const std::shared_ptr<const FlatPolicy> flat = flat_policy(sk.policy.first, sk.policy.second);
+  struct Plan {
+    std::string err;
+    struct E { uint32_t ct_row, sk_row; Fr c; };
+    std::vector<E> ent;
+  };
+  std::map<std::string, std::shared_ptr<Plan>> plans;
+  std::mutex plans_mu;
+  FastPlans<Plan> fast_plans;
+  auto plan_of = [&](const std::string& names) -> std::shared_ptr<Plan> {          // names: (u32 length, bytes) per row, as the record holds them
+    std::lock_guard<std::mutex> g(plans_mu);
+    auto it = plans.find(names);
+    if (it != plans.end()) return it->second;
+    auto pl = std::make_shared<Plan>();
+    try {
+      std::vector<std::string> attr;
+      for (size_t at = 0; at < names.size();) {
+        const uint32_t l = get_u32((const uint8_t*)names.data() + at);
+        attr.push_back(names.substr(at + 4, l));
+        at += 4 + (size_t)l;
+      }
+      PrunedList list;
+      if (!calc_pruned(attr, flat->tree, &list)) throw RabeError("Error in lsw/decrypt: attributes do not match policy.");
+      for (const auto& a : list) {
+        if (is_negative(a.first)) throw RabeError("lsw::decrypt_packed: a negative attribute is selected; rabe_lsw_decrypt reproduces the reference's branch");
+        size_t cr = 0, sr = 0, co = 0;
+        while (cr < attr.size() && attr[cr] != a.first) cr++;
+        while (sr < sk.dj.size() && sk.dj[sr].name != a.first) sr++;
+        while (co < flat->leaf_name_col.size() && flat->leaf_name_col[co] != a.second) co++;
+        if (cr == attr.size() || sr == sk.dj.size() || co == flat->leaf_name_col.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
+        pl->ent.push_back({(uint32_t)cr, (uint32_t)sr, flat->leaf_coeff[co]});
+      }
+      if (pl->ent.empty()) throw RabeError("Error in lsw/decrypt: attributes do not match policy.");
+    } catch (const std::exception& ex) {
+      pl->err = ex.what();
+      if (pl->err.empty()) pl->err = "policy error";
+    }
+    plans[names] = pl;
+    return pl;
+  };
+  struct View { const uint8_t* e1; const uint8_t* e2; const uint8_t* first_row; uint32_t rows; std::shared_ptr<Plan> plan; };
+  std::vector<View> v(n);
+  std::vector<Sealed> sealed(n);
+  std::vector<uint8_t> parsed(n, 0);
+  parallel_for(n, [&](size_t i) {
+    if (!(*errors)[i].empty()) return;
+    try {
+      Cursor r{ct_blob + ct_off[i], ct_blob + ct_off[i + 1]};
+      v[i].e1 = r.raw(384);
+      v[i].e2 = r.raw(128);
+      const uint32_t rows = r.u32();
+      if ((size_t)rows * 196 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
+      v[i].rows = rows;
+      v[i].first_row = r.p;
+      std::string names;
+      for (uint32_t y = 0; y < rows; y++) {
+        const auto nm = r.str();
+        names.append(nm.first - 4, (size_t)nm.second + 4);
+        (void)r.raw(192);
+      }
+      sealed[i].len = r.u32();
+      sealed[i].p = r.raw(sealed[i].len);
+      parsed[i] = 1;
+      auto pl = fast_plans.find(names.data(), names.size(), PolicyLanguage::JsonPolicy);
+      if (!pl) { pl = plan_of(names); fast_plans.put(names.data(), names.size(), PolicyLanguage::JsonPolicy, pl); }
+      if (!pl->err.empty()) throw RabeError(pl->err);
+      v[i].plan = pl;
+    } catch (const std::exception& ex) {
+      (*errors)[i] = ex.what();
+      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
+    }
+  });
+  tm.lap("parse + plan");
+  uint64_t need = 0;
+  for (size_t i = 0; i < n; i++) if (parsed[i]) need += sealed[i].len;
+  if (!pt_buf || pt_cap < need) { pt_off[n] = need; return false; }
+  std::vector<size_t> live;
+  std::vector<uint32_t> row_off{0}, attr_off{0}, pair_off{0}, sel_start, sel_sk, sel_ct, group_off{0}, item_group;
+  std::vector<Fr> sel_z;
+  std::map<const Plan*, uint32_t> group_of;
+  size_t max_pairs = 1;
+  for (size_t i = 0; i < n; i++) {
+    if (!(*errors)[i].empty()) continue;
+    live.push_back(i);
+    row_off.push_back(row_off.back() + v[i].rows);
+    attr_off.push_back(3 * row_off.back());
+    const Plan& pl = *v[i].plan;
+    auto it = group_of.find(&pl);
+    if (it == group_of.end()) {
+      it = group_of.insert({&pl, (uint32_t)group_off.size() - 1}).first;
+      for (const auto& e : pl.ent) { sel_sk.push_back(e.sk_row); sel_ct.push_back(3 * e.ct_row); sel_z.push_back(e.c); }
+      group_off.push_back((uint32_t)sel_sk.size());
+    }
+    item_group.push_back(it->second);
+    sel_start.push_back(group_off[it->second]);
+    const uint32_t m = (uint32_t)pl.ent.size();
+    pair_off.push_back(pair_off.back() + m + 1);
+    if ((size_t)m + 1 > max_pairs) max_pairs = m + 1;
+  }
+  const size_t m_items = live.size();
+  std::vector<uint64_t> sealed_off(m_items);
+  std::vector<uint32_t> sealed_len(m_items);
+  DBuf d_out(&eng, m_items * 384 + 4);
+  std::unique_ptr<MemberChecks> mc;
+  std::unique_ptr<WalkedG2> walked;          // read after the open (records.h: retract_item): it and what it refers to outlive the block
+  std::vector<uint32_t> e2_off;
+  DBuf d_e2;
+  if (m_items) {
+    const size_t total = row_off[m_items];
+    DBuf d_e1(&eng, m_items * 384), d_rows(&eng, total * 192 + 4);
+    d_e2 = DBuf(&eng, m_items * 128);
+    std::vector<uint64_t> dst_off(3 * m_items);
+    for (size_t j = 0; j < m_items; j++) {
+      const View& w = v[live[j]];
+      const uint8_t* rec = ct_blob + ct_off[live[j]];
+      sealed_off[j] = (uint64_t)(sealed[live[j]].p - ct_blob);
+      sealed_len[j] = sealed[live[j]].len;
+      dst_off[j] = 384ull * j; dst_off[m_items + j] = 128ull * j; dst_off[2 * m_items + j] = 192ull * row_off[j];
+      int shape = gather.find(w.plan.get());          // the same list of names: the same skeleton
+      if (shape < 0) {
+        std::vector<RecordLayout::Part> parts;
+        parts.push_back({(uint32_t)(w.e1 - rec), 384, 0, 0});
+        parts.push_back({(uint32_t)(w.e2 - rec), 128, 1, 0});
+        Cursor r{w.first_row, ct_blob + ct_off[live[j] + 1]};
+        for (uint32_t y = 0; y < w.rows; y++) { (void)r.str(); parts.push_back({(uint32_t)(r.raw(192) - rec), 192, 2, 192 * y}); }
+        shape = (int)gather.add_shape(w.plan.get(), std::move(parts));
+      }
+      gather.item(ct_off[live[j]], (uint32_t)shape);
+    }
+    tm.lap("shapes");
+    rhip_ctx* cx = eng.ctx();
+    std::vector<uint8_t> kd1;
+    std::string kd2;
+    for (const auto& d : sk.dj) { kd1.insert(kd1.end(), d.d1.begin(), d.d1.end()); kd2.append((const char*)d.d2.data(), 128); }
+    for (size_t j = 0; j <= m_items; j++) e2_off.push_back((uint32_t)j);
+    DBuf d_row_off = up32(eng, row_off), d_attr_off = up32(eng, attr_off), d_pair_off = up32(eng, pair_off), d_sel_start = up32(eng, sel_start),
+         d_sel_sk = up32(eng, sel_sk), d_sel_ct = up32(eng, sel_ct), d_sel_z = up_bytes(eng, flatten_fr(sel_z)), d_group_off = up32(eng, group_off),
+         d_item_group = up32(eng, item_group), d_kd1 = up_bytes(eng, kd1), d_e2_off = up32(eng, e2_off);
+    gather.run({d_e1.ptr(), d_e2.ptr(), d_rows.ptr()}, dst_off);
+    // the key's prepared lines (every D2: 17 KB per row) are a function of the key alone: kept across calls
+    rhip_g2_lines* lines = (rhip_g2_lines*)eng.aux("lsw_sk_d2_lines", kd2, make_sk_d2_lines, &kd2, destroy_e2_lines, 4);
+    if (!trusted) {
+      mc.reset(new MemberChecks(eng));
+      mc->add(1, d_rows.ptr(), total * 3, d_row_off.as<uint32_t>(), m_items, 3);
+      mc->add(3, d_e1.ptr(), m_items);
+      // e2 is the one walking argument of an item (the key's side replays prepared lines): membership out of the decrypt's own Miller
+      // loop; an item whose last pair was skipped gets the stand-alone test (common.h: WalkedG2)
+      if (walk_checks()) walked.reset(new WalkedG2(eng, *mc, d_e2.ptr(), m_items, d_e2_off.as<uint32_t>(), e2_off, 1));
+      else mc->add(2, d_e2.ptr(), m_items);
+    }
+    if (walked) walked->arm();
+    int32_t rc = rhip_lsw_decrypt_batch_one_sk(cx, m_items, max_pairs, pair_off[m_items], sel_sk.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
+                                               d_sel_sk.as<uint32_t>(), d_sel_ct.as<uint32_t>(), d_sel_z.as<rhip_fr>(), group_off.size() - 1,
+                                               d_group_off.as<uint32_t>(), d_item_group.as<uint32_t>(), d_e1.as<rhip_gt>(), d_e2.as<rhip_g2>(),
+                                               d_rows.as<rhip_g1>(), d_attr_off.as<uint32_t>(), d_kd1.as<rhip_g1>(), lines, d_out.as<rhip_gt>());
+    eng.check(rc, "rhip_lsw_decrypt_batch_one_sk");
+    if (mc) {
+      mc->collect();
+      const auto &ok_rows = mc->ok(0), &ok_e1 = mc->ok(1);
+      std::vector<uint8_t> ok_e2(m_items, 1);
+      if (!walked) { const auto& e = mc->ok(2); ok_e2.assign(e.begin(), e.end()); }
+      for (size_t j = 0; j < m_items; j++) {
+        const char* bad = !ok_e1[j] ? "deserialize: e1 is not a member of Gt (FieldError::NotMember)"
+                          : !ok_rows[j] ? "deserialize: a row element is not a point of G1 (FieldError::NotMember)"
+                          : !ok_e2[j] ? "deserialize: e2 is not a member of G2 (FieldError::NotMember)" : nullptr;
+        if (bad) (*errors)[live[j]] = bad;
+      }
+    }
+  }
+  // KDF + AES-GCM open on the device: the decrypted Gt never leaves HBM; plaintext bytes come back in one copy
+  open_sealed_records(eng, n, live, d_out.ptr(), gather.dev_blob(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
+  if (walked) {
+    std::vector<uint8_t> ok_e2;
+    walked->finish(&ok_e2);
+    for (size_t j = 0; j < m_items; j++)
+      if (!ok_e2[j]) retract_item(live[j], "deserialize: e2 is not a member of G2 (FieldError::NotMember)", status, pt_buf, pt_off, errors);
+  }
+  tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
+  return true;
+}
 }  // namespace lsw
 
 // ================================================================================================================= AW11

@@ -528,6 +528,16 @@ def lsw_decrypt_one_ct_dev(eng, n_items, max_pairs, total_pairs, n_sel, d_pair_o
                                                      _p(d_sk_d1), _p(d_sk_d2), _p(d_sk_leaf_off), _p(d_sk_idx), _p(e2_lines), _p(d_out)))
 
 
+def lsw_decrypt_one_sk_dev(eng, n_items, max_pairs, total_pairs, n_sel, d_pair_off, d_sel_start, d_sel_sk_leaf, d_sel_ct_attr, d_sel_coeff, n_groups,
+                           d_group_off, d_item_group, d_ct_e1, d_ct_e2, d_ct_e1j, d_ct_attr_off, d_sk_d1, sk_d2_lines, d_out):
+    """every item is decrypted with the SAME key (rhip_lsw_decrypt_batch_one_sk): the key-side Miller loops replay sk_d2_lines (G2Lines over the
+    key's D2 rows) and sum -c_e D1_e is computed once per selection group (entries of group g: [group_off[g], group_off[g+1]))"""
+    eng._check(eng.lib.rhip_lsw_decrypt_batch_one_sk(eng.ctx, _sz(n_items), _sz(max_pairs), _sz(total_pairs), _sz(n_sel), _p(d_pair_off), _p(d_sel_start),
+                                                     _p(d_sel_sk_leaf), _p(d_sel_ct_attr), _p(d_sel_coeff), _sz(n_groups), _p(d_group_off),
+                                                     _p(d_item_group), _p(d_ct_e1), _p(d_ct_e2), _p(d_ct_e1j), _p(d_ct_attr_off), _p(d_sk_d1),
+                                                     _p(sk_d2_lines), _p(d_out)))
+
+
 class Aw11Pk:
     def __init__(self, eng, g1, g2, egg_alpha, g2_y):
         self.eng = eng

@@ -57,6 +57,12 @@ def decrypt_packed(host, ct, sk_blob, sk_off, out=None, trusted=False):
     return packed_decrypt(host, "rabe_lsw_decrypt_packed", (ct.ptr,), sk_blob, sk_off, out, trusted)
 
 
+def decrypt_one_sk_packed(host, sk, ct_blob, ct_off, out=None, trusted=False):
+    """ONE key against n ciphertexts (a blob of KpAbeCiphertext records, as encrypt_packed writes them) -> (pt_blob, pt_off, status)"""
+    from ..hostlib import packed_decrypt
+    return packed_decrypt(host, "rabe_lsw_decrypt_one_sk_packed", (sk.ptr,), ct_blob, ct_off, out, trusted)
+
+
 def encrypt_packed(host, pk, attr_sets, item_set, pt_blob, pt_off, out=None):
     """n encrypts (rabe_lsw_encrypt_packed): item i under the attribute list attr_sets[item_set[i]]; records = KpAbeCiphertext.
     Returns (ct_blob view, ct_off uint64 [n+1])."""
