@@ -526,6 +526,19 @@ void rhip_ghw11_keys_destroy(rhip_ghw11_keys* keys);
 int32_t rhip_ghw11_keygen_batch(rhip_ctx* ctx, const rhip_ghw11_keys* keys, size_t n_items, size_t n_rows, const uint32_t* dev_item_row_off /*[n_items+1]*/,
                                 const uint32_t* dev_item_hash_off /*[n_items]*/, const rhip_fr* dev_hash, const rhip_fr* dev_r /*[n_items]*/,
                                 rhip_g2* dev_out /*[n_rows]*/);
+/* GHW11 keygen + tkgen (ghw11/mod.rs:123-178) fused, for an authority that issues a user's secret key and the transform key of that user's
+ * proxy in one go: it knows r_i and z_i, so every transform-key element is a fixed-base multiple as well.  Rows as in
+ * rhip_ghw11_keygen_batch, for both outputs:
+ *   dev_out_tk: L_z = g2 * (r z^-1), K_z = g2_alpha * z^-1 + g2_a * (r z^-1), K_x_z = g2 * (h(x) r z^-1)
+ *   dev_out_sk: the rows rhip_ghw11_keygen_batch writes for the same r (that kernel, unchanged); NULL: not computed
+ * z_i^-1 and r_i z_i^-1 are formed on the device (k_ghw11_tk_scalars: one Fr inversion per block); dev_flags[i] = 1 where z_i = 0 (that
+ * item's transform-key rows are then the point at infinity), else 0.  One lane per transform-key row (k_ghw11_provision_rows), row 1 as
+ * two walks on one accumulator.  The 16-bit window table of g2_alpha is built on the first call with a handle and kept in it (134 MB;
+ * rhip_ghw11_keys_create alone does not build it); the build is serialised, so contexts may share the handle. */
+int32_t rhip_ghw11_provision_batch(rhip_ctx* ctx, rhip_ghw11_keys* keys, size_t n_items, size_t n_rows,
+                                   const uint32_t* dev_item_row_off /*[n_items+1]*/, const uint32_t* dev_item_hash_off /*[n_items]*/,
+                                   const rhip_fr* dev_hash, const rhip_fr* dev_r /*[n_items]*/, const rhip_fr* dev_z /*[n_items]*/,
+                                   rhip_g2* dev_out_sk /*[n_rows] or NULL*/, rhip_g2* dev_out_tk /*[n_rows]*/, uint32_t* dev_flags /*[n_items]*/);
 /* BDABE / MKE08 keygen (bdabe/mod.rs:201-222, mke08/mod.rs:185-206) for n_items users under one authority key (MKE08: the master key).
  * rhip_dnf_keys: 8- and 16-bit window tables of p1, g1, p2, g2 and the authority's a1 / a2 (MKE08: msk.g1 / msk.g2).  Item i owns rows
  * 2 i, 2 i + 1 of both outputs: out_g1 = sk.u1 = a1 + p1 * r_i, pk.u1 = g1 * r_i; out_g2 = sk.u2 = a2 + p2 * r_i, pk.u2 = g2 * r_i.

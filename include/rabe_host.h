@@ -331,6 +331,24 @@ int32_t rabe_ghw11_keygen_packed(rabe_host* h, const void* pk, const void* msk, 
 int32_t rabe_ghw11_tkgen_packed(rabe_host* h, size_t n_items, const uint8_t* sk_blob, size_t sk_len, const uint64_t* sk_off /*[n_items+1]*/,
                                 uint32_t flags, int32_t* status /*[n_items]*/,
                                 uint8_t* tk_buf, size_t tk_cap, uint64_t* tk_off /*[n_items+1]*/, uint8_t* rk_buf /*32 n_items*/);
+/* Bulk provisioning for an authority that issues a user's secret key and the transform / retrieve keys of that user's proxy in one go:
+ * BY DEFINITION rabe_ghw11_keygen_packed followed by rabe_ghw11_tkgen_packed on its output, byte for byte and draw for draw (arguments as
+ * rabe_ghw11_keygen_packed; item i's Ghw11SecretKey record at sk_buf + sk_off[i], its Ghw11TransformKey record -- the secret key's layout --
+ * at tk_buf + tk_off[i], its Ghw11RetrieveKey record z_i at rk_buf + 32 i).  sk_off = NULL: transform and retrieve keys only -- sk_buf is
+ * ignored, no secret-key row is computed, the draws are the same.
+ * DRAW ORDER: r_0 .. r_{n-1}, then z_0 .. z_{n-1}: a tape that drives the two calls back to back drives this one.  z = 0 fails the whole call,
+ * as tkgen's inverse().unwrap() does, and writes no record.
+ * The authority knows r and z, so every transform-key element is a fixed-base multiple too (L_z = g2 * (r z^-1), K_z = g2_alpha * z^-1 +
+ * g2_a * (r z^-1), K_x_z = g2 * (h(x) r z^-1)): no parse, no membership pass, no variable-base chain; z^-1 and r z^-1 are formed on the
+ * device, the elements never leave it between the two halves, both record sets are written there.  The key tables are the ones
+ * rabe_ghw11_keygen_packed caches; the window table of g2_alpha is added to them on the first provision call.
+ * tk_off, and sk_off if given, are always filled; returns 1, with nothing drawn, when tk_cap < tk_off[n_items] or sk_cap < sk_off[n_items].
+ * An empty attribute list or an item_set out of range fails the call before any draw.  The staging that held r, z, z^-1 or r z^-1 is zeroed,
+ * on the host and on the device, when the call ends. */
+int32_t rabe_ghw11_provision_packed(rabe_host* h, const void* pk, const void* msk, const char* const* attributes, const size_t* counts,
+                                    size_t n_sets, size_t n_items, const uint32_t* item_set /*[n_items]*/,
+                                    uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off /*[n_items+1] or NULL*/,
+                                    uint8_t* tk_buf, size_t tk_cap, uint64_t* tk_off /*[n_items+1]*/, uint8_t* rk_buf /*32 n_items*/);
 /* `data` of the reference's decrypt_out is the ciphertext's data field: pass the ciphertext object */
 int32_t rabe_ghw11_decrypt_out(rabe_host* h, const void* tct, const void* rk, const void* ct, uint8_t** plaintext, size_t* len);
 int32_t rabe_ghw11_decrypt_out_gt(rabe_host* h, const void* tct, const void* rk, uint8_t out_gt[384]);

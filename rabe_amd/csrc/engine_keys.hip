@@ -1,12 +1,14 @@
 // engine_keys.hip -- bulk key issuing: the GHW11 keygen row kernel (fixed-base) and the variable-base G2 multiplication over rows that
 // share a scalar (four-way split over the twist endomorphism, bn254/gls4.h), which serves ghw11::tkgen; the user-key row kernels of
 // BDABE / MKE08 (fixed-base) and the variable-base G1 multiplication over rows that share a scalar (GLV, bn254/curve.h), which with the G2
-// one serves their secret attribute keys.
+// one serves their secret attribute keys; GHW11's fused keygen + tkgen for an authority that knows r and z (fixed-base again: an Fr kernel
+// that inverts the z of a block together, and a row kernel over a third window table).
 //
 // A translation unit of its own: docs/rr29.md records that adding a kernel to a unit can move its neighbours' register allocation, and
 // engine_jobs.hip holds the kernels BASELINE configs 3 - 5 time.
 #include "engine_internal.h"
 #include "bn254/gls4.h"
+#include <mutex>
 
 // Montgomery records are 128 bytes and 16-byte aligned: 128-bit accesses
 __device__ __forceinline__ Fp ld_fp_q(const uint4* p) {
@@ -44,18 +46,24 @@ struct rhip_ghw11_keys {
   rhip_g2_table* g2;
   rhip_g2_table* g2_a;
   rhip_g2* g2_alpha;          // device, wire form
+  // rhip_ghw11_provision_batch alone walks a table of g2_alpha: built on its first call (134 MB, a launch over 2^20 entries -- a process
+  // that only issues secret keys pays neither), from the host copy, under the mutex (the lanes of an engine share the handle)
+  rhip_g2 g2_alpha_host;
+  std::mutex mu;
+  rhip_g2_table* g2_alpha_tbl;
 };
 extern "C" void rhip_ghw11_keys_destroy(rhip_ghw11_keys* k) {
   if (!k) return;
   rhip_g2_table_destroy(k->g2);
   rhip_g2_table_destroy(k->g2_a);
+  rhip_g2_table_destroy(k->g2_alpha_tbl);
   if (k->g2_alpha) (void)hipFree(k->g2_alpha);
   delete k;
 }
 extern "C" int32_t rhip_ghw11_keys_create(rhip_ctx* ctx, const rhip_g2* g2, const rhip_g2* g2_a, const rhip_g2* g2_alpha, rhip_ghw11_keys** out) {
   if (!ctx || !g2 || !g2_a || !g2_alpha || !out) return RHIP_ERR_ARG;
   *out = nullptr;
-  rhip_ghw11_keys* k = new rhip_ghw11_keys{ctx, nullptr, nullptr, nullptr};
+  rhip_ghw11_keys* k = new rhip_ghw11_keys{ctx, nullptr, nullptr, nullptr, *g2_alpha, {}, nullptr};
   int32_t rc = rhip_g2_table_create(ctx, g2, &k->g2);
   if (!rc) rc = rhip_g2_table_add_w16(ctx, k->g2);
   if (!rc) rc = rhip_g2_table_create(ctx, g2_a, &k->g2_a);
@@ -102,6 +110,192 @@ extern "C" int32_t rhip_ghw11_keygen_batch(rhip_ctx* ctx, const rhip_ghw11_keys*
   if (!item_row_off || !item_hash_off || !hash || !r || !out) return RHIP_ERR_ARG;
   KLAUNCH(ctx, "k_ghw11_keygen_rows", k_ghw11_keygen_rows, dim3(blocks_for(n_rows, 128)), dim3(128), 0, ctx->stream, (const G2M*)keys->g2->dev16,
           (const G2M*)keys->g2_a->dev16, (const rhip_g2*)keys->g2_alpha, n_items, n_rows, item_row_off, item_hash_off, hash, r, out);
+  return RHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ GHW11 keygen + tkgen, r and z known
+// block_batch_inverse_n (engine_internal.h) over Fr: every thread of the NT = 64 E thread block contributes one non-zero scalar and gets
+// its inverse back for ONE field inversion, computed by wave 0 on a wave-uniform value.  lds: 2 x 8 x NT words.  All NT threads must call.
+__device__ __forceinline__ Fr shfl_up_fr(const Fr& x, int d) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = (uint32_t)__shfl_up((int)x.v[i], d);
+  return r;
+}
+__device__ __forceinline__ Fr shfl_down_fr(const Fr& x, int d) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = (uint32_t)__shfl_down((int)x.v[i], d);
+  return r;
+}
+__device__ __forceinline__ Fr shfl_fr(const Fr& x, int src) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = (uint32_t)__shfl((int)x.v[i], src);
+  return r;
+}
+__device__ __forceinline__ Fr sel_fr(bool c, const Fr& a, const Fr& b) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = c ? a.v[i] : b.v[i];
+  return r;
+}
+template <int NT>
+__device__ __noinline__ Fr block_batch_inverse_fr(uint32_t* lds, const Fr& mine) {
+  uint32_t (*val)[NT] = (uint32_t (*)[NT])lds;
+  uint32_t (*pre)[NT] = (uint32_t (*)[NT])(lds + 8 * NT);
+  constexpr int E = NT / 64;
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int i = 0; i < 8; i++) val[i][tid] = mine.v[i];
+  __syncthreads();
+  if (tid < 64) {
+    Fr run;
+#pragma unroll
+    for (int i = 0; i < 8; i++) run.v[i] = val[i][tid];
+#pragma unroll 1
+    for (int e = 1; e < E; e++) {
+      Fr v;
+#pragma unroll
+      for (int i = 0; i < 8; i++) { pre[i][tid + 64 * (e - 1)] = run.v[i]; v.v[i] = val[i][tid + 64 * e]; }
+      run = mul(run, v);
+    }
+    Fr prefix = run, suffix = run;
+#pragma unroll 1
+    for (int d = 1; d < 64; d <<= 1) {
+      const Fr u = shfl_up_fr(prefix, d);
+      const Fr w = shfl_down_fr(suffix, d);
+      const Fr pu = mul(prefix, u);
+      const Fr sw = mul(suffix, w);
+      prefix = sel_fr(tid >= d, pu, prefix);
+      suffix = sel_fr(tid + d < 64, sw, suffix);
+    }
+    const Fr total_inv = inv(shfl_fr(prefix, 63));
+    Fr ex_pre = shfl_up_fr(prefix, 1), ex_suf = shfl_down_fr(suffix, 1);
+    ex_pre = sel_fr(tid >= 1, ex_pre, one<FrParams>());
+    ex_suf = sel_fr(tid < 63, ex_suf, one<FrParams>());
+    Fr inv_run = mul(total_inv, mul(ex_pre, ex_suf));       // 1 / (product of this lane's E elements)
+#pragma unroll 1
+    for (int e = E - 1; e >= 1; e--) {
+      Fr v, p;
+#pragma unroll
+      for (int i = 0; i < 8; i++) { v.v[i] = val[i][tid + 64 * e]; p.v[i] = pre[i][tid + 64 * (e - 1)]; }
+      const Fr r = mul(inv_run, p);                          // 1 / v_e
+      inv_run = mul(inv_run, v);                             // 1 / (v_0 .. v_{e-1})
+#pragma unroll
+      for (int i = 0; i < 8; i++) val[i][tid + 64 * e] = r.v[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) val[i][tid] = inv_run.v[i];
+  }
+  __syncthreads();
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = val[i][tid];
+  return r;
+}
+// one lane per item: zinv[i] = z_i^-1, rz[i] = r_i z_i^-1 (canonical), one inversion per block.  z_i = 0 sets flags[i] and gives
+// zinv[i] = rz[i] = 0; in the block's product it is replaced by one, as are the lanes past n, so its neighbours' inverses stand.
+__global__ void __launch_bounds__(128, RB_MIN_WAVES) k_ghw11_tk_scalars(size_t n, const rhip_fr* r, const rhip_fr* z, rhip_fr* zinv, rhip_fr* rz,
+                                                                       uint32_t* flags) {
+  __shared__ uint32_t sh[2 * 8 * 128];
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = i < n;
+  uint32_t zz[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (active) ld_scalar(zz, z + i);          // below the group order: zero is the word 0
+  const bool z0 = (zz[0] | zz[1] | zz[2] | zz[3] | zz[4] | zz[5] | zz[6] | zz[7]) == 0;
+  Fr zi = block_batch_inverse_fr<128>(sh, z0 ? one<FrParams>() : to_mont<FrParams>(zz));
+  if (!active) return;
+  if (z0) zi = zero<FrParams>();
+  flags[i] = z0 ? 1u : 0u;
+  store_fr(zinv[i].l, zi);
+  store_fr(rz[i].l, mul(load_fr(r[i].l), zi));
+}
+// two fixed-base products on one accumulator: tbl1 * k1 + tbl2 * k2 over the 16-bit windows of both tables (table_mul_g2_w16 twice, without
+// leaving Jacobian form in between); a lane with k2 = 0 adds nothing in the second half
+__device__ __forceinline__ G2Jac table_mul2_g2_w16(const G2M* tbl1, const uint32_t k1[8], const G2M* tbl2, const uint32_t k2[8]) {
+  G2Jac acc = jac_inf<Fp2>();
+#pragma unroll 1
+  for (int s = 0; s < 2 * TBL16_WINDOWS; s++) {
+    const bool second = s >= TBL16_WINDOWS;
+    const int w = s & (TBL16_WINDOWS - 1);
+    uint32_t word;
+    switch (w >> 1) {
+      case 0: word = second ? k2[0] : k1[0]; break;
+      case 1: word = second ? k2[1] : k1[1]; break;
+      case 2: word = second ? k2[2] : k1[2]; break;
+      case 3: word = second ? k2[3] : k1[3]; break;
+      case 4: word = second ? k2[4] : k1[4]; break;
+      case 5: word = second ? k2[5] : k1[5]; break;
+      case 6: word = second ? k2[6] : k1[6]; break;
+      default: word = second ? k2[7] : k1[7]; break;
+    }
+    const uint32_t d = (w & 1) ? (word >> 16) : (word & 0xffffu);
+    if (d) acc = jac_add_aff(acc, ld_g2_m((second ? tbl2 : tbl1) + (size_t)w * TBL16_DIGITS + (d - 1)));
+  }
+  return acc;
+}
+// one lane per transform-key element (ghw11/mod.rs:156-178 on the elements of :123-152), rows as in k_ghw11_keygen_rows; with
+// u = z^-1 and v = r z^-1 of the row's item (k_ghw11_tk_scalars):
+//   row 0: L_z   = g2 * v
+//   row 1: K_z   = g2_alpha * u + g2_a * v          (two walks on one accumulator)
+//   row y: K_x_z = g2 * (h(x) v),  h(x) = hash[item_hash_off[i] + y - 2]
+// One inversion per block.
+__global__ void __launch_bounds__(128, RB_G2_WAVES) k_ghw11_provision_rows(const G2M* g2_tbl, const G2M* g2a_tbl, const G2M* alpha_tbl, size_t n_items,
+                                                                          size_t n_rows, const uint32_t* item_row_off, const uint32_t* item_hash_off,
+                                                                          const rhip_fr* hash, const rhip_fr* zinv, const rhip_fr* rz, rhip_g2* out) {
+  __shared__ uint32_t sh[2 * 8 * 128];
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = t < n_rows;
+  if (!active) t = n_rows - 1;        // inactive lanes shadow the last row (no stores) and still join the block inversion
+  const size_t item = owner_of(item_row_off, n_items, t);
+  const uint32_t row = (uint32_t)(t - item_row_off[item]);
+  uint32_t k1[8], k2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (row == 0) {
+    ld_scalar(k1, rz + item);
+  } else if (row == 1) {
+    ld_scalar(k1, zinv + item);
+    ld_scalar(k2, rz + item);
+  } else {
+    const Fr e = mul_inl(load_fr(hash[(size_t)item_hash_off[item] + (row - 2)].l), load_fr(rz[item].l));
+    from_mont_inl<FrParams>(k1, e);
+  }
+  const G2Jac a = table_mul2_g2_w16(row == 1 ? alpha_tbl : g2_tbl, k1, g2a_tbl, k2);
+  store_g2_block128(sh, active, out + t, a);
+}
+extern "C" int32_t rhip_ghw11_provision_batch(rhip_ctx* ctx, rhip_ghw11_keys* keys, size_t n_items, size_t n_rows, const uint32_t* item_row_off,
+                                              const uint32_t* item_hash_off, const rhip_fr* hash, const rhip_fr* r, const rhip_fr* z, rhip_g2* out_sk,
+                                              rhip_g2* out_tk, uint32_t* flags) {
+  NEED(ctx);
+  if (!keys) return RHIP_ERR_ARG;
+  if (!n_items || !n_rows) return RHIP_OK;
+  if (!item_row_off || !item_hash_off || !hash || !r || !z || !out_tk || !flags) return RHIP_ERR_ARG;
+  {
+    std::lock_guard<std::mutex> lock(keys->mu);          // the build waits for its stream: the table is whole when the lock is released
+    if (!keys->g2_alpha_tbl) {
+      rhip_g2_table* tbl = nullptr;
+      int32_t rc = rhip_g2_table_create(ctx, &keys->g2_alpha_host, &tbl);
+      if (!rc) rc = rhip_g2_table_add_w16(ctx, tbl);
+      if (rc) { rhip_g2_table_destroy(tbl); return rc; }
+      keys->g2_alpha_tbl = tbl;
+    }
+  }
+  if (out_sk) {
+    const int32_t rc = rhip_ghw11_keygen_batch(ctx, keys, n_items, n_rows, item_row_off, item_hash_off, hash, r, out_sk);
+    if (rc) return rc;
+  }
+  // z^-1 | r z^-1 per item: the per-item slot of rhip_g2_mul_rows (both are scratch of key issuing, in stream order on this context),
+  // zeroed behind the row kernel -- the pair is the retrieve key and the key's r in another form
+  void* work = nullptr;
+  const int32_t rc = rhip_ensure_work(ctx, 16, 2 * n_items * sizeof(rhip_fr), &work);
+  if (rc) return rc;
+  rhip_fr* zinv = (rhip_fr*)work;
+  rhip_fr* rz = zinv + n_items;
+  KLAUNCH(ctx, "k_ghw11_tk_scalars", k_ghw11_tk_scalars, dim3(blocks_for(n_items, 128)), dim3(128), 0, ctx->stream, n_items, r, z, zinv, rz, flags);
+  KLAUNCH(ctx, "k_ghw11_provision_rows", k_ghw11_provision_rows, dim3(blocks_for(n_rows, 128)), dim3(128), 0, ctx->stream,
+          (const G2M*)keys->g2->dev16, (const G2M*)keys->g2_a->dev16, (const G2M*)keys->g2_alpha_tbl->dev16, n_items, n_rows, item_row_off,
+          item_hash_off, hash, (const rhip_fr*)zinv, (const rhip_fr*)rz, out_tk);
+  HIP_TRY(ctx, hipMemsetAsync(work, 0, 2 * n_items * sizeof(rhip_fr), ctx->stream));
   return RHIP_OK;
 }
 

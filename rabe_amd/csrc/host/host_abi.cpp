@@ -1929,6 +1929,14 @@ int32_t rabe_ghw11_tkgen_packed(rabe_host* h, size_t n_items, const uint8_t* sk_
   return 0;
   GUARD_END(h)
 }
+int32_t rabe_ghw11_provision_packed(rabe_host* h, const void* pk, const void* msk, const char* const* attributes, const size_t* counts, size_t n_sets,
+                                    size_t n_items, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off, uint8_t* tk_buf, size_t tk_cap,
+                                    uint64_t* tk_off, uint8_t* rk_buf) {
+  GUARD_BEGIN
+  return ghw11::provision_packed(h->eng, h->rng(), *(const ghw11::Ghw11PublicKey*)pk, *(const ghw11::Ghw11MasterKey*)msk,
+                                 attr_sets(attributes, counts, n_sets), n_items, item_set, sk_buf, sk_cap, sk_off, tk_buf, tk_cap, tk_off, rk_buf) ? 0 : 1;
+  GUARD_END(h)
+}
 int32_t rabe_ghw11_decrypt_out(rabe_host* h, const void* tct, const void* rk, const void* ct, uint8_t** plaintext, size_t* len) {
   GUARD_BEGIN
   return give_bytes(ghw11::decrypt_out(h->eng, *(const ghw11::Ghw11TransformCiphertext*)tct, *(const ghw11::Ghw11RetrieveKey*)rk,

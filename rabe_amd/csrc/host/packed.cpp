@@ -2544,6 +2544,82 @@ bool tkgen_packed(Engine& eng, Rng& rng, size_t n, const uint8_t* sk_blob, size_
   tm.lap("assembly");
   return true;
 }
+
+// keygen_packed followed by tkgen_packed on its output, for an authority that issues both and so knows r and z: every transform-key element
+// is a fixed-base multiple as well -- L_z = g2 * (r z^-1), K_z = g2_alpha * z^-1 + g2_a * (r z^-1), K_x_z = g2 * (h(x) r z^-1) -- so there
+// is no parse, no membership pass and no variable-base chain, and z^-1, r z^-1 are formed on the device (rhip_ghw11_provision_batch).  Draw
+// order: r_0 .. r_{n-1}, then z_0 .. z_{n-1} (the two calls back to back).  Both record sets are written on the device from one template per
+// list (the transform key has the secret key's layout); rk = z.  sk_off == nullptr: no secret-key rows, the same draws.  z = 0 fails the call
+// before any record is written.
+bool provision_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw11MasterKey& msk, const std::vector<std::vector<std::string>>& sets,
+                      size_t n, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off, uint8_t* tk_buf, size_t tk_cap,
+                      uint64_t* tk_off, uint8_t* rk_buf) {
+  Timer tm("ghw11::provision_packed");
+  Engine::ArenaScope arena(eng);
+  eng.scrub_when_done();          // r, z, z^-1 and r z^-1 pass through the staging buffers
+  const bool want_sk = sk_off != nullptr;
+  if (!tk_off || (n && (!item_set || !rk_buf))) throw RabeError("ghw11::provision_packed: null input");
+  for (size_t i = 0; i < n; i++) if (item_set[i] >= sets.size()) throw RabeError("ghw11::provision_packed: item_set out of range");
+  std::vector<size_t> fixed(sets.size());
+  std::vector<uint32_t> hash_off(sets.size() + 1, 0);
+  std::vector<Fr> hashes;
+  for (size_t s = 0; s < sets.size(); s++) {
+    if (sets[s].empty()) throw RabeError("ghw11::provision_packed: an empty attribute list (ghw11::keygen returns None for it)");
+    fixed[s] = 128 + 128 + 4;
+    for (const auto& a : sets[s]) { fixed[s] += 4 + a.size() + 128; hashes.push_back(sha3_hash_fr(a)); }
+    hash_off[s + 1] = (uint32_t)hashes.size();
+  }
+  tk_off[0] = 0;
+  for (size_t i = 0; i < n; i++) tk_off[i + 1] = tk_off[i] + fixed[item_set[i]];
+  if (want_sk) memcpy(sk_off, tk_off, (n + 1) * sizeof(uint64_t));
+  if (n && (!tk_buf || tk_cap < tk_off[n] || (want_sk && (!sk_buf || sk_cap < sk_off[n])))) return false;
+  if (!n) return true;
+  std::vector<uint32_t> row_off(n + 1, 0), item_hash(n);
+  for (size_t i = 0; i < n; i++) {
+    const uint64_t next = (uint64_t)row_off[i] + 2 + sets[item_set[i]].size();
+    if (next > 0xFFFFFFF0ull) throw RabeError("ghw11::provision_packed: more than 2^32 key elements in one call");
+    row_off[i + 1] = (uint32_t)next;
+    item_hash[i] = hash_off[item_set[i]];
+  }
+  const size_t total = row_off[n];
+  uint8_t* h_rz = eng.pinned(0, 2 * n * 32 + n * 4 + 32);          // r | z | the flags coming back
+  draw_items(rng, 2 * n, [&](Rng& r, size_t i) { const Fr v = r.next_fr(); memcpy(h_rz + 32 * i, v.l, 32); });
+  tm.lap("draws");
+  std::string key((const char*)pk.g2.data(), 128);
+  key.append((const char*)pk.g2_a.data(), 128).append((const char*)msk.g2_alpha.data(), 128);
+  const KeysArg ka{&pk, &msk};
+  rhip_ghw11_keys* keys = (rhip_ghw11_keys*)eng.aux("ghw11_keys", key, make_keys, &ka, destroy_keys, 4);
+  rhip_ctx* cx = eng.ctx();
+  DBuf d_rz(&eng, 2 * n * 32), d_flags(&eng, n * 4), d_row_off = up32(eng, row_off), d_item_hash = up32(eng, item_hash),
+      d_hash = up_bytes(eng, flatten_fr(hashes)), d_tk(&eng, total * 128 + 4), d_sk;
+  if (want_sk) d_sk = DBuf(&eng, total * 128 + 4);
+  eng.check(rhip_upload_async(cx, d_rz.ptr(), h_rz, 2 * n * 32), "upload");
+  eng.check(rhip_ghw11_provision_batch(cx, keys, n, total, d_row_off.as<uint32_t>(), d_item_hash.as<uint32_t>(), d_hash.as<rhip_fr>(), d_rz.as<rhip_fr>(),
+                                       d_rz.as<rhip_fr>() + n, want_sk ? d_sk.as<rhip_g2>() : nullptr, d_tk.as<rhip_g2>(), d_flags.as<uint32_t>()),
+            "rhip_ghw11_provision_batch");
+  uint8_t* h_flags = h_rz + 2 * n * 32;
+  eng.check(rhip_download_async(cx, h_flags, d_flags.ptr(), n * 4), "download");
+  std::vector<RecordLayout> layouts(sets.size());
+  for (size_t s = 0; s < sets.size(); s++) {
+    RecordLayout& L = layouts[s];
+    L.src(0, 128, 128);          // k / k_z: row 1
+    L.src(0, 0, 128);            // l / l_z: row 0
+    L.u32((uint32_t)sets[s].size());
+    for (size_t y = 0; y < sets[s].size(); y++) { L.str(sets[s][y]); L.src(0, (uint32_t)(128 * (2 + y)), 128); }
+    if (L.bytes() != fixed[s]) throw RabeError("ghw11::provision_packed: record layout and size disagree");
+  }
+  std::vector<uint64_t> src_off(n);
+  for (size_t i = 0; i < n; i++) src_off[i] = 128ull * row_off[i];
+  eng.check(rhip_sync(cx), "rhip_sync");
+  for (size_t i = 0; i < n; i++)
+    if (get_u32(h_flags + 4 * i)) throw std::runtime_error("called `Option::unwrap()` on a `None` value (Fr::inverse of zero)");
+  tm.lap("device: scalars, rows");
+  if (want_sk) emit_plain_records(eng, layouts, n, item_set, {d_sk.ptr()}, src_off, sk_off, sk_buf);
+  emit_plain_records(eng, layouts, n, item_set, {d_tk.ptr()}, src_off, tk_off, tk_buf);
+  memcpy(rk_buf, h_rz + n * 32, n * 32);
+  tm.lap("device: records; copies out");
+  return true;
+}
 }  // namespace ghw11
 
 // ================================================================================================ BDABE / MKE08 packed encrypt

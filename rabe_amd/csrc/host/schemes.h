@@ -211,6 +211,11 @@ bool keygen_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw11M
                    const uint32_t* item_set, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
 bool tkgen_packed(Engine& eng, Rng& rng, size_t n, const uint8_t* sk_blob, size_t sk_len, const uint64_t* sk_off, bool trusted, int32_t* status,
                   uint8_t* tk_buf, size_t tk_cap, uint64_t* tk_off, uint8_t* rk_buf, std::vector<std::string>* errors);
+// keygen_packed followed by tkgen_packed on its output, fused for an authority that knows r and z (packed.cpp): draws r_0 .. r_{n-1}, then
+// z_0 .. z_{n-1}; sk_off == nullptr: transform and retrieve keys only (same draws); false = a capacity too small, nothing drawn
+bool provision_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw11MasterKey& msk, const std::vector<std::vector<std::string>>& sets,
+                      size_t n, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off, uint8_t* tk_buf, size_t tk_cap,
+                      uint64_t* tk_off, uint8_t* rk_buf);
 Gt decrypt_out_gt(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11RetrieveKey& rk);
 Bytes decrypt_out(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11RetrieveKey& rk, const Bytes& data);
 }  // namespace ghw11

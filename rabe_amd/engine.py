@@ -209,6 +209,47 @@ class Engine:
         self._check(self.lib.rhip_g1_mul_rows(self.ctx, ctypes.c_size_t(n_rows), doff.ptr, dp.ptr, ctypes.c_size_t(n_items), dk.ptr, out.ptr))
         raw = self.download(out, n_rows * G1)
         return [raw[i * G1:(i + 1) * G1] for i in range(n_rows)]
+
+    def _ghw11_rows_in(self, what, item_row_off, item_hash_off, hashes, per_item):
+        n_items = len(item_hash_off)
+        if len(item_row_off) != n_items + 1 or item_row_off[0] != 0 or any(len(x) != n_items for x in per_item):
+            raise ValueError("%s: item_row_off must hold len(item_hash_off) + 1 offsets from 0, and one scalar per item" % what)
+        for i in range(n_items):
+            cnt = item_row_off[i + 1] - item_row_off[i] - 2
+            if cnt < 1 or item_hash_off[i] + cnt > len(hashes):
+                raise ValueError("%s: item %d needs L, K and at least one attribute row, with its hashes inside `hashes`" % (what, i))
+        return n_items, (item_row_off[-1] if n_items else 0)
+
+    def ghw11_keygen_dev(self, keys, item_row_off, item_hash_off, hashes, r):
+        """rhip_ghw11_keygen_batch on host bytes: the rows L, K, K_x... of every item under `keys` (Ghw11Keys), 128 bytes each"""
+        n_items, n_rows = self._ghw11_rows_in("ghw11_keygen_dev", item_row_off, item_hash_off, hashes, [r])
+        if not n_rows:
+            return []
+        doff, dho, dh, dr = self.upload_u32(item_row_off), self.upload_u32(item_hash_off), self.upload(b"".join(hashes)), self.upload(b"".join(r))
+        out = self.alloc(n_rows * G2)
+        self._check(self.lib.rhip_ghw11_keygen_batch(self.ctx, keys.h, ctypes.c_size_t(n_items), ctypes.c_size_t(n_rows), doff.ptr, dho.ptr, dh.ptr,
+                                                     dr.ptr, out.ptr))
+        raw = self.download(out, n_rows * G2)
+        return [raw[i * G2:(i + 1) * G2] for i in range(n_rows)]
+
+    def ghw11_provision_dev(self, keys, item_row_off, item_hash_off, hashes, r, z, want_sk=True):
+        """rhip_ghw11_provision_batch on host bytes: (sk_rows or None, tk_rows, flags) -- the secret-key rows of ghw11_keygen_dev, the
+        transform-key rows L_z = g2 * (r / z), K_z = g2_alpha / z + g2_a * (r / z), K_x_z = g2 * (h(x) r / z) in the same layout, and
+        flags[i] = 1 where z[i] = 0.  The first call with `keys` builds its window table of g2_alpha."""
+        n_items, n_rows = self._ghw11_rows_in("ghw11_provision_dev", item_row_off, item_hash_off, hashes, [r, z])
+        if not n_rows:
+            return ([] if want_sk else None), [], []
+        doff, dho, dh = self.upload_u32(item_row_off), self.upload_u32(item_hash_off), self.upload(b"".join(hashes))
+        dr, dz = self.upload(b"".join(r)), self.upload(b"".join(z))
+        sk = self.alloc(n_rows * G2) if want_sk else None
+        tk, fl = self.alloc(n_rows * G2), self.alloc(4 * n_items)
+        self._check(self.lib.rhip_ghw11_provision_batch(self.ctx, keys.h, ctypes.c_size_t(n_items), ctypes.c_size_t(n_rows), doff.ptr, dho.ptr, dh.ptr,
+                                                        dr.ptr, dz.ptr, sk.ptr if want_sk else None, tk.ptr, fl.ptr))
+        rows = lambda raw: [raw[i * G2:(i + 1) * G2] for i in range(n_rows)]
+        flags = self.download(fl, 4 * n_items)
+        return (rows(self.download(sk, n_rows * G2)) if want_sk else None), rows(self.download(tk, n_rows * G2)), \
+            [int.from_bytes(flags[4 * i:4 * i + 4], "little") for i in range(n_items)]
+
     def gt_mul(self, a, b): return self._elem("rhip_gt_mul", len(a), [a, b], GT)
     def gt_inv(self, a): return self._elem("rhip_gt_inv", len(a), [a], GT)
     def gt_pow(self, a, k): return self._elem("rhip_gt_pow", len(a), [a, k], GT)
@@ -335,6 +376,20 @@ class Ac17Pk:
     def destroy(self):
         if self.h:
             self.eng.lib.rhip_ac17_pk_destroy(self.h)
+            self.h = None
+
+
+class Ghw11Keys:
+    """Device tables of the G2 side of a GHW11 key pair (rhip_ghw11_keys: g2, g2_a, the master key's g2_alpha), 128 host bytes each."""
+
+    def __init__(self, eng, g2, g2_a, g2_alpha):
+        self.eng = eng
+        self.h = ctypes.c_void_p()
+        eng._check(eng.lib.rhip_ghw11_keys_create(eng.ctx, bytes(g2), bytes(g2_a), bytes(g2_alpha), ctypes.byref(self.h)))
+
+    def destroy(self):
+        if self.h:
+            self.eng.lib.rhip_ghw11_keys_destroy(self.h)
             self.h = None
 
 

@@ -145,3 +145,41 @@ def tkgen_packed(host, sk_blob, sk_off, trusted=False):
     host.call("rabe_ghw11_tkgen_packed", ctypes.c_size_t(n), _np_ptr(sk), ctypes.c_size_t(sk.size), _np_ptr(so),
               ctypes.c_uint32(PACKED_TRUSTED if trusted else 0), _np_ptr(status), _np_ptr(buf), ctypes.c_size_t(buf.size), _np_ptr(to), _np_ptr(rk))
     return buf[:int(to[n])], to, rk[:n], status[:n]
+
+
+def provision_packed(host, pk, msk, sets, item_set, want_sk=True):
+    """n users and their proxies provisioned in one call (rabe_ghw11_provision_packed): by definition keygen_packed followed by tkgen_packed
+    on its output -- draws r_0 .. r_{n-1}, then z_0 .. z_{n-1} -- for an authority that issues both, so every element is a fixed-base
+    multiple and nothing leaves the device in between.  sets = distinct attribute lists, item_set[i] indexes them.  Returns (sk_blob, sk_off,
+    tk_blob, tk_off, rk): the Ghw11SecretKey records (None, None with want_sk=False: not computed, same draws), the Ghw11TransformKey
+    records, and rk: numpy uint8 [n, 32], row i = the Ghw11RetrieveKey record z_i.  An empty attribute list or an item_set out of range is
+    refused here, before the device is touched."""
+    import numpy as np
+    from ..hostlib import _check, _np_ptr
+    sets = [list(s_) for s_ in sets]
+    for s_ in sets:
+        if not s_:
+            raise ValueError("provision_packed: an empty attribute list (ghw11::keygen returns None for it)")
+    n = len(item_set)
+    if any(not 0 <= int(s_) < len(sets) for s_ in item_set):
+        raise ValueError("provision_packed: item_set out of range")
+    arr, _ = _strs([a for s_ in sets for a in s_])
+    counts = (ctypes.c_size_t * max(len(sets), 1))(*[len(s_) for s_ in sets])
+    it = np.ascontiguousarray(item_set, dtype=np.uint32)
+    so = np.zeros(n + 1, dtype=np.uint64) if want_sk else None
+    to = np.zeros(n + 1, dtype=np.uint64)
+    rk = np.zeros((max(n, 1), 32), dtype=np.uint8)
+    sk_buf = tk_buf = np.empty(0, dtype=np.uint8)
+    for _ in range(2):
+        rc = host.lib.rabe_ghw11_provision_packed(host.h, pk.ptr, msk.ptr, arr, counts, ctypes.c_size_t(len(sets)), ctypes.c_size_t(n), _np_ptr(it),
+                                                  _np_ptr(sk_buf), ctypes.c_size_t(sk_buf.size), _np_ptr(so) if want_sk else None,
+                                                  _np_ptr(tk_buf), ctypes.c_size_t(tk_buf.size), _np_ptr(to), _np_ptr(rk))
+        if rc != 1:
+            break
+        tk_buf = np.empty(int(to[n]), dtype=np.uint8)
+        if want_sk:
+            sk_buf = np.empty(int(so[n]), dtype=np.uint8)
+    _check(rc, host.h)
+    if not want_sk:
+        return None, None, tk_buf[:int(to[n])], to, rk[:n]
+    return sk_buf[:int(so[n])], so, tk_buf[:int(to[n])], to, rk[:n]
