@@ -250,6 +250,18 @@ class Engine:
         return (rows(self.download(sk, n_rows * G2)) if want_sk else None), rows(self.download(tk, n_rows * G2)), \
             [int.from_bytes(flags[4 * i:4 * i + 4], "little") for i in range(n_items)]
 
+    def dnf_keygen_dev(self, keys, r):
+        """rhip_dnf_keygen_batch on host bytes: (g1_rows, g2_rows) under `keys` (DnfKeys) -- item i owns rows 2 i, 2 i + 1 of both:
+        sk.u1 = a1 + p1 * r_i, pk.u1 = g1 * r_i (64 bytes each) and sk.u2 = a2 + p2 * r_i, pk.u2 = g2 * r_i (128 bytes each)"""
+        n_items = len(r)
+        if not n_items:
+            return [], []
+        dr = self.upload(b"".join(r))
+        o1, o2 = self.alloc(2 * n_items * G1), self.alloc(2 * n_items * G2)
+        self._check(self.lib.rhip_dnf_keygen_batch(self.ctx, keys.h, ctypes.c_size_t(n_items), dr.ptr, o1.ptr, o2.ptr))
+        raw1, raw2 = self.download(o1, 2 * n_items * G1), self.download(o2, 2 * n_items * G2)
+        return [raw1[i * G1:(i + 1) * G1] for i in range(2 * n_items)], [raw2[i * G2:(i + 1) * G2] for i in range(2 * n_items)]
+
     def gt_mul(self, a, b): return self._elem("rhip_gt_mul", len(a), [a, b], GT)
     def gt_inv(self, a): return self._elem("rhip_gt_inv", len(a), [a], GT)
     def gt_pow(self, a, k): return self._elem("rhip_gt_pow", len(a), [a, k], GT)
@@ -393,6 +405,21 @@ class Ghw11Keys:
             self.h = None
 
 
+class DnfKeys:
+    """Device tables of a BDABE authority's / the MKE08 master's user-key bases (rhip_dnf_keys: p1, g1, a1 in G1 with 64 host bytes each,
+    p2, g2, a2 in G2 with 128)."""
+
+    def __init__(self, eng, p1, g1, p2, g2, a1, a2):
+        self.eng = eng
+        self.h = ctypes.c_void_p()
+        eng._check(eng.lib.rhip_dnf_keys_create(eng.ctx, bytes(p1), bytes(g1), bytes(p2), bytes(g2), bytes(a1), bytes(a2), ctypes.byref(self.h)))
+
+    def destroy(self):
+        if self.h:
+            self.eng.lib.rhip_dnf_keys_destroy(self.h)
+            self.h = None
+
+
 def _sz(n):
     return ctypes.c_size_t(int(n))
 
@@ -518,6 +545,29 @@ def bsw_encrypt_dev(eng, pk, n_items, total_leaves, d_item_leaf_off, d_item_tree
                                               _p(d_item_tree_gate), _p(dtt.path_off), _p(dtt.path_gate), _p(dtt.path_x), _p(dtt.gate_k),
                                               _p(dtt.gate_coef_off), _p(dtt.leaf_hash), _p(d_secret), _p(d_coef), _p(d_item_coef_off),
                                               _p(d_msg), _p(d_c), _p(d_cp), _p(d_cy_g1), _p(d_cy_g2)))
+
+
+class Ghw11Pk:
+    """Device tables of the G1 / Gt side of a Ghw11PublicKey (g1, g1_a, e_gg_alpha)."""
+
+    def __init__(self, eng, g1, g1_a, e_gg_alpha):
+        self.eng = eng
+        self.h = ctypes.c_void_p()
+        eng._check(eng.lib.rhip_ghw11_pk_create(eng.ctx, bytes(g1), bytes(g1_a), bytes(e_gg_alpha), ctypes.byref(self.h)))
+
+    def destroy(self):
+        if self.h:
+            self.eng.lib.rhip_ghw11_pk_destroy(self.h)
+            self.h = None
+
+
+def ghw11_encrypt_dev(eng, pk, n_items, total_leaves, d_item_leaf_off, d_item_tree_leaf, d_item_tree_gate, dtt, d_secret, d_coef,
+                      d_item_coef_off, d_t, d_msg, d_c, d_c1, d_cd):
+    """rhip_ghw11_encrypt_batch: d_t holds one draw per leaf row, d_cd takes C and D of every row (2 x 64 bytes per row)"""
+    eng._check(eng.lib.rhip_ghw11_encrypt_batch(eng.ctx, pk.h, _sz(n_items), _sz(total_leaves), _p(d_item_leaf_off), _p(d_item_tree_leaf),
+                                                _p(d_item_tree_gate), _p(dtt.path_off), _p(dtt.path_gate), _p(dtt.path_x), _p(dtt.gate_k),
+                                                _p(dtt.gate_coef_off), _p(dtt.leaf_hash), _p(d_secret), _p(d_coef), _p(d_item_coef_off),
+                                                _p(d_t), _p(d_msg), _p(d_c), _p(d_c1), _p(d_cd)))
 
 
 def bsw_decrypt_dev(eng, n_items, max_pairs, total_pairs, d_pair_off, d_sel_start, d_sel_ct_leaf, d_sel_sk_attr, d_sel_coeff,

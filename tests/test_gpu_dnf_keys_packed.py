@@ -455,3 +455,34 @@ def test_device_group_runs_on_its_first_device_with_the_same_bytes(setups, name)
         finally:
             h.close()
     assert got[0] == got[1]
+
+
+# ------------------------------------------------------------------------------------------------ a user key whose u1 cancels
+def test_bdabe_user_key_with_u1_at_infinity(host):
+    """the tape draws group elements as generator * fr, so the same draw for g1 and p1 makes p1 = g1; with r_u = R - alpha the sum
+    sk.u1 = a1 + p1 * r_u = g1 * alpha - g1 * alpha is the point at infinity (64 zero bytes in the reference's encoding), its neighbours and
+    sk.u2 stay finite, and every record equals oracle.schemes on the same tape"""
+    from oracle import schemes as sch
+    from oracle.tape import ListRng
+    rnd = random.Random(2018)
+    x1, x2, x4, y, alpha, a3 = (rnd.randrange(1, R) for _ in range(6))
+    setup_tape, auth_tape = [x1, x2, x1, x4, y], [alpha, a3]
+    host.set_tape(setup_tape)
+    pk, msk = bdabe.setup(host)
+    host.set_tape(auth_tape)
+    ska = bdabe.authgen(host, pk, msk, "aa1")
+    opk, omsk = sch.bdabe_setup(ListRng(setup_tape))
+    oska = sch.bdabe_authgen(opk, omsk, "aa1", ListRng(auth_tape))
+    assert opk["p1"] == opk["g1"]
+    names = ["u0", "u1", "u2"]
+    tape = [rnd.randrange(1, R), R - alpha, rnd.randrange(1, R)]
+    host.set_tape(tape)
+    blob, off = bdabe.keygen_packed(host, pk, ska, names)
+    host.clear_tape()
+    for i, rec in enumerate(records(blob, off)):
+        g = hl.parse_obj("bdabe_uk", rec)
+        want = sch.bdabe_keygen(opk, oska, names[i], ListRng([tape[i]]))
+        assert (g["sk"]["u1"], g["sk"]["u2"]) == (bn.g1_to_le(want["sk"]["u1"]), bn.g2_to_le(want["sk"]["u2"]))
+        assert (g["pk"]["u1"], g["pk"]["u2"]) == (bn.g1_to_le(want["pk"]["u1"]), bn.g2_to_le(want["pk"]["u2"]))
+        assert (want["sk"]["u1"] is None) == (g["sk"]["u1"] == bytes(64)) == (i == 1)
+        assert g["sk"]["u2"] != bytes(128) and g["sk_a"] == []

@@ -238,3 +238,37 @@ def test_bulk_on_os_randomness(host, keys):
     pt, po, status = ghw11.decrypt_out_packed(host, rk, tct, sblob, soff)
     assert (status == 0).all()
     assert [bytes(pt[int(po[j]):int(po[j + 1])]) for j in range(len(pick))] == [pts[i] for i in pick]
+
+
+def test_a_row_whose_c_cancels_carries_the_encoding_of_infinity(host):
+    """a = 1 in the setup tape makes g1_a = g1, so on a one-leaf policy C = g1 * (secret - H t): the t of item 1 is secret / H, its C is the
+    point at infinity (64 zero bytes in the reference's encoding) and its D finite; the records equal oracle.schemes on the same tape"""
+    from oracle import bn254 as bn
+    from oracle import policy as opol
+    from oracle import schemes as sch
+    from oracle.tape import ListRng
+    rnd = random.Random(2011)
+    setup_tape = [rnd.randrange(1, R), rnd.randrange(1, R), 1, rnd.randrange(1, R)]
+    host.set_tape(setup_tape)
+    pk, _msk = ghw11.setup(host)
+    host.clear_tape()
+    opk, _omsk = sch.ghw11_setup(ListRng(setup_tape))
+    assert opk["g1_a"] == opk["g1"]
+    policy = '{"name": "A"}'
+    h = sch.sha3_hash_fr("A")
+    n = 3
+    secrets, rhos = [rnd.randrange(1, R) for _ in range(n)], [rnd.randrange(1, R) for _ in range(n)]
+    ts = [rnd.randrange(1, R), secrets[1] * bn.fr_inv(h) % R, rnd.randrange(1, R)]
+    assert (secrets[1] - h * ts[1]) % R == 0
+    tape = [x for i in range(n) for x in (secrets[i], rhos[i], ts[i], 13 + i)]          # secret, msg, t, nonce per item
+    host.set_tape(tape)
+    blob, off = ghw11.encrypt_packed(host, pk, [policy], [0] * n, PLAINTEXT * n, [len(PLAINTEXT) * i for i in range(n + 1)], hl.JSON_POLICY)
+    host.clear_tape()
+    e_gen = bn.pairing(bn.G1_GEN, bn.G2_GEN)
+    for i, rec in enumerate(records(blob, off)):
+        g = hl.parse_obj("ghw11_ct", rec)
+        ct = sch.ghw11_encrypt(opk, policy, opol.JSON, ListRng([secrets[i], ts[i]]), bn.gt_pow(e_gen, rhos[i]))
+        assert (g["c"], g["c1"]) == (bn.gt_to_le(ct["c"]), bn.g1_to_le(ct["c1"]))
+        assert g["ci_di"] == [(node, bn.g1_to_le(ci), bn.g1_to_le(di)) for node, ci, di in ct["ci_di"]]
+        assert (ct["ci_di"][0][1] is None) == (g["ci_di"][0][1] == bytes(64)) == (i == 1)
+        assert g["ci_di"][0][2] != bytes(64)

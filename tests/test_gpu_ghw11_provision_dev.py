@@ -18,17 +18,18 @@ INF = bytes(128)
 
 
 class Windows:
-    """k * base as a sum of table entries (d 2^(w i)) * base, every entry and every sum made by bn.g2_add"""
+    """k * base as a sum of table entries (d 2^(w i)) * base, every entry and every sum made by the oracle's addition (bn.g2_add; bn.g1_add for
+    a base in G1)"""
 
-    def __init__(self, base, w):
-        self.w, self.rows = w, []
+    def __init__(self, base, w, add=bn.g2_add):
+        self.w, self.rows, self.add = w, [], add
         for _ in range((254 + w - 1) // w):
             row, acc = [None], None
             for _d in range(1, 1 << w):
-                acc = bn.g2_add(acc, base)
+                acc = add(acc, base)
                 row.append(acc)
             self.rows.append(row)
-            base = bn.g2_add(row[-1], base)
+            base = add(row[-1], base)
 
     def mul(self, k):
         k %= R
@@ -37,7 +38,7 @@ class Windows:
             d = k & ((1 << self.w) - 1)
             k >>= self.w
             if d:
-                acc = bn.g2_add(acc, row[d])
+                acc = self.add(acc, row[d])
         return acc
 
 
