@@ -499,6 +499,18 @@ int32_t rhip_ghw11_transform_batch(rhip_ctx* ctx, size_t n_items, size_t max_pai
                                    const uint32_t* dev_sel_ct_row, const uint32_t* dev_sel_tk_attr, const rhip_fr* dev_sel_coeff,
                                    const rhip_g1* dev_ct_c1 /*[n_items]*/, const rhip_g1* dev_ct_c /*[rows]: ci*/, const rhip_g1* dev_ct_d /*[rows]: di*/,
                                    const uint32_t* dev_ct_row_off /*[n_items+1]*/, const rhip_g2_lines* tk_lines, rhip_gt* dev_out /*[n_items]*/);
+/* ghw11 decrypt for the HOLDER of the secret key (no proxy): arguments of rhip_ghw11_transform_batch with sk_lines = rhip_g2_lines_prepare over
+ * k, l, k_x[0], k_x[1], ... of the Ghw11SecretKey (a transform key has that layout), plus c of every item.
+ *   msg[i] = c[i] * t_1[i]^-1,  t_1 = the transform's expression on the secret key's own elements
+ * which is decrypt_out(transform(ct, tk), rk) for every z tkgen may draw (t_z = t_1^(1/z); ghw11/mod.rs:252-282, :302).  One launch set: the
+ * G1 arguments enter the Miller loops with the opposite sign (t_1^-1 costs nothing), and c is the leading factor of the final-exponentiation
+ * kernel of whichever pairing family the context selects -- t_1 is never written to device memory and no Gt power is taken. */
+int32_t rhip_ghw11_decrypt_batch(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel,
+                                 const uint32_t* dev_pair_off /*[n_items+1]*/, const uint32_t* dev_sel_start /*[n_items]*/,
+                                 const uint32_t* dev_sel_ct_row, const uint32_t* dev_sel_sk_attr, const rhip_fr* dev_sel_coeff,
+                                 const rhip_g1* dev_ct_c1 /*[n_items]*/, const rhip_g1* dev_ct_c /*[rows]: ci*/, const rhip_g1* dev_ct_d /*[rows]: di*/,
+                                 const uint32_t* dev_ct_row_off /*[n_items+1]*/, const rhip_g2_lines* sk_lines,
+                                 const rhip_gt* dev_c /*[n_items]*/, rhip_gt* dev_msg /*[n_items]*/);
 /* GHW11 encrypt (ghw11/mod.rs:189-225) over the flattened policy trees of the BSW block above.  rhip_ghw11_pk: window tables
  * (8-bit and 16-bit) of g1, g1_a and e_gg_alpha (Ghw11PublicKey).  Explicit randomness per item = secret, the Gt `msg` and the gate
  * coefficients, plus one draw t per leaf row.  Outputs: c = e_gg_alpha^secret * msg, c1 = g1 * secret, and per leaf row

@@ -362,6 +362,29 @@ int32_t rabe_ghw11_decrypt_out_packed(rabe_host* h, const void* rk, size_t n_ite
                                       const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags,
                                       int32_t* status /*[n_items]*/, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off /*[n_items+1]*/);
 
+/* GHW11 for a key holder WITHOUT a proxy: n_items Ghw11Ciphertext records (one blob + n_items + 1 offsets, ct_len) under ONE secret key of
+ * the holder's own.  DEFINITION: the plaintexts and verdicts of rabe_ghw11_tkgen -> rabe_ghw11_transform_packed -> rabe_ghw11_decrypt_out_packed,
+ * for ANY z tkgen may draw.  With k_z = k / z, l_z = l / z, k_x_z = k_x / z the transform returns t_z = t_1^(1/z), where t_1 is the transform's own
+ * expression on the secret key's elements (ghw11/mod.rs:252-282), and decrypt_out computes c * (t_z^z)^-1 = c * t_1^-1 (:302): the blinding
+ * cancels.  Like rabe_ghw11_provision_packed this is not a function of the reference but a composition of functions that are.
+ * SKIPPED against the three calls: z and its inversion, the m + 2 variable-base G2 multiplications of tkgen, the Gt power t^z, the second parse of
+ * the blob, the 384 bytes per item that transform_packed brings back and the 768 that decrypt_out_packed sends again.  The records are parsed once,
+ * the blob goes to the device once, every Miller loop replays the secret key's prepared lines (kept across calls, keyed on the key's bytes), the
+ * G1 arguments enter with the opposite sign so that the Miller product is t_1^-1, c is the leading factor of the same final-exponentiation
+ * kernel, and the KDF + AES-GCM open reads the device copy of the blob: no Gt element leaves the device, only plaintexts and verdicts come back.
+ * Conventions of rabe_bsw_decrypt_packed and rabe_ghw11_decrypt_out_packed: nothing outside [0, ct_len) is read; bad bounds, a malformed record,
+ * a key whose attributes do not satisfy the record's policy, a row name missing from the record, a non-member element, trailing bytes or a tag
+ * that does not verify fail that item alone -- status -1, an EMPTY plaintext slot, the first error in rabe_host_last_error (the texts of
+ * rabe_ghw11_transform_packed / rabe_ghw11_decrypt_out_packed).  Unless RABE_PACKED_TRUSTED: rabe_ghw11_transform_packed's membership checks
+ * (c1, every C_i and D_i on the G1 curve with canonical coordinates, c in Gt).  No randomness is drawn; a seeded source or tape is left
+ * untouched.  Returns 1 when pt_cap is below the total of the well-formed records' sealed lengths; pt_off[n_items] = that size. */
+int32_t rabe_ghw11_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
+                                  const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/,
+                                  uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off /*[n_items+1]*/);
+/* the same for one ciphertext object (one pairing job through rhip_pairing_jobs, as rabe_ghw11_transform); _gt returns c * t_1^-1 */
+int32_t rabe_ghw11_decrypt(rabe_host* h, const void* sk, const void* ct, uint8_t** plaintext, size_t* len);
+int32_t rabe_ghw11_decrypt_gt(rabe_host* h, const void* sk, const void* ct, uint8_t out_gt[384]);
+
 /* ---- bdabe (src/schemes/bdabe/mod.rs:149-399) and mke08 (src/schemes/mke08/mod.rs:130-380): DNF policies, attributes named
  * "authority::attribute".  `request_attribute_sk` / `request_authority_sk` APPEND the new secret attribute key to the user key
  * (the reference returns it and its callers push it onto `sk.sk_a`: bdabe/mod.rs:21, mke08 tests).  decrypt: every item's

@@ -1599,6 +1599,10 @@ extern "C" int32_t rhip_lsw_decrypt_batch_one_sk(rhip_ctx* ctx, size_t n_items, 
 //   m     : P = C1[i],                           lines of k_z            (block 0)
 //   m + 1 : P = sum_e (-w_e) * C[ct row]  (MSM), lines of l_z            (block 1)
 //   t_i = FE( prod of the Miller values ) = e(c1, k_z) / ( prod_e e(w_e D_e, K_e) * e(sum_e w_e C_e, l_z) )
+// INV (rhip_ghw11_decrypt_batch): every G1 argument with the opposite sign -- the product of the same Miller loops is then t_i^-1, and the
+// final-exponentiation kernel's own leading factor (mul_in = c) makes its output c * t_i^-1 = msg: no Gt inversion, no t in HBM.  A second
+// instantiation: the transform's kernel is compiled as before.
+template <bool INV>
 __global__ void __launch_bounds__(RB_PAIRS_BLOCK, 2) k_ghw11_pairs(size_t n_items, size_t total_pairs, const uint32_t* pair_off, uint32_t ppi, const uint32_t* tile_off, const uint32_t* sel_start,
                                                                   const uint32_t* sel_ct_row, const uint32_t* sel_tk_attr, const rhip_fr* sel_coeff,
                                                                   const rhip_g1* ct_c1, const rhip_g1* ct_c, const rhip_g1* ct_d, const uint32_t* ct_row_off,
@@ -1623,16 +1627,17 @@ __global__ void __launch_bounds__(RB_PAIRS_BLOCK, 2) k_ghw11_pairs(size_t n_item
     line = 0;
   }
   bool p_inf;
-  scale_and_store(lds, active && j <= m, base, k, j < m, P + t, &p_inf);
+  scale_and_store(lds, active && j <= m, base, k, INV ? j >= m : j < m, P + t, &p_inf);
   if (!active) return;
   if (j > m) { qref[t] = line_inf[1] ? RHIP_Q_SKIP : 1u; return; }          // P comes from k_msm_finish_g1 (which may turn the pair into a skip)
   if (j < m) st_g1_q(terms + (t - 2 * item), load_g1(ct_c[row].l));
   qref[t] = (p_inf || line_inf[line]) ? RHIP_Q_SKIP : line;
 }
-extern "C" int32_t rhip_ghw11_transform_batch(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
-                                              const uint32_t* sel_start, const uint32_t* sel_ct_row, const uint32_t* sel_tk_attr, const rhip_fr* sel_coeff,
-                                              const rhip_g1* ct_c1, const rhip_g1* ct_c, const rhip_g1* ct_d, const uint32_t* ct_row_off,
-                                              const rhip_g2_lines* tk_lines, rhip_gt* out) {
+// the launches of transform (inv = false: out = t) and of the key holder's decrypt (inv = true: out = lead * t^-1)
+static int32_t ghw11_pairs_batch(rhip_ctx* ctx, bool inv, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
+                                 const uint32_t* sel_start, const uint32_t* sel_ct_row, const uint32_t* sel_tk_attr, const rhip_fr* sel_coeff,
+                                 const rhip_g1* ct_c1, const rhip_g1* ct_c, const rhip_g1* ct_d, const uint32_t* ct_row_off,
+                                 const rhip_g2_lines* tk_lines, const rhip_gt* lead, rhip_gt* out) {
   NEED(ctx);
   if (!n_items) return RHIP_OK;
   if (!total_pairs || !pair_off || !tk_lines || max_pairs < 2 || total_pairs < 2 * n_items) return RHIP_ERR_ARG;
@@ -1654,14 +1659,39 @@ extern "C" int32_t rhip_ghw11_transform_batch(rhip_ctx* ctx, size_t n_items, siz
   size_t g_lanes = 0;
   const uint32_t* tile_off = nullptr;
   if ((rc = gather_lanes(ctx, n_items, max_pairs, total_pairs, pair_off, ppi, &tile_off, &g_lanes)) != RHIP_OK) return rc;
-  KLAUNCH(ctx, "k_ghw11_pairs", k_ghw11_pairs, dim3(blocks_for(g_lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items,
-          total_pairs, pair_off, ppi, tile_off, sel_start, sel_ct_row, sel_tk_attr, sel_coeff, ct_c1, ct_c, ct_d, ct_row_off, (const uint8_t*)tk_lines->q_inf, pl.P,
-          pl.qref, (G1M*)w_terms);
+  if (inv)
+    KLAUNCH(ctx, "k_ghw11_pairs_inv", k_ghw11_pairs<true>, dim3(blocks_for(g_lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items,
+            total_pairs, pair_off, ppi, tile_off, sel_start, sel_ct_row, sel_tk_attr, sel_coeff, ct_c1, ct_c, ct_d, ct_row_off, (const uint8_t*)tk_lines->q_inf, pl.P,
+            pl.qref, (G1M*)w_terms);
+  else
+    KLAUNCH(ctx, "k_ghw11_pairs", k_ghw11_pairs<false>, dim3(blocks_for(g_lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items,
+            total_pairs, pair_off, ppi, tile_off, sel_start, sel_ct_row, sel_tk_attr, sel_coeff, ct_c1, ct_c, ct_d, ct_row_off, (const uint8_t*)tk_lines->q_inf, pl.P,
+            pl.qref, (G1M*)w_terms);
+  // the sum's sign is the masks' orientation: flipped (sum_e (-w_e) C_e) for t, as they are (sum_e w_e C_e) for t^-1
   KLAUNCH(ctx, "k_msm_partial_g1", (k_msm_partial<Fp, G1M, G1JM>), dim3(blocks_for(n_items * L, 64)), dim3(64), 0, ctx->stream, n_items, L, C,
-          (const uint32_t*)w_off, sel_start, (const G1M*)w_terms, (const uint32_t*)w_masks, 1, (G1JM*)w_part);
+          (const uint32_t*)w_off, sel_start, (const G1M*)w_terms, (const uint32_t*)w_masks, inv ? 0 : 1, (G1JM*)w_part);
   KLAUNCH(ctx, "k_msm_finish_g1", k_msm_finish_g1, dim3(blocks_for(n_items, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items, L,
           (const G1JM*)w_part, pair_off, pl.P, pl.qref);
-  return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, (const LineM*)tk_lines->lines, tk_lines->lines29, (const rhip_gt*)nullptr, out);
+  return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, (const LineM*)tk_lines->lines, tk_lines->lines29, lead, out);
+}
+extern "C" int32_t rhip_ghw11_transform_batch(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
+                                              const uint32_t* sel_start, const uint32_t* sel_ct_row, const uint32_t* sel_tk_attr, const rhip_fr* sel_coeff,
+                                              const rhip_g1* ct_c1, const rhip_g1* ct_c, const rhip_g1* ct_d, const uint32_t* ct_row_off,
+                                              const rhip_g2_lines* tk_lines, rhip_gt* out) {
+  return ghw11_pairs_batch(ctx, false, n_items, max_pairs, total_pairs, n_sel, pair_off, sel_start, sel_ct_row, sel_tk_attr, sel_coeff, ct_c1, ct_c, ct_d, ct_row_off,
+                           tk_lines, (const rhip_gt*)nullptr, out);
+}
+// ghw11 decrypt for the holder of the secret key: decrypt_out(transform(ct, tk), rk) for ANY z of tkgen is c * t_1^-1 with t_1 = transform's
+// expression on the secret key's own (k, l, k_x) -- the blinding cancels (ghw11/mod.rs:252-282, :302).  sk_lines: prepared lines of k, l, k_x[0], ...
+// (the order of rhip_ghw11_transform_batch).  One launch set, the transform's: the G1 arguments take the opposite sign, so the Miller product is
+// t_1^-1, and c goes in as the leading factor of the final exponentiation of whichever pairing family runs -- msg is formed where t_1^-1 is held.
+extern "C" int32_t rhip_ghw11_decrypt_batch(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
+                                            const uint32_t* sel_start, const uint32_t* sel_ct_row, const uint32_t* sel_sk_attr, const rhip_fr* sel_coeff,
+                                            const rhip_g1* ct_c1, const rhip_g1* ct_c, const rhip_g1* ct_d, const uint32_t* ct_row_off,
+                                            const rhip_g2_lines* sk_lines, const rhip_gt* c, rhip_gt* msg) {
+  if (n_items && (!c || !msg)) return RHIP_ERR_ARG;
+  return ghw11_pairs_batch(ctx, true, n_items, max_pairs, total_pairs, n_sel, pair_off, sel_start, sel_ct_row, sel_sk_attr, sel_coeff, ct_c1, ct_c, ct_d, ct_row_off,
+                           sk_lines, c, msg);
 }
 
 // ------------------------------------------------------------------------------------------------ AW11 multi-authority CP-ABE

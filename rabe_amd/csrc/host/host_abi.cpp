@@ -1907,6 +1907,29 @@ int32_t rabe_ghw11_decrypt_out_packed(rabe_host* h, const void* rk, size_t n_ite
   return 0;
   GUARD_END(h)
 }
+int32_t rabe_ghw11_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
+                                  int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  if (!ghw11::decrypt_packed(h->eng, *(const ghw11::Ghw11SecretKey*)sk, n_items, ct_blob, ct_len, ct_off, (flags & RABE_PACKED_TRUSTED) != 0, status, pt_buf,
+                             pt_cap, pt_off, &errors))
+    return 1;
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
+int32_t rabe_ghw11_decrypt(rabe_host* h, const void* sk, const void* ct, uint8_t** plaintext, size_t* len) {
+  GUARD_BEGIN
+  return give_bytes(ghw11::decrypt(h->eng, *(const ghw11::Ghw11SecretKey*)sk, *(const ghw11::Ghw11Ciphertext*)ct), plaintext, len);
+  GUARD_END(h)
+}
+int32_t rabe_ghw11_decrypt_gt(rabe_host* h, const void* sk, const void* ct, uint8_t out_gt[384]) {
+  GUARD_BEGIN
+  Gt g = ghw11::decrypt_gt(h->eng, *(const ghw11::Ghw11SecretKey*)sk, *(const ghw11::Ghw11Ciphertext*)ct);
+  memcpy(out_gt, g.data(), 384);
+  return 0;
+  GUARD_END(h)
+}
 int32_t rabe_ghw11_keygen_packed(rabe_host* h, const void* pk, const void* msk, const char* const* attributes, const size_t* counts, size_t n_sets,
                                  size_t n_items, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off) {
   GUARD_BEGIN

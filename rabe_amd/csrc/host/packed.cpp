@@ -2180,27 +2180,36 @@ bool decrypt_out_packed(Engine& eng, const Ghw11RetrieveKey& rk, size_t n, const
   return true;
 }
 
-// n calls of ghw11::transform (ghw11/mod.rs:227-295) under ONE transform key -- the outsourced half of a decryption, what a server
-// holding users' transform keys runs (SURVEY.md 8f-1).  Records in: Ghw11Ciphertext (policy, c, c1, rows (name, c_i, d_i), sealed
-// data); records out: Ghw11TransformCiphertext = c | t, 768 bytes per item at out_buf + 768 i (zeros where status[i] = -1).
-// Per distinct policy: traverse_policy, calc_pruned, and per pruned (name, name_col) the FIRST coefficient named name_col, the FIRST
-// key attribute named `name`, the FIRST ciphertext row named name_col (:259-281); a missing one is the reference's unwrap panic.
-// Every G2 argument is the key's: the batch replays prepared lines (kept across calls) and does no G2 arithmetic.
-bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                      int32_t* status, uint8_t* out_buf, size_t out_cap, std::vector<std::string>* errors) {
-  Timer tm("ghw11::transform_packed");
-  Engine::ArenaScope arena(eng);
-  errors->assign(n, "");
-  if (!ct_off || (n && !ct_blob) || !status) throw RabeError("ghw11::transform_packed: null input");
-  if (!out_buf || out_cap < n * 768) return false;
-  (void)check_offsets(n, ct_off, ct_len, errors);
+namespace {
+// The host half that transform_packed and decrypt_packed share: bounds, the parse of every Ghw11Ciphertext record, the plan per distinct
+// policy against the key's attribute names (a Ghw11SecretKey and a Ghw11TransformKey carry the same names in the same places -- only the G2
+// elements whose lines are prepared differ), and the selection tables of rhip_ghw11_transform_batch, shared by the records in standard layout.
+struct CtPlan {
+  std::shared_ptr<const FlatPolicy> flat; std::string err;
+  struct E { std::string name_col; uint32_t tk_attr; Fr w; uint32_t std_ct_row; };
+  std::vector<E> ent;
+};
+struct CtView { const uint8_t* c; const uint8_t* c1; uint32_t rows; std::vector<const uint8_t*> ci, di; std::shared_ptr<CtPlan> plan;
+                std::vector<uint32_t> ct_row; bool standard; };
+struct CtBatch {
+  std::vector<CtView> v;
+  std::vector<Sealed> sealed;          // with_sealed: the data slice of every record whose fields decoded
+  std::vector<uint8_t> parsed;         // with_sealed: 1 where the record's fields, the sealed slice included, decoded
+  std::vector<size_t> live;
+  std::vector<uint32_t> row_off{0}, pair_off{0}, sel_start, sel_ct, sel_tk;
+  std::vector<Fr> sel_w;
+  size_t max_pairs = 2;
+  // with_sealed = false: the sealed data stays with the client (transform); true: it is kept, and the record has to end with it, as
+  // decrypt_out_packed demands of the same record -- checked last, after everything the transform would have refused
+  void parse(const std::vector<Ghw11Attribute>& key_attr, size_t n, const uint8_t* ct_blob, const uint64_t* ct_off, bool with_sealed,
+             std::vector<std::string>* errors);
+  void select(size_t n, const std::vector<std::string>& errors);
+};
+void CtBatch::parse(const std::vector<Ghw11Attribute>& key_attr, size_t n, const uint8_t* ct_blob, const uint64_t* ct_off, bool with_sealed,
+                    std::vector<std::string>* errors) {
   std::vector<std::string> attr;
-  for (const auto& a : tk.attr_key_z) attr.push_back(a.string);
-  struct Plan {
-    std::shared_ptr<const FlatPolicy> flat; std::string err;
-    struct E { std::string name_col; uint32_t tk_attr; Fr w; uint32_t std_ct_row; };
-    std::vector<E> ent;
-  };
+  for (const auto& a : key_attr) attr.push_back(a.string);
+  typedef CtPlan Plan;
   std::map<std::pair<int, std::string>, std::shared_ptr<Plan>> plans;
   std::mutex plans_mu;
   FastPlans<Plan> fast_plans;
@@ -2218,9 +2227,9 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
       if (!calc_pruned(attr, pl->flat->tree, &list)) throw RabeError("Error in Ghw11/decrypt: attributes in sk do not match policy in ct.");
       for (const auto& cur : list) {
         size_t a = 0, co = 0;
-        while (a < tk.attr_key_z.size() && tk.attr_key_z[a].string != cur.first) a++;
+        while (a < key_attr.size() && key_attr[a].string != cur.first) a++;
         while (co < names.size() && names[co] != cur.second) co++;
-        if (a == tk.attr_key_z.size() || co == names.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
+        if (a == key_attr.size() || co == names.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
         pl->ent.push_back({cur.second, (uint32_t)a, pl->flat->leaf_coeff[co], (uint32_t)co});
       }
     } catch (const std::exception& ex) {
@@ -2230,9 +2239,8 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
     plans[key] = pl;
     return pl;
   };
-  struct View { const uint8_t* c; const uint8_t* c1; uint32_t rows; std::vector<const uint8_t*> ci, di; std::shared_ptr<Plan> plan;
-                std::vector<uint32_t> ct_row; bool standard; };
-  std::vector<View> v(n);
+  v.resize(n);
+  if (with_sealed) { sealed.resize(n); parsed.assign(n, 0); }
   parallel_for(n, [&](size_t i) {
     if (!(*errors)[i].empty()) return;
     try {
@@ -2249,7 +2257,8 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
       std::vector<std::pair<const char*, uint32_t>> names(rows);
       for (uint32_t y = 0; y < rows; y++) { names[y] = r.str(); v[i].ci[y] = r.raw(64); v[i].di[y] = r.raw(64); }
       const uint32_t dl = r.u32();
-      (void)r.raw(dl);                                   // the sealed data stays with the client (decrypt_out)
+      const uint8_t* data = r.raw(dl);                   // transform: the sealed data stays with the client (decrypt_out)
+      if (with_sealed) { sealed[i].len = dl; sealed[i].p = data; parsed[i] = 1; }
       auto pl = fast_plans.find(pol.first, pol.second, lang);
       if (!pl) { pl = plan_of(std::string(pol.first, pol.second), lang); fast_plans.put(pol.first, pol.second, lang, pl); }
       if (!pl->err.empty()) throw RabeError(pl->err);
@@ -2266,19 +2275,18 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
           v[i].ct_row.push_back(y);
         }
       }
+      if (with_sealed && r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
     } catch (const std::exception& ex) {
       (*errors)[i] = ex.what();
       if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
     }
   });
-  tm.lap("parse + plan");
-  std::vector<size_t> live;
-  std::vector<uint32_t> row_off{0}, pair_off{0}, sel_start, sel_ct, sel_tk;
-  std::vector<Fr> sel_w;
+}
+void CtBatch::select(size_t n, const std::vector<std::string>& errors) {
+  typedef CtPlan Plan;
   std::map<const Plan*, uint32_t> shared_start;
-  size_t max_pairs = 2;
   for (size_t i = 0; i < n; i++) {
-    if (!(*errors)[i].empty()) continue;
+    if (!errors[i].empty()) continue;
     live.push_back(i);
     row_off.push_back(row_off.back() + v[i].rows);
     const Plan& pl = *v[i].plan;
@@ -2297,6 +2305,39 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
     pair_off.push_back(pair_off.back() + m + 2);
     if ((size_t)m + 2 > max_pairs) max_pairs = m + 2;
   }
+}
+// the prepared lines of a key's G2 elements in the order k, l, k_x[0], k_x[1], ... (kept per engine under `aux_name`, keyed on the bytes)
+rhip_g2_lines* key_lines(Engine& eng, const char* aux_name, const G2& k, const G2& l, const std::vector<Ghw11Attribute>& attrs) {
+  std::string key((const char*)k.data(), 128);
+  key.append((const char*)l.data(), 128);
+  for (const auto& a : attrs) key.append((const char*)a.k_x.data(), 128);
+  return (rhip_g2_lines*)eng.aux(aux_name, key, make_tk_lines, &key, destroy_tk_lines, 4);
+}
+}  // namespace
+
+// n calls of ghw11::transform (ghw11/mod.rs:227-295) under ONE transform key -- the outsourced half of a decryption, what a server
+// holding users' transform keys runs (SURVEY.md 8f-1).  Records in: Ghw11Ciphertext (policy, c, c1, rows (name, c_i, d_i), sealed
+// data); records out: Ghw11TransformCiphertext = c | t, 768 bytes per item at out_buf + 768 i (zeros where status[i] = -1).
+// Per distinct policy: traverse_policy, calc_pruned, and per pruned (name, name_col) the FIRST coefficient named name_col, the FIRST
+// key attribute named `name`, the FIRST ciphertext row named name_col (:259-281); a missing one is the reference's unwrap panic.
+// Every G2 argument is the key's: the batch replays prepared lines (kept across calls) and does no G2 arithmetic.
+bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                      int32_t* status, uint8_t* out_buf, size_t out_cap, std::vector<std::string>* errors) {
+  Timer tm("ghw11::transform_packed");
+  Engine::ArenaScope arena(eng);
+  errors->assign(n, "");
+  if (!ct_off || (n && !ct_blob) || !status) throw RabeError("ghw11::transform_packed: null input");
+  if (!out_buf || out_cap < n * 768) return false;
+  (void)check_offsets(n, ct_off, ct_len, errors);
+  CtBatch b;
+  b.parse(tk.attr_key_z, n, ct_blob, ct_off, false, errors);
+  tm.lap("parse + plan");
+  b.select(n, *errors);
+  const std::vector<CtView>& v = b.v;
+  const std::vector<size_t>& live = b.live;
+  const std::vector<uint32_t>&row_off = b.row_off, &pair_off = b.pair_off, &sel_start = b.sel_start, &sel_ct = b.sel_ct, &sel_tk = b.sel_tk;
+  const std::vector<Fr>& sel_w = b.sel_w;
+  const size_t max_pairs = b.max_pairs;
   const size_t m_items = live.size();
   uint8_t* h_out = nullptr;
   if (m_items) {
@@ -2304,7 +2345,7 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
     uint8_t* h_l = eng.pinned(1, total * 128 + 4);
     uint8_t* h_x = eng.pinned(2, m_items * (64 + 384 + 384));
     parallel_for(m_items, [&](size_t j) {
-      const View& w = v[live[j]];
+      const CtView& w = v[live[j]];
       memcpy(h_x + 64 * j, w.c1, 64);
       memcpy(h_x + m_items * 64 + 384 * j, w.c, 384);
       for (uint32_t y = 0; y < w.rows; y++) {
@@ -2314,10 +2355,7 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
     });
     tm.lap("pack");
     rhip_ctx* cx = eng.ctx();
-    std::string key((const char*)tk.k_z.data(), 128);
-    key.append((const char*)tk.l_z.data(), 128);
-    for (const auto& a : tk.attr_key_z) key.append((const char*)a.k_x.data(), 128);
-    rhip_g2_lines* lines = (rhip_g2_lines*)eng.aux("ghw11_tk_lines", key, make_tk_lines, &key, destroy_tk_lines, 4);
+    rhip_g2_lines* lines = key_lines(eng, "ghw11_tk_lines", tk.k_z, tk.l_z, tk.attr_key_z);
     DBuf d_c1(&eng, m_items * 64), d_c(&eng, m_items * 384), d_ci(&eng, total * 64 + 4), d_di(&eng, total * 64 + 4), d_row_off = up32(eng, row_off),
         d_pair_off = up32(eng, pair_off), d_sel_start = up32(eng, sel_start), d_sel_ct = up32(eng, sel_ct), d_sel_tk = up32(eng, sel_tk),
         d_sel_w = up_bytes(eng, flatten_fr(sel_w)), d_out(&eng, m_items * 384);
@@ -2356,6 +2394,101 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
     status[i] = 0;
   });
   tm.lap("assembly");
+  return true;
+}
+// ghw11 for a key holder WITHOUT a proxy: n ciphertext records under ONE secret key.  By definition the plaintexts of tkgen -> transform_packed
+// -> decrypt_out_packed for any z: with k_z = k / z, l_z = l / z, k_x_z = k_x / z the transform returns t_z = t_1^(1/z), t_1 = its own
+// expression on the secret key's elements (ghw11/mod.rs:252-282), and decrypt_out computes c * (t_z^z)^-1 = c * t_1^-1 (:302).  So z, the m + 2
+// G2 multiplications of tkgen, the Gt power of decrypt_out, the second parse and the 768 bytes per item between the two calls are skipped:
+// the records are parsed once (CtBatch, transform_packed's own half), the blob goes to the device once and the elements are gathered out of
+// it there, rhip_ghw11_decrypt_batch replays the SECRET key's prepared lines (kept under "ghw11_sk_lines", keyed on the key's bytes) and
+// leaves msg = c * t_1^-1 in HBM, and the KDF + AES-GCM open reads the sealed data from the device copy of the blob.  Only plaintexts and
+// verdicts come back.  Failures stay with their item, with transform_packed's error texts (bounds, a malformed record, a policy the key does
+// not satisfy, a missing row name, a non-member unless trusted) or decrypt_out_packed's (trailing bytes, a tag that does not verify): status
+// -1 and an EMPTY plaintext slot.  pt_cap below the sealed lengths of the well-formed records: returns false with that size in pt_off[n].
+bool decrypt_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                    int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
+  Timer tm("ghw11::decrypt_packed");
+  Engine::ArenaScope arena(eng);
+  errors->assign(n, "");
+  if (!ct_off || !pt_off || (n && (!ct_blob || !status))) throw RabeError("ghw11::decrypt_packed: null input");
+  if (!n) { pt_off[0] = 0; return true; }
+  (void)check_offsets(n, ct_off, ct_len, errors);
+  BlobGather gather(eng, ct_blob, ct_len);          // the blob starts for the device now, beside the parsing below (records.h)
+  CtBatch b;
+  b.parse(sk.attr_key, n, ct_blob, ct_off, true, errors);
+  tm.lap("parse + plan");
+  uint64_t need = 0;
+  for (size_t i = 0; i < n; i++) if (b.parsed[i]) need += b.sealed[i].len;
+  if (!pt_buf || pt_cap < need) { pt_off[n] = need; return false; }
+  b.select(n, *errors);
+  const std::vector<size_t>& live = b.live;
+  const size_t m_items = live.size();
+  std::vector<uint64_t> sealed_off(m_items);
+  std::vector<uint32_t> sealed_len(m_items);
+  DBuf d_msg(&eng, m_items * 384 + 4);
+  if (m_items) {
+    const size_t total = b.row_off[m_items];
+    DBuf d_c(&eng, m_items * 384), d_c1(&eng, m_items * 64), d_ci(&eng, total * 64 + 4), d_di(&eng, total * 64 + 4);
+    std::vector<uint64_t> dst_off(4 * m_items);
+    for (size_t j = 0; j < m_items; j++) {
+      const CtView& w = b.v[live[j]];
+      const uint8_t* rec = ct_blob + ct_off[live[j]];
+      sealed_off[j] = (uint64_t)(b.sealed[live[j]].p - ct_blob);
+      sealed_len[j] = b.sealed[live[j]].len;
+      dst_off[j] = 384ull * j; dst_off[m_items + j] = 64ull * j; dst_off[2 * m_items + j] = dst_off[3 * m_items + j] = 64ull * b.row_off[j];
+      int shape = w.standard ? gather.find(w.plan.get()) : -1;          // the same policy text and row names: the same skeleton
+      if (shape < 0) {
+        std::vector<RecordLayout::Part> parts;
+        parts.push_back({(uint32_t)(w.c - rec), 384, 0, 0});
+        parts.push_back({(uint32_t)(w.c1 - rec), 64, 1, 0});
+        for (uint32_t y = 0; y < w.rows; y++) {
+          parts.push_back({(uint32_t)(w.ci[y] - rec), 64, 2, 64 * y});
+          parts.push_back({(uint32_t)(w.di[y] - rec), 64, 3, 64 * y});
+        }
+        shape = (int)gather.add_shape(w.standard ? (const void*)w.plan.get() : nullptr, std::move(parts));
+      }
+      gather.item(ct_off[live[j]], (uint32_t)shape);
+    }
+    tm.lap("shapes");
+    rhip_ctx* cx = eng.ctx();
+    rhip_g2_lines* lines = key_lines(eng, "ghw11_sk_lines", sk.k, sk.l, sk.attr_key);
+    DBuf d_row_off = up32(eng, b.row_off), d_pair_off = up32(eng, b.pair_off), d_sel_start = up32(eng, b.sel_start), d_sel_ct = up32(eng, b.sel_ct),
+         d_sel_sk = up32(eng, b.sel_tk), d_sel_w = up_bytes(eng, flatten_fr(b.sel_w));
+    gather.run({d_c.ptr(), d_c1.ptr(), d_ci.ptr(), d_di.ptr()}, dst_off);
+    std::unique_ptr<MemberChecks> mc;
+    if (!trusted) {          // transform_packed's checks; every G2 argument is the key's own, so no walk verdicts
+      mc.reset(new MemberChecks(eng));
+      mc->add(1, d_c1.ptr(), m_items); mc->add(1, d_ci.ptr(), total, d_row_off.as<uint32_t>(), m_items);
+      mc->add(1, d_di.ptr(), total, d_row_off.as<uint32_t>(), m_items); mc->add(3, d_c.ptr(), m_items);
+    }
+    eng.check(rhip_ghw11_decrypt_batch(cx, m_items, b.max_pairs, b.pair_off[m_items], b.sel_ct.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
+                                       d_sel_ct.as<uint32_t>(), d_sel_sk.as<uint32_t>(), d_sel_w.as<rhip_fr>(), d_c1.as<rhip_g1>(), d_ci.as<rhip_g1>(),
+                                       d_di.as<rhip_g1>(), d_row_off.as<uint32_t>(), lines, d_c.as<rhip_gt>(), d_msg.as<rhip_gt>()),
+              "rhip_ghw11_decrypt_batch");
+    if (mc) {
+      mc->collect();
+      const auto &ok_c1 = mc->ok(0), &ok_ci = mc->ok(1), &ok_di = mc->ok(2), &ok_c = mc->ok(3);
+      for (size_t j = 0; j < m_items; j++)
+        if (!ok_c1[j] || !ok_ci[j] || !ok_di[j] || !ok_c[j]) (*errors)[live[j]] = "deserialize: a ciphertext element is not a group member (FieldError::NotMember)";
+    }
+  }
+  // KDF + AES-GCM open on the device: msg never leaves HBM; plaintext bytes come back in one copy
+  open_sealed_records(eng, n, live, d_msg.ptr(), gather.dev_blob(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
+  // a tag that did not verify leaves a zeroed slot behind: close it up, so that every failed item has an empty one
+  bool holes = false;
+  for (size_t i = 0; i < n && !holes; i++) holes = status[i] != 0 && pt_off[i + 1] != pt_off[i];
+  if (holes) {
+    uint64_t at = 0;
+    for (size_t i = 0; i < n; i++) {
+      const uint64_t lo = pt_off[i], len = status[i] == 0 ? pt_off[i + 1] - lo : 0;
+      if (len && at != lo) memmove(pt_buf + at, pt_buf + lo, (size_t)len);
+      pt_off[i] = at;
+      at += len;
+    }
+    pt_off[n] = at;
+  }
+  tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
   return true;
 }
 // n calls of ghw11::keygen (ghw11/mod.rs:123-152) under one master key.  Item i gets the attribute list sets[item_set[i]]; draw order: one r

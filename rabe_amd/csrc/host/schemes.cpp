@@ -2649,7 +2649,11 @@ Ghw11Ciphertext encrypt(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const s
   ct.data = seal(rng, pw[1], plaintext);
   return ct;
 }
-static void plan_transform(PolicyMemo& memo, const Ghw11Ciphertext& ct, const Ghw11TransformKey& tk, PairingJob* job) {      // :231-295
+// inverse = false: the transform's t under the triple (k_z, l_z, k_x_z...).  inverse = true (the key holder's decrypt; the triple is the
+// secret key's own k, l, k_x...): every G1 argument with the opposite sign and c as the leading factor -- c * t^-1 in the same launch set
+static void plan_transform(PolicyMemo& memo, const Ghw11Ciphertext& ct, const G2& k_z, const G2& l_z, const std::vector<Ghw11Attribute>& attr_key_z, bool inverse,
+                           PairingJob* job) {      // :231-295
+  struct { const G2& k_z; const G2& l_z; const std::vector<Ghw11Attribute>& attr_key_z; } tk{k_z, l_z, attr_key_z};
   std::vector<std::string> attr;
   for (const auto& v : tk.attr_key_z) attr.push_back(v.string);
   const PolicyMemo::Entry& pe = memo.get(ct.policy.first, ct.policy.second);
@@ -2659,8 +2663,8 @@ static void plan_transform(PolicyMemo& memo, const Ghw11Ciphertext& ct, const Gh
   if (!ok) throw RabeError("Error in Ghw11/decrypt: attributes in sk do not match policy in ct.");
   // t = e(c1, k_z) / ( prod_i e(w_i D_i, K_i) * e(sum_i w_i C_i, l_z) )
   //   = FE( ML(c1, k_z) * prod_i ML(-w_i D_i, K_i) * ML(sum_i (-w_i) C_i, l_z) )
-  job->lead_one = true;
-  job->base.push_back(ct.c1); job->scal.push_back(fr_one()); job->q.push_back(tk.k_z);
+  if (inverse) job->lead = ct.c; else job->lead_one = true;
+  job->base.push_back(ct.c1); job->scal.push_back(inverse ? fr_neg(fr_one()) : fr_one()); job->q.push_back(tk.k_z);
   for (const auto& cur : list) {
     const Fr* coeff = nullptr;
     const Ghw11Attribute* tk_attr = nullptr;
@@ -2669,7 +2673,7 @@ static void plan_transform(PolicyMemo& memo, const Ghw11Ciphertext& ct, const Gh
     for (const auto& x : tk.attr_key_z) if (x.string == cur.first) { tk_attr = &x; break; }
     for (const auto& x : ct.ci_di) if (x.name == cur.second) { ct_attr = &x; break; }
     if (!coeff || !tk_attr || !ct_attr) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
-    const Fr nw = fr_neg(*coeff);
+    const Fr nw = inverse ? *coeff : fr_neg(*coeff);
     job->base.push_back(ct_attr->d); job->scal.push_back(nw); job->q.push_back(tk_attr->k_x);
     job->sbase.push_back(ct_attr->c); job->sscal.push_back(nw);
   }
@@ -2679,7 +2683,7 @@ std::vector<Ghw11TransformCiphertext> transform_batch(Engine& eng, const std::ve
                                                       const std::vector<const Ghw11TransformKey*>& tks, std::vector<std::string>* errors) {
   if (cts.size() != tks.size()) throw RabeError("transform_batch: cts and tks differ in length");
   PolicyMemo memo;
-  std::vector<PairingJob> jobs = plan_jobs(cts.size(), [&](size_t i, PairingJob* j) { plan_transform(memo, *cts[i], *tks[i], j); });
+  std::vector<PairingJob> jobs = plan_jobs(cts.size(), [&](size_t i, PairingJob* j) { plan_transform(memo, *cts[i], tks[i]->k_z, tks[i]->l_z, tks[i]->attr_key_z, false, j); });
   std::vector<Gt> t = run_pairing_jobs(eng, jobs);
   std::vector<Ghw11TransformCiphertext> out(cts.size());
   if (errors) errors->assign(cts.size(), "");
@@ -2695,6 +2699,15 @@ Ghw11TransformCiphertext transform(Engine& eng, const Ghw11Ciphertext& ct, const
   if (!errors[0].empty()) throw RabeError(errors[0]);
   return r[0];
 }
+// decrypt_out(transform(ct, tk), rk) for ANY (tk, rk) = tkgen(sk): t_z^z = t_1, the transform's expression on the secret key's own elements
+// (:252-282, :302), so msg = c * t_1^-1 -- one pairing job with c as its leading factor, no z, no G2 multiplication, no Gt power
+Gt decrypt_gt(Engine& eng, const Ghw11SecretKey& sk, const Ghw11Ciphertext& ct) {
+  std::vector<PairingJob> jobs(1);
+  PolicyMemo memo;
+  plan_transform(memo, ct, sk.k, sk.l, sk.attr_key, true, &jobs[0]);
+  return run_pairing_jobs(eng, jobs)[0];
+}
+Bytes decrypt(Engine& eng, const Ghw11SecretKey& sk, const Ghw11Ciphertext& ct) { return open_or_error(decrypt_gt(eng, sk, ct), ct.data); }
 Gt decrypt_out_gt(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11RetrieveKey& rk) {       // :298-305
   // msg = c * (t^z)^-1 = c * t^(-z)   (Gt has order r)
   Gt p = eng.gt_pow({pct.t}, {fr_neg(rk.z)})[0];

@@ -216,6 +216,13 @@ bool tkgen_packed(Engine& eng, Rng& rng, size_t n, const uint8_t* sk_blob, size_
 bool provision_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw11MasterKey& msk, const std::vector<std::vector<std::string>>& sets,
                       size_t n, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off, uint8_t* tk_buf, size_t tk_cap,
                       uint64_t* tk_off, uint8_t* rk_buf);
+// the key holder's own decrypt (no proxy): c * t_1^-1 with t_1 = transform's expression on the secret key's elements -- what
+// decrypt_out(transform(ct, tkgen(sk).0), tkgen(sk).1) gives for every z -- as one pairing job; and its packed form (packed.cpp): n ciphertext
+// records under ONE secret key, false (pt_off[n] = the size needed) when pt_cap is below the well-formed records' sealed lengths
+Gt decrypt_gt(Engine& eng, const Ghw11SecretKey& sk, const Ghw11Ciphertext& ct);
+Bytes decrypt(Engine& eng, const Ghw11SecretKey& sk, const Ghw11Ciphertext& ct);
+bool decrypt_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                    int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors);
 Gt decrypt_out_gt(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11RetrieveKey& rk);
 Bytes decrypt_out(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11RetrieveKey& rk, const Bytes& data);
 }  // namespace ghw11

@@ -58,6 +58,25 @@ def decrypt_out_gt(host, tct, rk):
     return host.out_gt("rabe_ghw11_decrypt_out_gt", tct.ptr, rk.ptr)
 
 
+def decrypt(host, sk, ct):
+    """The key holder's own decrypt, no proxy (rabe_ghw11_decrypt): what decrypt_out(transform(ct, tk), rk, ct) gives for any (tk, rk) =
+    tkgen(sk), without z, the G2 multiplications or the Gt power."""
+    return host.out_bytes("rabe_ghw11_decrypt", sk.ptr, ct.ptr)
+
+
+def decrypt_gt(host, sk, ct):
+    """c * t_1^-1, t_1 = transform's expression on the secret key's own elements (rabe_ghw11_decrypt_gt)."""
+    return host.out_gt("rabe_ghw11_decrypt_gt", sk.ptr, ct.ptr)
+
+
+def decrypt_packed(host, sk, ct_blob, ct_off, out=None, trusted=False):
+    """n ciphertext records under one secret key of the holder's own (rabe_ghw11_decrypt_packed): by definition the result of tkgen ->
+    transform_packed -> decrypt_out_packed for any z.  Returns (pt_blob view, pt_off uint64 [n+1], status int32 [n]); a failed item has
+    status -1 and an empty plaintext slot."""
+    from ..hostlib import packed_decrypt
+    return packed_decrypt(host, "rabe_ghw11_decrypt_packed", (sk.ptr,), ct_blob, ct_off, out, trusted)
+
+
 def transform_packed(host, tk, ct_blob, ct_off, trusted=False):
     """n transforms under one transform key over a blob of serialized ciphertexts (rabe_ghw11_transform_packed).
     Returns (tct: numpy uint8 [n, 768] -- row i = the Ghw11TransformCiphertext record c | t --, status: numpy int32 [n])."""
