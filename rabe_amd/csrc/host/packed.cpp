@@ -1,11 +1,15 @@
-// Packed batch entry points of bsw / lsw / aw11 (include/rabe_host.h: rabe_{bsw,lsw,aw11}_*_packed): n independent calls of the
-// reference's scheme functions -- bsw::encrypt / decrypt (src/schemes/bsw/mod.rs:217-318), lsw::keygen / decrypt
-// (lsw/mod.rs:121-290), aw11::encrypt / decrypt (aw11/mod.rs:241-366) -- with ONE blob of canonical records + offsets on each side
-// of the boundary, fed to the device-resident Level B paths (rhip_{bsw,lsw,aw11}_*_batch, include/rabe_hip.h) instead of the
-// per-object pairing jobs.  What stays on the host is what the reference does with strings and bytes: policy parsing, flattening
-// the tree into the index tables the share kernels walk, traverse / calc_pruned / calc_coefficients per distinct policy, record
-// assembly, KDF + AES-GCM.  Records are the byte form rabe_obj_serialize gives the corresponding struct (host_abi.cpp), so packed
-// and object APIs interoperate.
+// Packed batch entry points (include/rabe_host.h: rabe_*_packed): n independent calls of one of the reference's scheme functions with ONE blob
+// of canonical records + offsets on each side of the boundary, fed to the device-resident Level B paths (rhip_*_batch, include/rabe_hip.h)
+// instead of the per-object pairing jobs.  In file order: AC17 bulk keygen; BSW keygen / delegate / encrypt / decrypt; LSW encrypt / keygen /
+// decrypt (n keys, one ciphertext) / decrypt (n ciphertexts, one key); AW11 encrypt / keygen / decrypt; GHW11 encrypt / decrypt_out /
+// transform / decrypt / keygen / tkgen / provision; BDABE and MKE08 (one body, dnfabe) encrypt / keygen / secret attribute keys.  AC17's
+// packed encrypt, decrypt and KP keygen are in schemes.cpp.
+// What stays on the host is what the reference does with strings and bytes: policy parsing, flattening the tree into the index tables the
+// share kernels walk, traverse / calc_pruned / calc_coefficients per distinct policy, the selection tables, record layouts.  Records are the
+// byte form rabe_obj_serialize gives the corresponding struct (host_abi.cpp), so packed and object APIs interoperate.
+// The six "many records under one key" decrypts (bsw, lsw x 2, aw11, ghw11 transform and decrypt) are top-to-bottom functions -- parse body,
+// plan body, buffers, launch, messages -- over the helpers of the anonymous namespace below: PlanCache, for_each_record, Selection,
+// WalkScope, gather_record.
 #include "schemes.h"
 #include "records.h"
 
@@ -173,38 +177,182 @@ struct Cursor {
 };
 inline bool same(const std::pair<const char*, uint32_t>& a, const std::string& b) { return a.second == b.size() && memcmp(a.first, b.data(), b.size()) == 0; }
 
-// The plans of one call by (language, policy text), looked up WITHOUT copying the text and without serialising the readers: every item
-// of a batch asks for its policy's plan, the texts are kilobytes (a 200-leaf policy: ~10 KB), and a mutex around a std::map of strings
-// made the parse stage of a 4096-item call 8 ms long.  Misses go through the caller's (locking) maker and are remembered here.
+// The plans of one call by (language, key text), looked up WITHOUT copying the text and without serialising the readers: every item of a
+// batch asks for its policy's plan, the texts are kilobytes (a 200-leaf policy: ~10 KB), and a mutex around a std::map of strings made the
+// parse stage of a 4096-item call 8 ms long.  A miss runs `make(plan, text, lang)` under plans_mu -- once per distinct key, so no plan is
+// built twice -- and keeps what it threw in the plan's `err`: the items of that key then fail with it, one by one.
 template <class Plan>
-class FastPlans {
+class PlanCache {
  public:
-  std::shared_ptr<Plan> find(const char* txt, size_t len, PolicyLanguage lang) {
+  template <class MAKE>
+  std::shared_ptr<Plan> get(const char* txt, size_t len, PolicyLanguage lang, MAKE make) {
     const uint64_t h = hash(txt, len, lang);
+    if (auto hit = find(h, txt, len, lang)) return hit;
+    std::lock_guard<std::mutex> g(plans_mu);
+    if (auto hit = find(h, txt, len, lang)) return hit;
+    auto pl = std::make_shared<Plan>();
+    std::string text(txt, len);
+    try {
+      make(*pl, text, lang);
+    } catch (const std::exception& ex) {
+      pl->err = ex.what();
+      if (pl->err.empty()) pl->err = "policy error";
+    }
+    std::unique_lock<std::shared_mutex> w(mu_);
+    tab_[h].push_back(Entry{std::move(text), lang, pl});
+    return pl;
+  }
+ private:
+  struct Entry { std::string text; PolicyLanguage lang; std::shared_ptr<Plan> plan; };
+  std::shared_ptr<Plan> find(uint64_t h, const char* txt, size_t len, PolicyLanguage lang) {
     std::shared_lock<std::shared_mutex> g(mu_);
     auto it = tab_.find(h);
     if (it != tab_.end())
       for (const auto& e : it->second) if (e.lang == lang && e.text.size() == len && memcmp(e.text.data(), txt, len) == 0) return e.plan;
     return nullptr;
   }
-  void put(const char* txt, size_t len, PolicyLanguage lang, const std::shared_ptr<Plan>& plan) {
-    const uint64_t h = hash(txt, len, lang);
-    std::unique_lock<std::shared_mutex> g(mu_);
-    auto& bucket = tab_[h];
-    for (const auto& e : bucket) if (e.lang == lang && e.text.size() == len && memcmp(e.text.data(), txt, len) == 0) return;
-    bucket.push_back(Entry{std::string(txt, len), lang, plan});
-  }
- private:
-  struct Entry { std::string text; PolicyLanguage lang; std::shared_ptr<Plan> plan; };
   static uint64_t hash(const char* txt, size_t len, PolicyLanguage lang) {
     uint64_t h = 1469598103934665603ull ^ (uint64_t)lang;
     for (size_t i = 0; i + 8 <= len; i += 8) { uint64_t w; memcpy(&w, txt + i, 8); h = (h ^ w) * 1099511628211ull; }
     for (size_t i = len & ~(size_t)7; i < len; i++) h = (h ^ (uint8_t)txt[i]) * 1099511628211ull;
     return h;
   }
+  std::mutex plans_mu;          // the makers, one at a time
   std::shared_mutex mu_;
   std::unordered_map<uint64_t, std::vector<Entry>> tab_;
 };
+
+// fn(i) for every record that has no error yet, on the host's cores; what it throws is that record's error
+template <class FN>
+void for_each_record(size_t n, std::vector<std::string>* errors, FN fn) {
+  parallel_for(n, [&](size_t i) {
+    std::string& err = (*errors)[i];
+    if (!err.empty()) return;
+    try {
+      fn(i);
+    } catch (const std::exception& ex) {
+      err = ex.what();
+      if (err.empty()) err = "malformed record";
+    }
+  });
+}
+
+// The selection tables of a "many records against one key" decrypt (include/rabe_hip.h: rhip_*_decrypt_batch_one_sk and kin).  Live item j
+// (record live[j] of the call) has its rows at [row_off[j], row_off[j + 1]) of the gathered arrays, its pairs at [pair_off[j], pair_off[j + 1])
+// and its entries at sel_start[j]: entry e pairs row sel_rec[e] of the record with row sel_one[e] of the call's ONE object (the key; the
+// ciphertext of lsw::decrypt_packed), weighted by sel_z[e].  Records in the standard layout of one plan share their entries.
+struct Selection {
+  const uint32_t per_entry, extra;          // an item of m entries takes per_entry * m + extra pairs
+  std::vector<size_t> live;
+  std::vector<uint8_t> standard;            // per live item
+  std::vector<uint32_t> row_off{0}, pair_off{0}, sel_start, sel_rec, sel_one;
+  std::vector<Fr> sel_z;
+  size_t max_pairs;
+  Selection(uint32_t per_entry_, uint32_t extra_) : per_entry(per_entry_), extra(extra_), max_pairs(extra_) {}
+  uint32_t entries(size_t j) const { return (pair_off[j + 1] - pair_off[j] - extra) / per_entry; }
+  // record i with `rows` rows; entries(emit) calls emit(record row, row of the one object, weight) per entry of THIS record -- it is not
+  // called for a standard-layout record whose plan's entries are there already
+  template <class ENTRIES>
+  void add(size_t i, uint32_t rows, const void* plan, bool std_layout, ENTRIES entries) {
+    live.push_back(i);
+    standard.push_back(std_layout);
+    row_off.push_back(row_off.back() + rows);
+    auto emit = [&](uint32_t rec_row, uint32_t one_row, const Fr& z) { sel_rec.push_back(rec_row); sel_one.push_back(one_row); sel_z.push_back(z); };
+    std::pair<uint32_t, uint32_t> at{(uint32_t)sel_rec.size(), 0};          // start, count
+    auto it = std_layout ? shared_start.find(plan) : shared_start.end();
+    if (it != shared_start.end()) {
+      at = it->second;
+    } else {
+      entries(emit);
+      at.second = (uint32_t)sel_rec.size() - at.first;
+      if (std_layout) shared_start.insert({plan, at});
+    }
+    sel_start.push_back(at.first);
+    const uint32_t pairs = per_entry * at.second + extra;
+    pair_off.push_back(pair_off.back() + pairs);
+    if (pairs > max_pairs) max_pairs = pairs;
+  }
+ private:
+  std::map<const void*, std::pair<uint32_t, uint32_t>> shared_start;
+};
+
+// The membership checks of one untrusted batch (common.h: MemberChecks beside the decrypt, WalkedG2 out of its own Miller loops) and what
+// they refer to.  ONE lifetime rule: the walk's verdicts are read after the open (records.h: retract_item), so this object -- the checks,
+// the index lists WalkedG2 points to and the device array it reads -- is declared before the launch block and outlives it.
+struct WalkScope {
+  std::unique_ptr<MemberChecks> mc;
+  std::unique_ptr<WalkedG2> walked;
+  std::vector<uint32_t> walked_idx, walked_off;
+  DBuf d_g2;                                // the array whose elements the decrypt walks
+  size_t k_alone = (size_t)-1;              // without walk verdicts: the index of d_g2's stand-alone test among mc's checks
+  // Does the decrypt walk EVERY row of every item's G2 array (the rows its selection names)?  Only where it is verified: a record in the
+  // standard layout, as many entries as rows, the selected rows distinct and in range -- rows matched by name can coincide in a crafted record,
+  // and two plan entries can name one row (a policy that repeats an attribute); then some other row is walked by nobody.  Otherwise: false, and
+  // the walked elements of item j are walked_idx[walked_off[j] .. walked_off[j + 1]) (common.h: WalkedG2 tests the others stand-alone).
+  bool every_row_walked(const Selection& s) {
+    const size_t m_items = s.live.size();
+    bool all = true;
+    std::vector<uint8_t> seen;
+    for (size_t j = 0; j < m_items && all; j++) {
+      const uint32_t mj = s.entries(j), rows = s.row_off[j + 1] - s.row_off[j];
+      all = s.standard[j] && mj == rows;
+      if (!all) break;
+      seen.assign(rows, 0);
+      for (uint32_t e = 0; e < mj && all; e++) {
+        const uint32_t row = s.sel_rec[s.sel_start[j] + e];
+        all = row < rows && !seen[row];
+        if (all) seen[row] = 1;
+      }
+    }
+    if (all) return true;
+    walked_off.push_back(0);
+    for (size_t j = 0; j < m_items; j++) {
+      for (uint32_t e = 0; e < s.entries(j); e++) walked_idx.push_back(s.row_off[j] + s.sel_rec[s.sel_start[j] + e]);
+      walked_off.push_back((uint32_t)walked_idx.size());
+    }
+    return false;
+  }
+  // d_g2 = `total` rows in the selection's segments, its selected rows walking arguments of the decrypt's pairings (plus extra_walks arguments
+  // per item that are no elements of it): verdicts from those walks where `walk`, from the stand-alone test of every row otherwise
+  void check_g2(Engine& eng, bool walk, const Selection& s, size_t total, const uint32_t* dev_row_off, uint32_t extra_walks = 0) {
+    if (walk) {
+      const bool all = every_row_walked(s);
+      walked.reset(new WalkedG2(eng, *mc, d_g2.ptr(), total, dev_row_off, s.row_off, 1, all ? nullptr : &walked_idx, all ? nullptr : &walked_off, extra_walks));
+    } else {
+      k_alone = mc->add_count();
+      mc->add(2, d_g2.ptr(), total, dev_row_off, s.live.size());
+    }
+  }
+  // before the open: a live item that any of mc's checks `ks` refused fails with `msg` (k_alone counts where it exists); an earlier call's
+  // message stays, so the calls go in the decoder's order
+  void fail(const std::vector<size_t>& live, std::initializer_list<size_t> ks, const char* msg, std::vector<std::string>* errors) const {
+    for (size_t k : ks) {
+      if (k == (size_t)-1) continue;
+      const auto& ok = mc->ok(k);
+      for (size_t j = 0; j < live.size(); j++) if (!ok[j] && (*errors)[live[j]].empty()) (*errors)[live[j]] = msg;
+    }
+  }
+  // after the open: the items whose walk refused an element
+  void retract(const std::vector<size_t>& live, const char* msg, int32_t* status, uint8_t* pt_buf, const uint64_t* pt_off, std::vector<std::string>* errors) {
+    if (!walked) return;
+    std::vector<uint8_t> ok;
+    walked->finish(&ok);
+    for (size_t j = 0; j < live.size(); j++) if (!ok[j]) retract_item(live[j], msg, status, pt_buf, pt_off, errors);
+  }
+};
+
+// One live record of a BlobGather (records.h): records that share `key` (null: this record alone) share a shape; fill(parts) lists the
+// parts of a shape nobody registered yet
+template <class FILL>
+void gather_record(BlobGather& gather, uint64_t rec_off, const void* key, FILL fill) {
+  int shape = key ? gather.find(key) : -1;
+  if (shape < 0) {
+    std::vector<RecordLayout::Part> parts;
+    fill(parts);
+    shape = (int)gather.add_shape(key, std::move(parts));
+  }
+  gather.item(rec_off, (uint32_t)shape);
+}
 
 // where an item's sealed plaintext sits in the caller's blob (opened on the device: records.h, open_sealed_records)
 struct Sealed { const uint8_t* p = nullptr; uint32_t len = 0; };
@@ -682,119 +830,81 @@ bool decrypt_packed(Engine& eng, const CpAbeSecretKey& sk, size_t n, const uint8
     struct E { std::string name_col; uint32_t sk_row; Fr z; uint32_t std_ct_row; };
     std::vector<E> ent;
   };
-  std::map<std::pair<int, std::string>, std::shared_ptr<Plan>> plans;
-  std::mutex plans_mu;
-  FastPlans<Plan> fast_plans;
-  auto plan_of = [&](const std::string& text, PolicyLanguage lang) -> std::shared_ptr<Plan> {
-    std::lock_guard<std::mutex> g(plans_mu);
-    auto key = std::make_pair((int)lang, text);
-    auto it = plans.find(key);
-    if (it != plans.end()) return it->second;
-    auto pl = std::make_shared<Plan>();
-    try {
-      pl->flat = flat_policy(text, lang);
-      const PolicyNode& tree = pl->flat->tree;
-      if (!traverse_policy(attr, tree)) throw RabeError("Error in bsw/encrypt: attributes do not match policy.");
-      PrunedList pruned;
-      if (!calc_pruned(attr, tree, &pruned)) throw RabeError("Error in bsw/encrypt: attributes do not match policy.");
-      for (const auto& pr : pruned) {
-        size_t dj = 0;
-        while (dj < sk.d_j.size() && sk.d_j[dj].string != pr.first) dj++;
-        if (dj == sk.d_j.size()) continue;
-        size_t std_row = 0;
-        while (std_row < pl->flat->leaf_name_col.size() && pl->flat->leaf_name_col[std_row] != pr.second) std_row++;
-        for (size_t y = 0; y < pl->flat->leaf_name_col.size(); y++)
-          if (pl->flat->leaf_name_col[y] == pr.second) pl->ent.push_back({pr.second, (uint32_t)dj, pl->flat->leaf_coeff[y], (uint32_t)std_row});
-      }
-    } catch (const std::exception& ex) {
-      pl->err = ex.what();
-      if (pl->err.empty()) pl->err = "policy error";
+  PlanCache<Plan> plans;
+  auto make_plan = [&](Plan& pl, const std::string& text, PolicyLanguage lang) {
+    pl.flat = flat_policy(text, lang);
+    const PolicyNode& tree = pl.flat->tree;
+    if (!traverse_policy(attr, tree)) throw RabeError("Error in bsw/encrypt: attributes do not match policy.");
+    PrunedList pruned;
+    if (!calc_pruned(attr, tree, &pruned)) throw RabeError("Error in bsw/encrypt: attributes do not match policy.");
+    for (const auto& pr : pruned) {
+      size_t dj = 0;
+      while (dj < sk.d_j.size() && sk.d_j[dj].string != pr.first) dj++;
+      if (dj == sk.d_j.size()) continue;
+      size_t std_row = 0;
+      while (std_row < pl.flat->leaf_name_col.size() && pl.flat->leaf_name_col[std_row] != pr.second) std_row++;
+      for (size_t y = 0; y < pl.flat->leaf_name_col.size(); y++)
+        if (pl.flat->leaf_name_col[y] == pr.second) pl.ent.push_back({pr.second, (uint32_t)dj, pl.flat->leaf_coeff[y], (uint32_t)std_row});
     }
-    plans[key] = pl;
-    return pl;
   };
   struct View { const uint8_t* c; const uint8_t* cp; uint32_t rows; std::vector<const uint8_t*> g1, g2; std::shared_ptr<Plan> plan;
                 std::vector<uint32_t> ct_row; bool standard; };
   std::vector<View> v(n);
   std::vector<Sealed> sealed(n);
-  parallel_for(n, [&](size_t i) {
-    if (!(*errors)[i].empty()) return;
-    try {
-      Cursor r{ct_blob + ct_off[i], ct_blob + ct_off[i + 1]};
-      auto pol = r.str();
-      const PolicyLanguage lang = *r.raw(1) ? PolicyLanguage::HumanPolicy : PolicyLanguage::JsonPolicy;
-      v[i].c = r.raw(64);
-      v[i].cp = r.raw(384);
-      const uint32_t rows = r.u32();
-      if ((size_t)rows * 196 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
-      v[i].rows = rows;
-      v[i].g1.resize(rows);
-      v[i].g2.resize(rows);
-      std::vector<std::pair<const char*, uint32_t>> names(rows);
-      for (uint32_t y = 0; y < rows; y++) { names[y] = r.str(); v[i].g1[y] = r.raw(64); v[i].g2[y] = r.raw(128); }
-      sealed[i].len = r.u32();
-      sealed[i].p = r.raw(sealed[i].len);
-      auto pl = fast_plans.find(pol.first, pol.second, lang);
-      if (!pl) { pl = plan_of(std::string(pol.first, pol.second), lang); fast_plans.put(pol.first, pol.second, lang, pl); }
-      if (!pl->err.empty()) throw RabeError(pl->err);
-      v[i].plan = pl;
-      const auto& std_names = pl->flat->leaf_name_col;
-      bool standard = rows == std_names.size();
-      for (uint32_t y = 0; y < rows && standard; y++) standard = same(names[y], std_names[y]);
-      v[i].standard = standard;
-      if (!standard) {                              // rows in another order / other names: the name-matching loop itself (:283-287)
-        for (const auto& e : pl->ent) {
-          uint32_t y = 0;
-          while (y < rows && !same(names[y], e.name_col)) y++;
-          v[i].ct_row.push_back(y);               // y == rows: no such row -> the entry is skipped below
-        }
+  for_each_record(n, errors, [&](size_t i) {
+    Cursor r{ct_blob + ct_off[i], ct_blob + ct_off[i + 1]};
+    auto pol = r.str();
+    const PolicyLanguage lang = *r.raw(1) ? PolicyLanguage::HumanPolicy : PolicyLanguage::JsonPolicy;
+    v[i].c = r.raw(64);
+    v[i].cp = r.raw(384);
+    const uint32_t rows = r.u32();
+    if ((size_t)rows * 196 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
+    v[i].rows = rows;
+    v[i].g1.resize(rows);
+    v[i].g2.resize(rows);
+    std::vector<std::pair<const char*, uint32_t>> names(rows);
+    for (uint32_t y = 0; y < rows; y++) { names[y] = r.str(); v[i].g1[y] = r.raw(64); v[i].g2[y] = r.raw(128); }
+    sealed[i].len = r.u32();
+    sealed[i].p = r.raw(sealed[i].len);
+    auto pl = plans.get(pol.first, pol.second, lang, make_plan);
+    if (!pl->err.empty()) throw RabeError(pl->err);
+    v[i].plan = pl;
+    const auto& std_names = pl->flat->leaf_name_col;
+    bool standard = rows == std_names.size();
+    for (uint32_t y = 0; y < rows && standard; y++) standard = same(names[y], std_names[y]);
+    v[i].standard = standard;
+    if (!standard) {                              // rows in another order / other names: the name-matching loop itself (:283-287)
+      for (const auto& e : pl->ent) {
+        uint32_t y = 0;
+        while (y < rows && !same(names[y], e.name_col)) y++;
+        v[i].ct_row.push_back(y);               // y == rows: no such row -> the entry is skipped below
       }
-    } catch (const std::exception& ex) {
-      (*errors)[i] = ex.what();
-      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
     }
   });
   tm.lap("parse + plan");
-  std::vector<size_t> live;
-  std::vector<uint32_t> leaf_off{0}, pair_off{0}, sel_start, sel_ct, sel_sk;
-  std::vector<Fr> sel_z;
-  std::map<const Plan*, uint32_t> shared_start;          // standard-layout items of one policy share their selection entries
-  size_t max_pairs = 1;
+  Selection sel(2, 1);          // m entries: 2 m + 1 pairs
   for (size_t i = 0; i < n; i++) {
     if (!(*errors)[i].empty()) continue;
-    live.push_back(i);
-    leaf_off.push_back(leaf_off.back() + v[i].rows);
-    const Plan& pl = *v[i].plan;
-    uint32_t m = 0;
-    if (v[i].standard) {
-      auto it = shared_start.find(&pl);
-      if (it == shared_start.end()) {
-        it = shared_start.insert({&pl, (uint32_t)sel_ct.size()}).first;
-        for (const auto& e : pl.ent) { sel_ct.push_back(e.std_ct_row); sel_sk.push_back(e.sk_row); sel_z.push_back(e.z); }
+    const View& w = v[i];
+    sel.add(i, w.rows, w.plan.get(), w.standard, [&](auto emit) {
+      const auto& ent = w.plan->ent;
+      for (size_t e = 0; e < ent.size(); e++) {
+        if (w.standard) emit(ent[e].std_ct_row, ent[e].sk_row, ent[e].z);
+        else if (w.ct_row[e] < w.rows) emit(w.ct_row[e], ent[e].sk_row, ent[e].z);
       }
-      sel_start.push_back(it->second);
-      m = (uint32_t)pl.ent.size();
-    } else {
-      sel_start.push_back((uint32_t)sel_ct.size());
-      for (size_t e = 0; e < pl.ent.size(); e++)
-        if (v[i].ct_row[e] < v[i].rows) { sel_ct.push_back(v[i].ct_row[e]); sel_sk.push_back(pl.ent[e].sk_row); sel_z.push_back(pl.ent[e].z); m++; }
-    }
-    pair_off.push_back(pair_off.back() + 2 * m + 1);
-    if ((size_t)2 * m + 1 > max_pairs) max_pairs = 2 * m + 1;
+    });
   }
+  const std::vector<size_t>& live = sel.live;
+  const std::vector<uint32_t>& leaf_off = sel.row_off;
   const size_t m_items = live.size();
   std::vector<uint64_t> sealed_off(m_items);
   std::vector<uint32_t> sealed_len(m_items);
   DBuf d_out(&eng, m_items * 384 + 4);
-  // what the walk's verdicts refer to outlives the block below: they are read after the open (records.h: retract_item)
-  std::unique_ptr<MemberChecks> mc;          // the decoding checks run on the side context, beside the decrypt kernels (common.h)
-  std::unique_ptr<WalkedG2> walked;
-  std::vector<uint32_t> walked_idx, walked_off;
-  DBuf d_g2;
+  WalkScope ws;          // the decoding checks run on the side context, beside the decrypt kernels (common.h)
   if (m_items) {
     const size_t total = leaf_off[m_items];
     DBuf d_c(&eng, m_items * 64), d_cp(&eng, m_items * 384), d_g1(&eng, total * 64 + 4);
-    d_g2 = DBuf(&eng, total * 128 + 4);
+    DBuf& d_g2 = ws.d_g2 = DBuf(&eng, total * 128 + 4);
     std::vector<uint64_t> dst_off(4 * m_items);
     for (size_t j = 0; j < m_items; j++) {
       const View& w = v[live[j]];
@@ -802,27 +912,24 @@ bool decrypt_packed(Engine& eng, const CpAbeSecretKey& sk, size_t n, const uint8
       sealed_off[j] = (uint64_t)(sealed[live[j]].p - ct_blob);
       sealed_len[j] = sealed[live[j]].len;
       dst_off[j] = 64ull * j; dst_off[m_items + j] = 384ull * j; dst_off[2 * m_items + j] = 64ull * leaf_off[j]; dst_off[3 * m_items + j] = 128ull * leaf_off[j];
-      int shape = w.standard ? gather.find(w.plan.get()) : -1;          // standard layout: policy text and names as encrypt writes them -> one skeleton
-      if (shape < 0) {
-        std::vector<RecordLayout::Part> parts;
+      // standard layout: policy text and names as encrypt writes them -> one skeleton
+      gather_record(gather, ct_off[live[j]], w.standard ? w.plan.get() : nullptr, [&](std::vector<RecordLayout::Part>& parts) {
         parts.push_back({(uint32_t)(w.c - rec), 64, 0, 0});
         parts.push_back({(uint32_t)(w.cp - rec), 384, 1, 0});
         for (uint32_t y = 0; y < w.rows; y++) {
           parts.push_back({(uint32_t)(w.g1[y] - rec), 64, 2, 64 * y});
           parts.push_back({(uint32_t)(w.g2[y] - rec), 128, 3, 128 * y});
         }
-        shape = (int)gather.add_shape(w.standard ? (const void*)w.plan.get() : nullptr, std::move(parts));
-      }
-      gather.item(ct_off[live[j]], (uint32_t)shape);
+      });
     }
     tm.lap("shapes");
     rhip_ctx* cx = eng.ctx();
     std::vector<uint8_t> kg1, kg2;
     for (const auto& a : sk.d_j) { kg1.insert(kg1.end(), a.g1.begin(), a.g1.end()); kg2.insert(kg2.end(), a.g2.begin(), a.g2.end()); }
     std::vector<uint32_t> sk_attr_off{0, (uint32_t)sk.d_j.size()};
-    auto fz = flatten_fr(sel_z);
+    auto fz = flatten_fr(sel.sel_z);
     DBuf d_leaf_off = up32(eng, leaf_off),
-        d_pair_off = up32(eng, pair_off), d_sel_start = up32(eng, sel_start), d_sel_ct = up32(eng, sel_ct), d_sel_sk = up32(eng, sel_sk),
+        d_pair_off = up32(eng, sel.pair_off), d_sel_start = up32(eng, sel.sel_start), d_sel_ct = up32(eng, sel.sel_rec), d_sel_sk = up32(eng, sel.sel_one),
         d_sel_z = up_bytes(eng, fz), d_skd(&eng, sk.d.data(), 128), d_kg1 = up_bytes(eng, kg1), d_kg2 = up_bytes(eng, kg2),
         d_sk_attr_off = up32(eng, sk_attr_off);
     gather.run({d_c.ptr(), d_cp.ptr(), d_g1.ptr(), d_g2.ptr()}, dst_off);
@@ -834,69 +941,30 @@ bool decrypt_packed(Engine& eng, const CpAbeSecretKey& sk, size_t n, const uint8
       lines = (rhip_bsw_sk_lines*)eng.aux("bsw_sk_lines", key, make_sk_lines, &key, destroy_sk_lines, 4);
     }
     if (!trusted) {
-      mc.reset(new MemberChecks(eng));
-      mc->add(1, d_c.ptr(), m_items); mc->add(1, d_g1.ptr(), total, d_leaf_off.as<uint32_t>(), m_items);
-      mc->add(3, d_cp.ptr(), m_items);
+      ws.mc.reset(new MemberChecks(eng));
+      ws.mc->add(1, d_c.ptr(), m_items); ws.mc->add(1, d_g1.ptr(), total, d_leaf_off.as<uint32_t>(), m_items);
+      ws.mc->add(3, d_cp.ptr(), m_items);
       // Cy.g2 of every selected leaf is the walking argument of a pairing (the key's side replays prepared lines): the decrypt's own
       // Miller loops say whether it is a member of G2; leaves the policy did not select get the stand-alone test (common.h: WalkedG2)
-      if (walk_checks() && lines) {
-        // "every leaf is walked" may only be concluded from the counts for records in the standard layout (their selection is the plan's:
-        // distinct rows); rows matched by NAME can coincide in a crafted record, and then some other row is walked by nobody
-        // ... and the count argument needs the selected rows of an item to be DISTINCT: it is verified, not assumed (two plan entries
-        // that named one row would leave another one walked by nobody)
-        bool all = true;
-        std::vector<uint8_t> seen;
-        for (size_t j = 0; j < m_items && all; j++) {
-          const uint32_t mj = (pair_off[j + 1] - pair_off[j] - 1) / 2, leaves = leaf_off[j + 1] - leaf_off[j];
-          all = v[live[j]].standard && mj == leaves;
-          if (!all) break;
-          seen.assign(leaves, 0);
-          for (uint32_t e = 0; e < mj && all; e++) {
-            const uint32_t row = sel_ct[sel_start[j] + e];
-            all = row < leaves && !seen[row];
-            if (all) seen[row] = 1;
-          }
-        }
-        if (!all) {
-          walked_off.push_back(0);
-          for (size_t j = 0; j < m_items; j++) {
-            const uint32_t mj = (pair_off[j + 1] - pair_off[j] - 1) / 2;
-            for (uint32_t e = 0; e < mj; e++) walked_idx.push_back(leaf_off[j] + sel_ct[sel_start[j] + e]);
-            walked_off.push_back((uint32_t)walked_idx.size());
-          }
-        }
-        walked.reset(new WalkedG2(eng, *mc, d_g2.ptr(), total, d_leaf_off.as<uint32_t>(), leaf_off, 1, all ? nullptr : &walked_idx, all ? nullptr : &walked_off));
-      } else {
-        mc->add(2, d_g2.ptr(), total, d_leaf_off.as<uint32_t>(), m_items);
-      }
+      ws.check_g2(eng, walk_checks() && lines, sel, total, d_leaf_off.as<uint32_t>());
     }
     // one key for all ciphertexts: its scaled Dj.g1 are computed once per selection entry (ciphertexts that share a policy share them)
-    if (walked) walked->arm();
-    int32_t rc = rhip_bsw_decrypt_batch_one_sk(cx, m_items, max_pairs, pair_off[m_items], sel_ct.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
-                                               d_sel_ct.as<uint32_t>(), d_sel_sk.as<uint32_t>(), d_sel_z.as<rhip_fr>(), d_c.as<rhip_g1>(), d_cp.as<rhip_gt>(),
-                                               d_g1.as<rhip_g1>(), d_g2.as<rhip_g2>(), d_leaf_off.as<uint32_t>(), d_skd.as<rhip_g2>(), d_kg1.as<rhip_g1>(),
-                                               d_kg2.as<rhip_g2>(), d_sk_attr_off.as<uint32_t>(), lines, d_out.as<rhip_gt>());
+    if (ws.walked) ws.walked->arm();
+    int32_t rc = rhip_bsw_decrypt_batch_one_sk(cx, m_items, sel.max_pairs, sel.pair_off[m_items], sel.sel_rec.size(), d_pair_off.as<uint32_t>(),
+                                               d_sel_start.as<uint32_t>(), d_sel_ct.as<uint32_t>(), d_sel_sk.as<uint32_t>(), d_sel_z.as<rhip_fr>(), d_c.as<rhip_g1>(),
+                                               d_cp.as<rhip_gt>(), d_g1.as<rhip_g1>(), d_g2.as<rhip_g2>(), d_leaf_off.as<uint32_t>(), d_skd.as<rhip_g2>(),
+                                               d_kg1.as<rhip_g1>(), d_kg2.as<rhip_g2>(), d_sk_attr_off.as<uint32_t>(), lines, d_out.as<rhip_gt>());
     eng.check(rc, "rhip_bsw_decrypt_batch");
-    if (mc) {
-      mc->collect();
-      const auto &ok_c = mc->ok(0), &ok_g1 = mc->ok(1), &ok_cp = mc->ok(2);
-      std::vector<uint8_t> ok_g2(m_items, 1);
-      if (!walked) { const auto& e = mc->ok(3); ok_g2.assign(e.begin(), e.end()); }
-      for (size_t j = 0; j < m_items; j++) {
-        const char* bad = !ok_c[j] ? "deserialize: c is not a point of G1 (FieldError::NotMember)" : !ok_cp[j] ? "deserialize: c_p is not a member of Gt (FieldError::NotMember)" : nullptr;
-        if (!bad && (!ok_g1[j] || !ok_g2[j])) bad = "deserialize: a leaf element is not a group member (FieldError::NotMember)";
-        if (bad) (*errors)[live[j]] = bad;
-      }
+    if (ws.mc) {
+      ws.mc->collect();
+      ws.fail(live, {0}, "deserialize: c is not a point of G1 (FieldError::NotMember)", errors);
+      ws.fail(live, {2}, "deserialize: c_p is not a member of Gt (FieldError::NotMember)", errors);
+      ws.fail(live, {1, ws.k_alone}, "deserialize: a leaf element is not a group member (FieldError::NotMember)", errors);
     }
   }
   // KDF + AES-GCM open on the device: the decrypted Gt never leaves HBM; plaintext bytes come back in one copy
   open_sealed_records(eng, n, live, d_out.ptr(), gather.dev_blob(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
-  if (walked) {
-    std::vector<uint8_t> ok_g2;
-    walked->finish(&ok_g2);
-    for (size_t j = 0; j < m_items; j++)
-      if (!ok_g2[j]) retract_item(live[j], "deserialize: a leaf element is not a group member (FieldError::NotMember)", status, pt_buf, pt_off, errors);
-  }
+  ws.retract(live, "deserialize: a leaf element is not a group member (FieldError::NotMember)", status, pt_buf, pt_off, errors);
   tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
   return true;
 }
@@ -1178,124 +1246,82 @@ bool decrypt_packed(Engine& eng, const KpAbeCiphertext& ct, size_t n, const uint
     struct E { std::string name; uint32_t ct_row; Fr c; uint32_t std_sk_row; };
     std::vector<E> ent;
   };
-  std::map<std::pair<int, std::string>, std::shared_ptr<Plan>> plans;
-  std::mutex plans_mu;
-  FastPlans<Plan> fast_plans;
-  auto plan_of = [&](const std::string& text, PolicyLanguage lang) -> std::shared_ptr<Plan> {
-    std::lock_guard<std::mutex> g(plans_mu);
-    auto key = std::make_pair((int)lang, text);
-    auto it = plans.find(key);
-    if (it != plans.end()) return it->second;
-    auto pl = std::make_shared<Plan>();
-    try {
-      pl->flat = flat_policy(text, lang);
-      for (const auto& nc : pl->flat->leaf_name_col) pl->std_names.push_back(remove_index(nc));
-      PrunedList list;
-      if (!calc_pruned(attr, pl->flat->tree, &list)) throw RabeError("Error in lsw/decrypt: attributes do not match policy.");
-      for (const auto& a : list) {
-        if (is_negative(a.first)) throw RabeError("lsw::decrypt_packed: a negative attribute is selected; rabe_lsw_decrypt reproduces the reference's branch");
-        size_t cr = 0, sr = 0, co = 0;
-        while (cr < ct.ej.size() && ct.ej[cr].name != a.first) cr++;
-        while (sr < pl->std_names.size() && pl->std_names[sr] != a.first) sr++;
-        while (co < pl->flat->leaf_name_col.size() && pl->flat->leaf_name_col[co] != a.second) co++;
-        if (cr == ct.ej.size() || co == pl->flat->leaf_name_col.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
-        pl->ent.push_back({a.first, (uint32_t)cr, pl->flat->leaf_coeff[co], (uint32_t)sr});
-      }
-    } catch (const std::exception& ex) {
-      pl->err = ex.what();
-      if (pl->err.empty()) pl->err = "policy error";
+  PlanCache<Plan> plans;
+  auto make_plan = [&](Plan& pl, const std::string& text, PolicyLanguage lang) {
+    pl.flat = flat_policy(text, lang);
+    for (const auto& nc : pl.flat->leaf_name_col) pl.std_names.push_back(remove_index(nc));
+    PrunedList list;
+    if (!calc_pruned(attr, pl.flat->tree, &list)) throw RabeError("Error in lsw/decrypt: attributes do not match policy.");
+    for (const auto& a : list) {
+      if (is_negative(a.first)) throw RabeError("lsw::decrypt_packed: a negative attribute is selected; rabe_lsw_decrypt reproduces the reference's branch");
+      size_t cr = 0, sr = 0, co = 0;
+      while (cr < ct.ej.size() && ct.ej[cr].name != a.first) cr++;
+      while (sr < pl.std_names.size() && pl.std_names[sr] != a.first) sr++;
+      while (co < pl.flat->leaf_name_col.size() && pl.flat->leaf_name_col[co] != a.second) co++;
+      if (cr == ct.ej.size() || co == pl.flat->leaf_name_col.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
+      pl.ent.push_back({a.first, (uint32_t)cr, pl.flat->leaf_coeff[co], (uint32_t)sr});
     }
-    plans[key] = pl;
-    return pl;
   };
   struct View { uint32_t rows; std::vector<const uint8_t*> d1, d2; std::shared_ptr<Plan> plan; std::vector<uint32_t> sk_row; bool standard; };
   std::vector<View> v(n);
-  parallel_for(n, [&](size_t i) {
-    if (!(*errors)[i].empty()) return;
-    try {
-      Cursor r{sk_blob + sk_off[i], sk_blob + sk_off[i + 1]};
-      auto pol = r.str();
-      const PolicyLanguage lang = *r.raw(1) ? PolicyLanguage::HumanPolicy : PolicyLanguage::JsonPolicy;
-      const uint32_t rows = r.u32();
-      if ((size_t)rows * 388 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
-      v[i].rows = rows;
-      v[i].d1.resize(rows);
-      v[i].d2.resize(rows);
-      std::vector<std::pair<const char*, uint32_t>> names(rows);
-      for (uint32_t y = 0; y < rows; y++) { names[y] = r.str(); v[i].d1[y] = r.raw(64); v[i].d2[y] = r.raw(128); (void)r.raw(192); }
-      auto pl = fast_plans.find(pol.first, pol.second, lang);
-      if (!pl) { pl = plan_of(std::string(pol.first, pol.second), lang); fast_plans.put(pol.first, pol.second, lang, pl); }
-      if (!pl->err.empty()) throw RabeError(pl->err);
-      v[i].plan = pl;
-      bool standard = rows == pl->std_names.size();
-      for (uint32_t y = 0; y < rows && standard; y++) standard = same(names[y], pl->std_names[y]);
-      v[i].standard = standard;
-      if (!standard) {
-        for (const auto& e : pl->ent) {
-          uint32_t y = 0;
-          while (y < rows && !same(names[y], e.name)) y++;
-          if (y == rows) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
-          v[i].sk_row.push_back(y);
-        }
-      } else {
-        for (const auto& e : pl->ent) if (e.std_sk_row >= rows) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
+  for_each_record(n, errors, [&](size_t i) {
+    Cursor r{sk_blob + sk_off[i], sk_blob + sk_off[i + 1]};
+    auto pol = r.str();
+    const PolicyLanguage lang = *r.raw(1) ? PolicyLanguage::HumanPolicy : PolicyLanguage::JsonPolicy;
+    const uint32_t rows = r.u32();
+    if ((size_t)rows * 388 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
+    v[i].rows = rows;
+    v[i].d1.resize(rows);
+    v[i].d2.resize(rows);
+    std::vector<std::pair<const char*, uint32_t>> names(rows);
+    for (uint32_t y = 0; y < rows; y++) { names[y] = r.str(); v[i].d1[y] = r.raw(64); v[i].d2[y] = r.raw(128); (void)r.raw(192); }
+    auto pl = plans.get(pol.first, pol.second, lang, make_plan);
+    if (!pl->err.empty()) throw RabeError(pl->err);
+    v[i].plan = pl;
+    bool standard = rows == pl->std_names.size();
+    for (uint32_t y = 0; y < rows && standard; y++) standard = same(names[y], pl->std_names[y]);
+    v[i].standard = standard;
+    if (!standard) {
+      for (const auto& e : pl->ent) {
+        uint32_t y = 0;
+        while (y < rows && !same(names[y], e.name)) y++;
+        if (y == rows) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
+        v[i].sk_row.push_back(y);
       }
-    } catch (const std::exception& ex) {
-      (*errors)[i] = ex.what();
-      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
+    } else {
+      for (const auto& e : pl->ent) if (e.std_sk_row >= rows) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
     }
   });
   tm.lap("parse + plan");
-  std::vector<size_t> live;
-  std::vector<uint32_t> leaf_off{0}, pair_off{0}, sel_start, sel_sk, sel_ct;
-  std::vector<Fr> sel_z;
-  std::map<const Plan*, uint32_t> shared_start;
-  size_t max_pairs = 1;
+  Selection sel(1, 1);          // m entries: m + 1 pairs
   for (size_t i = 0; i < n; i++) {
     if (!(*errors)[i].empty()) continue;
-    live.push_back(i);
-    leaf_off.push_back(leaf_off.back() + v[i].rows);
-    const Plan& pl = *v[i].plan;
-    if (v[i].standard) {
-      auto it = shared_start.find(&pl);
-      if (it == shared_start.end()) {
-        it = shared_start.insert({&pl, (uint32_t)sel_sk.size()}).first;
-        for (const auto& e : pl.ent) { sel_sk.push_back(e.std_sk_row); sel_ct.push_back(e.ct_row); sel_z.push_back(e.c); }
-      }
-      sel_start.push_back(it->second);
-    } else {
-      sel_start.push_back((uint32_t)sel_sk.size());
-      for (size_t e = 0; e < pl.ent.size(); e++) { sel_sk.push_back(v[i].sk_row[e]); sel_ct.push_back(pl.ent[e].ct_row); sel_z.push_back(pl.ent[e].c); }
-    }
-    const uint32_t m = (uint32_t)pl.ent.size();
-    pair_off.push_back(pair_off.back() + m + 1);
-    if ((size_t)m + 1 > max_pairs) max_pairs = m + 1;
+    const View& w = v[i];
+    sel.add(i, w.rows, w.plan.get(), w.standard, [&](auto emit) {
+      const auto& ent = w.plan->ent;
+      for (size_t e = 0; e < ent.size(); e++) emit(w.standard ? ent[e].std_sk_row : w.sk_row[e], ent[e].ct_row, ent[e].c);
+    });
   }
+  const std::vector<size_t>& live = sel.live;
+  const std::vector<uint32_t>& leaf_off = sel.row_off;
   const size_t m_items = live.size();
   DBuf d_out(&eng, m_items * 384 + 4);
-  std::unique_ptr<MemberChecks> mc;
-  std::unique_ptr<WalkedG2> walked;          // read after the open (records.h: retract_item): it and what it refers to outlive the block
-  std::vector<uint32_t> walked_idx, walked_off;
-  DBuf d_d2;
+  WalkScope ws;
   if (m_items) {
     const size_t total = leaf_off[m_items];
     DBuf d_d1(&eng, total * 64 + 4);
-    d_d2 = DBuf(&eng, total * 128 + 4);
+    DBuf& d_d2 = ws.d_g2 = DBuf(&eng, total * 128 + 4);
     std::vector<uint64_t> dst_off(2 * m_items);
     for (size_t j = 0; j < m_items; j++) {
       const View& w = v[live[j]];
       const uint8_t* rec = sk_blob + sk_off[live[j]];
       dst_off[j] = 64ull * leaf_off[j]; dst_off[m_items + j] = 128ull * leaf_off[j];
-      int shape = w.standard ? gather.find(w.plan.get()) : -1;
-      if (shape < 0) {
-        std::vector<RecordLayout::Part> parts;
+      gather_record(gather, sk_off[live[j]], w.standard ? w.plan.get() : nullptr, [&](std::vector<RecordLayout::Part>& parts) {
         for (uint32_t y = 0; y < w.rows; y++) {
           parts.push_back({(uint32_t)(w.d1[y] - rec), 64, 0, 64 * y});
           parts.push_back({(uint32_t)(w.d2[y] - rec), 128, 1, 128 * y});
         }
-        shape = (int)gather.add_shape(w.standard ? (const void*)w.plan.get() : nullptr, std::move(parts));
-      }
-      gather.item(sk_off[live[j]], (uint32_t)shape);
+      });
     }
     tm.lap("shapes");
     rhip_ctx* cx = eng.ctx();
@@ -1303,47 +1329,29 @@ bool decrypt_packed(Engine& eng, const KpAbeCiphertext& ct, size_t n, const uint
     for (const auto& a : ct.ej) e1j.insert(e1j.end(), a.e1.begin(), a.e1.end());
     for (size_t j = 0; j < m_items; j++) memcpy(e1rep.data() + 384 * j, ct.e1.data(), 384);
 
-    DBuf d_leaf_off = up32(eng, leaf_off), d_pair_off = up32(eng, pair_off),
-        d_sel_start = up32(eng, sel_start), d_sel_sk = up32(eng, sel_sk), d_sel_ct = up32(eng, sel_ct), d_sel_z = up_bytes(eng, flatten_fr(sel_z)),
+    DBuf d_leaf_off = up32(eng, leaf_off), d_pair_off = up32(eng, sel.pair_off),
+        d_sel_start = up32(eng, sel.sel_start), d_sel_sk = up32(eng, sel.sel_rec), d_sel_ct = up32(eng, sel.sel_one), d_sel_z = up_bytes(eng, flatten_fr(sel.sel_z)),
         d_e1 = up_bytes(eng, e1rep), d_e2(&eng, ct.e2.data(), 128), d_e1j = up_bytes(eng, e1j);
     gather.run({d_d1.ptr(), d_d2.ptr()}, dst_off);
     std::string e2_key((const char*)ct.e2.data(), 128);         // the ciphertext's prepared e2 lines: kept across calls
     rhip_g2_lines* lines = (rhip_g2_lines*)eng.aux("lsw_e2_lines", e2_key, make_e2_lines, &e2_key, destroy_e2_lines, 4);
     if (!trusted) {
-      mc.reset(new MemberChecks(eng));
-      mc->add(1, d_d1.ptr(), total, d_leaf_off.as<uint32_t>(), m_items);
+      ws.mc.reset(new MemberChecks(eng));
+      ws.mc->add(1, d_d1.ptr(), total, d_leaf_off.as<uint32_t>(), m_items);
       // D2 of every selected key leaf is the walking argument of a pairing (e2 replays prepared lines): membership out of the decrypt's
       // own Miller loops, the stand-alone test for the leaves the selection left out (common.h: WalkedG2)
-      if (walk_checks() && lines) {
-        bool all = true;          // concluded from the counts for standard-layout records only (see bsw::decrypt_packed)
-        for (size_t j = 0; j < m_items && all; j++) all = v[live[j]].standard && pair_off[j + 1] - pair_off[j] - 1 == leaf_off[j + 1] - leaf_off[j];
-        if (!all) {
-          walked_off.push_back(0);
-          for (size_t j = 0; j < m_items; j++) {
-            const uint32_t mj = pair_off[j + 1] - pair_off[j] - 1;
-            for (uint32_t e = 0; e < mj; e++) walked_idx.push_back(leaf_off[j] + sel_sk[sel_start[j] + e]);
-            walked_off.push_back((uint32_t)walked_idx.size());
-          }
-        }
-        walked.reset(new WalkedG2(eng, *mc, d_d2.ptr(), total, d_leaf_off.as<uint32_t>(), leaf_off, 1, all ? nullptr : &walked_idx, all ? nullptr : &walked_off));
-      } else {
-        mc->add(2, d_d2.ptr(), total, d_leaf_off.as<uint32_t>(), m_items);
-      }
+      ws.check_g2(eng, walk_checks() && lines, sel, total, d_leaf_off.as<uint32_t>());
     }
-    if (walked) walked->arm();
+    if (ws.walked) ws.walked->arm();
     // one ciphertext for all keys: the scaled ciphertext rows are computed once per selection entry (keys that share a policy share them)
-    int32_t rc = rhip_lsw_decrypt_batch_one_ct(cx, m_items, max_pairs, pair_off[m_items], sel_sk.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
-                                               d_sel_sk.as<uint32_t>(), d_sel_ct.as<uint32_t>(), d_sel_z.as<rhip_fr>(), d_e1.as<rhip_gt>(), d_e2.as<rhip_g2>(),
-                                               d_e1j.as<rhip_g1>(), d_d1.as<rhip_g1>(), d_d2.as<rhip_g2>(), d_leaf_off.as<uint32_t>(), (const uint32_t*)nullptr, lines,
-                                               d_out.as<rhip_gt>());
+    int32_t rc = rhip_lsw_decrypt_batch_one_ct(cx, m_items, sel.max_pairs, sel.pair_off[m_items], sel.sel_rec.size(), d_pair_off.as<uint32_t>(),
+                                               d_sel_start.as<uint32_t>(), d_sel_sk.as<uint32_t>(), d_sel_ct.as<uint32_t>(), d_sel_z.as<rhip_fr>(), d_e1.as<rhip_gt>(),
+                                               d_e2.as<rhip_g2>(), d_e1j.as<rhip_g1>(), d_d1.as<rhip_g1>(), d_d2.as<rhip_g2>(), d_leaf_off.as<uint32_t>(),
+                                               (const uint32_t*)nullptr, lines, d_out.as<rhip_gt>());
     eng.check(rc, "rhip_lsw_decrypt_batch");
-    if (mc) {
-      mc->collect();
-      const auto& ok1 = mc->ok(0);
-      std::vector<uint8_t> ok2(m_items, 1);
-      if (!walked) { const auto& e = mc->ok(1); ok2.assign(e.begin(), e.end()); }
-      for (size_t j = 0; j < m_items; j++)
-        if (!ok1[j] || !ok2[j]) (*errors)[live[j]] = "deserialize: a key element is not a group member (FieldError::NotMember)";
+    if (ws.mc) {
+      ws.mc->collect();
+      ws.fail(live, {0, ws.k_alone}, "deserialize: a key element is not a group member (FieldError::NotMember)", errors);
     }
   }
   // the ONE ciphertext's sealed data, opened under every key's Gt on the device (KDF + AES-GCM; the Gt never leaves HBM)
@@ -1351,12 +1359,7 @@ bool decrypt_packed(Engine& eng, const KpAbeCiphertext& ct, size_t n, const uint
   std::vector<uint64_t> sealed_off(m_items, 0);
   std::vector<uint32_t> sealed_len(m_items, (uint32_t)ct.ct.size());
   open_sealed_records(eng, n, live, d_out.ptr(), d_sealed.as<uint8_t>(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
-  if (walked) {
-    std::vector<uint8_t> ok2;
-    walked->finish(&ok2);
-    for (size_t j = 0; j < m_items; j++)
-      if (!ok2[j]) retract_item(live[j], "deserialize: a key element is not a group member (FieldError::NotMember)", status, pt_buf, pt_off, errors);
-  }
+  ws.retract(live, "deserialize: a key element is not a group member (FieldError::NotMember)", status, pt_buf, pt_off, errors);
   tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
   return true;
 }
@@ -1394,111 +1397,82 @@ bool decrypt_one_sk_packed(Engine& eng, const KpAbeSecretKey& sk, size_t n, cons
     struct E { uint32_t ct_row, sk_row; Fr c; };
     std::vector<E> ent;
   };
-  std::map<std::string, std::shared_ptr<Plan>> plans;
-  std::mutex plans_mu;
-  FastPlans<Plan> fast_plans;
-  auto plan_of = [&](const std::string& names) -> std::shared_ptr<Plan> {          // names: (u32 length, bytes) per row, as the record holds them
-    std::lock_guard<std::mutex> g(plans_mu);
-    auto it = plans.find(names);
-    if (it != plans.end()) return it->second;
-    auto pl = std::make_shared<Plan>();
-    try {
-      std::vector<std::string> attr;
-      for (size_t at = 0; at < names.size();) {
-        const uint32_t l = get_u32((const uint8_t*)names.data() + at);
-        attr.push_back(names.substr(at + 4, l));
-        at += 4 + (size_t)l;
-      }
-      PrunedList list;
-      if (!calc_pruned(attr, flat->tree, &list)) throw RabeError("Error in lsw/decrypt: attributes do not match policy.");
-      for (const auto& a : list) {
-        if (is_negative(a.first)) throw RabeError("lsw::decrypt_packed: a negative attribute is selected; rabe_lsw_decrypt reproduces the reference's branch");
-        size_t cr = 0, sr = 0, co = 0;
-        while (cr < attr.size() && attr[cr] != a.first) cr++;
-        while (sr < sk.dj.size() && sk.dj[sr].name != a.first) sr++;
-        while (co < flat->leaf_name_col.size() && flat->leaf_name_col[co] != a.second) co++;
-        if (cr == attr.size() || sr == sk.dj.size() || co == flat->leaf_name_col.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
-        pl->ent.push_back({(uint32_t)cr, (uint32_t)sr, flat->leaf_coeff[co]});
-      }
-      if (pl->ent.empty()) throw RabeError("Error in lsw/decrypt: attributes do not match policy.");
-    } catch (const std::exception& ex) {
-      pl->err = ex.what();
-      if (pl->err.empty()) pl->err = "policy error";
+  PlanCache<Plan> plans;          // keyed on the bytes of the row names; the language is no part of that key
+  auto make_plan = [&](Plan& pl, const std::string& names, PolicyLanguage) {          // names: (u32 length, bytes) per row, as the record holds them
+    std::vector<std::string> attr;
+    for (size_t at = 0; at < names.size();) {
+      const uint32_t l = get_u32((const uint8_t*)names.data() + at);
+      attr.push_back(names.substr(at + 4, l));
+      at += 4 + (size_t)l;
     }
-    plans[names] = pl;
-    return pl;
+    PrunedList list;
+    if (!calc_pruned(attr, flat->tree, &list)) throw RabeError("Error in lsw/decrypt: attributes do not match policy.");
+    for (const auto& a : list) {
+      if (is_negative(a.first)) throw RabeError("lsw::decrypt_packed: a negative attribute is selected; rabe_lsw_decrypt reproduces the reference's branch");
+      size_t cr = 0, sr = 0, co = 0;
+      while (cr < attr.size() && attr[cr] != a.first) cr++;
+      while (sr < sk.dj.size() && sk.dj[sr].name != a.first) sr++;
+      while (co < flat->leaf_name_col.size() && flat->leaf_name_col[co] != a.second) co++;
+      if (cr == attr.size() || sr == sk.dj.size() || co == flat->leaf_name_col.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
+      pl.ent.push_back({(uint32_t)cr, (uint32_t)sr, flat->leaf_coeff[co]});
+    }
+    if (pl.ent.empty()) throw RabeError("Error in lsw/decrypt: attributes do not match policy.");
   };
   struct View { const uint8_t* e1; const uint8_t* e2; const uint8_t* first_row; uint32_t rows; std::shared_ptr<Plan> plan; };
   std::vector<View> v(n);
   std::vector<Sealed> sealed(n);
   std::vector<uint8_t> parsed(n, 0);
-  parallel_for(n, [&](size_t i) {
-    if (!(*errors)[i].empty()) return;
-    try {
-      Cursor r{ct_blob + ct_off[i], ct_blob + ct_off[i + 1]};
-      v[i].e1 = r.raw(384);
-      v[i].e2 = r.raw(128);
-      const uint32_t rows = r.u32();
-      if ((size_t)rows * 196 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
-      v[i].rows = rows;
-      v[i].first_row = r.p;
-      std::string names;
-      for (uint32_t y = 0; y < rows; y++) {
-        const auto nm = r.str();
-        names.append(nm.first - 4, (size_t)nm.second + 4);
-        (void)r.raw(192);
-      }
-      sealed[i].len = r.u32();
-      sealed[i].p = r.raw(sealed[i].len);
-      parsed[i] = 1;
-      auto pl = fast_plans.find(names.data(), names.size(), PolicyLanguage::JsonPolicy);
-      if (!pl) { pl = plan_of(names); fast_plans.put(names.data(), names.size(), PolicyLanguage::JsonPolicy, pl); }
-      if (!pl->err.empty()) throw RabeError(pl->err);
-      v[i].plan = pl;
-    } catch (const std::exception& ex) {
-      (*errors)[i] = ex.what();
-      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
+  for_each_record(n, errors, [&](size_t i) {
+    Cursor r{ct_blob + ct_off[i], ct_blob + ct_off[i + 1]};
+    v[i].e1 = r.raw(384);
+    v[i].e2 = r.raw(128);
+    const uint32_t rows = r.u32();
+    if ((size_t)rows * 196 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
+    v[i].rows = rows;
+    v[i].first_row = r.p;
+    std::string names;
+    for (uint32_t y = 0; y < rows; y++) {
+      const auto nm = r.str();
+      names.append(nm.first - 4, (size_t)nm.second + 4);
+      (void)r.raw(192);
     }
+    sealed[i].len = r.u32();
+    sealed[i].p = r.raw(sealed[i].len);
+    parsed[i] = 1;
+    auto pl = plans.get(names.data(), names.size(), PolicyLanguage::JsonPolicy, make_plan);
+    if (!pl->err.empty()) throw RabeError(pl->err);
+    v[i].plan = pl;
   });
   tm.lap("parse + plan");
   uint64_t need = 0;
   for (size_t i = 0; i < n; i++) if (parsed[i]) need += sealed[i].len;
   if (!pt_buf || pt_cap < need) { pt_off[n] = need; return false; }
-  std::vector<size_t> live;
-  std::vector<uint32_t> row_off{0}, attr_off{0}, pair_off{0}, sel_start, sel_sk, sel_ct, group_off{0}, item_group;
-  std::vector<Fr> sel_z;
+  // every record is in the standard layout of ITS list of names; the records of one list are one selection group of the kernel
+  Selection sel(1, 1);
+  std::vector<uint32_t> attr_off{0}, group_off{0}, item_group;
   std::map<const Plan*, uint32_t> group_of;
-  size_t max_pairs = 1;
   for (size_t i = 0; i < n; i++) {
     if (!(*errors)[i].empty()) continue;
-    live.push_back(i);
-    row_off.push_back(row_off.back() + v[i].rows);
-    attr_off.push_back(3 * row_off.back());
     const Plan& pl = *v[i].plan;
-    auto it = group_of.find(&pl);
-    if (it == group_of.end()) {
-      it = group_of.insert({&pl, (uint32_t)group_off.size() - 1}).first;
-      for (const auto& e : pl.ent) { sel_sk.push_back(e.sk_row); sel_ct.push_back(3 * e.ct_row); sel_z.push_back(e.c); }
-      group_off.push_back((uint32_t)sel_sk.size());
+    sel.add(i, v[i].rows, &pl, true, [&](auto emit) { for (const auto& e : pl.ent) emit(3 * e.ct_row, e.sk_row, e.c); });
+    attr_off.push_back(3 * sel.row_off.back());
+    if (sel.sel_start.back() == group_off.back()) {          // its entries were appended just now: a new group
+      group_of[&pl] = (uint32_t)group_off.size() - 1;
+      group_off.push_back((uint32_t)sel.sel_rec.size());
     }
-    item_group.push_back(it->second);
-    sel_start.push_back(group_off[it->second]);
-    const uint32_t m = (uint32_t)pl.ent.size();
-    pair_off.push_back(pair_off.back() + m + 1);
-    if ((size_t)m + 1 > max_pairs) max_pairs = m + 1;
+    item_group.push_back(group_of[&pl]);
   }
+  const std::vector<size_t>& live = sel.live;
+  const std::vector<uint32_t>& row_off = sel.row_off;
   const size_t m_items = live.size();
   std::vector<uint64_t> sealed_off(m_items);
   std::vector<uint32_t> sealed_len(m_items);
   DBuf d_out(&eng, m_items * 384 + 4);
-  std::unique_ptr<MemberChecks> mc;
-  std::unique_ptr<WalkedG2> walked;          // read after the open (records.h: retract_item): it and what it refers to outlive the block
-  std::vector<uint32_t> e2_off;
-  DBuf d_e2;
+  WalkScope ws;
   if (m_items) {
     const size_t total = row_off[m_items];
     DBuf d_e1(&eng, m_items * 384), d_rows(&eng, total * 192 + 4);
-    d_e2 = DBuf(&eng, m_items * 128);
+    DBuf& d_e2 = ws.d_g2 = DBuf(&eng, m_items * 128);
     std::vector<uint64_t> dst_off(3 * m_items);
     for (size_t j = 0; j < m_items; j++) {
       const View& w = v[live[j]];
@@ -1506,65 +1480,52 @@ bool decrypt_one_sk_packed(Engine& eng, const KpAbeSecretKey& sk, size_t n, cons
       sealed_off[j] = (uint64_t)(sealed[live[j]].p - ct_blob);
       sealed_len[j] = sealed[live[j]].len;
       dst_off[j] = 384ull * j; dst_off[m_items + j] = 128ull * j; dst_off[2 * m_items + j] = 192ull * row_off[j];
-      int shape = gather.find(w.plan.get());          // the same list of names: the same skeleton
-      if (shape < 0) {
-        std::vector<RecordLayout::Part> parts;
+      // the same list of names: the same skeleton
+      gather_record(gather, ct_off[live[j]], w.plan.get(), [&](std::vector<RecordLayout::Part>& parts) {
         parts.push_back({(uint32_t)(w.e1 - rec), 384, 0, 0});
         parts.push_back({(uint32_t)(w.e2 - rec), 128, 1, 0});
         Cursor r{w.first_row, ct_blob + ct_off[live[j] + 1]};
         for (uint32_t y = 0; y < w.rows; y++) { (void)r.str(); parts.push_back({(uint32_t)(r.raw(192) - rec), 192, 2, 192 * y}); }
-        shape = (int)gather.add_shape(w.plan.get(), std::move(parts));
-      }
-      gather.item(ct_off[live[j]], (uint32_t)shape);
+      });
     }
     tm.lap("shapes");
     rhip_ctx* cx = eng.ctx();
     std::vector<uint8_t> kd1;
     std::string kd2;
     for (const auto& d : sk.dj) { kd1.insert(kd1.end(), d.d1.begin(), d.d1.end()); kd2.append((const char*)d.d2.data(), 128); }
+    std::vector<uint32_t> e2_off;
     for (size_t j = 0; j <= m_items; j++) e2_off.push_back((uint32_t)j);
-    DBuf d_row_off = up32(eng, row_off), d_attr_off = up32(eng, attr_off), d_pair_off = up32(eng, pair_off), d_sel_start = up32(eng, sel_start),
-         d_sel_sk = up32(eng, sel_sk), d_sel_ct = up32(eng, sel_ct), d_sel_z = up_bytes(eng, flatten_fr(sel_z)), d_group_off = up32(eng, group_off),
+    DBuf d_row_off = up32(eng, row_off), d_attr_off = up32(eng, attr_off), d_pair_off = up32(eng, sel.pair_off), d_sel_start = up32(eng, sel.sel_start),
+         d_sel_sk = up32(eng, sel.sel_one), d_sel_ct = up32(eng, sel.sel_rec), d_sel_z = up_bytes(eng, flatten_fr(sel.sel_z)), d_group_off = up32(eng, group_off),
          d_item_group = up32(eng, item_group), d_kd1 = up_bytes(eng, kd1), d_e2_off = up32(eng, e2_off);
     gather.run({d_e1.ptr(), d_e2.ptr(), d_rows.ptr()}, dst_off);
     // the key's prepared lines (every D2: 17 KB per row) are a function of the key alone: kept across calls
     rhip_g2_lines* lines = (rhip_g2_lines*)eng.aux("lsw_sk_d2_lines", kd2, make_sk_d2_lines, &kd2, destroy_e2_lines, 4);
     if (!trusted) {
-      mc.reset(new MemberChecks(eng));
-      mc->add(1, d_rows.ptr(), total * 3, d_row_off.as<uint32_t>(), m_items, 3);
-      mc->add(3, d_e1.ptr(), m_items);
+      ws.mc.reset(new MemberChecks(eng));
+      ws.mc->add(1, d_rows.ptr(), total * 3, d_row_off.as<uint32_t>(), m_items, 3);
+      ws.mc->add(3, d_e1.ptr(), m_items);
       // e2 is the one walking argument of an item (the key's side replays prepared lines): membership out of the decrypt's own Miller
       // loop; an item whose last pair was skipped gets the stand-alone test (common.h: WalkedG2)
-      if (walk_checks()) walked.reset(new WalkedG2(eng, *mc, d_e2.ptr(), m_items, d_e2_off.as<uint32_t>(), e2_off, 1));
-      else mc->add(2, d_e2.ptr(), m_items);
+      if (walk_checks()) ws.walked.reset(new WalkedG2(eng, *ws.mc, d_e2.ptr(), m_items, d_e2_off.as<uint32_t>(), e2_off, 1));
+      else { ws.k_alone = ws.mc->add_count(); ws.mc->add(2, d_e2.ptr(), m_items); }
     }
-    if (walked) walked->arm();
-    int32_t rc = rhip_lsw_decrypt_batch_one_sk(cx, m_items, max_pairs, pair_off[m_items], sel_sk.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
-                                               d_sel_sk.as<uint32_t>(), d_sel_ct.as<uint32_t>(), d_sel_z.as<rhip_fr>(), group_off.size() - 1,
+    if (ws.walked) ws.walked->arm();
+    int32_t rc = rhip_lsw_decrypt_batch_one_sk(cx, m_items, sel.max_pairs, sel.pair_off[m_items], sel.sel_rec.size(), d_pair_off.as<uint32_t>(),
+                                               d_sel_start.as<uint32_t>(), d_sel_sk.as<uint32_t>(), d_sel_ct.as<uint32_t>(), d_sel_z.as<rhip_fr>(), group_off.size() - 1,
                                                d_group_off.as<uint32_t>(), d_item_group.as<uint32_t>(), d_e1.as<rhip_gt>(), d_e2.as<rhip_g2>(),
                                                d_rows.as<rhip_g1>(), d_attr_off.as<uint32_t>(), d_kd1.as<rhip_g1>(), lines, d_out.as<rhip_gt>());
     eng.check(rc, "rhip_lsw_decrypt_batch_one_sk");
-    if (mc) {
-      mc->collect();
-      const auto &ok_rows = mc->ok(0), &ok_e1 = mc->ok(1);
-      std::vector<uint8_t> ok_e2(m_items, 1);
-      if (!walked) { const auto& e = mc->ok(2); ok_e2.assign(e.begin(), e.end()); }
-      for (size_t j = 0; j < m_items; j++) {
-        const char* bad = !ok_e1[j] ? "deserialize: e1 is not a member of Gt (FieldError::NotMember)"
-                          : !ok_rows[j] ? "deserialize: a row element is not a point of G1 (FieldError::NotMember)"
-                          : !ok_e2[j] ? "deserialize: e2 is not a member of G2 (FieldError::NotMember)" : nullptr;
-        if (bad) (*errors)[live[j]] = bad;
-      }
+    if (ws.mc) {
+      ws.mc->collect();
+      ws.fail(live, {1}, "deserialize: e1 is not a member of Gt (FieldError::NotMember)", errors);
+      ws.fail(live, {0}, "deserialize: a row element is not a point of G1 (FieldError::NotMember)", errors);
+      ws.fail(live, {ws.k_alone}, "deserialize: e2 is not a member of G2 (FieldError::NotMember)", errors);
     }
   }
   // KDF + AES-GCM open on the device: the decrypted Gt never leaves HBM; plaintext bytes come back in one copy
   open_sealed_records(eng, n, live, d_out.ptr(), gather.dev_blob(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
-  if (walked) {
-    std::vector<uint8_t> ok_e2;
-    walked->finish(&ok_e2);
-    for (size_t j = 0; j < m_items; j++)
-      if (!ok_e2[j]) retract_item(live[j], "deserialize: e2 is not a member of G2 (FieldError::NotMember)", status, pt_buf, pt_off, errors);
-  }
+  ws.retract(live, "deserialize: e2 is not a member of G2 (FieldError::NotMember)", status, pt_buf, pt_off, errors);
   tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
   return true;
 }
@@ -1792,110 +1753,72 @@ bool decrypt_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11SecretKey& s
     struct E { std::string name_col; uint32_t sk_row; Fr c; uint32_t std_ct_row; };
     std::vector<E> ent;
   };
-  std::map<std::pair<int, std::string>, std::shared_ptr<Plan>> plans;
-  std::mutex plans_mu;
-  FastPlans<Plan> fast_plans;
-  auto plan_of = [&](const std::string& text, PolicyLanguage lang) -> std::shared_ptr<Plan> {
-    std::lock_guard<std::mutex> g(plans_mu);
-    auto key = std::make_pair((int)lang, text);
-    auto it = plans.find(key);
-    if (it != plans.end()) return it->second;
-    auto pl = std::make_shared<Plan>();
-    try {
-      pl->flat = flat_policy(text, lang);
-      for (const auto& nc : pl->flat->leaf_name_col) pl->std_names.push_back(upper(nc));
-      if (!traverse_policy(str_attr, pl->flat->tree)) throw RabeError("Error: attributes in sk do not match policy in ct.");
-      PrunedList list;
-      if (!calc_pruned(str_attr, pl->flat->tree, &list)) throw RabeError("Error in aw11/decrypt: attributes in sk do not match policy in ct.");
-      for (const auto& cur : list) {
-        size_t sr = 0, co = 0, cr = 0;
-        while (sr < sk.attr.size() && sk.attr[sr].first != cur.first) sr++;
-        while (co < pl->flat->leaf_name_col.size() && pl->flat->leaf_name_col[co] != cur.second) co++;
-        while (cr < pl->std_names.size() && pl->std_names[cr] != cur.second) cr++;
-        if (sr == sk.attr.size() || co == pl->flat->leaf_name_col.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
-        pl->ent.push_back({cur.second, (uint32_t)sr, pl->flat->leaf_coeff[co], (uint32_t)cr});
-      }
-    } catch (const std::exception& ex) {
-      pl->err = ex.what();
-      if (pl->err.empty()) pl->err = "policy error";
+  PlanCache<Plan> plans;
+  auto make_plan = [&](Plan& pl, const std::string& text, PolicyLanguage lang) {
+    pl.flat = flat_policy(text, lang);
+    for (const auto& nc : pl.flat->leaf_name_col) pl.std_names.push_back(upper(nc));
+    if (!traverse_policy(str_attr, pl.flat->tree)) throw RabeError("Error: attributes in sk do not match policy in ct.");
+    PrunedList list;
+    if (!calc_pruned(str_attr, pl.flat->tree, &list)) throw RabeError("Error in aw11/decrypt: attributes in sk do not match policy in ct.");
+    for (const auto& cur : list) {
+      size_t sr = 0, co = 0, cr = 0;
+      while (sr < sk.attr.size() && sk.attr[sr].first != cur.first) sr++;
+      while (co < pl.flat->leaf_name_col.size() && pl.flat->leaf_name_col[co] != cur.second) co++;
+      while (cr < pl.std_names.size() && pl.std_names[cr] != cur.second) cr++;
+      if (sr == sk.attr.size() || co == pl.flat->leaf_name_col.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
+      pl.ent.push_back({cur.second, (uint32_t)sr, pl.flat->leaf_coeff[co], (uint32_t)cr});
     }
-    plans[key] = pl;
-    return pl;
   };
   struct View { const uint8_t* c0; uint32_t rows; std::vector<const uint8_t*> c1, c2, c3; std::shared_ptr<Plan> plan; std::vector<uint32_t> ct_row; bool standard; };
   std::vector<View> v(n);
   std::vector<Sealed> sealed(n);
-  parallel_for(n, [&](size_t i) {
-    if (!(*errors)[i].empty()) return;
-    try {
-      Cursor r{ct_blob + ct_off[i], ct_blob + ct_off[i + 1]};
-      auto pol = r.str();
-      const PolicyLanguage lang = *r.raw(1) ? PolicyLanguage::HumanPolicy : PolicyLanguage::JsonPolicy;
-      v[i].c0 = r.raw(384);
-      const uint32_t rows = r.u32();
-      if ((size_t)rows * 644 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
-      v[i].rows = rows;
-      v[i].c1.resize(rows); v[i].c2.resize(rows); v[i].c3.resize(rows);
-      std::vector<std::pair<const char*, uint32_t>> names(rows);
-      for (uint32_t y = 0; y < rows; y++) { names[y] = r.str(); v[i].c1[y] = r.raw(384); v[i].c2[y] = r.raw(128); v[i].c3[y] = r.raw(128); }
-      sealed[i].len = r.u32();
-      sealed[i].p = r.raw(sealed[i].len);
-      auto pl = fast_plans.find(pol.first, pol.second, lang);
-      if (!pl) { pl = plan_of(std::string(pol.first, pol.second), lang); fast_plans.put(pol.first, pol.second, lang, pl); }
-      if (!pl->err.empty()) throw RabeError(pl->err);
-      v[i].plan = pl;
-      bool standard = rows == pl->std_names.size();
-      for (uint32_t y = 0; y < rows && standard; y++) standard = same(names[y], pl->std_names[y]);
-      v[i].standard = standard;
-      for (size_t e = 0; e < pl->ent.size(); e++) {
-        uint32_t y = standard ? pl->ent[e].std_ct_row : 0;
-        if (!standard) while (y < rows && !same(names[y], pl->ent[e].name_col)) y++;
-        if (y >= rows) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
-        if (!standard) v[i].ct_row.push_back(y);
-      }
-    } catch (const std::exception& ex) {
-      (*errors)[i] = ex.what();
-      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
+  for_each_record(n, errors, [&](size_t i) {
+    Cursor r{ct_blob + ct_off[i], ct_blob + ct_off[i + 1]};
+    auto pol = r.str();
+    const PolicyLanguage lang = *r.raw(1) ? PolicyLanguage::HumanPolicy : PolicyLanguage::JsonPolicy;
+    v[i].c0 = r.raw(384);
+    const uint32_t rows = r.u32();
+    if ((size_t)rows * 644 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
+    v[i].rows = rows;
+    v[i].c1.resize(rows); v[i].c2.resize(rows); v[i].c3.resize(rows);
+    std::vector<std::pair<const char*, uint32_t>> names(rows);
+    for (uint32_t y = 0; y < rows; y++) { names[y] = r.str(); v[i].c1[y] = r.raw(384); v[i].c2[y] = r.raw(128); v[i].c3[y] = r.raw(128); }
+    sealed[i].len = r.u32();
+    sealed[i].p = r.raw(sealed[i].len);
+    auto pl = plans.get(pol.first, pol.second, lang, make_plan);
+    if (!pl->err.empty()) throw RabeError(pl->err);
+    v[i].plan = pl;
+    bool standard = rows == pl->std_names.size();
+    for (uint32_t y = 0; y < rows && standard; y++) standard = same(names[y], pl->std_names[y]);
+    v[i].standard = standard;
+    for (size_t e = 0; e < pl->ent.size(); e++) {
+      uint32_t y = standard ? pl->ent[e].std_ct_row : 0;
+      if (!standard) while (y < rows && !same(names[y], pl->ent[e].name_col)) y++;
+      if (y >= rows) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
+      if (!standard) v[i].ct_row.push_back(y);
     }
   });
   tm.lap("parse + plan");
-  std::vector<size_t> live;
-  std::vector<uint32_t> row_off{0}, pair_off{0}, sel_start, sel_ct, sel_sk;
-  std::vector<Fr> sel_z;
-  std::map<const Plan*, uint32_t> shared_start;
-  size_t max_pairs = 1;
+  Selection sel(1, 1);          // m entries: m + 1 pairs
   for (size_t i = 0; i < n; i++) {
     if (!(*errors)[i].empty()) continue;
-    live.push_back(i);
-    row_off.push_back(row_off.back() + v[i].rows);
-    const Plan& pl = *v[i].plan;
-    if (v[i].standard) {
-      auto it = shared_start.find(&pl);
-      if (it == shared_start.end()) {
-        it = shared_start.insert({&pl, (uint32_t)sel_ct.size()}).first;
-        for (const auto& e : pl.ent) { sel_ct.push_back(e.std_ct_row); sel_sk.push_back(e.sk_row); sel_z.push_back(e.c); }
-      }
-      sel_start.push_back(it->second);
-    } else {
-      sel_start.push_back((uint32_t)sel_ct.size());
-      for (size_t e = 0; e < pl.ent.size(); e++) { sel_ct.push_back(v[i].ct_row[e]); sel_sk.push_back(pl.ent[e].sk_row); sel_z.push_back(pl.ent[e].c); }
-    }
-    const uint32_t m = (uint32_t)pl.ent.size();
-    pair_off.push_back(pair_off.back() + m + 1);
-    if ((size_t)m + 1 > max_pairs) max_pairs = m + 1;
+    const View& w = v[i];
+    sel.add(i, w.rows, w.plan.get(), w.standard, [&](auto emit) {
+      const auto& ent = w.plan->ent;
+      for (size_t e = 0; e < ent.size(); e++) emit(w.standard ? ent[e].std_ct_row : w.ct_row[e], ent[e].sk_row, ent[e].c);
+    });
   }
+  const std::vector<size_t>& live = sel.live;
+  const std::vector<uint32_t>& row_off = sel.row_off;
   const size_t m_items = live.size();
   std::vector<uint64_t> sealed_off(m_items);
   std::vector<uint32_t> sealed_len(m_items);
   DBuf d_out(&eng, m_items * 384 + 4);
-  std::unique_ptr<MemberChecks> mc;
-  std::unique_ptr<WalkedG2> walked;          // read after the open (records.h: retract_item): it and what it refers to outlive the block
-  std::vector<uint32_t> walked_idx, walked_off;
-  DBuf d_c2;
+  WalkScope ws;
   if (m_items) {
     const size_t total = row_off[m_items];
     DBuf d_c0(&eng, m_items * 384), d_c1(&eng, total * 384 + 4), d_c3(&eng, total * 128 + 4);
-    d_c2 = DBuf(&eng, total * 128 + 4);
+    DBuf& d_c2 = ws.d_g2 = DBuf(&eng, total * 128 + 4);
     std::vector<uint64_t> dst_off(4 * m_items);
     for (size_t j = 0; j < m_items; j++) {
       const View& w = v[live[j]];
@@ -1903,18 +1826,14 @@ bool decrypt_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11SecretKey& s
       sealed_off[j] = (uint64_t)(sealed[live[j]].p - ct_blob);
       sealed_len[j] = sealed[live[j]].len;
       dst_off[j] = 384ull * j; dst_off[m_items + j] = 384ull * row_off[j]; dst_off[2 * m_items + j] = dst_off[3 * m_items + j] = 128ull * row_off[j];
-      int shape = w.standard ? gather.find(w.plan.get()) : -1;
-      if (shape < 0) {
-        std::vector<RecordLayout::Part> parts;
+      gather_record(gather, ct_off[live[j]], w.standard ? w.plan.get() : nullptr, [&](std::vector<RecordLayout::Part>& parts) {
         parts.push_back({(uint32_t)(w.c0 - rec), 384, 0, 0});
         for (uint32_t y = 0; y < w.rows; y++) {
           parts.push_back({(uint32_t)(w.c1[y] - rec), 384, 1, 384 * y});
           parts.push_back({(uint32_t)(w.c2[y] - rec), 128, 2, 128 * y});
           parts.push_back({(uint32_t)(w.c3[y] - rec), 128, 3, 128 * y});
         }
-        shape = (int)gather.add_shape(w.standard ? (const void*)w.plan.get() : nullptr, std::move(parts));
-      }
-      gather.item(ct_off[live[j]], (uint32_t)shape);
+      });
     }
     tm.lap("shapes");
     rhip_ctx* cx = eng.ctx();
@@ -1923,56 +1842,31 @@ bool decrypt_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11SecretKey& s
     for (const auto& a : sk.attr) kk.insert(kk.end(), a.second.begin(), a.second.end());
     std::vector<uint32_t> sk_attr_off{0, (uint32_t)sk.attr.size()}, sk_idx(m_items, 0);
     DBuf d_row_off = up32(eng, row_off),
-        d_pair_off = up32(eng, pair_off), d_sel_start = up32(eng, sel_start), d_sel_ct = up32(eng, sel_ct), d_sel_sk = up32(eng, sel_sk),
-        d_sel_z = up_bytes(eng, flatten_fr(sel_z)), d_hash(&eng, hash.data(), 64), d_kk = up_bytes(eng, kk), d_sk_attr_off = up32(eng, sk_attr_off),
+        d_pair_off = up32(eng, sel.pair_off), d_sel_start = up32(eng, sel.sel_start), d_sel_ct = up32(eng, sel.sel_rec), d_sel_sk = up32(eng, sel.sel_one),
+        d_sel_z = up_bytes(eng, flatten_fr(sel.sel_z)), d_hash(&eng, hash.data(), 64), d_kk = up_bytes(eng, kk), d_sk_attr_off = up32(eng, sk_attr_off),
         d_sk_idx = up32(eng, sk_idx);
     gather.run({d_c0.ptr(), d_c1.ptr(), d_c2.ptr(), d_c3.ptr()}, dst_off);
     if (!trusted) {
-      mc.reset(new MemberChecks(eng));
-      mc->add(3, d_c0.ptr(), m_items); mc->add(3, d_c1.ptr(), total, d_row_off.as<uint32_t>(), m_items);
-      mc->add(2, d_c3.ptr(), total, d_row_off.as<uint32_t>(), m_items);          // C3 enters its pairing as a SUM: every term keeps the stand-alone test
+      ws.mc.reset(new MemberChecks(eng));
+      ws.mc->add(3, d_c0.ptr(), m_items); ws.mc->add(3, d_c1.ptr(), total, d_row_off.as<uint32_t>(), m_items);
+      ws.mc->add(2, d_c3.ptr(), total, d_row_off.as<uint32_t>(), m_items);          // C3 enters its pairing as a SUM: every term keeps the stand-alone test
       // C2 of every selected row is the walking argument of a pairing; one more argument walks per item (the sum of the C3 terms)
-      if (walk_checks()) {
-        bool all = true;          // concluded from the counts for standard-layout records only (see bsw::decrypt_packed)
-        for (size_t j = 0; j < m_items && all; j++) all = v[live[j]].standard && pair_off[j + 1] - pair_off[j] - 1 == row_off[j + 1] - row_off[j];
-        if (!all) {
-          walked_off.push_back(0);
-          for (size_t j = 0; j < m_items; j++) {
-            const uint32_t mj = pair_off[j + 1] - pair_off[j] - 1;
-            for (uint32_t e = 0; e < mj; e++) walked_idx.push_back(row_off[j] + sel_ct[sel_start[j] + e]);
-            walked_off.push_back((uint32_t)walked_idx.size());
-          }
-        }
-        walked.reset(new WalkedG2(eng, *mc, d_c2.ptr(), total, d_row_off.as<uint32_t>(), row_off, 1, all ? nullptr : &walked_idx, all ? nullptr : &walked_off, 1));
-      } else {
-        mc->add(2, d_c2.ptr(), total, d_row_off.as<uint32_t>(), m_items);
-      }
+      ws.check_g2(eng, walk_checks(), sel, total, d_row_off.as<uint32_t>(), 1);
     }
-    if (walked) walked->arm();
-    int32_t rc = rhip_aw11_decrypt_batch(cx, m_items, max_pairs, pair_off[m_items], sel_ct.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
+    if (ws.walked) ws.walked->arm();
+    int32_t rc = rhip_aw11_decrypt_batch(cx, m_items, sel.max_pairs, sel.pair_off[m_items], sel.sel_rec.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
                                          d_sel_ct.as<uint32_t>(), d_sel_sk.as<uint32_t>(), d_sel_z.as<rhip_fr>(), d_c0.as<rhip_gt>(), d_c1.as<rhip_gt>(),
                                          d_c2.as<rhip_g2>(), d_c3.as<rhip_g2>(), d_row_off.as<uint32_t>(), d_hash.as<rhip_g1>(), d_kk.as<rhip_g1>(),
                                          d_sk_attr_off.as<uint32_t>(), d_sk_idx.as<uint32_t>(), d_out.as<rhip_gt>());
     eng.check(rc, "rhip_aw11_decrypt_batch");
-    if (mc) {
-      mc->collect();
-      const auto &ok0 = mc->ok(0), &ok1 = mc->ok(1), &ok3 = mc->ok(2);
-      std::vector<uint8_t> ok2(m_items, 1);
-      if (!walked) { const auto& e = mc->ok(3); ok2.assign(e.begin(), e.end()); }
-      for (size_t j = 0; j < m_items; j++) {
-        const bool bad = !ok0[j] || !ok1[j] || !ok2[j] || !ok3[j];
-        if (bad) (*errors)[live[j]] = "deserialize: a ciphertext element is not a group member (FieldError::NotMember)";
-      }
+    if (ws.mc) {
+      ws.mc->collect();
+      ws.fail(live, {0, 1, 2, ws.k_alone}, "deserialize: a ciphertext element is not a group member (FieldError::NotMember)", errors);
     }
   }
   // KDF + AES-GCM open on the device: the decrypted Gt never leaves HBM; plaintext bytes come back in one copy
   open_sealed_records(eng, n, live, d_out.ptr(), gather.dev_blob(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
-  if (walked) {
-    std::vector<uint8_t> ok2;
-    walked->finish(&ok2);
-    for (size_t j = 0; j < m_items; j++)
-      if (!ok2[j]) retract_item(live[j], "deserialize: a ciphertext element is not a group member (FieldError::NotMember)", status, pt_buf, pt_off, errors);
-  }
+  ws.retract(live, "deserialize: a ciphertext element is not a group member (FieldError::NotMember)", status, pt_buf, pt_off, errors);
   tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
   return true;
 }
@@ -2103,26 +1997,20 @@ bool decrypt_out_packed(Engine& eng, const Ghw11RetrieveKey& rk, size_t n, const
   const uint64_t span = check_offsets(n, ct_off, ct_len, errors);
   if (!pt_buf || pt_cap < span) { pt_off[n] = span; return false; }
   std::vector<Sealed> sealed(n);
-  parallel_for(n, [&](size_t i) {
-    if (!(*errors)[i].empty()) return;
+  for_each_record(n, errors, [&](size_t i) {
     const uint8_t* rec = tct + 768 * i;
     bool zero = true;
     for (size_t b = 0; b < 768 && zero; b++) zero = rec[b] == 0;
     if (zero) { (*errors)[i] = "ghw11::decrypt_out_packed: no transformed ciphertext for this item (transform failed)"; return; }
-    try {
-      Cursor r{ct_blob + ct_off[i], ct_blob + ct_off[i + 1]};
-      (void)r.str();
-      (void)r.raw(1 + 384 + 64);
-      const uint32_t rows = r.u32();
-      if ((size_t)rows * 132 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
-      for (uint32_t y = 0; y < rows; y++) { (void)r.str(); (void)r.raw(128); }
-      sealed[i].len = r.u32();
-      sealed[i].p = r.raw(sealed[i].len);
-      if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
-    } catch (const std::exception& ex) {
-      (*errors)[i] = ex.what();
-      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
-    }
+    Cursor r{ct_blob + ct_off[i], ct_blob + ct_off[i + 1]};
+    (void)r.str();
+    (void)r.raw(1 + 384 + 64);
+    const uint32_t rows = r.u32();
+    if ((size_t)rows * 132 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
+    for (uint32_t y = 0; y < rows; y++) { (void)r.str(); (void)r.raw(128); }
+    sealed[i].len = r.u32();
+    sealed[i].p = r.raw(sealed[i].len);
+    if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
   });
   tm.lap("parse");
   std::vector<size_t> live;
@@ -2195,10 +2083,7 @@ struct CtBatch {
   std::vector<CtView> v;
   std::vector<Sealed> sealed;          // with_sealed: the data slice of every record whose fields decoded
   std::vector<uint8_t> parsed;         // with_sealed: 1 where the record's fields, the sealed slice included, decoded
-  std::vector<size_t> live;
-  std::vector<uint32_t> row_off{0}, pair_off{0}, sel_start, sel_ct, sel_tk;
-  std::vector<Fr> sel_w;
-  size_t max_pairs = 2;
+  Selection sel{1, 2};                 // m entries: m + 2 pairs; sel_one = the key's attribute
   // with_sealed = false: the sealed data stays with the client (transform); true: it is kept, and the record has to end with it, as
   // decrypt_out_packed demands of the same record -- checked last, after everything the transform would have refused
   void parse(const std::vector<Ghw11Attribute>& key_attr, size_t n, const uint8_t* ct_blob, const uint64_t* ct_off, bool with_sealed,
@@ -2209,101 +2094,65 @@ void CtBatch::parse(const std::vector<Ghw11Attribute>& key_attr, size_t n, const
                     std::vector<std::string>* errors) {
   std::vector<std::string> attr;
   for (const auto& a : key_attr) attr.push_back(a.string);
-  typedef CtPlan Plan;
-  std::map<std::pair<int, std::string>, std::shared_ptr<Plan>> plans;
-  std::mutex plans_mu;
-  FastPlans<Plan> fast_plans;
-  auto plan_of = [&](const std::string& text, PolicyLanguage lang) -> std::shared_ptr<Plan> {
-    std::lock_guard<std::mutex> g(plans_mu);
-    auto key = std::make_pair((int)lang, text);
-    auto it = plans.find(key);
-    if (it != plans.end()) return it->second;
-    auto pl = std::make_shared<Plan>();
-    try {
-      pl->flat = flat_policy(text, lang);
-      const auto& names = pl->flat->leaf_name_col;
-      if (!traverse_policy(attr, pl->flat->tree)) throw RabeError("Error: attributes in tk do not match policy in ct.");
-      PrunedList list;
-      if (!calc_pruned(attr, pl->flat->tree, &list)) throw RabeError("Error in Ghw11/decrypt: attributes in sk do not match policy in ct.");
-      for (const auto& cur : list) {
-        size_t a = 0, co = 0;
-        while (a < key_attr.size() && key_attr[a].string != cur.first) a++;
-        while (co < names.size() && names[co] != cur.second) co++;
-        if (a == key_attr.size() || co == names.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
-        pl->ent.push_back({cur.second, (uint32_t)a, pl->flat->leaf_coeff[co], (uint32_t)co});
-      }
-    } catch (const std::exception& ex) {
-      pl->err = ex.what();
-      if (pl->err.empty()) pl->err = "policy error";
+  PlanCache<CtPlan> plans;
+  auto make_plan = [&](CtPlan& pl, const std::string& text, PolicyLanguage lang) {
+    pl.flat = flat_policy(text, lang);
+    const auto& names = pl.flat->leaf_name_col;
+    if (!traverse_policy(attr, pl.flat->tree)) throw RabeError("Error: attributes in tk do not match policy in ct.");
+    PrunedList list;
+    if (!calc_pruned(attr, pl.flat->tree, &list)) throw RabeError("Error in Ghw11/decrypt: attributes in sk do not match policy in ct.");
+    for (const auto& cur : list) {
+      size_t a = 0, co = 0;
+      while (a < key_attr.size() && key_attr[a].string != cur.first) a++;
+      while (co < names.size() && names[co] != cur.second) co++;
+      if (a == key_attr.size() || co == names.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
+      pl.ent.push_back({cur.second, (uint32_t)a, pl.flat->leaf_coeff[co], (uint32_t)co});
     }
-    plans[key] = pl;
-    return pl;
   };
   v.resize(n);
   if (with_sealed) { sealed.resize(n); parsed.assign(n, 0); }
-  parallel_for(n, [&](size_t i) {
-    if (!(*errors)[i].empty()) return;
-    try {
-      Cursor r{ct_blob + ct_off[i], ct_blob + ct_off[i + 1]};
-      auto pol = r.str();
-      const PolicyLanguage lang = *r.raw(1) ? PolicyLanguage::HumanPolicy : PolicyLanguage::JsonPolicy;
-      v[i].c = r.raw(384);
-      v[i].c1 = r.raw(64);
-      const uint32_t rows = r.u32();
-      if ((size_t)rows * 132 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
-      v[i].rows = rows;
-      v[i].ci.resize(rows);
-      v[i].di.resize(rows);
-      std::vector<std::pair<const char*, uint32_t>> names(rows);
-      for (uint32_t y = 0; y < rows; y++) { names[y] = r.str(); v[i].ci[y] = r.raw(64); v[i].di[y] = r.raw(64); }
-      const uint32_t dl = r.u32();
-      const uint8_t* data = r.raw(dl);                   // transform: the sealed data stays with the client (decrypt_out)
-      if (with_sealed) { sealed[i].len = dl; sealed[i].p = data; parsed[i] = 1; }
-      auto pl = fast_plans.find(pol.first, pol.second, lang);
-      if (!pl) { pl = plan_of(std::string(pol.first, pol.second), lang); fast_plans.put(pol.first, pol.second, lang, pl); }
-      if (!pl->err.empty()) throw RabeError(pl->err);
-      v[i].plan = pl;
-      const auto& std_names = pl->flat->leaf_name_col;
-      bool standard = rows == std_names.size();
-      for (uint32_t y = 0; y < rows && standard; y++) standard = same(names[y], std_names[y]);
-      v[i].standard = standard;
-      if (!standard) {
-        for (const auto& e : pl->ent) {
-          uint32_t y = 0;
-          while (y < rows && !same(names[y], e.name_col)) y++;
-          if (y == rows) throw RabeError("called `Option::unwrap()` on a `None` value");
-          v[i].ct_row.push_back(y);
-        }
+  for_each_record(n, errors, [&](size_t i) {
+    Cursor r{ct_blob + ct_off[i], ct_blob + ct_off[i + 1]};
+    auto pol = r.str();
+    const PolicyLanguage lang = *r.raw(1) ? PolicyLanguage::HumanPolicy : PolicyLanguage::JsonPolicy;
+    v[i].c = r.raw(384);
+    v[i].c1 = r.raw(64);
+    const uint32_t rows = r.u32();
+    if ((size_t)rows * 132 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
+    v[i].rows = rows;
+    v[i].ci.resize(rows);
+    v[i].di.resize(rows);
+    std::vector<std::pair<const char*, uint32_t>> names(rows);
+    for (uint32_t y = 0; y < rows; y++) { names[y] = r.str(); v[i].ci[y] = r.raw(64); v[i].di[y] = r.raw(64); }
+    const uint32_t dl = r.u32();
+    const uint8_t* data = r.raw(dl);                   // transform: the sealed data stays with the client (decrypt_out)
+    if (with_sealed) { sealed[i].len = dl; sealed[i].p = data; parsed[i] = 1; }
+    auto pl = plans.get(pol.first, pol.second, lang, make_plan);
+    if (!pl->err.empty()) throw RabeError(pl->err);
+    v[i].plan = pl;
+    const auto& std_names = pl->flat->leaf_name_col;
+    bool standard = rows == std_names.size();
+    for (uint32_t y = 0; y < rows && standard; y++) standard = same(names[y], std_names[y]);
+    v[i].standard = standard;
+    if (!standard) {
+      for (const auto& e : pl->ent) {
+        uint32_t y = 0;
+        while (y < rows && !same(names[y], e.name_col)) y++;
+        if (y == rows) throw RabeError("called `Option::unwrap()` on a `None` value");
+        v[i].ct_row.push_back(y);
       }
-      if (with_sealed && r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
-    } catch (const std::exception& ex) {
-      (*errors)[i] = ex.what();
-      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
     }
+    if (with_sealed && r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
   });
 }
 void CtBatch::select(size_t n, const std::vector<std::string>& errors) {
-  typedef CtPlan Plan;
-  std::map<const Plan*, uint32_t> shared_start;
   for (size_t i = 0; i < n; i++) {
     if (!errors[i].empty()) continue;
-    live.push_back(i);
-    row_off.push_back(row_off.back() + v[i].rows);
-    const Plan& pl = *v[i].plan;
-    if (v[i].standard) {
-      auto it = shared_start.find(&pl);
-      if (it == shared_start.end()) {
-        it = shared_start.insert({&pl, (uint32_t)sel_ct.size()}).first;
-        for (const auto& e : pl.ent) { sel_ct.push_back(e.std_ct_row); sel_tk.push_back(e.tk_attr); sel_w.push_back(e.w); }
-      }
-      sel_start.push_back(it->second);
-    } else {
-      sel_start.push_back((uint32_t)sel_ct.size());
-      for (size_t e = 0; e < pl.ent.size(); e++) { sel_ct.push_back(v[i].ct_row[e]); sel_tk.push_back(pl.ent[e].tk_attr); sel_w.push_back(pl.ent[e].w); }
-    }
-    const uint32_t m = (uint32_t)pl.ent.size();
-    pair_off.push_back(pair_off.back() + m + 2);
-    if ((size_t)m + 2 > max_pairs) max_pairs = m + 2;
+    const CtView& w = v[i];
+    sel.add(i, w.rows, w.plan.get(), w.standard, [&](auto emit) {
+      const auto& ent = w.plan->ent;
+      for (size_t e = 0; e < ent.size(); e++) emit(w.standard ? ent[e].std_ct_row : w.ct_row[e], ent[e].tk_attr, ent[e].w);
+    });
   }
 }
 // the prepared lines of a key's G2 elements in the order k, l, k_x[0], k_x[1], ... (kept per engine under `aux_name`, keyed on the bytes)
@@ -2333,32 +2182,29 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
   b.parse(tk.attr_key_z, n, ct_blob, ct_off, false, errors);
   tm.lap("parse + plan");
   b.select(n, *errors);
-  const std::vector<CtView>& v = b.v;
-  const std::vector<size_t>& live = b.live;
-  const std::vector<uint32_t>&row_off = b.row_off, &pair_off = b.pair_off, &sel_start = b.sel_start, &sel_ct = b.sel_ct, &sel_tk = b.sel_tk;
-  const std::vector<Fr>& sel_w = b.sel_w;
-  const size_t max_pairs = b.max_pairs;
+  const Selection& sel = b.sel;
+  const std::vector<size_t>& live = sel.live;
   const size_t m_items = live.size();
   uint8_t* h_out = nullptr;
   if (m_items) {
-    const size_t total = row_off[m_items];
+    const size_t total = sel.row_off[m_items];
     uint8_t* h_l = eng.pinned(1, total * 128 + 4);
     uint8_t* h_x = eng.pinned(2, m_items * (64 + 384 + 384));
     parallel_for(m_items, [&](size_t j) {
-      const CtView& w = v[live[j]];
+      const CtView& w = b.v[live[j]];
       memcpy(h_x + 64 * j, w.c1, 64);
       memcpy(h_x + m_items * 64 + 384 * j, w.c, 384);
       for (uint32_t y = 0; y < w.rows; y++) {
-        memcpy(h_l + (size_t)(row_off[j] + y) * 64, w.ci[y], 64);
-        memcpy(h_l + total * 64 + (size_t)(row_off[j] + y) * 64, w.di[y], 64);
+        memcpy(h_l + (size_t)(sel.row_off[j] + y) * 64, w.ci[y], 64);
+        memcpy(h_l + total * 64 + (size_t)(sel.row_off[j] + y) * 64, w.di[y], 64);
       }
     });
     tm.lap("pack");
     rhip_ctx* cx = eng.ctx();
     rhip_g2_lines* lines = key_lines(eng, "ghw11_tk_lines", tk.k_z, tk.l_z, tk.attr_key_z);
-    DBuf d_c1(&eng, m_items * 64), d_c(&eng, m_items * 384), d_ci(&eng, total * 64 + 4), d_di(&eng, total * 64 + 4), d_row_off = up32(eng, row_off),
-        d_pair_off = up32(eng, pair_off), d_sel_start = up32(eng, sel_start), d_sel_ct = up32(eng, sel_ct), d_sel_tk = up32(eng, sel_tk),
-        d_sel_w = up_bytes(eng, flatten_fr(sel_w)), d_out(&eng, m_items * 384);
+    DBuf d_c1(&eng, m_items * 64), d_c(&eng, m_items * 384), d_ci(&eng, total * 64 + 4), d_di(&eng, total * 64 + 4), d_row_off = up32(eng, sel.row_off),
+        d_pair_off = up32(eng, sel.pair_off), d_sel_start = up32(eng, sel.sel_start), d_sel_ct = up32(eng, sel.sel_rec), d_sel_tk = up32(eng, sel.sel_one),
+        d_sel_w = up_bytes(eng, flatten_fr(sel.sel_z)), d_out(&eng, m_items * 384);
     eng.check(rhip_upload_async(cx, d_c1.ptr(), h_x, m_items * 64), "upload");
     eng.check(rhip_upload_async(cx, d_ci.ptr(), h_l, total * 64), "upload");
     eng.check(rhip_upload_async(cx, d_di.ptr(), h_l + total * 64, total * 64), "upload");
@@ -2369,7 +2215,7 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
       mc->add(1, d_c1.ptr(), m_items); mc->add(1, d_ci.ptr(), total, d_row_off.as<uint32_t>(), m_items);
       mc->add(1, d_di.ptr(), total, d_row_off.as<uint32_t>(), m_items); mc->add(3, d_c.ptr(), m_items);
     }
-    int32_t rc = rhip_ghw11_transform_batch(cx, m_items, max_pairs, pair_off[m_items], sel_ct.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
+    int32_t rc = rhip_ghw11_transform_batch(cx, m_items, sel.max_pairs, sel.pair_off[m_items], sel.sel_rec.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
                                             d_sel_ct.as<uint32_t>(), d_sel_tk.as<uint32_t>(), d_sel_w.as<rhip_fr>(), d_c1.as<rhip_g1>(), d_ci.as<rhip_g1>(),
                                             d_di.as<rhip_g1>(), d_row_off.as<uint32_t>(), lines, d_out.as<rhip_gt>());
     h_out = h_x + m_items * 448;
@@ -2389,7 +2235,7 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
   parallel_for(n, [&](size_t i) {
     uint8_t* o = out_buf + 768 * i;
     if (!(*errors)[i].empty() || slot[i] == (size_t)-1) { memset(o, 0, 768); status[i] = -1; return; }
-    memcpy(o, v[i].c, 384);
+    memcpy(o, b.v[i].c, 384);
     memcpy(o + 384, h_out + 384 * slot[i], 384);
     status[i] = 0;
   });
@@ -2422,13 +2268,14 @@ bool decrypt_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8
   for (size_t i = 0; i < n; i++) if (b.parsed[i]) need += b.sealed[i].len;
   if (!pt_buf || pt_cap < need) { pt_off[n] = need; return false; }
   b.select(n, *errors);
-  const std::vector<size_t>& live = b.live;
+  const Selection& sel = b.sel;
+  const std::vector<size_t>& live = sel.live;
   const size_t m_items = live.size();
   std::vector<uint64_t> sealed_off(m_items);
   std::vector<uint32_t> sealed_len(m_items);
   DBuf d_msg(&eng, m_items * 384 + 4);
   if (m_items) {
-    const size_t total = b.row_off[m_items];
+    const size_t total = sel.row_off[m_items];
     DBuf d_c(&eng, m_items * 384), d_c1(&eng, m_items * 64), d_ci(&eng, total * 64 + 4), d_di(&eng, total * 64 + 4);
     std::vector<uint64_t> dst_off(4 * m_items);
     for (size_t j = 0; j < m_items; j++) {
@@ -2436,25 +2283,22 @@ bool decrypt_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8
       const uint8_t* rec = ct_blob + ct_off[live[j]];
       sealed_off[j] = (uint64_t)(b.sealed[live[j]].p - ct_blob);
       sealed_len[j] = b.sealed[live[j]].len;
-      dst_off[j] = 384ull * j; dst_off[m_items + j] = 64ull * j; dst_off[2 * m_items + j] = dst_off[3 * m_items + j] = 64ull * b.row_off[j];
-      int shape = w.standard ? gather.find(w.plan.get()) : -1;          // the same policy text and row names: the same skeleton
-      if (shape < 0) {
-        std::vector<RecordLayout::Part> parts;
+      dst_off[j] = 384ull * j; dst_off[m_items + j] = 64ull * j; dst_off[2 * m_items + j] = dst_off[3 * m_items + j] = 64ull * sel.row_off[j];
+      // the same policy text and row names: the same skeleton
+      gather_record(gather, ct_off[live[j]], w.standard ? w.plan.get() : nullptr, [&](std::vector<RecordLayout::Part>& parts) {
         parts.push_back({(uint32_t)(w.c - rec), 384, 0, 0});
         parts.push_back({(uint32_t)(w.c1 - rec), 64, 1, 0});
         for (uint32_t y = 0; y < w.rows; y++) {
           parts.push_back({(uint32_t)(w.ci[y] - rec), 64, 2, 64 * y});
           parts.push_back({(uint32_t)(w.di[y] - rec), 64, 3, 64 * y});
         }
-        shape = (int)gather.add_shape(w.standard ? (const void*)w.plan.get() : nullptr, std::move(parts));
-      }
-      gather.item(ct_off[live[j]], (uint32_t)shape);
+      });
     }
     tm.lap("shapes");
     rhip_ctx* cx = eng.ctx();
     rhip_g2_lines* lines = key_lines(eng, "ghw11_sk_lines", sk.k, sk.l, sk.attr_key);
-    DBuf d_row_off = up32(eng, b.row_off), d_pair_off = up32(eng, b.pair_off), d_sel_start = up32(eng, b.sel_start), d_sel_ct = up32(eng, b.sel_ct),
-         d_sel_sk = up32(eng, b.sel_tk), d_sel_w = up_bytes(eng, flatten_fr(b.sel_w));
+    DBuf d_row_off = up32(eng, sel.row_off), d_pair_off = up32(eng, sel.pair_off), d_sel_start = up32(eng, sel.sel_start), d_sel_ct = up32(eng, sel.sel_rec),
+         d_sel_sk = up32(eng, sel.sel_one), d_sel_w = up_bytes(eng, flatten_fr(sel.sel_z));
     gather.run({d_c.ptr(), d_c1.ptr(), d_ci.ptr(), d_di.ptr()}, dst_off);
     std::unique_ptr<MemberChecks> mc;
     if (!trusted) {          // transform_packed's checks; every G2 argument is the key's own, so no walk verdicts
@@ -2462,7 +2306,7 @@ bool decrypt_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8
       mc->add(1, d_c1.ptr(), m_items); mc->add(1, d_ci.ptr(), total, d_row_off.as<uint32_t>(), m_items);
       mc->add(1, d_di.ptr(), total, d_row_off.as<uint32_t>(), m_items); mc->add(3, d_c.ptr(), m_items);
     }
-    eng.check(rhip_ghw11_decrypt_batch(cx, m_items, b.max_pairs, b.pair_off[m_items], b.sel_ct.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
+    eng.check(rhip_ghw11_decrypt_batch(cx, m_items, sel.max_pairs, sel.pair_off[m_items], sel.sel_rec.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
                                        d_sel_ct.as<uint32_t>(), d_sel_sk.as<uint32_t>(), d_sel_w.as<rhip_fr>(), d_c1.as<rhip_g1>(), d_ci.as<rhip_g1>(),
                                        d_di.as<rhip_g1>(), d_row_off.as<uint32_t>(), lines, d_c.as<rhip_gt>(), d_msg.as<rhip_gt>()),
               "rhip_ghw11_decrypt_batch");
@@ -2567,20 +2411,14 @@ bool tkgen_packed(Engine& eng, Rng& rng, size_t n, const uint8_t* sk_blob, size_
   if (!sk_off || !tk_off || (n && (!sk_blob || !status || !rk_buf))) throw RabeError("ghw11::tkgen_packed: null input");
   (void)check_offsets(n, sk_off, sk_len, errors);
   std::vector<uint32_t> rows(n, 0);
-  parallel_for(n, [&](size_t i) {
-    if (!(*errors)[i].empty()) return;
-    try {
-      Cursor r{sk_blob + sk_off[i], sk_blob + sk_off[i + 1]};
-      (void)r.raw(256);
-      const uint32_t cnt = r.u32();
-      if ((size_t)cnt * 132 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
-      for (uint32_t y = 0; y < cnt; y++) { (void)r.str(); (void)r.raw(128); }
-      if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
-      rows[i] = 2 + cnt;
-    } catch (const std::exception& ex) {
-      (*errors)[i] = ex.what();
-      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
-    }
+  for_each_record(n, errors, [&](size_t i) {
+    Cursor r{sk_blob + sk_off[i], sk_blob + sk_off[i + 1]};
+    (void)r.raw(256);
+    const uint32_t cnt = r.u32();
+    if ((size_t)cnt * 132 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
+    for (uint32_t y = 0; y < cnt; y++) { (void)r.str(); (void)r.raw(128); }
+    if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
+    rows[i] = 2 + cnt;
   });
   tm.lap("parse");
   std::vector<size_t> live;
@@ -3036,17 +2874,11 @@ bool request_sk_packed(Engine& eng, const char* what, const std::string& authori
     scal_base[s + 1] = scal_base[s] + (uint32_t)sets[s].size();
   }
   (void)check_offsets(n, in_off, blob_len, errors);
-  parallel_for(n, [&](size_t i) {
-    if (!(*errors)[i].empty()) return;
-    try {
-      Cursor r{blob + in_off[i], blob + in_off[i + 1]};
-      (void)r.str();
-      (void)r.raw(64 + 128);
-      if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
-    } catch (const std::exception& ex) {
-      (*errors)[i] = ex.what();
-      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
-    }
+  for_each_record(n, errors, [&](size_t i) {
+    Cursor r{blob + in_off[i], blob + in_off[i + 1]};
+    (void)r.str();
+    (void)r.raw(64 + 128);
+    if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
   });
   tm.lap("parse");
   std::vector<size_t> live;
