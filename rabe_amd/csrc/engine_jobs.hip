@@ -15,6 +15,7 @@
 // fixed-base table kernels of engine.hip.
 // There is no CPU fallback anywhere in this file.
 #include "engine_internal.h"
+#include "msm_chunks.h"
 
 // ------------------------------------------------------------------------------------------------ small device helpers
 __device__ __forceinline__ Fp ld_fp_q(const uint4* p) {
@@ -1217,25 +1218,9 @@ __global__ void __launch_bounds__(128, RB_G2_WAVES) k_msm_finish_g2(size_t n_ite
   const Fp2 zinv{mul(acc.z.c0, ninv), neg(mul(acc.z.c1, ninv))};
   st_g2_q(Q + last, jac_to_aff_with_zinv(acc, zinv));
 }
-// chunking of the shared-doubling sums: a lane pays its own 254 doublings / squarings (~1.8 k in G1, ~4 k in G2, ~4.6 k in Gt)
-// plus ~1 k (G1) .. 4.6 k (Gt) per term; same rounds x lane-time model as choose_chunks with a 2 : 1 doubling-to-term ratio
+// chunking of the shared-doubling sums: the cost model is rb_msm_chunks (msm_chunks.h, a pure host function the tests call too)
 static void choose_msm_chunks(const rhip_ctx* ctx, size_t n_items, size_t max_terms, uint32_t* L, uint32_t* C) {
-  if (max_terms < 1) max_terms = 1;
-  const size_t simds = (size_t)ctx->n_cu * 4;
-  double best = 0;
-  size_t best_c = 1;
-  for (size_t c = 1; c <= 256; c++) {
-    const size_t l = (max_terms + c - 1) / c;
-    const size_t c_eff = (max_terms + l - 1) / l;
-    const size_t waves = (n_items * l + 63) / 64;
-    const size_t rounds = (waves + simds - 1) / simds;
-    const double cost = (double)rounds * (2.0 + (double)c_eff);
-    if (best == 0 || cost < best) { best = cost; best_c = c; }
-    if (l == 1) break;
-  }
-  const size_t l = (max_terms + best_c - 1) / best_c;
-  *C = (uint32_t)((max_terms + l - 1) / l);
-  *L = (uint32_t)l;
+  rb_msm_chunks((size_t)ctx->n_cu * 4, n_items, max_terms, L, C);
 }
 
 // ------------------------------------------------------------------------------------------------ LSW KP-ABE

@@ -283,8 +283,11 @@ class Engine:
         raw = self.download(out, n_items * GT)
         return [raw[i * GT:(i + 1) * GT] for i in range(n_items)]
 
-    def pairing_jobs(self, offsets, p, q, scal=None, lead=None):
-        """rhip_pairing_jobs without a summed pair: out[i] = lead[i] * FE(prod_j ML(scal[j] * p[j], q[j])) over item i's pairs"""
+    def pairing_jobs(self, offsets, p, q, scal=None, lead=None, sum_offsets=None, s_base=None, s_scal=None, s_q=None):
+        """rhip_pairing_jobs: out[i] = lead[i] * FE(prod_j ML(scal[j] * p[j], q[j]) * ML(sum_t s_scal[t] * s_base[t], s_q[i])), j over item
+        i's pairs [offsets[i], offsets[i+1]) and t over its terms [sum_offsets[i], sum_offsets[i+1]).  Without sum_offsets there is no
+        summed pair; with them s_base / s_scal hold one record per term and s_q one G2 point per item (max_terms and n_terms are derived).
+        A pair with an argument at infinity -- the sum included -- contributes one."""
         n_items = len(offsets) - 1
         off = self.upload_u32(offsets)
         bp, bq = self.upload(b"".join(p) or b"\0"), self.upload(b"".join(q) or b"\0")
@@ -292,9 +295,21 @@ class Engine:
         bl = self.upload(b"".join(lead)) if lead else None
         out = self.alloc(n_items * GT)
         mx = max(offsets[i + 1] - offsets[i] for i in range(n_items))
+        max_terms = n_terms = 0
+        soff = sb = sk = sq = None
+        if sum_offsets is not None:
+            n_terms = sum_offsets[-1]
+            if len(sum_offsets) != n_items + 1 or sum_offsets[0] != 0 or any(sum_offsets[i] > sum_offsets[i + 1] for i in range(n_items)):
+                raise ValueError("pairing_jobs: sum_offsets must run from 0 in len(offsets) non-decreasing entries")
+            if len(s_base) != n_terms or len(s_scal) != n_terms or len(s_q) != n_items:
+                raise ValueError("pairing_jobs: one s_base and one s_scal per term, one s_q per item")
+            max_terms = max(sum_offsets[i + 1] - sum_offsets[i] for i in range(n_items))
+            soff, sq = self.upload_u32(sum_offsets), self.upload(b"".join(s_q))
+            sb, sk = self.upload(b"".join(s_base) or b"\0"), self.upload(b"".join(s_scal) or b"\0")
         self._check(self.lib.rhip_pairing_jobs(self.ctx, ctypes.c_size_t(n_items), ctypes.c_size_t(mx), ctypes.c_size_t(len(p)), off.ptr, bp.ptr,
-                                               bs.ptr if bs else None, bq.ptr, ctypes.c_size_t(0), ctypes.c_size_t(0), None, None, None, None,
-                                               bl.ptr if bl else None, out.ptr))
+                                               bs.ptr if bs else None, bq.ptr, ctypes.c_size_t(max_terms), ctypes.c_size_t(n_terms),
+                                               soff.ptr if soff else None, sb.ptr if sb else None, sk.ptr if sk else None,
+                                               sq.ptr if sq else None, bl.ptr if bl else None, out.ptr))
         raw = self.download(out, n_items * GT)
         return [raw[i * GT:(i + 1) * GT] for i in range(n_items)]
 

@@ -13,7 +13,7 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [SRC] + [os.path.join(HDR_DIR, f) for f in os.listdir(HDR_DIR)]
+    deps = [SRC, os.path.join(os.path.dirname(HDR_DIR), "msm_chunks.h")] + [os.path.join(HDR_DIR, f) for f in os.listdir(HDR_DIR)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

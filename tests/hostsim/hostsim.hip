@@ -8,6 +8,7 @@
 #include "../../rabe_amd/csrc/bn254/selftest.h"
 #include "../../rabe_amd/csrc/bn254/pairing29.h"
 #include "../../rabe_amd/csrc/bn254/pairing29p.h"
+#include "../../rabe_amd/csrc/msm_chunks.h"
 #include <thread>
 #include <pthread.h>
 #include <string.h>
@@ -325,6 +326,8 @@ void hs_g2_msm(int n, const uint32_t* p, const uint32_t* k, uint32_t* out) {
   store_g2(out, jac_to_aff(jac_msm_naf<Fp2>(HostTerms<Fp2>{n, P, pos, neg})));
   delete[] P; delete[] pos; delete[] neg;
 }
+// the chunking of the shared-doubling sums the engine's choose_msm_chunks runs (rabe_amd/csrc/msm_chunks.h), n_simds = 4 per CU
+void hs_msm_chunks(size_t n_simds, size_t n_items, size_t max_terms, uint32_t* L, uint32_t* C) { rb_msm_chunks(n_simds, n_items, max_terms, L, C); }
 void hs_gt_pow(const uint32_t* a, const uint32_t* k, uint32_t* out) { store_gt(out, gt_pow_binary(load_gt(a), k)); }
 void hs_gt_pow_window(const uint32_t* a, const uint32_t* k, uint32_t* out) { store_gt(out, gt_pow_window(load_gt(a), k)); }
 
