@@ -641,6 +641,11 @@ int32_t rhip_sha3_256_batch(rhip_ctx* ctx, size_t n, const uint8_t* dev_data, co
 int32_t rhip_sha3_fr_batch(rhip_ctx* ctx, size_t n, const uint8_t* dev_data, const uint64_t* dev_off /*[n+1]*/, rhip_fr* dev_out /*[n]*/);
 /* aes/mod.rs:47-55 kdf: key_i = SHA3-256(bytes(gt[idx ? idx[i] : i])), bytes = 12 coefficients as 32 big-endian bytes each */
 int32_t rhip_gt_kdf_batch(rhip_ctx* ctx, size_t n, const rhip_gt* dev_gt, const uint32_t* dev_gt_idx /*[n] or NULL*/, uint8_t* dev_keys /*[n][32]*/);
+/* The same KDF behind per-item verdicts (the ending of rabe_{ac17_cp,bsw}_decaps_packed): key_i = SHA3-256(bytes(gt[row[i]])) where
+ * row[i] < n_gt, 32 zero bytes where it is not (RHIP_KDF_NO_ROW: the item failed) -- a failed item's slot never holds a key derived from
+ * what its pairings left.  dev_gt must be a valid device pointer even when n_gt = 0. */
+#define RHIP_KDF_NO_ROW 0xFFFFFFFFu
+int32_t rhip_gt_kdf_rows(rhip_ctx* ctx, size_t n, const rhip_gt* dev_gt, size_t n_gt, const uint32_t* dev_row /*[n]*/, uint8_t* dev_keys /*[n][32]*/);
 /* AES-256 (FIPS 197) of n blocks under n keys (known-answer tests) */
 int32_t rhip_aes256_encrypt_blocks(rhip_ctx* ctx, size_t n, const uint8_t* dev_keys /*[n][32]*/, const uint8_t* dev_in /*[n][16]*/, uint8_t* dev_out /*[n][16]*/);
 size_t rhip_seal_workspace_bytes(size_t n, size_t total_segments);

@@ -88,6 +88,13 @@ const char* rabe_host_last_error(rabe_host* h);          /* h may be NULL: error
  * draw order, instead of the OS generator.  n = 0 switches back to OS randomness. */
 int32_t rabe_host_set_tape(rabe_host* h, const uint8_t* fr_le32, size_t n);
 
+/* The per-kernel launch record of the host's own engine (include/rabe_hip.h: rhip_ctx_timing on the calling thread's lane, main stream): while
+ * enabled every kernel launch there is timed; _read waits for the stream and drains the record as "kernel_name total_ms launches\n" lines
+ * (truncated to len).  For measurements and for tests that assert WHICH kernels a call launched; launches on the side stream (the
+ * membership pass) are not recorded. */
+int32_t rabe_host_kernel_timing(rabe_host* h, int32_t enable);
+int32_t rabe_host_kernel_timing_read(rabe_host* h, char* buf, size_t len);
+
 /* G*Fr / Gt^Fr elements that share one base are served from a cached fixed-base window table once n of them have been seen,
  * in one call or accumulated over calls (default 1024); the results do not depend on it.  Tests set 1 / SIZE_MAX to force
  * either path. */
@@ -151,6 +158,36 @@ int32_t rabe_ac17_cp_decrypt_packed(rabe_host* h, const void* sk, size_t n_items
                                     const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* pt_buf,
                                     size_t pt_cap, uint64_t* pt_off /*[n_items+1]*/);
 
+/* ---- key encapsulation: the packed pair WITHOUT payloads.  A caller that seals large objects where they live (files, streams, rows) wants per
+ * item the ciphertext HEADER and the 32-byte content key the reference's kdf derives (src/utils/aes/mod.rs:47-55), and on the other side the same
+ * 32 bytes back from the header and a secret key.  Not functions of the reference but compositions of functions that are (as
+ * rabe_ghw11_provision_packed is).  Built for ac17 (CP) and bsw; both run on devices[0] of a device group.
+ *   key = SHA3-256(bytes(Gt)): bytes(Gt) is the byte form the reference's kdf hashes -- the 12 coefficients in wire order, each as 32 BIG-endian
+ *   bytes -- i.e. exactly the AES key rabe_encrypt_symmetric / rabe_decrypt_symmetric derive from that Gt.
+ * ENCAPS.  Item i's header at hdr_buf + hdr_off[i] is the Ac17CpCiphertext record rabe_ac17_cp_encrypt_packed writes for the same draws with a
+ *   sealed part of length ZERO: the record's length field is 0 and no nonce, ciphertext or tag follows.  key_buf + 32 i = SHA3-256(bytes(msg_i)).
+ *   DRAW ORDER: rabe_ac17_cp_encrypt_packed's minus the AES nonce -- per item s0, s1, msg -- so a tape that drives encrypt_packed with the nonce
+ *   draws removed drives encaps_packed.  hdr_off is always filled; returns 1, with nothing drawn and nothing written, when
+ *   hdr_cap < hdr_off[n_items].  Arguments otherwise as rabe_ac17_cp_encrypt_packed.  The record-assembly template ends in the zero length field
+ *   and takes no sealed source; the keys come from the KDF kernel alone (rhip_gt_kdf_batch straight out of the msg array): no AES context, CTR,
+ *   GHASH or tag kernel is launched.  The staging that held the scalars, msg and the keys is zeroed, host and device, when the call ends.
+ * DECAPS.  key_buf + 32 i = SHA3-256(bytes(X)) where X is what rabe_ac17_cp_decrypt_gt(sk, record i) returns, for ANY well-formed
+ *   Ac17CpCiphertext record, whatever its sealed part: headers from encaps and full records from rabe_ac17_cp_encrypt_packed are both valid input.
+ *   The sealed bytes are skipped by their length field (which must lie inside the record); they are not read and NOT authenticated.  An item
+ *   fails alone -- status[i] = -1, 32 zero bytes in its slot, the first error in rabe_host_last_error: bad bounds, a malformed record, a
+ *   non-member element unless RABE_PACKED_TRUSTED, a key that does not satisfy the policy.  Nothing outside [0, ct_len) is read; no randomness
+ *   is drawn.  The launch set is rabe_ac17_cp_decrypt_packed's up to the final Gt (one upload of the blob, the cached plans and prepared key
+ *   lines); its ending is the KDF behind the verdict mask (rhip_gt_kdf_rows: a failed item's key is never computed) and one download of
+ *   32 n_items bytes -- no gather of sealed parts, no open.
+ * THE EXISTING PARSERS and the empty sealed part: rabe_obj_deserialize and the packed decrypts already ACCEPT a record whose sealed part is
+ *   empty -- the length field is read and the bytes it announces must lie inside the record -- and fail such a record only later, at the tag
+ *   ("decryption error: aead::Error": nonce + tag need 28 bytes).  They are unchanged; decaps parses with the same code and stops before the tag. */
+int32_t rabe_ac17_cp_encaps_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
+                                   const uint32_t* item_policy /*[n_items]*/, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off /*[n_items+1]*/,
+                                   uint8_t* key_buf /*32 n_items*/);
+int32_t rabe_ac17_cp_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
+                                   const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* key_buf /*32 n_items*/);
+
 /* KP-ABE variant (src/schemes/ac17/mod.rs:439-675) */
 int32_t rabe_ac17_kp_keygen(rabe_host* h, const void* msk, const char* policy, int32_t language, void** sk);
 /* n_items calls of ac17::kp_keygen (src/schemes/ac17/mod.rs:439-547) under one master key, item i under policies[item_policy[i]]: the triple
@@ -212,6 +249,15 @@ int32_t rabe_bsw_encrypt_packed(rabe_host* h, const void* pk, const char* const*
 int32_t rabe_bsw_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
                                 const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* pt_buf, size_t pt_cap,
                                 uint64_t* pt_off /*[n_items+1]*/);
+/* Key encapsulation for bsw: everything said at rabe_ac17_cp_{encaps,decaps}_packed, with CpAbeCiphertext records, rabe_bsw_encrypt_packed /
+ * rabe_bsw_decrypt_packed as the calls composed and rabe_bsw_decrypt_gt as the definition of X.  ENCAPS DRAW ORDER: rabe_bsw_encrypt_packed's
+ * minus the AES nonce -- per item secret, msg, the gate coefficients of gen_shares_policy.  The existing parser accepts an empty sealed part
+ * here too and fails it at the tag; it is unchanged. */
+int32_t rabe_bsw_encaps_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
+                               const uint32_t* item_policy /*[n_items]*/, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off /*[n_items+1]*/,
+                               uint8_t* key_buf /*32 n_items*/);
+int32_t rabe_bsw_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
+                               const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* key_buf /*32 n_items*/);
 
 /* ---- lsw (src/schemes/lsw/mod.rs:86-290) */
 int32_t rabe_lsw_setup(rabe_host* h, void** pk, void** msk);

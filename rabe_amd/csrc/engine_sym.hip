@@ -245,6 +245,18 @@ __global__ void __launch_bounds__(256) k_sym_kdf(uint32_t n, const rhip_gt* gt, 
 #pragma unroll
   for (int k = 0; k < 8; k++) keys[(size_t)i * 8 + k] = key[k];
 }
+// The KEM ending of a one-key decrypt (host layer: rabe_*_decaps_packed): item i's content key is the KDF of row[i] of the decrypted Gt
+// array; an item whose verdict is a failure has no row (row[i] >= n_gt) and gets 32 zero bytes -- its slot never holds a key derived from
+// whatever its pairings left behind.  k_sym_kdf's sponge, no AES context after it.
+__global__ void __launch_bounds__(256) k_sym_kdf_rows(uint32_t n, const rhip_gt* gt, uint32_t n_gt, const uint32_t* row, uint32_t* keys /*[n][8]*/) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const uint32_t r = row[i];
+  if (r < n_gt) kdf_of_gt(gt[r].l, key);
+#pragma unroll
+  for (int k = 0; k < 8; k++) keys[(size_t)i * 8 + k] = key[k];
+}
 __global__ void __launch_bounds__(256) k_sha3_256(uint32_t n, const uint8_t* data, const uint64_t* off, uint32_t* digest /*[n][8]*/) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -489,6 +501,14 @@ extern "C" int32_t rhip_gt_kdf_batch(rhip_ctx* ctx, size_t n, const rhip_gt* dev
   if (!n) return RHIP_OK;
   if (n > 0xFFFFFFFFull || !dev_gt || !dev_keys) return RHIP_ERR_ARG;
   KLAUNCH(ctx, "k_sym_kdf", k_sym_kdf, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, (uint32_t)n, dev_gt, dev_gt_idx, (uint32_t*)dev_keys);
+  return RHIP_OK;
+}
+extern "C" int32_t rhip_gt_kdf_rows(rhip_ctx* ctx, size_t n, const rhip_gt* dev_gt, size_t n_gt, const uint32_t* dev_row, uint8_t* dev_keys) {
+  NEED(ctx);
+  if (!n) return RHIP_OK;
+  if (n > 0xFFFFFFFFull || n_gt >= 0xFFFFFFFFull || !dev_gt || !dev_row || !dev_keys) return RHIP_ERR_ARG;
+  KLAUNCH(ctx, "k_sym_kdf_rows", k_sym_kdf_rows, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, (uint32_t)n, dev_gt, (uint32_t)n_gt, dev_row,
+          (uint32_t*)dev_keys);
   return RHIP_OK;
 }
 extern "C" int32_t rhip_aes256_encrypt_blocks(rhip_ctx* ctx, size_t n, const uint8_t* dev_keys, const uint8_t* dev_in, uint8_t* dev_out) {

@@ -799,6 +799,20 @@ int32_t rabe_host_set_fixed_base_min(rabe_host* h, size_t n) {
   h->eng.fixed_base_min = n ? n : 1;
   return 0;
 }
+int32_t rabe_host_kernel_timing(rabe_host* h, int32_t enable) {
+  if (!h) return -1;
+  GUARD_BEGIN
+  h->eng.check(rhip_ctx_timing(h->eng.ctx(), enable), "rhip_ctx_timing");
+  return 0;
+  GUARD_END(h)
+}
+int32_t rabe_host_kernel_timing_read(rabe_host* h, char* buf, size_t len) {
+  if (!h) return -1;
+  GUARD_BEGIN
+  h->eng.check(rhip_ctx_timing_read(h->eng.ctx(), buf, len), "rhip_ctx_timing_read");
+  return 0;
+  GUARD_END(h)
+}
 int32_t rabe_host_set_tape(rabe_host* h, const uint8_t* fr_le32, size_t n) {
   if (!h) return -1;
   if (!n) { h->tape.reset(); return 0; }
@@ -1145,6 +1159,42 @@ int32_t rabe_ac17_cp_decrypt_packed(rabe_host* h, const void* sk, size_t n_items
         return ac17::cp_decrypt_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
       }, status, pt_buf, pt_cap, pt_off, &errors))
     return 1;
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
+// key encapsulation: the packed pair without payloads, on the host's own engine (include/rabe_host.h)
+int32_t rabe_ac17_cp_encaps_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
+                                   const uint32_t* item_policy, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {
+  GUARD_BEGIN
+  if (!item_policy || !hdr_off) throw RabeError("cp_encaps_packed: null input");
+  return ac17::cp_encaps_packed(h->eng, h->rng(), *(const ac17::Ac17PublicKey*)pk, strs(policies, n_policies), lang_of(language), n_items, item_policy,
+                                hdr_buf, hdr_cap, hdr_off, key_buf) ? 0 : 1;
+  GUARD_END(h)
+}
+int32_t rabe_ac17_cp_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
+                                   uint32_t flags, int32_t* status, uint8_t* key_buf) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  ac17::cp_decaps_packed(h->eng, *(const ac17::Ac17CpSecretKey*)sk, n_items, ct_blob, ct_len, ct_off, (flags & RABE_PACKED_TRUSTED) != 0, status, key_buf,
+                         &errors);
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
+int32_t rabe_bsw_encaps_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
+                               const uint32_t* item_policy, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {
+  GUARD_BEGIN
+  if (!item_policy || !hdr_off) throw RabeError("bsw::encaps_packed: null input");
+  return bsw::encaps_packed(h->eng, h->rng(), *(const bsw::CpAbePublicKey*)pk, strs(policies, n_policies), lang_of(language), n_items, item_policy, hdr_buf,
+                            hdr_cap, hdr_off, key_buf) ? 0 : 1;
+  GUARD_END(h)
+}
+int32_t rabe_bsw_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
+                               int32_t* status, uint8_t* key_buf) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  bsw::decaps_packed(h->eng, *(const bsw::CpAbeSecretKey*)sk, n_items, ct_blob, ct_len, ct_off, (flags & RABE_PACKED_TRUSTED) != 0, status, key_buf, &errors);
   for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
   return 0;
   GUARD_END(h)

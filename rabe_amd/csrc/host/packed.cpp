@@ -3,7 +3,8 @@
 // instead of the per-object pairing jobs.  In file order: AC17 bulk keygen; BSW keygen / delegate / encrypt / decrypt; LSW encrypt / keygen /
 // decrypt (n keys, one ciphertext) / decrypt (n ciphertexts, one key); AW11 encrypt / keygen / decrypt; GHW11 encrypt / decrypt_out /
 // transform / decrypt / keygen / tkgen / provision; BDABE and MKE08 (one body, dnfabe) encrypt / keygen / secret attribute keys.  AC17's
-// packed encrypt, decrypt and KP keygen are in schemes.cpp.
+// packed encrypt, decrypt and KP keygen are in schemes.cpp.  The key-encapsulation forms (rabe_{ac17_cp,bsw}_{encaps,decaps}_packed) are a mode of
+// the encrypt / decrypt bodies: same caches, plans and launch sets, another ending.
 // What stays on the host is what the reference does with strings and bytes: policy parsing, flattening the tree into the index tables the
 // share kernels walk, traverse / calc_pruned / calc_coefficients per distinct policy, the selection tables, record layouts.  Records are the
 // byte form rabe_obj_serialize gives the corresponding struct (host_abi.cpp), so packed and object APIs interoperate.
@@ -331,6 +332,13 @@ struct WalkScope {
       const auto& ok = mc->ok(k);
       for (size_t j = 0; j < live.size(); j++) if (!ok[j] && (*errors)[live[j]].empty()) (*errors)[live[j]] = msg;
     }
+  }
+  // a decaps has no open to queue behind the pairings: the walk's verdicts are read before the keys are derived, like every other verdict
+  void fail_walked(const std::vector<size_t>& live, const char* msg, std::vector<std::string>* errors) {
+    if (!walked) return;
+    std::vector<uint8_t> ok;
+    walked->finish(&ok);
+    for (size_t j = 0; j < live.size(); j++) if (!ok[j]) (*errors)[live[j]] = msg;
   }
   // after the open: the items whose walk refused an element
   void retract(const std::vector<size_t>& live, const char* msg, int32_t* status, uint8_t* pt_buf, const uint64_t* pt_off, std::vector<std::string>* errors) {
@@ -736,9 +744,13 @@ bool delegate_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const CpAb
 // n calls of bsw::encrypt (bsw/mod.rs:217-251).  Draw order per item: secret (:228), msg (:229), the gate coefficients of
 // gen_shares_policy (secretsharing/mod.rs:128-134), the AES nonce (aes/mod.rs:17).  Record = CpAbeCiphertext:
 //   policy text, language, c, c_p, leaf count, per leaf (name_col, g1 * q_y, (g2 * h(name)) * q_y), sealed plaintext.
-bool encrypt_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
-                    const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  Timer tm("bsw::encrypt_packed");
+// key_buf != nullptr is the key encapsulation (encaps_packed below): no plaintexts, no nonce draw, records that end in the length field of an
+// empty sealed part, and per item the content key SHA3-256(bytes(msg)) instead of a payload sealed under it.
+static bool encrypt_core(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                         const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off,
+                         uint8_t* key_buf) {
+  const bool kem = key_buf != nullptr;
+  Timer tm(kem ? "bsw::encaps_packed" : "bsw::encrypt_packed");
   Engine::ArenaScope arena(eng);
   std::vector<std::shared_ptr<const FlatPolicy>> pols;
   for (const auto& p : policies) pols.push_back(flat_policy(p, language));
@@ -747,7 +759,7 @@ bool encrypt_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const std::
   for (size_t p = 0; p < policies.size(); p++)
     fixed[p] = 4 + policies[p].size() + 1 + 64 + 384 + 4 + pols[p]->leaf_name.size() * (4 + 64 + 128) + pols[p]->names_bytes + 4;
   out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_policy[i]] + (pt_off[i + 1] - pt_off[i]) + 28;
+  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_policy[i]] + (kem ? 0 : (pt_off[i + 1] - pt_off[i]) + 28);
   if (!out_buf || out_cap < out_off[n]) return false;
   std::vector<uint32_t> leaf_off(n + 1, 0), coef_off(n + 1, 0), tree_leaf(n), tree_gate(n);
   for (size_t i = 0; i < n; i++) {
@@ -766,7 +778,7 @@ bool encrypt_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const std::
     memcpy(h_sec + 32 * i, s.l, 32);
     memcpy(h_rho + 32 * i, rho.l, 32);
     for (uint32_t c = coef_off[i]; c < coef_off[i + 1]; c++) { Fr a = r.next_fr(); memcpy(h_coef + 32 * (size_t)c, a.l, 32); }
-    r.fill(nonces[i].data(), 12);
+    if (!kem) r.fill(nonces[i].data(), 12);
   });
   tm.lap("draws");
   rhip_ctx* cx = eng.ctx();
@@ -801,27 +813,50 @@ bool encrypt_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const std::
       L.src(3, (uint32_t)(128 * y), 128);
     }
     if (L.bytes() + 4 != fixed[p_]) throw RabeError("bsw::encrypt_packed: record layout and size disagree");
+    if (kem) L.u32(0);          // the length field of an empty sealed part; no sealed source
   }
   std::vector<uint64_t> src_off(4 * n);
   for (size_t i = 0; i < n; i++) { src_off[i] = 64ull * i; src_off[n + i] = 384ull * i; src_off[2 * n + i] = 64ull * leaf_off[i]; src_off[3 * n + i] = 128ull * leaf_off[i]; }
+  if (kem) {          // headers from the template alone, keys straight out of the msg array: no seal kernel is launched
+    DBuf d_keys(&eng, n * 32 + 4);
+    eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
+    eng.check(rhip_gt_kdf_batch(cx, n, d_msg.as<rhip_gt>(), nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
+    emit_plain_records(eng, layouts, n, item_policy, {d_c.ptr(), d_cp.ptr(), d_g1.ptr(), d_g2.ptr()}, src_off, out_off, out_buf);
+    if (n) eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
+    tm.lap("device: group arithmetic, headers, keys; two copies out");
+    return true;
+  }
   emit_sealed_records(eng, layouts, n, item_policy, {d_c.ptr(), d_cp.ptr(), d_g1.ptr(), d_g2.ptr()}, src_off, d_msg.ptr(), (const uint8_t*)nonces.data(),
                       pt_blob, pt_off, out_off, out_buf);
   tm.lap("device: group arithmetic, records, sealing; one copy out");
   return true;
+}
+bool encrypt_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                    const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  return encrypt_core(eng, rng, pk, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off, nullptr);
+}
+bool encaps_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                   const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  if (n && !key_buf) throw RabeError("bsw::encaps_packed: null input");
+  if (!n) { out_off[0] = 0; return true; }
+  return encrypt_core(eng, rng, pk, policies, language, n, item_policy, nullptr, nullptr, out_buf, out_cap, out_off, key_buf);
 }
 
 // n calls of bsw::decrypt (bsw/mod.rs:260-318) with one key.  Per distinct policy text: traverse_policy, calc_pruned and the
 // coefficients, turned into the selection entries the device path takes -- entry = (ciphertext leaf row, key attribute row, z):
 // for every pruned (name, name_col) the FIRST ciphertext row named name_col, the FIRST key row named name, and one entry per
 // coefficient named name_col (:283-299 as index lists).  status / errors / buffers as ac17::cp_decrypt_packed.
-bool decrypt_packed(Engine& eng, const CpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                    int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
-  Timer tm("bsw::decrypt_packed");
+// key_buf != nullptr is the key decapsulation (decaps_packed below): the same launch set up to the final Gt, then the KDF behind the verdict mask
+// (records.h: derive_keys) instead of the open; pt_buf / pt_cap / pt_off are unused, the sealed part is skipped by its length field and never read.
+static bool decrypt_core(Engine& eng, const CpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                         int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors, uint8_t* key_buf) {
+  const bool kem = key_buf != nullptr;
+  Timer tm(kem ? "bsw::decaps_packed" : "bsw::decrypt_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
   if (!ct_off || (n && !ct_blob)) throw RabeError("bsw::decrypt_packed: null input");
   const uint64_t span = check_offsets(n, ct_off, ct_len, errors);
-  if (!pt_buf || pt_cap < span) return false;
+  if (!kem && (!pt_buf || pt_cap < span)) return false;
   BlobGather gather(eng, ct_blob, ct_len);          // the blob starts for the device now, beside the parsing below (records.h)
   std::vector<std::string> attr;
   for (const auto& v : sk.d_j) attr.push_back(v.string);
@@ -962,11 +997,27 @@ bool decrypt_packed(Engine& eng, const CpAbeSecretKey& sk, size_t n, const uint8
       ws.fail(live, {1, ws.k_alone}, "deserialize: a leaf element is not a group member (FieldError::NotMember)", errors);
     }
   }
+  if (kem) {
+    ws.fail_walked(live, "deserialize: a leaf element is not a group member (FieldError::NotMember)", errors);
+    derive_keys(eng, n, live, d_out.ptr(), status, key_buf, *errors);
+    tm.lap(trusted ? "device: gather, pairings, keys" : "device: gather, pairings, keys; membership beside");
+    return true;
+  }
   // KDF + AES-GCM open on the device: the decrypted Gt never leaves HBM; plaintext bytes come back in one copy
   open_sealed_records(eng, n, live, d_out.ptr(), gather.dev_blob(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
   ws.retract(live, "deserialize: a leaf element is not a group member (FieldError::NotMember)", status, pt_buf, pt_off, errors);
   tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
   return true;
+}
+bool decrypt_packed(Engine& eng, const CpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                    int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
+  return decrypt_core(eng, sk, n, ct_blob, ct_len, ct_off, trusted, status, pt_buf, pt_cap, pt_off, errors, nullptr);
+}
+void decaps_packed(Engine& eng, const CpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                   int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
+  if (n && (!status || !key_buf)) throw RabeError("bsw::decaps_packed: null input");
+  uint8_t none = 0;          // n = 0: nothing is written
+  decrypt_core(eng, sk, n, ct_blob, ct_len, ct_off, trusted, status, nullptr, 0, nullptr, errors, key_buf ? key_buf : &none);
 }
 }  // namespace bsw
 

@@ -287,5 +287,20 @@ void open_sealed_records(Engine& eng, size_t n, const std::vector<size_t>& live,
   }
 }
 
+void derive_keys(Engine& eng, size_t n, const std::vector<size_t>& live, const void* d_gt, int32_t* status, uint8_t* key_buf,
+                 const std::vector<std::string>& errors) {
+  if (!n) return;
+  std::vector<uint32_t> row(n, RHIP_KDF_NO_ROW);
+  for (size_t j = 0; j < live.size(); j++) if (errors[live[j]].empty()) row[live[j]] = (uint32_t)j;
+  for (size_t i = 0; i < n; i++) status[i] = row[i] == RHIP_KDF_NO_ROW ? -1 : 0;
+  ParamPack pp(eng);
+  const size_t h_row = pp.add(row);
+  pp.upload();
+  DBuf d_keys(&eng, n * 32);
+  eng.scrub_session_when_done();          // the decrypted Gt values and the keys do not outlive the call
+  eng.check(rhip_gt_kdf_rows(eng.ctx(), n, (const rhip_gt*)d_gt, live.size(), pp.dev<uint32_t>(h_row), d_keys.as<uint8_t>()), "rhip_gt_kdf_rows");
+  eng.check(rhip_download(eng.ctx(), key_buf, d_keys.ptr(), n * 32), "download (keys)");
+}
+
 }  // namespace schemes
 }  // namespace rabe

@@ -107,6 +107,14 @@ void open_sealed_records(Engine& eng, size_t n, const std::vector<size_t>& live,
                          const std::vector<uint64_t>& sealed_off, const std::vector<uint32_t>& sealed_len, int32_t* status, uint8_t* pt_buf,
                          uint64_t* pt_off, std::vector<std::string>* errors);
 
+// Tail of a packed decaps (key encapsulation: the caller wants the content key, not the payload).  Live item j = item live[j] of the call,
+// its Gt is d_gt[j].  EVERY verdict must be in `errors` by now (walk verdicts included: there is no open to queue behind the pairings, so
+// nothing is gained by reading them later).  status[i] = 0 and key_buf + 32 i = SHA3-256(bytes(Gt)) for the items without an error; -1
+// and 32 zero bytes for the others -- the mask is applied by the kernel (rhip_gt_kdf_rows), a failed item's key is never computed.  One
+// download of 32 n bytes; the device copy of the keys lies in the call's arena, which is scrubbed when the call ends.
+void derive_keys(Engine& eng, size_t n, const std::vector<size_t>& live, const void* d_gt, int32_t* status, uint8_t* key_buf,
+                 const std::vector<std::string>& errors);
+
 // A verdict that arrives after open_sealed_records ran (the G2 membership a decrypt's own Miller loops establish, common.h: WalkedG2 --
 // reading it earlier would make the host wait for the pairings before it prepares the open): the item fails like an item whose tag did not
 // verify -- status -1, its plaintext slot zeroed -- with the decoder's error, which comes first in the reference's order of events.

@@ -1259,12 +1259,23 @@ static std::shared_ptr<const EncPolicy> enc_attr_set(const std::vector<std::stri
 }
 static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::shared_ptr<const EncPolicy>>& pols,
                                 const std::vector<std::string>* policies /* CP: the texts; KP: nullptr */, PolicyLanguage language, size_t n,
-                                const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
+                                const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off,
+                                uint8_t* key_buf = nullptr /* encaps: no plaintexts, no sealing; 32 bytes of content key per item */);
 bool cp_encrypt_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
                        const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
   std::vector<std::shared_ptr<const EncPolicy>> pols;
   for (const auto& pol : policies) pols.push_back(enc_policy(pol, language));
   return encrypt_packed_core(eng, rng, pk, pols, &policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off);
+}
+// Key encapsulation (include/rabe_host.h: rabe_ac17_cp_encaps_packed): cp_encrypt_packed's records with a sealed part of length zero and,
+// per item, the content key SHA3-256(bytes(msg)) instead of a payload sealed under it.  Draws: cp_encrypt_packed's without the nonce.
+bool cp_encaps_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                      const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  if (n && !key_buf) throw RabeError("cp_encaps_packed: null input");
+  if (!n) { out_off[0] = 0; return true; }
+  std::vector<std::shared_ptr<const EncPolicy>> pols;
+  for (const auto& pol : policies) pols.push_back(enc_policy(pol, language));
+  return encrypt_packed_core(eng, rng, pk, pols, &policies, language, n, item_policy, nullptr, nullptr, out_buf, out_cap, out_off, key_buf);
 }
 // n calls of ac17::kp_encrypt: item i is encrypted under the attribute list sets[item_set[i]]; records = Ac17KpCiphertext
 bool kp_encrypt_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
@@ -1275,8 +1286,10 @@ bool kp_encrypt_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std
 }
 static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::shared_ptr<const EncPolicy>>& pols,
                                 const std::vector<std::string>* policies, PolicyLanguage language, size_t n,
-                                const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  StageTimer tm(policies ? "ac17::cp_encrypt_packed" : "ac17::kp_encrypt_packed");
+                                const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off,
+                                uint8_t* key_buf) {
+  const bool kem = key_buf != nullptr;
+  StageTimer tm(kem ? "ac17::cp_encaps_packed" : policies ? "ac17::cp_encrypt_packed" : "ac17::kp_encrypt_packed");
   Engine::ArenaScope arena(eng);
   if (pk.h_a.size() != 3 || pk.e_gh_ka.size() != 2) throw RabeError("malformed Ac17PublicKey");
   std::vector<uint32_t> a_off{0};
@@ -1287,10 +1300,10 @@ static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, 
   }
   for (size_t i = 0; i < n; i++) if (item_policy[i] >= pols.size()) throw RabeError("encrypt_packed: item_policy out of range");
   out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + pols[item_policy[i]]->fixed_bytes + (pt_off[i + 1] - pt_off[i]) + 28;
+  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + pols[item_policy[i]]->fixed_bytes + (kem ? 0 : (pt_off[i + 1] - pt_off[i]) + 28);
   if (!out_buf || out_cap < out_off[n]) return false;
   tm.lap("policies");
-  // randomness in the reference's per-call draw order: s0, s1, msg, nonce -- item after item
+  // randomness in the reference's per-call draw order: s0, s1, msg, nonce -- item after item (encaps: no nonce)
   uint8_t* h_s = eng.pinned(0, n * (64 + 32));
   uint8_t* h_rho = h_s + n * 64;
   std::vector<std::array<uint8_t, 12>> nonces(n);
@@ -1299,7 +1312,7 @@ static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, 
     memcpy(h_s + 64 * i, s0.l, 32);
     memcpy(h_s + 64 * i + 32, s1.l, 32);
     memcpy(h_rho + 32 * i, rho.l, 32);
-    r.fill(nonces[i].data(), 12);
+    if (!kem) r.fill(nonces[i].data(), 12);
   };
   {
     struct Turn { Rng& r; explicit Turn(Rng& x) : r(x) { r.begin_draws(); } ~Turn() { r.end_draws(); } } turn(rng);
@@ -1350,6 +1363,7 @@ static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, 
     }
     L.src(2, 0, 384);
     if (L.bytes() + 4 != pols[p_]->fixed_bytes) throw RabeError("ac17 encrypt_packed: record layout and size disagree");
+    if (kem) L.u32(0);                            // encaps: the template ends in the length field of an empty sealed part, no sealed source
   }
   // The batch can go through the device in PARTS of >= 16 384 items, a part's records copied out (10.4 KB per item at 50 rows, 15 ms per
   // 65 536 items) on the side stream while the next part's group arithmetic runs; randomness was drawn above for the whole batch, item
@@ -1357,7 +1371,7 @@ static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, 
   // measured no faster -- 37.2 against 36.9 ms at 65 536 items -- because the runtime's D2H copy of such a block is a blit kernel that
   // covers the chip: k_table_pow_gt of the next part takes 5.3 instead of 1.3 ms under it.
   static const size_t max_parts = [] { const char* e = getenv("RABE_AC17_ENC_PARTS"); const long v = e ? atol(e) : 1; return (size_t)(v > 0 ? v : 1); }();
-  const size_t parts = std::max<size_t>(1, std::min<size_t>(max_parts, n / 16384));
+  const size_t parts = kem ? 1 : std::max<size_t>(1, std::min<size_t>(max_parts, n / 16384));
   std::vector<PendingCopy> pending(parts);
   if (parts > 1) eng.pinned_reserve((size_t)out_off[n] + parts * ((size_t)8 << 20) + 300 * n);          // staging of every part + their parameter packs: no growth inside the loop
   // every part's row offsets (relative to the part's first row), uploaded once and asynchronously: nothing inside the loop may wait for
@@ -1384,12 +1398,20 @@ static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, 
                                          dm.as<rhip_gt>() + lo, dc0.as<rhip_g2>() + 3 * lo, dc_p, dcp.as<rhip_gt>() + lo), "rhip_ac17_cp_encrypt_batch");
     std::vector<uint64_t> src_off(3 * np);
     for (size_t i = 0; i < np; i++) { src_off[i] = 384ull * i; src_off[np + i] = 192ull * ro[i]; src_off[2 * np + i] = 384ull * i; }
+    if (kem) {          // one part: headers from the template alone, keys straight out of the msg array -- no seal kernel is launched
+      DBuf d_keys(&eng, n * 32 + 4);
+      eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
+      eng.check(rhip_gt_kdf_batch(cx, n, dm.as<rhip_gt>(), nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
+      emit_plain_records(eng, layouts, n, item_policy, {dc0.ptr(), (const void*)dc_p, dcp.ptr()}, src_off, out_off, out_buf);
+      if (n) eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
+      continue;
+    }
     emit_sealed_records(eng, layouts, np, item_policy + lo, {dc0.as<uint8_t>() + 384ull * lo, (const void*)dc_p, dcp.as<uint8_t>() + 384ull * lo}, src_off,
                         dm.as<uint8_t>() + 384ull * lo, (const uint8_t*)nonces.data() + 12 * lo, pt_blob, pt_off + lo, out_off + lo, out_buf,
                         parts > 1 ? &pending[part] : nullptr);
   }
   for (auto& pc : pending) pc.wait(eng);
-  tm.lap("device: group arithmetic, records, sealing; copies out beside the next part");
+  tm.lap(kem ? "device: group arithmetic, headers, keys; two copies out" : "device: group arithmetic, records, sealing; copies out beside the next part");
   return true;
 }
 
@@ -1440,11 +1462,21 @@ struct DecKey {
   const PolicyRef* kp_policy;                    // KP: the key's policy; the attributes come with every ciphertext
 };
 static bool decrypt_packed_core(Engine& eng, const DecKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                                int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors);
+                                int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors,
+                                uint8_t* key_buf = nullptr /* decaps: keys instead of plaintexts; pt_buf / pt_cap / pt_off unused */);
 bool cp_decrypt_packed(Engine& eng, const Ac17CpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                        int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
   if (sk.sk.k_p.size() != 3) throw RabeError("malformed Ac17CpSecretKey");
   return decrypt_packed_core(eng, DecKey{sk.sk, &sk.attr, nullptr}, n, ct_blob, ct_len, ct_off, trusted, status, pt_buf, pt_cap, pt_off, errors);
+}
+// Key decapsulation (include/rabe_host.h: rabe_ac17_cp_decaps_packed): cp_decrypt_packed up to the final Gt, then the KDF behind the verdict
+// mask (records.h: derive_keys) instead of gather + open.  The sealed part of a record is skipped by its length field and never read.
+void cp_decaps_packed(Engine& eng, const Ac17CpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                      int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
+  if (sk.sk.k_p.size() != 3) throw RabeError("malformed Ac17CpSecretKey");
+  if (n && (!status || !key_buf)) throw RabeError("cp_decaps_packed: null input");
+  uint8_t none = 0;          // n = 0: nothing is written
+  decrypt_packed_core(eng, DecKey{sk.sk, &sk.attr, nullptr}, n, ct_blob, ct_len, ct_off, trusted, status, nullptr, 0, nullptr, errors, key_buf ? key_buf : &none);
 }
 bool kp_decrypt_packed(Engine& eng, const Ac17KpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                        int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
@@ -1452,10 +1484,10 @@ bool kp_decrypt_packed(Engine& eng, const Ac17KpSecretKey& sk, size_t n, const u
   return decrypt_packed_core(eng, DecKey{sk.sk, nullptr, &sk.policy}, n, ct_blob, ct_len, ct_off, trusted, status, pt_buf, pt_cap, pt_off, errors);
 }
 static bool decrypt_packed_core(Engine& eng, const DecKey& key, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                                int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
-  const bool kp = key.kp_policy != nullptr;
+                                int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors, uint8_t* key_buf) {
+  const bool kp = key.kp_policy != nullptr, kem = key_buf != nullptr;
   const Ac17SecretKey& core = key.sk;
-  StageTimer tm(kp ? "ac17::kp_decrypt_packed" : "ac17::cp_decrypt_packed");
+  StageTimer tm(kem ? "ac17::cp_decaps_packed" : kp ? "ac17::kp_decrypt_packed" : "ac17::cp_decrypt_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
   if (!ct_off || (n && !ct_blob)) throw RabeError("cp_decrypt_packed: null input");
@@ -1465,7 +1497,7 @@ static bool decrypt_packed_core(Engine& eng, const DecKey& key, size_t n, const 
     if (ct_off[i] > ct_off[i + 1] || ct_off[i + 1] > ct_len) (*errors)[i] = "deserialize: record offsets are not monotone inside the blob";
     else span += ct_off[i + 1] - ct_off[i];
   }
-  if (!pt_buf || pt_cap < span) return false;
+  if (!kem && (!pt_buf || pt_cap < span)) return false;
   if (core.k_0.size() != 3) throw RabeError("malformed AC17 secret key");
   for (const auto& row : core.k) if (row.second.size() != 3) throw RabeError("malformed AC17 secret key: a row does not have 3 elements");
   PolicyNode kp_tree;                            // KP: the key's policy, parsed once (a policy that does not parse fails the call like kp_decrypt)
@@ -1632,6 +1664,7 @@ static bool decrypt_packed_core(Engine& eng, const DecKey& key, size_t n, const 
   const uint32_t* const d_ct_sel = d_sel.as<uint32_t>();
   const uint32_t* const d_sk_sel = d_ct_sel + n_ct_sel + 1;
   if (!m) {
+    if (kem) { for (size_t i = 0; i < n; i++) status[i] = -1; if (n) memset(key_buf, 0, n * 32); return true; }
     pt_off[0] = 0;
     for (size_t i = 0; i < n; i++) { pt_off[i + 1] = 0; status[i] = -1; }
     return true;
@@ -1725,6 +1758,16 @@ static bool decrypt_packed_core(Engine& eng, const DecKey& key, size_t n, const 
       if (!bad && !ok_cp[j]) bad = "deserialize: c_p is not a member of Gt (FieldError::NotMember)";
       if (bad) (*errors)[live[j]] = bad;
     }
+  }
+  if (kem) {          // every verdict first (there is no open to queue behind the pairings), then the KDF behind their mask: 32 n bytes come back
+    if (walked) {
+      std::vector<uint8_t> ok_c0;
+      walked->finish(&ok_c0);
+      for (size_t j = 0; j < m; j++) if (!ok_c0[j]) (*errors)[live[j]] = "deserialize: c_0 element is not a member of G2 (FieldError::NotMember)";
+    }
+    derive_keys(eng, n, live, dout.ptr(), status, key_buf, *errors);
+    tm.lap(trusted ? "device: gather, pairings, keys" : "device: gather, pairings, keys; membership beside");
+    return true;
   }
   // KDF + AES-GCM open on the device: the decrypted Gt never leaves HBM; plaintext bytes come back in one copy
   open_sealed_records(eng, n, live, dout.ptr(), gather.dev_blob(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);

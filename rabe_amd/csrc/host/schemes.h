@@ -46,6 +46,12 @@ bool cp_encrypt_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std
                        const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
 bool cp_decrypt_packed(Engine& eng, const Ac17CpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                        int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors);
+// key encapsulation (include/rabe_host.h: rabe_ac17_cp_{encaps,decaps}_packed): the two packed calls without payloads -- headers (records
+// with an empty sealed part) + 32-byte content keys out, content keys back; status[i] = -1 and 32 zero bytes for an item that fails
+bool cp_encaps_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                      const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf);
+void cp_decaps_packed(Engine& eng, const Ac17CpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                      int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors);
 std::vector<DecryptResult> cp_decrypt_batch(Engine& eng, const std::vector<const Ac17CpSecretKey*>& sks,
                                             const std::vector<const Ac17CpCiphertext*>& cts);
 // the Gt value handed to decrypt_symmetric (parity hook for tests; not part of the reference API)
@@ -103,6 +109,11 @@ bool encrypt_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const std::
                     const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
 bool decrypt_packed(Engine& eng, const CpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                     int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors);
+// key encapsulation (conventions of ac17::cp_{encaps,decaps}_packed)
+bool encaps_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                   const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf);
+void decaps_packed(Engine& eng, const CpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                   int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors);
 }  // namespace bsw
 
 namespace lsw {

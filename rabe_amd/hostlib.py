@@ -136,6 +136,16 @@ class Host:
         _check(self.lib.rabe_ticket_wait(self.h, ticket, ctypes.byref(obj), ctypes.byref(p), ctypes.byref(n)), self.h)
         return Obj(kind, obj) if kind else _take_bytes(p, n)
 
+    def kernel_timing(self, enable=True):
+        """record every kernel launch on the host engine's main stream (rabe_host_kernel_timing)"""
+        _check(self.lib.rabe_host_kernel_timing(self.h, ctypes.c_int32(1 if enable else 0)), self.h)
+
+    def kernel_launches(self):
+        """drains the record -> {kernel name: launches since the last read}"""
+        buf = ctypes.create_string_buffer(1 << 16)
+        _check(self.lib.rabe_host_kernel_timing_read(self.h, buf, ctypes.c_size_t(len(buf))), self.h)
+        return {f[0]: int(f[2]) for f in (line.split() for line in buf.value.decode().splitlines()) if len(f) == 3}
+
     def clear_tape(self):
         _check(self.lib.rabe_host_set_tape(self.h, None, ctypes.c_size_t(0)), self.h)
 
@@ -419,3 +429,39 @@ def packed_decrypt(host, fn, head_args, blob, off, out=None, trusted=False):
                                ctypes.c_uint32(PACKED_TRUSTED if trusted else 0), _np_ptr(status), _np_ptr(buf), ctypes.c_size_t(buf.size), _np_ptr(po))
     _check(rc, host.h)
     return buf[:int(po[n])], po, status[:n]
+
+
+def packed_encaps(host, fn, head_args, policies, item_policy, language, out=None):
+    """key encapsulation: calls `fn(host, *head_args, policies, n_policies, language, n, item_policy, hdr_buf, hdr_cap, hdr_off, key_buf)`, growing the
+    header buffer once when the library reports the size it needs (that first call draws nothing).
+    Returns (hdr_blob view, hdr_off uint64 [n+1], keys uint8 [n, 32])."""
+    import numpy as np
+    n = len(item_policy)
+    arr, npol = _strs(policies)
+    ip = np.ascontiguousarray(item_policy, dtype=np.uint32)
+    ho = np.zeros(n + 1, dtype=np.uint64)
+    keys = np.zeros((max(n, 1), 32), dtype=np.uint8)
+    buf = out if out is not None else np.empty(0, dtype=np.uint8)
+    for _ in range(2):
+        rc = getattr(host.lib, fn)(host.h, *head_args, arr, npol, language, ctypes.c_size_t(n), _np_ptr(ip), _np_ptr(buf), ctypes.c_size_t(buf.size),
+                                   _np_ptr(ho), _np_ptr(keys))
+        if rc != 1:
+            break
+        buf = np.empty(int(ho[n]), dtype=np.uint8)
+    _check(rc, host.h)
+    return buf[:int(ho[n])], ho, keys[:n]
+
+
+def packed_decaps(host, fn, head_args, blob, off, trusted=False):
+    """key decapsulation: calls `fn(host, *head_args, n, blob, len, off, flags, status, key_buf)`.
+    Returns (keys uint8 [n, 32] -- zeros where status is -1, status int32 [n])."""
+    import numpy as np
+    n = len(off) - 1
+    ct = _as_u8(blob)
+    co = np.ascontiguousarray(off, dtype=np.uint64)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    keys = np.full((max(n, 1), 32), 0xEE, dtype=np.uint8)
+    rc = getattr(host.lib, fn)(host.h, *head_args, ctypes.c_size_t(n), _np_ptr(ct), ctypes.c_size_t(ct.size), _np_ptr(co),
+                               ctypes.c_uint32(PACKED_TRUSTED if trusted else 0), _np_ptr(status), _np_ptr(keys))
+    _check(rc, host.h)
+    return keys[:n], status[:n]

@@ -212,3 +212,18 @@ def cp_decrypt_packed(host, sk, ct_blob, ct_off, out=None, trusted=False):
                                               ctypes.c_size_t(buf.size), _np_ptr(po))
     hostlib_check(rc, host)
     return buf[:int(po[n])], po, status[:n]
+
+
+# ---- key encapsulation (rabe_ac17_cp_{encaps,decaps}_packed): the packed pair without payloads
+def cp_encaps_packed(host, pk, policies, item_policy, language=JSON_POLICY, out=None):
+    """n headers (Ac17CpCiphertext records with an empty sealed part) + n 32-byte content keys SHA3-256(bytes(msg)).
+    Returns (hdr_blob view, hdr_off uint64 [n+1], keys uint8 [n, 32])."""
+    from ..hostlib import packed_encaps
+    return packed_encaps(host, "rabe_ac17_cp_encaps_packed", (pk.ptr,), policies, item_policy, language, out)
+
+
+def cp_decaps_packed(host, sk, ct_blob, ct_off, trusted=False):
+    """the content keys of n records (headers or full ciphertexts) under one key.  Returns (keys uint8 [n, 32], status int32 [n]); a failed item
+    has status -1 and 32 zero bytes.  The sealed parts are neither read nor authenticated."""
+    from ..hostlib import packed_decaps
+    return packed_decaps(host, "rabe_ac17_cp_decaps_packed", (sk.ptr,), ct_blob, ct_off, trusted)

@@ -110,3 +110,18 @@ def delegate_packed(host, pk, sk, subsets, item_subset, out=None):
         buf = np.empty(int(so[n]), dtype=np.uint8)
     _check(rc, host.h)
     return buf[:int(so[n])], so
+
+
+# ---- key encapsulation (rabe_bsw_{encaps,decaps}_packed): the packed pair without payloads
+def encaps_packed(host, pk, policies, item_policy, language=JSON_POLICY, out=None):
+    """n headers (CpAbeCiphertext records with an empty sealed part) + n 32-byte content keys SHA3-256(bytes(msg)).
+    Returns (hdr_blob view, hdr_off uint64 [n+1], keys uint8 [n, 32])."""
+    from ..hostlib import packed_encaps
+    return packed_encaps(host, "rabe_bsw_encaps_packed", (pk.ptr,), policies, item_policy, language, out)
+
+
+def decaps_packed(host, sk, ct_blob, ct_off, trusted=False):
+    """the content keys of n records (headers or full ciphertexts) under one key.  Returns (keys uint8 [n, 32], status int32 [n]); a failed item
+    has status -1 and 32 zero bytes.  The sealed parts are neither read nor authenticated."""
+    from ..hostlib import packed_decaps
+    return packed_decaps(host, "rabe_bsw_decaps_packed", (sk.ptr,), ct_blob, ct_off, trusted)

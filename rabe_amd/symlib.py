@@ -59,6 +59,18 @@ def gt_kdf(eng, gts, idx=None):
     return [raw[32 * i:32 * i + 32] for i in range(n)]
 
 
+NO_ROW = 0xFFFFFFFF
+
+
+def gt_kdf_rows(eng, gts, rows):
+    """rhip_gt_kdf_rows: key i = KDF(gts[rows[i]]); 32 zero bytes where rows[i] names no element (NO_ROW, or any index >= len(gts))"""
+    n = len(rows)
+    d, out = eng.upload(b"".join(gts) or b"\0" * 384), eng.alloc(32 * n)
+    eng._check(eng.lib.rhip_gt_kdf_rows(eng.ctx, ctypes.c_size_t(n), d.ptr, ctypes.c_size_t(len(gts)), eng.upload_u32(rows).ptr, out.ptr))
+    raw = eng.download(out, 32 * n)
+    return [raw[32 * i:32 * i + 32] for i in range(n)]
+
+
 def aes256_blocks(eng, keys, blocks):
     n = len(keys)
     dk, di, out = eng.upload(b"".join(keys)), eng.upload(b"".join(blocks)), eng.alloc(16 * n)
