@@ -41,18 +41,36 @@ int32_t rabe_host_create_checked(int32_t abi_version, int32_t device, rabe_host*
 int32_t rabe_host_create(int32_t device, rabe_host** out);
 /* ---- device group: ONE host over several GPUs of a node ----------------------------------------------------------------------
  * Every encrypt / keygen / decrypt call is independent (the reference's schemes are pure functions of their arguments and fresh
- * randomness), so a batch shards by item: the packed entry points of the four BASELINE schemes -- rabe_ac17_cp_{encrypt,decrypt}_packed,
- * rabe_bsw_{encrypt,decrypt}_packed, rabe_lsw_{keygen,decrypt,decrypt_one_sk}_packed, rabe_aw11_{encrypt,decrypt}_packed -- cut their n_items into one
- * contiguous block per device (sizes differ by at most one, blocks in device order), run every block on its own host thread and engine
- * (each device builds its replica of a key's window tables / prepared lines on first use and keeps it), and the records / plaintexts /
- * status entries land in the caller's buffers exactly where the single-device call puts them.  Randomness is drawn block after block
- * from the host's one source, so on a tape (rabe_host_set_tape) the bytes do not depend on the number of devices.  No data-path
- * collective: the only exchange is the results arriving in host memory.  A device may be listed more than once (two engines, i.e. two
- * streams with their own workspaces, on one GPU) -- how a one-GPU box tests the split.  Every other entry point runs on devices[0].
+ * randomness), so a batch shards by item.  The SHARDED calls:
+ *   the four BASELINE schemes: rabe_ac17_cp_encrypt_packed, rabe_ac17_cp_decrypt_packed, rabe_bsw_encrypt_packed, rabe_bsw_decrypt_packed,
+ *     rabe_lsw_keygen_packed, rabe_lsw_decrypt_packed, rabe_lsw_decrypt_one_sk_packed, rabe_aw11_encrypt_packed, rabe_aw11_decrypt_packed;
+ *   AC17 KP: rabe_ac17_kp_encrypt_packed, rabe_ac17_kp_decrypt_packed;
+ *   the KEM pair of both schemes: rabe_ac17_cp_encaps_packed, rabe_ac17_cp_decaps_packed, rabe_bsw_encaps_packed, rabe_bsw_decaps_packed;
+ *   the GHW11 service: rabe_ghw11_encrypt_packed, rabe_ghw11_transform_packed, rabe_ghw11_decrypt_out_packed, rabe_ghw11_decrypt_packed,
+ *     rabe_ghw11_keygen_packed, rabe_ghw11_provision_packed;
+ *   the DNF schemes' encrypt: rabe_bdabe_encrypt_packed, rabe_mke08_encrypt_packed.
+ * Each cuts its n_items into one contiguous block per device (sizes differ by at most one, blocks in device order; fewer items than
+ * devices: one item each for the first), runs every block on its own host thread with its engine's device current (each device builds its
+ * replica of a key's window tables / prepared lines on first use and keeps it), and the records / plaintexts / fixed-size slots (the
+ * 768-byte transform records, the 32-byte keys) / status entries land in the caller's buffers exactly where the single-device call puts them;
+ * rabe_host_last_error is the first failing item's text in item order.  Randomness is drawn block after block from the host's one source
+ * (rabe_ghw11_provision_packed: its two runs r_0 .., z_0 .. are drawn in that order before the blocks start), so on a tape
+ * (rabe_host_set_tape) the bytes do not depend on the number of devices.  Every engine that held secrets zeroes its staging when the call
+ * ends.  No data-path collective: the only exchange is the results arriving in host memory.  A device may be listed more than once (two
+ * engines, i.e. two streams with their own workspaces, on one GPU) -- how a one-GPU box tests the split.
+ * PLAINTEXT CAPACITY under a group: a decrypt-shaped call that is cut needs the total size of the well-formed records, not of their
+ * sealed parts (every block is handed the slice its records span); see the calls' own comments.
+ * NOT sharded, on devices[0]: rabe_ghw11_tkgen_packed (what it draws depends on which records decode on the host; the call is
+ * host-bound), the bulk keygen_packed calls of ac17 / bsw / aw11 / bdabe / mke08, the request_*_sk_packed pair, rabe_bsw_delegate_packed,
+ * rabe_lsw_encrypt_packed, rabe_{bdabe,mke08}_decrypt_packed, the object API and the submission queue.
  * Status: as rabe_host_create_checked. */
 int32_t rabe_host_open_group_checked(int32_t abi_version, size_t n_devices, const int32_t* devices, rabe_host** out);
 #define rabe_host_open_group(n_devices, devices, out) rabe_host_open_group_checked(RABE_HOST_ABI_VERSION, (n_devices), (devices), (out))
 int32_t rabe_host_group_size(rabe_host* h);          /* engines of the host: 1 for rabe_host_open */
+/* out[k] = the number of items whose block has run to its end on engine k since the host was opened, over all sharded calls (cumulative; a
+ * plain host counts the same calls in out[0]; a call that returns 1 for a short buffer counts nothing).  Shows that a node is in use -- and
+ * the tests that a call was cut at all.  Returns the group size, or -1 when cap is smaller than that. */
+int32_t rabe_host_group_items(rabe_host* h, uint64_t* out /*[cap]*/, size_t cap);
 void rabe_host_destroy(rabe_host* h);
 /* ---- submission queue: one call at a time, many callers ------------------------------------------------------------------------
  * The reference's API is one call per ciphertext (src/schemes/ac17/mod.rs:274-279, :385-388; rabe-console/src/mod.rs:1098, 1310) and one
@@ -161,7 +179,8 @@ int32_t rabe_ac17_cp_decrypt_packed(rabe_host* h, const void* sk, size_t n_items
 /* ---- key encapsulation: the packed pair WITHOUT payloads.  A caller that seals large objects where they live (files, streams, rows) wants per
  * item the ciphertext HEADER and the 32-byte content key the reference's kdf derives (src/utils/aes/mod.rs:47-55), and on the other side the same
  * 32 bytes back from the header and a secret key.  Not functions of the reference but compositions of functions that are (as
- * rabe_ghw11_provision_packed is).  Built for ac17 (CP) and bsw; both run on devices[0] of a device group.
+ * rabe_ghw11_provision_packed is).  Built for ac17 (CP) and bsw; all four calls are sharded over a device group (a block's headers at their
+ * offsets, its keys and verdicts at key_buf + 32 lo and status + lo).
  *   key = SHA3-256(bytes(Gt)): bytes(Gt) is the byte form the reference's kdf hashes -- the 12 coefficients in wire order, each as 32 BIG-endian
  *   bytes -- i.e. exactly the AES key rabe_encrypt_symmetric / rabe_decrypt_symmetric derive from that Gt.
  * ENCAPS.  Item i's header at hdr_buf + hdr_off[i] is the Ac17CpCiphertext record rabe_ac17_cp_encrypt_packed writes for the same draws with a
@@ -202,7 +221,9 @@ int32_t rabe_ac17_kp_decrypt_gt(rabe_host* h, const void* sk, const void* ct, ui
 /* The KP pair packed (conventions of rabe_ac17_cp_{encrypt,decrypt}_packed; records = Ac17KpCiphertext): n_items encrypts, item i under the
  * attribute list item_set[i] of the n_sets lists given once (list s = the next counts[s] entries of `attributes`); n_items decrypts
  * with ONE key (whose policy is checked against every ciphertext's attribute list).  Same kernels as the CP pair
- * (src/schemes/ac17/mod.rs:556-675). */
+ * (src/schemes/ac17/mod.rs:556-675).  The decrypt returns 1 when pt_cap is below the total size of the well-formed records -- one engine or
+ * a device group alike; for this call the two sizes coincide.  A group that cuts the batch needs the total size of the well-formed
+ * records, not of their sealed parts: the call returns 1, and pt_off[n_items] holds the size to come back with. */
 int32_t rabe_ac17_kp_encrypt_packed(rabe_host* h, const void* pk, const char* const* attributes, const size_t* counts, size_t n_sets, size_t n_items,
                                     const uint32_t* item_set /*[n_items]*/, const uint8_t* pt_blob, const uint64_t* pt_off /*[n_items+1]*/,
                                     uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off /*[n_items+1]*/);
@@ -350,7 +371,7 @@ int32_t rabe_ghw11_encrypt_packed(rabe_host* h, const void* pk, const char* cons
 /* The outsourced half as a service: n_items Ghw11Ciphertext records in one blob (+ n_items + 1 offsets, ct_len; bounds and --
  * unless RABE_PACKED_TRUSTED -- group membership of every decoded element are checked, an item fails alone with status -1) transformed under
  * ONE transform key.  tct_buf + 768 i receives item i's Ghw11TransformCiphertext record (c | t; zeros where status[i] = -1); returns 1 when
- * tct_cap < 768 n_items.  Device-resident: every G2 argument is the key's, so all m + 2 Miller loops of an item replay the key's prepared
+ * tct_cap < 768 n_items.  Under a device group a block writes its slots and verdicts in place (tct_buf + 768 lo, status + lo).  Device-resident: every G2 argument is the key's, so all m + 2 Miller loops of an item replay the key's prepared
  * lines (kept across calls) and the rows that share l_z collapse into one pairing of a multi-scalar sum (ghw11/mod.rs:227-295). */
 int32_t rabe_ghw11_transform_packed(rabe_host* h, const void* tk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
                                     const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* tct_buf, size_t tct_cap);
@@ -403,7 +424,9 @@ int32_t rabe_ghw11_decrypt_out_gt(rabe_host* h, const void* tct, const void* rk,
  * data.  msg = c * t^(-z), KDF and AES-GCM open run on the device; only plaintexts come back (pt_buf + pt_off).  Unless RABE_PACKED_TRUSTED,
  * c and t must be members of Gt.  An all-zero tct record, a malformed ciphertext record, a non-member or a tag that does not verify (e.g. a
  * wrong rk) fails that item alone: status -1, empty or zeroed plaintext slot, the first error in rabe_host_last_error.  Returns 1 when pt_cap
- * is below the total size of the well-formed ciphertext records; pt_off[n_items] = that size. */
+ * is below the total size of the well-formed ciphertext records; pt_off[n_items] = that size.  Under a device group both inputs are cut at
+ * the same item boundaries (tct_buf + 768 lo, record lo of the blob).  A group that cuts the batch needs the total size of the well-formed
+ * records, not of their sealed parts: the call returns 1, and pt_off[n_items] holds the size to come back with. */
 int32_t rabe_ghw11_decrypt_out_packed(rabe_host* h, const void* rk, size_t n_items, const uint8_t* tct_buf /*768 n_items*/,
                                       const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags,
                                       int32_t* status /*[n_items]*/, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off /*[n_items+1]*/);
@@ -423,7 +446,9 @@ int32_t rabe_ghw11_decrypt_out_packed(rabe_host* h, const void* rk, size_t n_ite
  * that does not verify fail that item alone -- status -1, an EMPTY plaintext slot, the first error in rabe_host_last_error (the texts of
  * rabe_ghw11_transform_packed / rabe_ghw11_decrypt_out_packed).  Unless RABE_PACKED_TRUSTED: rabe_ghw11_transform_packed's membership checks
  * (c1, every C_i and D_i on the G1 curve with canonical coordinates, c in Gt).  No randomness is drawn; a seeded source or tape is left
- * untouched.  Returns 1 when pt_cap is below the total of the well-formed records' sealed lengths; pt_off[n_items] = that size. */
+ * untouched.  Returns 1 when pt_cap is below the total of the well-formed records' sealed lengths; pt_off[n_items] = that size.
+ * A group that cuts the batch needs the total size of the well-formed records, not of their sealed parts: the call returns 1, and
+ * pt_off[n_items] holds the size to come back with. */
 int32_t rabe_ghw11_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
                                   const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/,
                                   uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off /*[n_items+1]*/);

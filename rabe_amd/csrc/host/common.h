@@ -5,6 +5,7 @@
 // container has no Rust toolchain; a Rust host would call the same rhip_* entry points.
 #pragma once
 #include <set>
+#include <atomic>
 #include <array>
 #include <map>
 #include <memory>
@@ -147,6 +148,7 @@ class Engine {
   rhip_ctx* ctx() const { return lanes_[cur_lane()]->ctx; }
   int device() const { return device_; }
   void make_current() const { check(rhip_ctx_make_current(lanes_[0]->ctx), "rhip_ctx_make_current"); }
+  std::atomic<uint64_t> items_run{0};              // items of packed calls whose block ran here (pipeline.cpp; rabe_host_group_items)
   void ensure_lanes(size_t count);                 // call before handing lanes to threads
   size_t lane_count();                             // lanes that exist: a LaneScope beyond them falls back to lane 0 (cur_lane)
   size_t lanes() const { return lanes_.size(); }

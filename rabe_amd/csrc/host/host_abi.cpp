@@ -18,6 +18,7 @@
 #include <thread>
 
 #include "../../../include/rabe_host.h"
+#include "predraw.h"
 #include "schemes.h"
 
 using namespace rabe;
@@ -65,7 +66,8 @@ struct rabe_host {
   OsRng q_rng[Q_LANES * Q_SUB];
   uint64_t q_stats[6] = {0, 0, 0, 0, 0, 0};  // batches, requests, groups, requests run singly, microseconds inside batches, largest batch
   // a device GROUP (rabe_host_open_group): the host's own engine + one more per further entry of the device list.  The packed entry
-  // points of ac17 / bsw / lsw / aw11 split their items into one contiguous block per engine (pipeline.cpp); everything else runs on `eng`.
+  // points that go through pipeline::{produce,consume,for_blocks} split their items into one contiguous block per engine (pipeline.cpp;
+  // include/rabe_host.h lists them); everything else runs on `eng`.
   std::vector<std::unique_ptr<Engine>> peers;
   explicit rabe_host(int device) : eng(device) {}
   std::vector<Engine*> engines() {
@@ -73,6 +75,9 @@ struct rabe_host {
     for (auto& p : peers) v.push_back(p.get());
     return v;
   }
+  // the engines a call is cut over: all of them, or -- when an array the blocks would be offset into is missing -- the host's own, whose
+  // uncut call then refuses the null argument as it always has
+  std::vector<Engine*> engines_if(bool arrays_given) { return arrays_given ? engines() : std::vector<Engine*>{&eng}; }
   Rng& rng() { return tape ? (Rng&)*tape : (Rng&)os; }
 };
 static thread_local std::string g_err;
@@ -792,6 +797,13 @@ int32_t rabe_host_open_group_checked(int32_t abi_version, size_t n_devices, cons
   GUARD_END((rabe_host*)nullptr)
 }
 int32_t rabe_host_group_size(rabe_host* h) { return h ? (int32_t)(1 + h->peers.size()) : -1; }
+int32_t rabe_host_group_items(rabe_host* h, uint64_t* out, size_t cap) {
+  if (!h || (!out && cap)) return -1;
+  const auto engines = h->engines();
+  if (cap < engines.size()) return -1;
+  for (size_t k = 0; k < engines.size(); k++) out[k] = engines[k]->items_run.load(std::memory_order_relaxed);
+  return (int32_t)engines.size();
+}
 void rabe_host_destroy(rabe_host* h) { delete h; }
 const char* rabe_host_last_error(rabe_host* h) { return h ? h->err.c_str() : g_err.c_str(); }
 int32_t rabe_host_set_fixed_base_min(rabe_host* h, size_t n) {
@@ -1125,6 +1137,13 @@ int32_t rabe_ac17_cp_encrypt_batch(rabe_host* h, const void* pk, size_t n, const
   return give_objects(h, ts, RABE_AC17_CP_CT, cts);
   GUARD_END(h)
 }
+// What a batch cut over a device group asks of the plaintext buffer (pipeline.cpp: consume): the total size of the well-formed records.  The
+// decrypt-shaped entry points leave it in pt_off[n_items] before they start; the uncut call states its own, never larger, size when it refuses.
+static uint64_t record_span(size_t n, const uint64_t* off, size_t len) {
+  uint64_t span = 0;
+  for (size_t i = 0; i < n; i++) if (off[i] <= off[i + 1] && off[i + 1] <= len) span += off[i + 1] - off[i];
+  return span;
+}
 int32_t rabe_ac17_cp_encrypt_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
                                     const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* ct_buf, size_t ct_cap,
                                     uint64_t* ct_off) {
@@ -1163,21 +1182,33 @@ int32_t rabe_ac17_cp_decrypt_packed(rabe_host* h, const void* sk, size_t n_items
   return 0;
   GUARD_END(h)
 }
-// key encapsulation: the packed pair without payloads, on the host's own engine (include/rabe_host.h)
+// key encapsulation: the packed pair without payloads (include/rabe_host.h).  Over a device group: the headers through `produce`, a block's
+// 32-byte key slots straight to key_buf + 32 lo (the sizing pass returns before a key is written); decaps through `for_blocks`.
+static const size_t KEM_KEY = 32;
 int32_t rabe_ac17_cp_encaps_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
                                    const uint32_t* item_policy, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {
   GUARD_BEGIN
   if (!item_policy || !hdr_off) throw RabeError("cp_encaps_packed: null input");
-  return ac17::cp_encaps_packed(h->eng, h->rng(), *(const ac17::Ac17PublicKey*)pk, strs(policies, n_policies), lang_of(language), n_items, item_policy,
-                                hdr_buf, hdr_cap, hdr_off, key_buf) ? 0 : 1;
+  const auto& key = *(const ac17::Ac17PublicKey*)pk;
+  const auto pols = strs(policies, n_policies);
+  const auto lang = lang_of(language);
+  return pipeline::produce(h->engines_if(key_buf != nullptr), h->rng(), n_items, pipeline::GROUP_ONLY,
+                           [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
+    return ac17::cp_encaps_packed(eng, r, key, pols, lang, hi - lo, item_policy + lo, out, cap, off, key_buf ? key_buf + KEM_KEY * lo : nullptr);
+  }, hdr_buf, hdr_cap, hdr_off) ? 0 : 1;
   GUARD_END(h)
 }
 int32_t rabe_ac17_cp_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
                                    uint32_t flags, int32_t* status, uint8_t* key_buf) {
   GUARD_BEGIN
   std::vector<std::string> errors;
-  ac17::cp_decaps_packed(h->eng, *(const ac17::Ac17CpSecretKey*)sk, n_items, ct_blob, ct_len, ct_off, (flags & RABE_PACKED_TRUSTED) != 0, status, key_buf,
-                         &errors);
+  const auto& key = *(const ac17::Ac17CpSecretKey*)sk;
+  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
+  pipeline::for_blocks(h->engines_if(ct_off && status && key_buf), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
+    ac17::cp_decaps_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
+                           key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
+    return true;
+  }, &errors);
   for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
   return 0;
   GUARD_END(h)
@@ -1186,15 +1217,26 @@ int32_t rabe_bsw_encaps_packed(rabe_host* h, const void* pk, const char* const* 
                                const uint32_t* item_policy, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {
   GUARD_BEGIN
   if (!item_policy || !hdr_off) throw RabeError("bsw::encaps_packed: null input");
-  return bsw::encaps_packed(h->eng, h->rng(), *(const bsw::CpAbePublicKey*)pk, strs(policies, n_policies), lang_of(language), n_items, item_policy, hdr_buf,
-                            hdr_cap, hdr_off, key_buf) ? 0 : 1;
+  const auto& key = *(const bsw::CpAbePublicKey*)pk;
+  const auto pols = strs(policies, n_policies);
+  const auto lang = lang_of(language);
+  return pipeline::produce(h->engines_if(key_buf != nullptr), h->rng(), n_items, pipeline::GROUP_ONLY,
+                           [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
+    return bsw::encaps_packed(eng, r, key, pols, lang, hi - lo, item_policy + lo, out, cap, off, key_buf ? key_buf + KEM_KEY * lo : nullptr);
+  }, hdr_buf, hdr_cap, hdr_off) ? 0 : 1;
   GUARD_END(h)
 }
 int32_t rabe_bsw_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
                                int32_t* status, uint8_t* key_buf) {
   GUARD_BEGIN
   std::vector<std::string> errors;
-  bsw::decaps_packed(h->eng, *(const bsw::CpAbeSecretKey*)sk, n_items, ct_blob, ct_len, ct_off, (flags & RABE_PACKED_TRUSTED) != 0, status, key_buf, &errors);
+  const auto& key = *(const bsw::CpAbeSecretKey*)sk;
+  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
+  pipeline::for_blocks(h->engines_if(ct_off && status && key_buf), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
+    bsw::decaps_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
+                       key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
+    return true;
+  }, &errors);
   for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
   return 0;
   GUARD_END(h)
@@ -1207,15 +1249,23 @@ int32_t rabe_ac17_kp_encrypt_packed(rabe_host* h, const void* pk, const char* co
   size_t at = 0;
   for (size_t s = 0; s < n_sets; s++)
     for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
-  return ac17::kp_encrypt_packed(h->eng, h->rng(), *(const ac17::Ac17PublicKey*)pk, sets, n_items, item_set, pt_blob, pt_off, ct_buf, ct_cap, ct_off) ? 0 : 1;
+  const auto& key = *(const ac17::Ac17PublicKey*)pk;
+  return pipeline::produce(h->engines(), h->rng(), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
+    return ac17::kp_encrypt_packed(eng, r, key, sets, hi - lo, item_set + lo, pt_blob, pt_off + lo, out, cap, off);
+  }, ct_buf, ct_cap, ct_off) ? 0 : 1;
   GUARD_END(h)
 }
 int32_t rabe_ac17_kp_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
                                     uint32_t flags, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
   GUARD_BEGIN
   std::vector<std::string> errors;
-  if (!ac17::kp_decrypt_packed(h->eng, *(const ac17::Ac17KpSecretKey*)sk, n_items, ct_blob, ct_len, ct_off, (flags & RABE_PACKED_TRUSTED) != 0, status,
-                               pt_buf, pt_cap, pt_off, &errors))
+  const auto& key = *(const ac17::Ac17KpSecretKey*)sk;
+  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
+  if (ct_off && pt_off) pt_off[n_items] = record_span(n_items, ct_off, ct_len);
+  if (!pipeline::consume(h->engines_if(pt_off && status), n_items, pipeline::GROUP_ONLY, ct_off, ct_len,
+                         [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off, std::vector<std::string>* errs) {
+        return ac17::kp_decrypt_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
+      }, status, pt_buf, pt_cap, pt_off, &errors))
     return 1;
   for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
   return 0;
@@ -1315,10 +1365,7 @@ int32_t rabe_lsw_decrypt_one_sk_packed(rabe_host* h, const void* sk, size_t n_it
   const auto& key = *(const lsw::KpAbeSecretKey*)sk;
   const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
   if (!ct_off || !pt_off) throw RabeError("lsw::decrypt_one_sk_packed: null input");
-  // what a batch cut over a device group asks of the plaintext buffer (pipeline.cpp: consume); the one-engine call states its own, smaller, size
-  uint64_t span = 0;
-  for (size_t i = 0; i < n_items; i++) if (ct_off[i] <= ct_off[i + 1] && ct_off[i + 1] <= ct_len) span += ct_off[i + 1] - ct_off[i];
-  pt_off[n_items] = span;
+  pt_off[n_items] = record_span(n_items, ct_off, ct_len);
   if (!pipeline::consume(h->engines(), n_items, CHUNK_LSW, ct_off, ct_len, [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off,
                                                                           std::vector<std::string>* errs) {
         return lsw::decrypt_one_sk_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
@@ -1927,8 +1974,16 @@ int32_t rabe_ghw11_transform_packed(rabe_host* h, const void* tk, size_t n_items
                                     int32_t* status, uint8_t* tct_buf, size_t tct_cap) {
   GUARD_BEGIN
   std::vector<std::string> errors;
-  if (!ghw11::transform_packed(h->eng, *(const ghw11::Ghw11TransformKey*)tk, n_items, ct_blob, ct_len, ct_off, (flags & RABE_PACKED_TRUSTED) != 0, status,
-                               tct_buf, tct_cap, &errors))
+  const auto& key = *(const ghw11::Ghw11TransformKey*)tk;
+  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
+  const size_t TCT = 768;
+  // fixed slots: block [lo, hi) writes its records at tct_buf + 768 lo and its verdicts at status + lo, where the uncut call puts them
+  const bool room = tct_buf && tct_cap >= n_items * TCT;
+  if (!pipeline::for_blocks(h->engines_if(ct_off && status && room), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
+    const bool whole = hi - lo == n_items;          // the uncut call judges the caller's own capacity
+    return ghw11::transform_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
+                                   tct_buf ? tct_buf + TCT * lo : nullptr, whole ? tct_cap : TCT * (hi - lo), errs);
+  }, &errors))
     return 1;
   for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
   return 0;
@@ -1950,8 +2005,14 @@ int32_t rabe_ghw11_decrypt_out_packed(rabe_host* h, const void* rk, size_t n_ite
                                       const uint64_t* ct_off, uint32_t flags, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
   GUARD_BEGIN
   std::vector<std::string> errors;
-  if (!ghw11::decrypt_out_packed(h->eng, *(const ghw11::Ghw11RetrieveKey*)rk, n_items, tct_buf, ct_blob, ct_len, ct_off, (flags & RABE_PACKED_TRUSTED) != 0,
-                                 status, pt_buf, pt_cap, pt_off, &errors))
+  const auto& key = *(const ghw11::Ghw11RetrieveKey*)rk;
+  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
+  if (ct_off && pt_off) pt_off[n_items] = record_span(n_items, ct_off, ct_len);
+  // two inputs cut at the same item boundaries: the 768-byte tct slots and the records of the blob
+  if (!pipeline::consume(h->engines_if(pt_off && status && tct_buf), n_items, pipeline::GROUP_ONLY, ct_off, ct_len,
+                         [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off, std::vector<std::string>* errs) {
+        return ghw11::decrypt_out_packed(eng, key, hi - lo, tct_buf ? tct_buf + 768 * lo : nullptr, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
+      }, status, pt_buf, pt_cap, pt_off, &errors))
     return 1;
   for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
   return 0;
@@ -1961,8 +2022,13 @@ int32_t rabe_ghw11_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, 
                                   int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
   GUARD_BEGIN
   std::vector<std::string> errors;
-  if (!ghw11::decrypt_packed(h->eng, *(const ghw11::Ghw11SecretKey*)sk, n_items, ct_blob, ct_len, ct_off, (flags & RABE_PACKED_TRUSTED) != 0, status, pt_buf,
-                             pt_cap, pt_off, &errors))
+  const auto& key = *(const ghw11::Ghw11SecretKey*)sk;
+  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
+  if (ct_off && pt_off) pt_off[n_items] = record_span(n_items, ct_off, ct_len);
+  if (!pipeline::consume(h->engines_if(pt_off && status), n_items, pipeline::GROUP_ONLY, ct_off, ct_len,
+                         [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off, std::vector<std::string>* errs) {
+        return ghw11::decrypt_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
+      }, status, pt_buf, pt_cap, pt_off, &errors))
     return 1;
   for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
   return 0;
@@ -1987,8 +2053,12 @@ int32_t rabe_ghw11_keygen_packed(rabe_host* h, const void* pk, const void* msk, 
   size_t at = 0;
   for (size_t s = 0; s < n_sets; s++)
     for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
-  return ghw11::keygen_packed(h->eng, h->rng(), *(const ghw11::Ghw11PublicKey*)pk, *(const ghw11::Ghw11MasterKey*)msk, sets, n_items, item_set, sk_buf,
-                              sk_cap, sk_off) ? 0 : 1;
+  const auto& key = *(const ghw11::Ghw11PublicKey*)pk;
+  const auto& master = *(const ghw11::Ghw11MasterKey*)msk;
+  return pipeline::produce(h->engines_if(sk_off && item_set), h->rng(), n_items, pipeline::GROUP_ONLY,
+                           [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
+    return ghw11::keygen_packed(eng, r, key, master, sets, hi - lo, item_set ? item_set + lo : nullptr, out, cap, off);
+  }, sk_buf, sk_cap, sk_off) ? 0 : 1;
   GUARD_END(h)
 }
 int32_t rabe_ghw11_tkgen_packed(rabe_host* h, size_t n_items, const uint8_t* sk_blob, size_t sk_len, const uint64_t* sk_off, uint32_t flags, int32_t* status,
@@ -2006,8 +2076,38 @@ int32_t rabe_ghw11_provision_packed(rabe_host* h, const void* pk, const void* ms
                                     size_t n_items, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off, uint8_t* tk_buf, size_t tk_cap,
                                     uint64_t* tk_off, uint8_t* rk_buf) {
   GUARD_BEGIN
-  return ghw11::provision_packed(h->eng, h->rng(), *(const ghw11::Ghw11PublicKey*)pk, *(const ghw11::Ghw11MasterKey*)msk,
-                                 attr_sets(attributes, counts, n_sets), n_items, item_set, sk_buf, sk_cap, sk_off, tk_buf, tk_cap, tk_off, rk_buf) ? 0 : 1;
+  const auto& key = *(const ghw11::Ghw11PublicKey*)pk;
+  const auto& master = *(const ghw11::Ghw11MasterKey*)msk;
+  const auto sets = attr_sets(attributes, counts, n_sets);
+  const auto engines = h->engines_if(tk_off && item_set && rk_buf);
+  if (engines.size() == 1 || n_items < 2)
+    return pipeline::for_blocks({&h->eng}, n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t, size_t, std::vector<std::string>*) {
+      return ghw11::provision_packed(eng, h->rng(), key, master, sets, n_items, item_set, sk_buf, sk_cap, sk_off, tk_buf, tk_cap, tk_off, rk_buf);
+    }, nullptr) ? 0 : 1;
+  // A device group.  The call's own sizing pass first (no transform-key buffer: it validates the lists, fills both offset arrays and
+  // returns before a draw); then the two runs of draws -- r_0 .. r_{n-1}, z_0 .. z_{n-1} -- on this thread, in the uncut call's order
+  // (predraw.h), z = 0 refused here, before any block has written a record; then block [lo, hi) runs the uncut call's code on its engine
+  // with a tape of its own slices, its records at the offsets the sizing pass announced.
+  (void)ghw11::provision_packed(h->eng, h->rng(), key, master, sets, n_items, item_set, nullptr, 0, sk_off, nullptr, 0, tk_off, rk_buf);
+  if (!tk_buf || tk_cap < tk_off[n_items] || (sk_off && (!sk_buf || sk_cap < sk_off[n_items]))) return 1;
+  Rng& rng = h->rng();
+  pipeline::RunDraws<Fr> draws(2, n_items, [&] { return rng.next_fr(); });
+  for (size_t i = 0; i < n_items; i++) {
+    const Fr& z = draws.at(1, i);
+    if (!(z.l[0] | z.l[1] | z.l[2] | z.l[3])) throw std::runtime_error("called `Option::unwrap()` on a `None` value (Fr::inverse of zero)");
+  }
+  pipeline::for_blocks(engines, n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>*) {
+    TapeRng slice(draws.block(lo, hi));
+    struct Scrub { TapeRng& t; ~Scrub() { pipeline::RunDraws<Fr>::scrub(t.tape); } } scrub{slice};
+    std::vector<uint64_t> sk_rel(sk_off ? hi - lo + 1 : 0), tk_rel(hi - lo + 1);
+    const bool done = ghw11::provision_packed(eng, slice, key, master, sets, hi - lo, item_set + lo, sk_off ? sk_buf + sk_off[lo] : nullptr,
+                                              sk_off ? (size_t)(sk_off[hi] - sk_off[lo]) : 0, sk_off ? sk_rel.data() : nullptr, tk_buf + tk_off[lo],
+                                              (size_t)(tk_off[hi] - tk_off[lo]), tk_rel.data(), rk_buf + 32 * lo);
+    if (!done || tk_rel[hi - lo] != tk_off[hi] - tk_off[lo] || (sk_off && sk_rel[hi - lo] != sk_off[hi] - sk_off[lo]))
+      throw RabeError("ghw11::provision_packed: a block's records do not have the announced size");
+    return true;
+  }, nullptr);
+  return 0;
   GUARD_END(h)
 }
 int32_t rabe_ghw11_decrypt_out(rabe_host* h, const void* tct, const void* rk, const void* ct, uint8_t** plaintext, size_t* len) {

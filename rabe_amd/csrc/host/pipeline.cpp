@@ -13,6 +13,9 @@
 //  * ordered randomness (a seeded source, the tests' tapes) is drawn chunk after chunk: the entry points bracket their draws with
 //    Rng::begin_draws / end_draws, and a chunk's source waits at begin_draws until every earlier chunk has passed end_draws;
 //  * per-item status / error texts are the chunk's, concatenated; a call-level exception of any chunk is rethrown after all have ended.
+//
+// Three forms: `produce` (records out, randomness in), `consume` (records in, plaintexts closed up behind each other) and `for_blocks`
+// (records in or out at FIXED strides, or at offsets the caller sized itself: a block writes straight to its final place, nothing to close up).
 #include <atomic>
 #include <condition_variable>
 #include <cstdlib>
@@ -85,12 +88,13 @@ static Cut even_cut(size_t n, size_t chunks, size_t lanes) { return {chunks, lan
 // verdict downloads): 20 480 items 339 k -> 311 k, 65 536 458 k -> 433 k, 131 072 406 k -> 402 k; finer chunks are worse still (20 480 as
 // 5 x 4096 on three lanes: 224 k) -- every stage of a chunk has a fixed cost, the host stages already use all cores, small launches
 // under-fill the GPU.  So host_abi.cpp passes min_chunk = "never"; RABE_PACKED_CHUNK / RABE_PACKED_LANES switch it on (the tests do).
-// A device group is cut into one block per engine, whatever the environment says.
+// A device group is cut into one block per engine, whatever the environment says; min_chunk = GROUP_ONLY is cut by nothing else.
 Cut cut(size_t n_engines, size_t n, size_t min_chunk) {
   if (n_engines > 1) {
     const size_t chunks = n < n_engines ? (n ? n : 1) : n_engines;
     return even_cut(n, chunks, chunks);
   }
+  if (min_chunk == GROUP_ONLY) return {1, 1, n, 0, n};
   size_t lanes = env_size("RABE_PACKED_LANES", 2);
   if (lanes > 8) lanes = 8;
   const bool forced = getenv("RABE_PACKED_CHUNK") != nullptr;
@@ -154,11 +158,18 @@ void fan_out(const std::vector<Engine*>& engines, const Cut& c, const std::funct
   if (first) std::rethrow_exception(first);
 }
 
+// rabe_host_group_items: the items whose block has run to its end on this engine
+void ran(Engine& eng, size_t items) { eng.items_run.fetch_add(items, std::memory_order_relaxed); }
+
 }  // namespace
 
 bool produce(const std::vector<Engine*>& engines, Rng& rng, size_t n, size_t min_chunk, const ProduceFn& call, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
   const Cut c = cut(engines.size(), n, min_chunk);
-  if (c.chunks == 1) return call(*engines[0], 0, n, rng, out_buf, out_cap, out_off);
+  if (c.chunks == 1) {
+    const bool done = call(*engines[0], 0, n, rng, out_buf, out_cap, out_off);
+    if (done) ran(*engines[0], n);
+    return done;
+  }
   // the entry point's own sizing pass (no buffer: it fills the offsets and returns before drawing anything)
   (void)call(*engines[0], 0, n, rng, nullptr, 0, out_off);
   if (!out_buf || out_cap < out_off[n]) return false;
@@ -170,6 +181,7 @@ bool produce(const std::vector<Engine*>& engines, Rng& rng, size_t n, size_t min
     std::vector<uint64_t> off(hi - lo + 1);
     if (!call(eng, lo, hi, r, out_buf + out_off[lo], (size_t)(out_off[hi] - out_off[lo]), off.data())) ok = false;
     else if (off[hi - lo] != out_off[hi] - out_off[lo]) throw RabeError("pipelined batch: a chunk's records do not have the announced size");
+    else ran(eng, hi - lo);
   }, [&](size_t k) { gate.enter(k); gate.leave(k); });          // a block that never started takes its turn at the draw gate and passes it on
   return ok;
 }
@@ -177,7 +189,11 @@ bool produce(const std::vector<Engine*>& engines, Rng& rng, size_t n, size_t min
 bool consume(const std::vector<Engine*>& engines, size_t n, size_t min_chunk, const uint64_t* in_off, size_t in_len, const ConsumeFn& call, int32_t* status,
              uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
   const Cut c = cut(engines.size(), n, min_chunk);
-  if (c.chunks == 1 || !in_off) return call(*engines[0], 0, n, status, pt_buf, pt_cap, pt_off, errors);
+  if (c.chunks == 1 || !in_off) {
+    const bool done = call(*engines[0], 0, n, status, pt_buf, pt_cap, pt_off, errors);
+    if (done) ran(*engines[0], n);
+    return done;
+  }
   // what the entry points require of the plaintext buffer: the total size of the well-formed records (packed.cpp: check_offsets)
   std::vector<uint64_t> span(c.chunks + 1, 0);
   for (size_t k = 0; k < c.chunks; k++) {
@@ -194,6 +210,7 @@ bool consume(const std::vector<Engine*>& engines, size_t n, size_t min_chunk, co
     const size_t lo = c.lo(k), hi = c.hi(k);
     off[k].assign(hi - lo + 1, 0);
     if (!call(eng, lo, hi, status + lo, pt_buf + span[k], (size_t)(span[k + 1] - span[k]), off[k].data(), &errs[k])) ok = false;
+    else ran(eng, hi - lo);
   });
   if (!ok) return false;
   // close the slices up: plaintexts contiguous in item order, as the unchunked call leaves them
@@ -211,6 +228,28 @@ bool consume(const std::vector<Engine*>& engines, size_t n, size_t min_chunk, co
     cur += len;
   }
   return true;
+}
+
+bool for_blocks(const std::vector<Engine*>& engines, size_t n, size_t min_chunk, const BlockFn& call, std::vector<std::string>* errors) {
+  const Cut c = cut(engines.size(), n, min_chunk);
+  if (c.chunks == 1) {
+    const bool done = call(*engines[0], 0, n, errors);
+    if (done) ran(*engines[0], n);
+    return done;
+  }
+  std::vector<std::vector<std::string>> errs(c.chunks);
+  std::atomic<bool> ok{true};
+  fan_out(engines, c, [&](size_t k, Engine& eng) {
+    const size_t lo = c.lo(k), hi = c.hi(k);
+    if (!call(eng, lo, hi, &errs[k])) ok = false;
+    else ran(eng, hi - lo);
+  });
+  if (errors) {
+    errors->assign(n, "");
+    for (size_t k = 0; k < c.chunks; k++)
+      for (size_t i = 0; i < errs[k].size() && c.lo(k) + i < c.hi(k); i++) (*errors)[c.lo(k) + i] = std::move(errs[k][i]);
+  }
+  return ok;
 }
 
 }  // namespace pipeline

@@ -336,4 +336,12 @@ typedef std::function<bool(Engine& eng, size_t lo, size_t hi, int32_t* status, u
 bool produce(const std::vector<Engine*>& engines, Rng& rng, size_t n, size_t min_chunk, const ProduceFn& call, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
 bool consume(const std::vector<Engine*>& engines, size_t n, size_t min_chunk, const uint64_t* in_off, size_t in_len, const ConsumeFn& call, int32_t* status, uint8_t* pt_buf,
              size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors);
+// min_chunk of a call that is cut over a device group and by nothing else: one engine runs it whole, whatever RABE_PACKED_CHUNK says
+static const size_t GROUP_ONLY = ~(size_t)0;
+// The form for outputs at FIXED strides (768-byte transform records, 32-byte key slots) or at offsets the caller has sized: block [lo, hi)
+// writes straight to its final place -- nothing is closed up afterwards.  `errors` (may be null) receives the blocks' per-item texts in
+// item order.  A block returns false when it refuses its buffers (the call then returns false; the caller sizes before it cuts, so only the
+// uncut call does).  No shared randomness source: a block that draws is handed a source of its own (rabe_ghw11_provision_packed, predraw.h).
+typedef std::function<bool(Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errors)> BlockFn;
+bool for_blocks(const std::vector<Engine*>& engines, size_t n, size_t min_chunk, const BlockFn& call, std::vector<std::string>* errors);
 }}  // namespace rabe::pipeline

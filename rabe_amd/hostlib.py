@@ -90,8 +90,8 @@ class Host:
     """One GPU context + randomness source.  `Host()` fails loudly without a HIP device."""
 
     def __init__(self, device=0, devices=None):
-        """devices: a list of HIP device indices opens a device GROUP (include/rabe_host.h: rabe_host_open_group) -- the packed entry
-        points of ac17 / bsw / lsw / aw11 then shard their items over the listed devices (a device may be listed more than once)"""
+        """devices: a list of HIP device indices opens a device GROUP (include/rabe_host.h: rabe_host_open_group) -- the sharded packed
+        entry points (the header lists them) then cut their items over the listed devices (a device may be listed more than once)"""
         self.lib = _lib()
         h = ctypes.c_void_p()
         if devices is not None:
@@ -105,6 +105,14 @@ class Host:
 
     def group_size(self):
         return int(self.lib.rabe_host_group_size(self.h))
+
+    def group_items(self):
+        """[items whose block has run on engine k since the host was opened, k = 0 .. group_size() - 1] (rabe_host_group_items): cumulative
+        over all packed calls that are cut over a device group; a plain host counts them in its one entry"""
+        out = (ctypes.c_uint64 * self.group_size())()
+        if self.lib.rabe_host_group_items(self.h, out, ctypes.c_size_t(len(out))) != len(out):
+            raise EngineError("rabe_host_group_items failed")
+        return [int(v) for v in out]
 
     def close(self):
         if self.h:
