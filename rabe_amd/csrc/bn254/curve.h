@@ -103,9 +103,15 @@ RB_MID Jac<F> jac_add_aff(const Jac<F>& p, const Aff<F>& q) {
   return r;
 }
 
-// G1 form of madd-2007-bl for the fixed-base table kernels: the 11 field products are expanded in place (no call,
-// so nothing has to sit in callee-saved registers around them) and issued as 1 + 5 interleaved pairs of
-// independent products.  Same formulas and special cases as jac_add_aff, hence the same values.
+// G1 mixed addition for the fixed-base table kernels, in the Z3 = Z1*H form (madd-2004-hmv):
+//   Z1Z1 = Z1^2, U2 = X2 Z1Z1, S2 = Y2 Z1 Z1Z1, H = U2 - X1, r = S2 - Y1, HH = H^2, HHH = H HH, V = X1 HH,
+//   X3 = r^2 - HHH - 2V, Y3 = r (V - X3) - Y1 HHH, Z3 = Z1 H.
+// madd-2007-bl (jac_add_aff) trades three products for squarings at the price of seven more additive steps (its doublings,
+// (Z1+H)^2 - Z1Z1 - HH, I = 4 HH); on 8 x 32-bit limbs a squaring IS a product (mul_inl(z, z)), so here that trade only costs: both
+// forms take 11 products, this one 7 additive steps instead of 14.  The point is the same, its representative is not: Z3 is half of
+// jac_add_aff's (X3 a quarter, Y3 an eighth).  Every consumer converts to affine through 1/Z, so every stored byte is unchanged.
+// The 11 field products are expanded in place (no call, so nothing has to sit in callee-saved registers around them) and issued
+// as 1 + 5 interleaved pairs of independent products.  Same special cases as jac_add_aff, in the same places.
 // The doubling case of the mixed addition (never taken with honest inputs) as a function that passes and returns FIELD elements
 // in registers, one coordinate per call: a call that takes the accumulator by reference, or returns a point through a memory
 // slot, pins the caller's accumulator to the stack -- a store and a reload of the whole point in every loop iteration of the
@@ -128,19 +134,15 @@ RB_HD Jac<Fp> g1_madd_inl(const Jac<Fp>& p, const Aff<Fp>& q) {
     if (is_zero(rr)) return Jac<Fp>{g1_dbl_coord(p.x, p.y, p.z, 0), g1_dbl_coord(p.x, p.y, p.z, 1), g1_dbl_coord(p.x, p.y, p.z, 2)};
     return jac_inf<Fp>();
   }
-  rr = dbl(rr);
-  Fp I = dbl(dbl(HH));
-  Fp J, V;
-  mul2_inl(J, V, H, I, p.x, I);
-  Fp zh = add(p.z, H);
-  Fp R2, ZH2;
-  mul2_inl(R2, ZH2, rr, rr, zh, zh);
   Jac<Fp> r;
-  r.x = sub(sub(R2, J), dbl(V));
-  r.z = sub(sub(ZH2, Z1Z1), HH);
+  Fp HHH, V;
+  mul2_inl(HHH, V, H, HH, p.x, HH);
+  Fp R2;
+  mul2_inl(R2, r.z, rr, rr, p.z, H);
+  r.x = sub(sub(R2, HHH), dbl(V));
   Fp A, B;
-  mul2_inl(A, B, rr, sub(V, r.x), p.y, J);
-  r.y = sub(A, dbl(B));
+  mul2_inl(A, B, rr, sub(V, r.x), p.y, HHH);
+  r.y = sub(A, B);
   return r;
 }
 
