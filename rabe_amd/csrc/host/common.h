@@ -7,6 +7,7 @@
 #include <set>
 #include <atomic>
 #include <array>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -114,6 +115,23 @@ struct TapeRng : Rng {
     }
   }
 };
+
+void parallel_for(size_t n, const std::function<void(size_t)>& fn);          // schemes.cpp
+// Randomness of a batch in the reference's per-call draw order, item after item: draw(source, i).  OS randomness has no order, so from
+// `parallel_from` items on, blocks of `per_block` items draw on their own sources in parallel -- small blocks where an item draws hundreds
+// of values, so that every core draws.
+template <class DRAW>
+void draw_items(Rng& rng, size_t n, size_t parallel_from, size_t per_block, DRAW draw) {
+  struct Turn { Rng& r; explicit Turn(Rng& x) : r(x) { r.begin_draws(); } ~Turn() { r.end_draws(); } } turn(rng);
+  if (rng.unordered() && n >= parallel_from) {
+    parallel_for((n + per_block - 1) / per_block, [&](size_t b) {
+      BatchRng local;
+      for (size_t i = b * per_block; i < n && i < (b + 1) * per_block; i++) draw(local, i);
+    });
+  } else {
+    for (size_t i = 0; i < n; i++) draw(rng, i);
+  }
+}
 
 // ---------------------------------------------------------------------------------------------- engine wrapper
 class Engine;

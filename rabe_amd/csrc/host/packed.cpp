@@ -10,7 +10,8 @@
 // byte form rabe_obj_serialize gives the corresponding struct (host_abi.cpp), so packed and object APIs interoperate.
 // The six "many records under one key" decrypts (bsw, lsw x 2, aw11, ghw11 transform and decrypt) are top-to-bottom functions -- parse body,
 // plan body, buffers, launch, messages -- over the helpers of the anonymous namespace below: PlanCache, for_each_record, Selection,
-// WalkScope, gather_record.
+// WalkScope, gather_record.  The issuers size their output with record_offsets (records.h), and the four that walk share trees (bsw / ghw11 /
+// aw11 encrypt, lsw keygen) keep them in a ShareTrees.
 #include "schemes.h"
 #include "records.h"
 
@@ -119,16 +120,39 @@ DBuf up_bytes(Engine& eng, const std::vector<uint8_t>& v) {
   return v.empty() ? DBuf(&eng, zero, 32) : DBuf(&eng, v.data(), v.size());
 }
 
-// the concatenated tables of a call's distinct policies, on the device
-struct DevTrees {
-  std::vector<uint32_t> first_leaf, first_gate;
-  DBuf path_off, path_gate, path_x, gate_k, gate_coef_off, leaf_hash;
-  DevTrees(Engine& eng, const std::vector<std::shared_ptr<const FlatPolicy>>& pols) {
+// The share trees of one issuing call (bsw / ghw11 / aw11 encrypt, lsw keygen).  add() flattens the call's distinct policies, in their order;
+// place() says where item i's leaves and coefficient draws start -- an AW11 item draws two coefficients per gate draw (the s-shares, then the
+// 0-shares) -- and which tree it walks; upload(), after the draws, puts those arrays and the concatenated tables of the trees on the
+// device, where d_* point to them: the tree arguments of rhip_*_batch, in that order.
+struct ShareTrees {
+  std::vector<std::shared_ptr<const FlatPolicy>> pols;
+  std::vector<uint32_t> leaf_off, coef_off, tree_leaf, tree_gate;          // per item
+  size_t total = 0, total_coef = 0;
+  const uint32_t *d_leaf_off = nullptr, *d_tree_leaf = nullptr, *d_tree_gate = nullptr, *d_path_off = nullptr, *d_path_gate = nullptr, *d_path_x = nullptr,
+                 *d_gate_k = nullptr, *d_gate_coef_off = nullptr, *d_coef_off = nullptr;
+  const rhip_fr* d_leaf_hash = nullptr;
+  const FlatPolicy& add(const std::string& policy, PolicyLanguage language) { pols.push_back(flat_policy(policy, language)); return *pols.back(); }
+  void place(size_t n, const uint32_t* item_policy, uint32_t coefs_per_gate_draw) {
+    std::vector<uint32_t> first_leaf(pols.size() + 1, 0), first_gate(pols.size() + 1, 0);
+    for (size_t p = 0; p < pols.size(); p++) {
+      first_leaf[p + 1] = first_leaf[p] + (uint32_t)pols[p]->leaf_name.size();
+      first_gate[p + 1] = first_gate[p] + (uint32_t)pols[p]->gate_k.size();
+    }
+    leaf_off.assign(n + 1, 0); coef_off.assign(n + 1, 0); tree_leaf.resize(n); tree_gate.resize(n);
+    for (size_t i = 0; i < n; i++) {
+      const uint32_t p = item_policy[i];
+      leaf_off[i + 1] = leaf_off[i] + (first_leaf[p + 1] - first_leaf[p]);
+      coef_off[i + 1] = coef_off[i] + coefs_per_gate_draw * pols[p]->n_coef;
+      tree_leaf[i] = first_leaf[p];
+      tree_gate[i] = first_gate[p];
+    }
+    total = leaf_off[n];
+    total_coef = coef_off[n];
+  }
+  void upload(Engine& eng) {
     std::vector<uint32_t> po{0}, pg, px, gk, gc;
     std::vector<Fr> lh;
     for (const auto& f : pols) {
-      first_leaf.push_back((uint32_t)lh.size());
-      first_gate.push_back((uint32_t)gk.size());
       const uint32_t base = (uint32_t)pg.size();
       for (size_t i = 1; i < f->path_off.size(); i++) po.push_back(base + f->path_off[i]);
       pg.insert(pg.end(), f->path_gate.begin(), f->path_gate.end());
@@ -137,27 +161,19 @@ struct DevTrees {
       gc.insert(gc.end(), f->gate_coef_off.begin(), f->gate_coef_off.end());
       lh.insert(lh.end(), f->leaf_hash.begin(), f->leaf_hash.end());
     }
-    path_off = up32(eng, po); path_gate = up32(eng, pg); path_x = up32(eng, px); gate_k = up32(eng, gk); gate_coef_off = up32(eng, gc);
-    leaf_hash = up_bytes(eng, flatten_fr(lh));
+    d_path_off = dev32(eng, po); d_path_gate = dev32(eng, pg); d_path_x = dev32(eng, px); d_gate_k = dev32(eng, gk); d_gate_coef_off = dev32(eng, gc);
+    bufs_.push_back(up_bytes(eng, flatten_fr(lh)));
+    d_leaf_hash = bufs_.back().as<rhip_fr>();
+    d_leaf_off = dev32(eng, leaf_off); d_tree_leaf = dev32(eng, tree_leaf); d_tree_gate = dev32(eng, tree_gate); d_coef_off = dev32(eng, coef_off);
   }
+ private:
+  std::vector<DBuf> bufs_;
+  const uint32_t* dev32(Engine& eng, const std::vector<uint32_t>& v) { bufs_.push_back(up32(eng, v)); return bufs_.back().as<uint32_t>(); }
 };
 
-// randomness of a batch in the reference's per-call draw order, item after item; OS randomness has no order, so blocks of items
-// may then draw on their own sources in parallel
+// common.h's draw_items for these schemes: an item draws hundreds of values (one per gate coefficient and leaf), hence the small blocks
 template <class DRAW>
-void draw_items(Rng& rng, size_t n, DRAW draw) {
-  struct Turn { Rng& r; explicit Turn(Rng& x) : r(x) { r.begin_draws(); } ~Turn() { r.end_draws(); } } turn(rng);
-  if (rng.unordered() && n >= 256) {
-    // an item of these schemes draws hundreds of values (one per gate coefficient and leaf): small blocks, so that every core draws
-    const size_t per = 16, blocks = (n + per - 1) / per;
-    parallel_for(blocks, [&](size_t b) {
-      BatchRng local;
-      for (size_t i = b * per; i < n && i < (b + 1) * per; i++) draw(local, i);
-    });
-  } else {
-    for (size_t i = 0; i < n; i++) draw(rng, i);
-  }
-}
+void draw_items(Rng& rng, size_t n, DRAW draw) { rabe::draw_items(rng, n, 256, 16, draw); }
 
 // bounds of the records of an untrusted blob: monotone, inside [0, len); span = total size of the well-formed ones
 uint64_t check_offsets(size_t n, const uint64_t* off, size_t len, std::vector<std::string>* errors) {
@@ -414,10 +430,7 @@ bool cp_keygen_packed(Engine& eng, Rng& rng, const Ac17MasterKey& msk, const std
     fixed[s] = 4 + 4 + 384 + 4 + 4 + 192;
     for (const auto& a : sets[s]) fixed[s] += (4 + a.size()) + (4 + a.size() + 4 + 192);
   }
-  for (size_t i = 0; i < n; i++) if (item_set[i] >= sets.size()) throw RabeError("cp_keygen_packed: item_set out of range");
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_set[i]];
-  if (!out_buf || out_cap < out_off[n]) return false;
+  if (!record_offsets("cp_keygen_packed", "item_set", n, item_set, sets.size(), fixed, nullptr, out_buf, out_cap, out_off)) return false;
   if (!n) return true;
   // items grouped by attribute list (stable: the order inside a group is the item order)
   std::vector<std::vector<size_t>> members(sets.size());
@@ -573,10 +586,7 @@ bool keygen_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const CpAbeM
     fixed[s] = 128 + 4;
     for (const auto& a : sets[s]) { fixed[s] += 4 + a.size() + 64 + 128; hashes[s].push_back(sha3_hash_fr(a)); }
   }
-  for (size_t i = 0; i < n; i++) if (item_set[i] >= sets.size()) throw RabeError("bsw::keygen_packed: item_set out of range");
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_set[i]];
-  if (!out_buf || out_cap < out_off[n]) return false;
+  if (!record_offsets("bsw::keygen_packed", "item_set", n, item_set, sets.size(), fixed, nullptr, out_buf, out_cap, out_off)) return false;
   if (!n) return true;
   Fr beta_inv;
   if (!fr_inv(msk.beta, &beta_inv)) throw std::runtime_error("called `Option::unwrap()` on a `None` value (Fr::inverse of zero)");
@@ -684,10 +694,8 @@ bool delegate_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const CpAb
       L.src(2, (uint32_t)(128 * y), 128);
     }
   }
-  for (size_t i = 0; i < n; i++) if (item_subset[i] >= subsets.size()) throw RabeError("bsw::delegate_packed: item_subset out of range");
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + layouts[item_subset[i]].bytes();
-  if (!out_buf || out_cap < out_off[n]) return false;
+  if (!record_offsets("bsw::delegate_packed", "item_subset", n, item_subset, subsets.size(), [&](size_t i) { return layouts[item_subset[i]].bytes(); }, nullptr,
+                      out_buf, out_cap, out_off)) return false;
   if (!n) return true;
   std::vector<size_t> row_off(n + 1, 0);
   for (size_t i = 0; i < n; i++) row_off[i + 1] = row_off[i] + subsets[item_subset[i]].size();
@@ -752,21 +760,16 @@ static bool encrypt_core(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const 
   const bool kem = key_buf != nullptr;
   Timer tm(kem ? "bsw::encaps_packed" : "bsw::encrypt_packed");
   Engine::ArenaScope arena(eng);
-  std::vector<std::shared_ptr<const FlatPolicy>> pols;
-  for (const auto& p : policies) pols.push_back(flat_policy(p, language));
-  for (size_t i = 0; i < n; i++) if (item_policy[i] >= policies.size()) throw RabeError("bsw::encrypt_packed: item_policy out of range");
+  ShareTrees st;
+  for (const auto& p : policies) st.add(p, language);
+  const auto& pols = st.pols;
   std::vector<size_t> fixed(policies.size());
   for (size_t p = 0; p < policies.size(); p++)
     fixed[p] = 4 + policies[p].size() + 1 + 64 + 384 + 4 + pols[p]->leaf_name.size() * (4 + 64 + 128) + pols[p]->names_bytes + 4;
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_policy[i]] + (kem ? 0 : (pt_off[i + 1] - pt_off[i]) + 28);
-  if (!out_buf || out_cap < out_off[n]) return false;
-  std::vector<uint32_t> leaf_off(n + 1, 0), coef_off(n + 1, 0), tree_leaf(n), tree_gate(n);
-  for (size_t i = 0; i < n; i++) {
-    leaf_off[i + 1] = leaf_off[i] + (uint32_t)pols[item_policy[i]]->leaf_name.size();
-    coef_off[i + 1] = coef_off[i] + pols[item_policy[i]]->n_coef;
-  }
-  const size_t total = leaf_off[n], total_coef = coef_off[n];
+  if (!record_offsets("bsw::encrypt_packed", "item_policy", n, item_policy, policies.size(), fixed, kem ? nullptr : pt_off, out_buf, out_cap, out_off)) return false;
+  st.place(n, item_policy, 1);
+  const std::vector<uint32_t>&leaf_off = st.leaf_off, &coef_off = st.coef_off;
+  const size_t total = st.total, total_coef = st.total_coef;
   tm.lap("policies");
   uint8_t* h_in = eng.pinned(0, n * 64 + (total_coef + 1) * 32);          // secret | msg exponent | coefficients
   uint8_t* h_sec = h_in;
@@ -785,25 +788,21 @@ static bool encrypt_core(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const 
   std::string key((const char*)pk.g1.data(), 64);
   key.append((const char*)pk.g2.data(), 128).append((const char*)pk.h.data(), 64).append((const char*)pk.e_gg_alpha.data(), 384);
   rhip_bsw_pk* dpk = (rhip_bsw_pk*)eng.aux("bsw_pk", key, make_pk, &pk, destroy_pk);
-  DevTrees dt(eng, pols);
-  for (size_t i = 0; i < n; i++) { tree_leaf[i] = dt.first_leaf[item_policy[i]]; tree_gate[i] = dt.first_gate[item_policy[i]]; }
-  DBuf d_leaf_off(&eng, leaf_off.data(), (n + 1) * 4), d_tl(&eng, tree_leaf.data(), n * 4), d_tg(&eng, tree_gate.data(), n * 4),
-      d_coef_off(&eng, coef_off.data(), n * 4), d_in(&eng, n * 64 + (total_coef + 1) * 32), d_msg(&eng, n * 384), d_c(&eng, n * 64), d_cp(&eng, n * 384),
-      d_g1(&eng, total * 64), d_g2(&eng, total * 128);
+  st.upload(eng);
+  DBuf d_in(&eng, n * 64 + (total_coef + 1) * 32), d_msg(&eng, n * 384), d_c(&eng, n * 64), d_cp(&eng, n * 384), d_g1(&eng, total * 64), d_g2(&eng, total * 128);
   eng.check(rhip_upload_async(cx, d_in.ptr(), h_in, n * 64 + total_coef * 32), "upload");
   const rhip_fr* dsec = d_in.as<rhip_fr>();
   eng.check(rhip_gt_table_pow(cx, eng.gt_generator_table(), n, dsec + n, d_msg.as<rhip_gt>()), "rhip_gt_table_pow");
-  eng.check(rhip_bsw_encrypt_batch(cx, dpk, n, total, d_leaf_off.as<uint32_t>(), d_tl.as<uint32_t>(), d_tg.as<uint32_t>(), dt.path_off.as<uint32_t>(),
-                                   dt.path_gate.as<uint32_t>(), dt.path_x.as<uint32_t>(), dt.gate_k.as<uint32_t>(), dt.gate_coef_off.as<uint32_t>(),
-                                   dt.leaf_hash.as<rhip_fr>(), dsec, dsec + 2 * n, d_coef_off.as<uint32_t>(), d_msg.as<rhip_gt>(), d_c.as<rhip_g1>(),
-                                   d_cp.as<rhip_gt>(), d_g1.as<rhip_g1>(), d_g2.as<rhip_g2>()), "rhip_bsw_encrypt_batch");
+  eng.check(rhip_bsw_encrypt_batch(cx, dpk, n, total,
+                                   st.d_leaf_off, st.d_tree_leaf, st.d_tree_gate, st.d_path_off, st.d_path_gate, st.d_path_x, st.d_gate_k, st.d_gate_coef_off, st.d_leaf_hash,
+                                   dsec, dsec + 2 * n, st.d_coef_off, d_msg.as<rhip_gt>(), d_c.as<rhip_g1>(), d_cp.as<rhip_gt>(), d_g1.as<rhip_g1>(),
+                                   d_g2.as<rhip_g2>()), "rhip_bsw_encrypt_batch");
   // records and sealing on the device (records.h)
   std::vector<RecordLayout> layouts(policies.size());
   for (size_t p_ = 0; p_ < policies.size(); p_++) {
     RecordLayout& L = layouts[p_];
     const FlatPolicy& f = *pols[p_];
-    L.str(policies[p_]);
-    L.u8((language == PolicyLanguage::HumanPolicy) ? 1 : 0);
+    policy_header(L, policies[p_], language);
     L.src(0, 0, 64);
     L.src(1, 0, 384);
     L.u32((uint32_t)f.leaf_name.size());
@@ -1091,13 +1090,9 @@ bool encrypt_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::
     fixed[s] = 384 + 128 + 4 + 4;
     for (const auto& a : sets[s]) { fixed[s] += 4 + a.size() + 3 * 64; hashes[s].push_back(sha3_hash_fr(a)); }
   }
-  for (size_t i = 0; i < n; i++) {
-    if (item_set[i] >= sets.size()) throw RabeError("lsw::encrypt_packed: item_set out of range");
-    if (pt_off[i + 1] <= pt_off[i]) throw RabeError("attributes or data empty");
-  }
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_set[i]] + (pt_off[i + 1] - pt_off[i]) + 28;
-  if (!out_buf || out_cap < out_off[n]) return false;
+  // the first bad item decides the message: an empty payload counts up to the first index out of range, which record_offsets reports
+  for (size_t i = 0; i < n && item_set[i] < sets.size(); i++) if (pt_off[i + 1] <= pt_off[i]) throw RabeError("attributes or data empty");
+  if (!record_offsets("lsw::encrypt_packed", "item_set", n, item_set, sets.size(), fixed, pt_off, out_buf, out_cap, out_off)) return false;
   if (!n) return true;
   std::vector<size_t> row_off(n + 1, 0);
   for (size_t i = 0; i < n; i++) row_off[i + 1] = row_off[i] + sets[item_set[i]].size();
@@ -1189,26 +1184,20 @@ bool keygen_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const KpAbeM
   Timer tm("lsw::keygen_packed");
   Engine::ArenaScope arena(eng);
   eng.scrub_when_done();          // master-key-derived scalars pass through the staging buffers
-  std::vector<std::shared_ptr<const FlatPolicy>> pols;
+  ShareTrees st;
   std::vector<std::vector<std::string>> striped(policies.size());
   std::vector<size_t> fixed(policies.size());
   bool any_negative = false;
   for (size_t p = 0; p < policies.size(); p++) {
-    pols.push_back(flat_policy(policies[p], language));
-    any_negative = any_negative || pols[p]->has_negative;
+    const FlatPolicy& f = st.add(policies[p], language);
+    any_negative = any_negative || f.has_negative;
     fixed[p] = 4 + policies[p].size() + 1 + 4;
-    for (const auto& nc : pols[p]->leaf_name_col) { striped[p].push_back(remove_index(nc)); fixed[p] += 4 + striped[p].back().size() + 64 + 128 + 3 * 64; }
+    for (const auto& nc : f.leaf_name_col) { striped[p].push_back(remove_index(nc)); fixed[p] += 4 + striped[p].back().size() + 64 + 128 + 3 * 64; }
   }
-  for (size_t i = 0; i < n; i++) if (item_policy[i] >= policies.size()) throw RabeError("lsw::keygen_packed: item_policy out of range");
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_policy[i]];
-  if (!out_buf || out_cap < out_off[n]) return false;
-  std::vector<uint32_t> leaf_off(n + 1, 0), coef_off(n + 1, 0), tree_leaf(n), tree_gate(n);
-  for (size_t i = 0; i < n; i++) {
-    leaf_off[i + 1] = leaf_off[i] + (uint32_t)pols[item_policy[i]]->leaf_name.size();
-    coef_off[i + 1] = coef_off[i] + pols[item_policy[i]]->n_coef;
-  }
-  const size_t total = leaf_off[n], total_coef = coef_off[n];
+  if (!record_offsets("lsw::keygen_packed", "item_policy", n, item_policy, policies.size(), fixed, nullptr, out_buf, out_cap, out_off)) return false;
+  st.place(n, item_policy, 1);
+  const std::vector<uint32_t>&leaf_off = st.leaf_off, &coef_off = st.coef_off;
+  const size_t total = st.total, total_coef = st.total_coef;
   uint8_t* h_in = eng.pinned(0, 64 + (total_coef + total + 1) * 32);        // alpha1 | alpha2 | coefficients | randoms
   memcpy(h_in, msk.alpha1.l, 32);
   memcpy(h_in + 32, msk.alpha2.l, 32);
@@ -1223,37 +1212,32 @@ bool keygen_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const KpAbeM
   std::string key((const char*)pk.g1.data(), 64);
   key.append((const char*)pk.g2.data(), 128);
   rhip_lsw_pk* dpk = (rhip_lsw_pk*)eng.aux("lsw_pk", key, make_pk, &pk, destroy_pk);
-  DevTrees dt(eng, pols);
-  for (size_t i = 0; i < n; i++) { tree_leaf[i] = dt.first_leaf[item_policy[i]]; tree_gate[i] = dt.first_gate[item_policy[i]]; }
-  DBuf d_leaf_off = up32(eng, leaf_off), d_tl = up32(eng, tree_leaf), d_tg = up32(eng, tree_gate), d_coef_off = up32(eng, coef_off),
-       d_in(&eng, 64 + (total_coef + total + 1) * 32), d_d1(&eng, total * 64 + 4), d_d2(&eng, total * 128 + 4);
+  st.upload(eng);
+  DBuf d_in(&eng, 64 + (total_coef + total + 1) * 32), d_d1(&eng, total * 64 + 4), d_d2(&eng, total * 128 + 4);
   eng.check(rhip_upload_async(cx, d_in.ptr(), h_in, 64 + (total_coef + total) * 32), "upload");
   const rhip_fr* din = d_in.as<rhip_fr>();
   DBuf d_d345;
   if (!any_negative) {
-    eng.check(rhip_lsw_keygen_batch(cx, dpk, n, total, d_leaf_off.as<uint32_t>(), d_tl.as<uint32_t>(), d_tg.as<uint32_t>(), dt.path_off.as<uint32_t>(),
-                                    dt.path_gate.as<uint32_t>(), dt.path_x.as<uint32_t>(), dt.gate_k.as<uint32_t>(), dt.gate_coef_off.as<uint32_t>(),
-                                    dt.leaf_hash.as<rhip_fr>(), din, din + 2, d_coef_off.as<uint32_t>(), din + 2 + total_coef, d_d1.as<rhip_g1>(),
-                                    d_d2.as<rhip_g2>()), "rhip_lsw_keygen_batch");
+    eng.check(rhip_lsw_keygen_batch(cx, dpk, n, total,
+                                    st.d_leaf_off, st.d_tree_leaf, st.d_tree_gate, st.d_path_off, st.d_path_gate, st.d_path_x, st.d_gate_k, st.d_gate_coef_off, st.d_leaf_hash,
+                                    din, din + 2, st.d_coef_off, din + 2 + total_coef, d_d1.as<rhip_g1>(), d_d2.as<rhip_g2>()), "rhip_lsw_keygen_batch");
   } else {                                   // negative leaves (lsw/mod.rs:137-146): d3, d4, d5 from the share, b and the master key's h_g1
     std::vector<uint32_t> leaf_neg;
-    for (const auto& f : pols) for (const auto& nm : f->leaf_name) leaf_neg.push_back(is_negative(nm) ? 1u : 0u);
+    for (const auto& f : st.pols) for (const auto& nm : f->leaf_name) leaf_neg.push_back(is_negative(nm) ? 1u : 0u);
     DBuf d_neg = up32(eng, leaf_neg), d_b(&eng, msk.b.l, 32);
     d_d345 = DBuf(&eng, total * 192 + 4);
     rhip_g1* d3 = d_d345.as<rhip_g1>();
-    eng.check(rhip_lsw_keygen_batch_signed(cx, dpk, n, total, d_leaf_off.as<uint32_t>(), d_tl.as<uint32_t>(), d_tg.as<uint32_t>(), dt.path_off.as<uint32_t>(),
-                                           dt.path_gate.as<uint32_t>(), dt.path_x.as<uint32_t>(), dt.gate_k.as<uint32_t>(), dt.gate_coef_off.as<uint32_t>(),
-                                           dt.leaf_hash.as<rhip_fr>(), d_neg.as<uint32_t>(), din, d_b.as<rhip_fr>(), (const rhip_g1*)msk.h_g1.data(),
-                                           din + 2, d_coef_off.as<uint32_t>(), din + 2 + total_coef, d_d1.as<rhip_g1>(), d_d2.as<rhip_g2>(), d3,
-                                           d3 + total, d3 + 2 * total), "rhip_lsw_keygen_batch_signed");
+    eng.check(rhip_lsw_keygen_batch_signed(cx, dpk, n, total,
+                                           st.d_leaf_off, st.d_tree_leaf, st.d_tree_gate, st.d_path_off, st.d_path_gate, st.d_path_x, st.d_gate_k, st.d_gate_coef_off,
+                                           st.d_leaf_hash, d_neg.as<uint32_t>(), din, d_b.as<rhip_fr>(), (const rhip_g1*)msk.h_g1.data(), din + 2, st.d_coef_off,
+                                           din + 2 + total_coef, d_d1.as<rhip_g1>(), d_d2.as<rhip_g2>(), d3, d3 + total, d3 + 2 * total), "rhip_lsw_keygen_batch_signed");
   }
   // the records are written on the device (records.h): policy text, leaf names and counts from the policy's template, the elements dropped
   // in (d3 .. d5 are the point at infinity -- zeros -- for a policy without negative leaves)
   std::vector<RecordLayout> layouts(policies.size());
   for (size_t p_ = 0; p_ < policies.size(); p_++) {
     RecordLayout& L = layouts[p_];
-    L.str(policies[p_]);
-    L.u8((language == PolicyLanguage::HumanPolicy) ? 1 : 0);
+    policy_header(L, policies[p_], language);
     L.u32((uint32_t)striped[p_].size());
     for (size_t y = 0; y < striped[p_].size(); y++) {
       L.str(striped[p_][y]);
@@ -1617,15 +1601,15 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::v
   key.append((const char*)gk.g2.data(), 128);
   for (const auto* pk : pks) for (const auto& t : pk->attr) { arg.attrs.push_back(&t); key.append((const char*)t.egg_alpha.data(), 384).append((const char*)t.g2_y.data(), 128); }
   if (arg.attrs.empty()) throw RabeError("aw11::encrypt_packed: no authority attributes");
-  std::vector<std::shared_ptr<const FlatPolicy>> pols;
+  ShareTrees st;
   std::vector<std::vector<std::string>> row_name(policies.size());
   std::vector<uint32_t> leaf_attr;
   std::vector<size_t> fixed(policies.size());
   for (size_t p = 0; p < policies.size(); p++) {
-    pols.push_back(flat_policy(policies[p], language));
-    (void)calculate_msp(pols[p]->tree);                    // built and unused in the reference (:253-255) -- but it must not panic
+    const FlatPolicy& f = st.add(policies[p], language);
+    (void)calculate_msp(f.tree);                           // built and unused in the reference (:253-255) -- but it must not panic
     fixed[p] = 4 + policies[p].size() + 1 + 384 + 4 + 4;
-    for (const auto& nc : pols[p]->leaf_name_col) {
+    for (const auto& nc : f.leaf_name_col) {
       const std::string up = upper(nc), want = remove_index(up);
       size_t a = 0;
       while (a < arg.attrs.size() && arg.attrs[a]->name != want) a++;
@@ -1635,18 +1619,12 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::v
       fixed[p] += 4 + up.size() + 384 + 128 + 128;
     }
   }
-  for (size_t i = 0; i < n; i++) if (item_policy[i] >= policies.size()) throw RabeError("aw11::encrypt_packed: item_policy out of range");
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_policy[i]] + (pt_off[i + 1] - pt_off[i]) + 28;
-  if (!out_buf || out_cap < out_off[n]) return false;
-  std::vector<uint32_t> row_off(n + 1, 0), coef_off(n + 1, 0), tree_leaf(n), tree_gate(n), n_coef(n);
-  for (size_t i = 0; i < n; i++) {
-    const FlatPolicy& f = *pols[item_policy[i]];
-    row_off[i + 1] = row_off[i] + (uint32_t)f.leaf_name.size();
-    coef_off[i + 1] = coef_off[i] + 2 * f.n_coef;
-    n_coef[i] = f.n_coef;
-  }
-  const size_t total = row_off[n], total_coef = coef_off[n];
+  if (!record_offsets("aw11::encrypt_packed", "item_policy", n, item_policy, policies.size(), fixed, pt_off, out_buf, out_cap, out_off)) return false;
+  st.place(n, item_policy, 2);          // the s-shares' coefficients, then the 0-shares'
+  std::vector<uint32_t> n_coef(n);
+  for (size_t i = 0; i < n; i++) n_coef[i] = st.pols[item_policy[i]]->n_coef;
+  const std::vector<uint32_t>&row_off = st.leaf_off, &coef_off = st.coef_off;
+  const size_t total = st.total, total_coef = st.total_coef;
   uint8_t* h_in = eng.pinned(0, (2 * n + total_coef + total + 1) * 32);      // s | msg exponent | coefficients | r_x
   uint8_t* h_s = h_in;
   uint8_t* h_rho = h_in + n * 32;
@@ -1665,25 +1643,21 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::v
   tm.lap("policies + draws");
   rhip_ctx* cx = eng.ctx();
   rhip_aw11_pk* dpk = (rhip_aw11_pk*)eng.aux("aw11_pk", key, make_pk, &arg, destroy_pk, 2);
-  DevTrees dt(eng, pols);
-  for (size_t i = 0; i < n; i++) { tree_leaf[i] = dt.first_leaf[item_policy[i]]; tree_gate[i] = dt.first_gate[item_policy[i]]; }
-  DBuf d_row_off = up32(eng, row_off), d_tl = up32(eng, tree_leaf), d_tg = up32(eng, tree_gate), d_nc = up32(eng, n_coef), d_coef_off = up32(eng, coef_off),
-       d_leaf_attr = up32(eng, leaf_attr), d_in(&eng, (2 * n + total_coef + total + 1) * 32), d_msg(&eng, n * 384), d_c0(&eng, n * 384),
+  st.upload(eng);
+  DBuf d_nc = up32(eng, n_coef), d_leaf_attr = up32(eng, leaf_attr), d_in(&eng, (2 * n + total_coef + total + 1) * 32), d_msg(&eng, n * 384), d_c0(&eng, n * 384),
        d_c1(&eng, total * 384 + 4), d_c2(&eng, total * 128 + 4), d_c3(&eng, total * 128 + 4);
   eng.check(rhip_upload_async(cx, d_in.ptr(), h_in, (2 * n + total_coef + total) * 32), "upload");
   const rhip_fr* din = d_in.as<rhip_fr>();
   eng.check(rhip_gt_table_pow(cx, eng.gt_generator_table(), n, din + n, d_msg.as<rhip_gt>()), "rhip_gt_table_pow");
-  eng.check(rhip_aw11_encrypt_batch(cx, dpk, n, total, d_row_off.as<uint32_t>(), d_tl.as<uint32_t>(), d_tg.as<uint32_t>(), d_nc.as<uint32_t>(),
-                                    dt.path_off.as<uint32_t>(), dt.path_gate.as<uint32_t>(), dt.path_x.as<uint32_t>(), dt.gate_k.as<uint32_t>(),
-                                    dt.gate_coef_off.as<uint32_t>(), d_leaf_attr.as<uint32_t>(), din, din + 2 * n, d_coef_off.as<uint32_t>(),
-                                    din + 2 * n + total_coef, d_msg.as<rhip_gt>(), d_c0.as<rhip_gt>(), d_c1.as<rhip_gt>(), d_c2.as<rhip_g2>(),
-                                    d_c3.as<rhip_g2>()), "rhip_aw11_encrypt_batch");
+  eng.check(rhip_aw11_encrypt_batch(cx, dpk, n, total,
+                                    st.d_leaf_off, st.d_tree_leaf, st.d_tree_gate, d_nc.as<uint32_t>(), st.d_path_off, st.d_path_gate, st.d_path_x, st.d_gate_k, st.d_gate_coef_off,
+                                    d_leaf_attr.as<uint32_t>(), din, din + 2 * n, st.d_coef_off, din + 2 * n + total_coef, d_msg.as<rhip_gt>(), d_c0.as<rhip_gt>(),
+                                    d_c1.as<rhip_gt>(), d_c2.as<rhip_g2>(), d_c3.as<rhip_g2>()), "rhip_aw11_encrypt_batch");
   // records and sealing on the device (records.h)
   std::vector<RecordLayout> layouts(policies.size());
   for (size_t p_ = 0; p_ < policies.size(); p_++) {
     RecordLayout& L = layouts[p_];
-    L.str(policies[p_]);
-    L.u8((language == PolicyLanguage::HumanPolicy) ? 1 : 0);
+    policy_header(L, policies[p_], language);
     L.src(0, 0, 384);
     L.u32((uint32_t)row_name[p_].size());
     for (size_t y = 0; y < row_name[p_].size(); y++) {
@@ -1739,13 +1713,10 @@ bool keygen_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11MasterKey& ms
       fixed[s] += 4 + names[s].back().size() + 64;
     }
   }
-  for (size_t i = 0; i < n; i++) {
-    if (item_set[i] >= sets.size()) throw RabeError("aw11::keygen_packed: item_set out of range");
-    if (gids[i].empty()) throw RabeError("empty _name");
-  }
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_set[i]] + gids[i].size();
-  if (!out_buf || out_cap < out_off[n]) return false;
+  // the first bad item decides the message: an empty gid counts up to the first index out of range, which record_offsets reports
+  for (size_t i = 0; i < n && item_set[i] < sets.size(); i++) if (gids[i].empty()) throw RabeError("empty _name");
+  if (!record_offsets("aw11::keygen_packed", "item_set", n, item_set, sets.size(), [&](size_t i) { return fixed[item_set[i]] + gids[i].size(); }, nullptr,
+                      out_buf, out_cap, out_off)) return false;
   if (!n) return true;
   std::vector<size_t> row_off(n + 1, 0);
   for (size_t i = 0; i < n; i++) row_off[i + 1] = row_off[i] + sets[item_set[i]].size();
@@ -1962,21 +1933,16 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::
                     const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
   Timer tm("ghw11::encrypt_packed");
   Engine::ArenaScope arena(eng);
-  std::vector<std::shared_ptr<const FlatPolicy>> pols;
-  for (const auto& p : policies) pols.push_back(flat_policy(p, language));
-  for (size_t i = 0; i < n; i++) if (item_policy[i] >= policies.size()) throw RabeError("ghw11::encrypt_packed: item_policy out of range");
+  ShareTrees st;
+  for (const auto& p : policies) st.add(p, language);
+  const auto& pols = st.pols;
   std::vector<size_t> fixed(policies.size());
   for (size_t p = 0; p < policies.size(); p++)
     fixed[p] = 4 + policies[p].size() + 1 + 384 + 64 + 4 + pols[p]->leaf_name.size() * (4 + 64 + 64) + pols[p]->names_bytes + 4;
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_policy[i]] + (pt_off[i + 1] - pt_off[i]) + 28;
-  if (!out_buf || out_cap < out_off[n]) return false;
-  std::vector<uint32_t> leaf_off(n + 1, 0), coef_off(n + 1, 0), tree_leaf(n), tree_gate(n);
-  for (size_t i = 0; i < n; i++) {
-    leaf_off[i + 1] = leaf_off[i] + (uint32_t)pols[item_policy[i]]->leaf_name.size();
-    coef_off[i + 1] = coef_off[i] + pols[item_policy[i]]->n_coef;
-  }
-  const size_t total = leaf_off[n], total_coef = coef_off[n];
+  if (!record_offsets("ghw11::encrypt_packed", "item_policy", n, item_policy, policies.size(), fixed, pt_off, out_buf, out_cap, out_off)) return false;
+  st.place(n, item_policy, 1);
+  const std::vector<uint32_t>&leaf_off = st.leaf_off, &coef_off = st.coef_off;
+  const size_t total = st.total, total_coef = st.total_coef;
   tm.lap("policies");
   const size_t in_bytes = (2 * n + total_coef + total) * 32;
   uint8_t* h_in = eng.pinned(0, in_bytes + 32);          // secret | msg exponent | coefficients | t per leaf row
@@ -1998,25 +1964,21 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::
   std::string key((const char*)pk.g1.data(), 64);
   key.append((const char*)pk.g1_a.data(), 64).append((const char*)pk.e_gg_alpha.data(), 384);
   rhip_ghw11_pk* dpk = (rhip_ghw11_pk*)eng.aux("ghw11_pk", key, make_pk, &pk, destroy_pk);
-  DevTrees dt(eng, pols);
-  for (size_t i = 0; i < n; i++) { tree_leaf[i] = dt.first_leaf[item_policy[i]]; tree_gate[i] = dt.first_gate[item_policy[i]]; }
-  DBuf d_leaf_off(&eng, leaf_off.data(), (n + 1) * 4), d_tl(&eng, tree_leaf.data(), n * 4), d_tg(&eng, tree_gate.data(), n * 4),
-      d_coef_off(&eng, coef_off.data(), n * 4), d_in(&eng, in_bytes + 32), d_msg(&eng, n * 384), d_c(&eng, n * 384), d_c1(&eng, n * 64),
-      d_cd(&eng, total * 128 + 4);
+  st.upload(eng);
+  DBuf d_in(&eng, in_bytes + 32), d_msg(&eng, n * 384), d_c(&eng, n * 384), d_c1(&eng, n * 64), d_cd(&eng, total * 128 + 4);
   eng.check(rhip_upload_async(cx, d_in.ptr(), h_in, in_bytes), "upload");
   const rhip_fr* dsec = d_in.as<rhip_fr>();
   eng.check(rhip_gt_table_pow(cx, eng.gt_generator_table(), n, dsec + n, d_msg.as<rhip_gt>()), "rhip_gt_table_pow");
-  eng.check(rhip_ghw11_encrypt_batch(cx, dpk, n, total, d_leaf_off.as<uint32_t>(), d_tl.as<uint32_t>(), d_tg.as<uint32_t>(), dt.path_off.as<uint32_t>(),
-                                     dt.path_gate.as<uint32_t>(), dt.path_x.as<uint32_t>(), dt.gate_k.as<uint32_t>(), dt.gate_coef_off.as<uint32_t>(),
-                                     dt.leaf_hash.as<rhip_fr>(), dsec, dsec + 2 * n, d_coef_off.as<uint32_t>(), dsec + 2 * n + total_coef,
-                                     d_msg.as<rhip_gt>(), d_c.as<rhip_gt>(), d_c1.as<rhip_g1>(), d_cd.as<rhip_g1>()), "rhip_ghw11_encrypt_batch");
+  eng.check(rhip_ghw11_encrypt_batch(cx, dpk, n, total,
+                                     st.d_leaf_off, st.d_tree_leaf, st.d_tree_gate, st.d_path_off, st.d_path_gate, st.d_path_x, st.d_gate_k, st.d_gate_coef_off, st.d_leaf_hash,
+                                     dsec, dsec + 2 * n, st.d_coef_off, dsec + 2 * n + total_coef, d_msg.as<rhip_gt>(), d_c.as<rhip_gt>(), d_c1.as<rhip_g1>(),
+                                     d_cd.as<rhip_g1>()), "rhip_ghw11_encrypt_batch");
   // records and sealing on the device (records.h)
   std::vector<RecordLayout> layouts(policies.size());
   for (size_t p_ = 0; p_ < policies.size(); p_++) {
     RecordLayout& L = layouts[p_];
     const FlatPolicy& f = *pols[p_];
-    L.str(policies[p_]);
-    L.u8((language == PolicyLanguage::HumanPolicy) ? 1 : 0);
+    policy_header(L, policies[p_], language);
     L.src(0, 0, 384);
     L.src(1, 0, 64);
     L.u32((uint32_t)f.leaf_name.size());
@@ -2396,7 +2358,7 @@ bool keygen_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw11M
   Engine::ArenaScope arena(eng);
   eng.scrub_when_done();          // the keys' r pass through the staging buffers
   if (!out_off || (n && !item_set)) throw RabeError("ghw11::keygen_packed: null input");
-  for (size_t i = 0; i < n; i++) if (item_set[i] >= sets.size()) throw RabeError("ghw11::keygen_packed: item_set out of range");
+  check_index("ghw11::keygen_packed", "item_set", n, item_set, sets.size());          // before the empty-list check, as ever
   std::vector<size_t> fixed(sets.size());
   std::vector<uint32_t> hash_off(sets.size() + 1, 0);
   std::vector<Fr> hashes;
@@ -2406,9 +2368,7 @@ bool keygen_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw11M
     for (const auto& a : sets[s]) { fixed[s] += 4 + a.size() + 128; hashes.push_back(sha3_hash_fr(a)); }
     hash_off[s + 1] = (uint32_t)hashes.size();
   }
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed[item_set[i]];
-  if (n && (!out_buf || out_cap < out_off[n])) return false;
+  if (!record_offsets("ghw11::keygen_packed", "item_set", n, item_set, sets.size(), fixed, nullptr, out_buf, out_cap, out_off) && n) return false;
   if (!n) return true;
   std::vector<uint32_t> row_off(n + 1, 0), item_hash(n);
   for (size_t i = 0; i < n; i++) {
@@ -2581,7 +2541,7 @@ bool provision_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw
   eng.scrub_when_done();          // r, z, z^-1 and r z^-1 pass through the staging buffers
   const bool want_sk = sk_off != nullptr;
   if (!tk_off || (n && (!item_set || !rk_buf))) throw RabeError("ghw11::provision_packed: null input");
-  for (size_t i = 0; i < n; i++) if (item_set[i] >= sets.size()) throw RabeError("ghw11::provision_packed: item_set out of range");
+  check_index("ghw11::provision_packed", "item_set", n, item_set, sets.size());          // before the empty-list check, as ever
   std::vector<size_t> fixed(sets.size());
   std::vector<uint32_t> hash_off(sets.size() + 1, 0);
   std::vector<Fr> hashes;
@@ -2591,10 +2551,9 @@ bool provision_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw
     for (const auto& a : sets[s]) { fixed[s] += 4 + a.size() + 128; hashes.push_back(sha3_hash_fr(a)); }
     hash_off[s + 1] = (uint32_t)hashes.size();
   }
-  tk_off[0] = 0;
-  for (size_t i = 0; i < n; i++) tk_off[i + 1] = tk_off[i] + fixed[item_set[i]];
+  const bool tk_fits = record_offsets("ghw11::provision_packed", "item_set", n, item_set, sets.size(), fixed, nullptr, tk_buf, tk_cap, tk_off);
   if (want_sk) memcpy(sk_off, tk_off, (n + 1) * sizeof(uint64_t));
-  if (n && (!tk_buf || tk_cap < tk_off[n] || (want_sk && (!sk_buf || sk_cap < sk_off[n])))) return false;
+  if (n && (!tk_fits || (want_sk && (!sk_buf || sk_cap < sk_off[n])))) return false;
   if (!n) return true;
   std::vector<uint32_t> row_off(n + 1, 0), item_hash(n);
   for (size_t i = 0; i < n; i++) {
@@ -2722,8 +2681,7 @@ bool encrypt_packed(Engine& eng, Rng& rng, const DnfScheme& sc, const G1& p1, co
       policy_error(std::runtime_error("called `Result::unwrap()` on an `Err` value: Error in json_to_dnf: could not parse policy as DNF"), true, p);
     // the record (host_abi.cpp: ser): policy, language, term count, per term its attribute names, Gt part(s), p1 r, p2 r, T1 r, T2 r
     RecordLayout& L = layouts[p];
-    L.str(policies[p]);
-    L.u8((language == PolicyLanguage::HumanPolicy) ? 1 : 0);
+    policy_header(L, policies[p], language);
     L.u32((uint32_t)terms[p].size());
     for (size_t y = 0; y < terms[p].size(); y++) {
       L.u32((uint32_t)terms[p][y].attrs.size());
@@ -2735,10 +2693,8 @@ bool encrypt_packed(Engine& eng, Rng& rng, const DnfScheme& sc, const G1& p1, co
       L.src(2, (uint32_t)(256 * y + 128), 128);
     }
   }
-  for (size_t i = 0; i < n; i++) if (item_policy[i] >= P) throw RabeError(std::string(sc.timer) + ": item_policy out of range");
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + layouts[item_policy[i]].bytes() + 4 + (pt_off[i + 1] - pt_off[i]) + 28;
-  if (!out_buf || out_cap < out_off[n]) return false;
+  if (!record_offsets(sc.timer, "item_policy", n, item_policy, P, [&](size_t i) { return layouts[item_policy[i]].bytes() + 4; }, pt_off, out_buf, out_cap,
+                      out_off)) return false;
   if (!n) return true;
   std::vector<uint32_t> row_off(n + 1, 0);
   for (size_t i = 0; i < n; i++) row_off[i + 1] = row_off[i] + (uint32_t)terms[item_policy[i]].size();
@@ -2911,12 +2867,13 @@ bool request_sk_packed(Engine& eng, const char* what, const std::string& authori
     for (const auto& a : sets[s])
       if (!from_authority(a, authority))
         throw RabeError("attribute " + a + " is not from_authority() or !is_eligible() (attribute list " + std::to_string(s) + ")");
+  // the first bad item decides the message: the rows count up to the first index out of range, which check_index reports -- before the parse
   uint64_t all_rows = 0;
-  for (size_t i = 0; i < n; i++) {
-    if (item_set[i] >= sets.size()) throw RabeError(std::string(what) + ": item_set out of range");
+  for (size_t i = 0; i < n && item_set[i] < sets.size(); i++) {
     all_rows += sets[item_set[i]].size();
     if (all_rows > 0xFFFFFFF0ull) throw RabeError(std::string(what) + ": more than 2^32 key elements in one call");
   }
+  check_index(what, "item_set", n, item_set, sets.size());
   std::vector<size_t> fixed(sets.size());
   std::vector<uint32_t> scal_base(sets.size() + 1, 0);
   for (size_t s = 0; s < sets.size(); s++) {
@@ -2933,13 +2890,10 @@ bool request_sk_packed(Engine& eng, const char* what, const std::string& authori
   });
   tm.lap("parse");
   std::vector<size_t> live;
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) {
-    const bool ok = (*errors)[i].empty();
-    if (ok) live.push_back(i);
-    out_off[i + 1] = out_off[i] + (ok ? fixed[item_set[i]] : 0);
-  }
-  if (out_off[n] && (!out_buf || out_cap < out_off[n])) return false;
+  for (size_t i = 0; i < n; i++) if ((*errors)[i].empty()) live.push_back(i);
+  // a failed item's slot is empty
+  if (!record_offsets(what, "item_set", n, item_set, sets.size(), [&](size_t i) { return (*errors)[i].empty() ? fixed[item_set[i]] : 0; }, nullptr, out_buf,
+                      out_cap, out_off) && out_off[n]) return false;
   const size_t m = live.size();
   std::vector<uint8_t> good(m, 1);
   if (m) {

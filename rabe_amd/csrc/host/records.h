@@ -32,6 +32,32 @@ struct RecordLayout {
   size_t bytes() const { return map.size(); }
 };
 
+// the head of a record that starts with its policy: the text, then the language as one byte
+inline void policy_header(RecordLayout& L, const std::string& text, PolicyLanguage language) {
+  L.str(text);
+  L.u8(language == PolicyLanguage::HumanPolicy ? 1 : 0);
+}
+
+// Sizing of an issuing call (n records out, item i of kind idx[i] < n_kinds).  check_index throws "<what>: <index_name> out of range";
+// record_offsets calls it, then fills out_off[0 .. n]: record i takes fixed(i) bytes -- or fixed[idx[i]], for a table by kind -- and, where
+// pt_off is given, its sealed plaintext (the payload + 28 bytes of nonce and tag).  Returns whether out_buf is there and holds out_off[n]
+// bytes.  Nothing is drawn or written before a caller has seen the answer; what a caller does at n == 0 is its own line.
+inline void check_index(const std::string& what, const char* index_name, size_t n, const uint32_t* idx, size_t n_kinds) {
+  for (size_t i = 0; i < n; i++) if (idx[i] >= n_kinds) throw RabeError(what + ": " + index_name + " out of range");
+}
+template <class FIXED>
+bool record_offsets(const std::string& what, const char* index_name, size_t n, const uint32_t* idx, size_t n_kinds, FIXED fixed, const uint64_t* pt_off,
+                    const uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  check_index(what, index_name, n, idx, n_kinds);
+  out_off[0] = 0;
+  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed(i) + (pt_off ? (pt_off[i + 1] - pt_off[i]) + 28 : 0);
+  return out_buf && out_cap >= out_off[n];
+}
+inline bool record_offsets(const std::string& what, const char* index_name, size_t n, const uint32_t* idx, size_t n_kinds, const std::vector<size_t>& fixed,
+                           const uint64_t* pt_off, const uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  return record_offsets(what, index_name, n, idx, n_kinds, [&](size_t i) { return fixed[idx[i]]; }, pt_off, out_buf, out_cap, out_off);
+}
+
 // many small host arrays -> one staging area -> ONE upload; device pointers by handle afterwards
 class ParamPack {
  public:

@@ -1298,34 +1298,20 @@ static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, 
     A.insert(A.end(), e->tab.begin(), e->tab.end());
     a_off.push_back(a_off.back() + (uint32_t)e->msp.m.size());
   }
-  for (size_t i = 0; i < n; i++) if (item_policy[i] >= pols.size()) throw RabeError("encrypt_packed: item_policy out of range");
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + pols[item_policy[i]]->fixed_bytes + (kem ? 0 : (pt_off[i + 1] - pt_off[i]) + 28);
-  if (!out_buf || out_cap < out_off[n]) return false;
+  if (!record_offsets("encrypt_packed", "item_policy", n, item_policy, pols.size(), [&](size_t i) { return pols[item_policy[i]]->fixed_bytes; },
+                      kem ? nullptr : pt_off, out_buf, out_cap, out_off)) return false;
   tm.lap("policies");
   // randomness in the reference's per-call draw order: s0, s1, msg, nonce -- item after item (encaps: no nonce)
   uint8_t* h_s = eng.pinned(0, n * (64 + 32));
   uint8_t* h_rho = h_s + n * 64;
   std::vector<std::array<uint8_t, 12>> nonces(n);
-  auto draw_item = [&](Rng& r, size_t i) {
+  draw_items(rng, n, 1024, 256, [&](Rng& r, size_t i) {
     Fr s0 = r.next_fr(), s1 = r.next_fr(), rho = r.next_fr();
     memcpy(h_s + 64 * i, s0.l, 32);
     memcpy(h_s + 64 * i + 32, s1.l, 32);
     memcpy(h_rho + 32 * i, rho.l, 32);
     if (!kem) r.fill(nonces[i].data(), 12);
-  };
-  {
-    struct Turn { Rng& r; explicit Turn(Rng& x) : r(x) { r.begin_draws(); } ~Turn() { r.end_draws(); } } turn(rng);
-    if (rng.unordered() && n >= 1024) {          // OS randomness has no order: blocks of items draw on their own sources
-      const size_t blocks = (n + 255) / 256;
-      parallel_for(blocks, [&](size_t b) {
-        BatchRng local;
-        for (size_t i = b * 256; i < n && i < (b + 1) * 256; i++) draw_item(local, i);
-      });
-    } else {
-      for (size_t i = 0; i < n; i++) draw_item(rng, i);
-    }
-  }
+  });
   std::vector<uint32_t> item_a_off(n), row_off(n + 1, 0);
   for (size_t i = 0; i < n; i++) {
     item_a_off[i] = a_off[item_policy[i]];
@@ -1347,8 +1333,7 @@ static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, 
     RecordLayout& L = layouts[p_];
     const AbePolicy& msp = pols[p_]->msp;
     if (policies) {                               // Ac17CpCiphertext: policy text + language
-      L.str((*policies)[p_]);
-      L.u8((language == PolicyLanguage::HumanPolicy) ? 1 : 0);
+      policy_header(L, (*policies)[p_], language);
     } else {                                      // Ac17KpCiphertext: the attribute strings
       L.u32((uint32_t)msp.pi.size());
       for (const auto& a : msp.pi) L.str(a);
@@ -1887,18 +1872,15 @@ bool kp_keygen_packed(Engine& eng, Rng& rng, const Ac17MasterKey& msk, const std
     kps.push_back(kp_policy(policies[p_], lang));
     RecordLayout& L = layouts[p_];
     const AbePolicy& msp = kps.back().msp;
-    L.str(policies[p_]);
-    L.u8(lang == PolicyLanguage::HumanPolicy ? 1 : 0);
+    policy_header(L, policies[p_], lang);
     L.u32(3);
     L.src(0, 0, 384);
     L.u32((uint32_t)msp.m.size());
     for (size_t r = 0; r < msp.m.size(); r++) { L.str(msp.pi[r]); L.u32(3); L.src(1, (uint32_t)(192 * r), 192); }
     L.u32(0);                                   // k_p: empty for a KP key
   }
-  for (size_t i = 0; i < n; i++) if (item_policy[i] >= policies.size()) throw RabeError("kp_keygen_packed: item_policy out of range");
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + layouts[item_policy[i]].bytes();
-  if (!out_buf || out_cap < out_off[n]) return false;
+  if (!record_offsets("kp_keygen_packed", "item_policy", n, item_policy, policies.size(), [&](size_t i) { return layouts[item_policy[i]].bytes(); }, nullptr,
+                      out_buf, out_cap, out_off)) return false;
   if (!n) return true;
   std::vector<uint32_t> row_off(n + 1, 0), draw_off(n + 1, 0);
   for (size_t i = 0; i < n; i++) {
@@ -1908,18 +1890,7 @@ bool kp_keygen_packed(Engine& eng, Rng& rng, const Ac17MasterKey& msk, const std
   }
   const size_t total_rows = row_off[n];
   std::vector<Fr> draws(draw_off[n] + 1);
-  {
-    struct Turn { Rng& r; explicit Turn(Rng& x) : r(x) { r.begin_draws(); } ~Turn() { r.end_draws(); } } turn(rng);
-    if (rng.unordered() && n >= 1024) {
-      const size_t blocks = (n + 255) / 256;
-      parallel_for(blocks, [&](size_t b) {
-        BatchRng local;
-        for (size_t i = b * 256; i < n && i < (b + 1) * 256; i++) for (uint32_t d = draw_off[i]; d < draw_off[i + 1]; d++) draws[d] = local.next_fr();
-      });
-    } else {
-      for (size_t d = 0; d < draw_off[n]; d++) draws[d] = rng.next_fr();
-    }
-  }
+  draw_items(rng, n, 1024, 256, [&](Rng& r, size_t i) { for (uint32_t d = draw_off[i]; d < draw_off[i + 1]; d++) draws[d] = r.next_fr(); });
   tm.lap("policies + draws");
   Fr a_inv[2] = {must_inv(msk.a[0]), must_inv(msk.a[1])};
   uint8_t* h_scal = eng.pinned(0, total_rows * 96 + n * 96 + 32);          // row scalars | br
