@@ -201,6 +201,20 @@ int32_t rhip_gt_mul(rhip_ctx* ctx, size_t n, const rhip_gt* dev_a, const rhip_gt
 int32_t rhip_gt_product(rhip_ctx* ctx, size_t n_items, const uint32_t* dev_off /*[n_items+1]*/, const rhip_gt* dev_a, rhip_gt* dev_out);
 int32_t rhip_gt_inv(rhip_ctx* ctx, size_t n, const rhip_gt* dev_a, rhip_gt* dev_out);
 int32_t rhip_gt_pow(rhip_ctx* ctx, size_t n, const rhip_gt* dev_a, const rhip_fr* dev_k, rhip_gt* dev_out);
+/* Gt powers of rows that share exponents, the shape of rhip_g2_mul_rows: out[t] = (dev_mul ? mul[t] : 1) * a[t]^(+-k[i]) for the rows t in
+ * [item_row_off[i], item_row_off[i+1]) of item i (n_items + 1 non-decreasing offsets, item_row_off[0] = 0, item_row_off[n_items] =
+ * n_rows; an item may own no row); the sign is minus with RHIP_GT_POW_INVERT (an inverse in Gt is a conjugation: it costs nothing).
+ * What a GHW11 client does with a transformed ciphertext (c * t^-z, src/schemes/ghw11/mod.rs decrypt_out), every record of a call under
+ * the one z.  Frobenius is the power L = p mod r on Gt, so the exponent is split four ways once per item (k = k0 + k1 L + k2 L^2 +
+ * k3 L^3 mod r, |k_i| < 2^65, the split of rhip_g2_mul_rows) and every row runs one joint chain of at most 66 cyclotomic squarings
+ * (bn254/gtpow4.h) instead of rhip_gt_pow's 256.  Any 256-bit scalar word is accepted (0 and multiples of r give 1 -- times mul[t]).
+ * The elements a[t] must be members of Gt (rhip_gt_is_member): for an element outside the order-r subgroup the result is NOT a^k --
+ * rhip_gt_pow is the entry point for those; mul[t] may be any field element.  dev_out may be dev_a or dev_mul.  Same bytes as
+ * rhip_gt_pow followed by rhip_gt_inv / rhip_gt_mul.  The per-item staging of the exponents is zeroed when the call's kernels are done. */
+#define RHIP_GT_POW_INVERT 1u
+int32_t rhip_gt_pow_rows(rhip_ctx* ctx, size_t n_rows, const uint32_t* dev_item_row_off /*[n_items+1]*/, const rhip_gt* dev_a /*[n_rows]*/,
+                         size_t n_items, const rhip_fr* dev_k /*[n_items]*/, const rhip_gt* dev_mul /*[n_rows] or NULL*/, uint32_t flags,
+                         rhip_gt* dev_out /*[n_rows]*/);
 
 /* n independent pairings e(p_i, q_i) */
 int32_t rhip_pairing(rhip_ctx* ctx, size_t n, const rhip_g1* dev_p, const rhip_g2* dev_q, rhip_gt* dev_out);

@@ -46,6 +46,7 @@ int32_t rabe_host_create(int32_t device, rabe_host** out);
  *     rabe_lsw_keygen_packed, rabe_lsw_decrypt_packed, rabe_lsw_decrypt_one_sk_packed, rabe_aw11_encrypt_packed, rabe_aw11_decrypt_packed;
  *   AC17 KP: rabe_ac17_kp_encrypt_packed, rabe_ac17_kp_decrypt_packed;
  *   the KEM pair of both schemes: rabe_ac17_cp_encaps_packed, rabe_ac17_cp_decaps_packed, rabe_bsw_encaps_packed, rabe_bsw_decaps_packed;
+ *   the GHW11 KEM: rabe_ghw11_encaps_packed, rabe_ghw11_decaps_out_packed, rabe_ghw11_decaps_packed;
  *   the GHW11 service: rabe_ghw11_encrypt_packed, rabe_ghw11_transform_packed, rabe_ghw11_decrypt_out_packed, rabe_ghw11_decrypt_packed,
  *     rabe_ghw11_keygen_packed, rabe_ghw11_provision_packed;
  *   the DNF schemes' encrypt: rabe_bdabe_encrypt_packed, rabe_mke08_encrypt_packed.
@@ -372,7 +373,9 @@ int32_t rabe_ghw11_encrypt_packed(rabe_host* h, const void* pk, const char* cons
  * unless RABE_PACKED_TRUSTED -- group membership of every decoded element are checked, an item fails alone with status -1) transformed under
  * ONE transform key.  tct_buf + 768 i receives item i's Ghw11TransformCiphertext record (c | t; zeros where status[i] = -1); returns 1 when
  * tct_cap < 768 n_items.  Under a device group a block writes its slots and verdicts in place (tct_buf + 768 lo, status + lo).  Device-resident: every G2 argument is the key's, so all m + 2 Miller loops of an item replay the key's prepared
- * lines (kept across calls) and the rows that share l_z collapse into one pairing of a multi-scalar sum (ghw11/mod.rs:227-295). */
+ * lines (kept across calls) and the rows that share l_z collapse into one pairing of a multi-scalar sum (ghw11/mod.rs:227-295).
+ * The sealed part of a record is skipped by its length field and never read: the headers rabe_ghw11_encaps_packed writes (an empty sealed
+ * part) pass through this call as full records do, with the same 768-byte output. */
 int32_t rabe_ghw11_transform_packed(rabe_host* h, const void* tk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
                                     const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* tct_buf, size_t tct_cap);
 /* Bulk key issuing (conventions of rabe_bsw_keygen_packed): n_items calls of ghw11::keygen (ghw11/mod.rs:123-152) under one master key, item i
@@ -452,6 +455,33 @@ int32_t rabe_ghw11_decrypt_out_packed(rabe_host* h, const void* rk, size_t n_ite
 int32_t rabe_ghw11_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
                                   const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/,
                                   uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off /*[n_items+1]*/);
+/* ---- GHW11 as a key encapsulation: the packed service WITHOUT payloads (what is said at rabe_ac17_cp_{encaps,decaps}_packed about the format
+ * holds here with Ghw11Ciphertext records).  Outsourced decryption exists so that a thin client does almost nothing: a KEM client holds its
+ * 32-byte z, is handed c | t (768 bytes per item) by the proxy, and computes one Gt power per item -- no ciphertext blob, no policy text, no
+ * G1 element ever reaches it.
+ * ENCAPS: header i is the Ghw11Ciphertext record rabe_ghw11_encrypt_packed writes for the same draws with a sealed part of length zero,
+ *   key_buf + 32 i = SHA3-256(bytes(msg_i)) (the KDF of encrypt_symmetric).  Draw order: encrypt_packed's minus the AES nonce -- per item the
+ *   secret, msg, the gate coefficients, then one t per share.  No seal kernel is launched.  hdr_off is always filled; returns 1, with nothing
+ *   drawn and nothing written, when hdr_cap < hdr_off[n_items].  The staging that held the scalars, msg and the keys is scrubbed.
+ * DECAPS_OUT (the client's half): tct_buf + 768 i = item i's c | t record as rabe_ghw11_transform_packed writes it; key_buf + 32 i =
+ *   SHA3-256(bytes(c_i * t_i^-z)), BY DEFINITION the KDF of what rabe_ghw11_decrypt_out_gt returns.  The power runs over a four-way split of
+ *   z along the Frobenius map (rhip_gt_pow_rows: one split for the call, z uploaded once, at most 66 squarings per item instead of 256, the
+ *   inverse a conjugation, c multiplied in by the same kernel), then the KDF behind the verdict mask.  An item fails alone -- status -1 and
+ *   32 zero bytes -- on an all-zero record (the transform's failure mark) and, unless RABE_PACKED_TRUSTED, when c or t is not a member of Gt.
+ *   With the flag a non-member is not rejected and its key is UNSPECIFIED (the split relies on membership): set it only for records this
+ *   process transformed.  A wrong rk gives another key with status 0: a KEM has no tag.  The staging that held z is zeroed when the call ends.
+ * DECAPS (the holder without a proxy): rabe_ghw11_decrypt_packed's launch set up to c * t_1^-1, then the KDF.  Headers and full records are
+ *   both valid input; the sealed bytes are skipped by their length field, neither read nor authenticated.  Failures and texts are those of
+ *   rabe_ghw11_decrypt_packed; a failed item has status -1 and 32 zero bytes.  No Gt power and no AES kernel is launched.
+ * Under a device group all three are cut as the AC17 / BSW pair is: headers through the producing pipeline, key slots and verdicts in place. */
+int32_t rabe_ghw11_encaps_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
+                                 const uint32_t* item_policy /*[n_items]*/, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off /*[n_items+1]*/,
+                                 uint8_t* key_buf /*32 n_items*/);
+int32_t rabe_ghw11_decaps_out_packed(rabe_host* h, const void* rk, size_t n_items, const uint8_t* tct_buf /*768 n_items*/, uint32_t flags,
+                                     int32_t* status /*[n_items]*/, uint8_t* key_buf /*32 n_items*/);
+int32_t rabe_ghw11_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
+                                 const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/,
+                                 uint8_t* key_buf /*32 n_items*/);
 /* the same for one ciphertext object (one pairing job through rhip_pairing_jobs, as rabe_ghw11_transform); _gt returns c * t_1^-1 */
 int32_t rabe_ghw11_decrypt(rabe_host* h, const void* sk, const void* ct, uint8_t** plaintext, size_t* len);
 int32_t rabe_ghw11_decrypt_gt(rabe_host* h, const void* sk, const void* ct, uint8_t out_gt[384]);

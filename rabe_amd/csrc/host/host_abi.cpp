@@ -2034,6 +2034,51 @@ int32_t rabe_ghw11_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, 
   return 0;
   GUARD_END(h)
 }
+// key encapsulation (include/rabe_host.h).  Over a device group, as the AC17 / BSW pair: the headers through `produce`, a block's 32-byte
+// key slots and verdicts in place through `for_blocks`.
+int32_t rabe_ghw11_encaps_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
+                                 const uint32_t* item_policy, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {
+  GUARD_BEGIN
+  if (!item_policy || !hdr_off) throw RabeError("ghw11::encaps_packed: null input");
+  const auto& key = *(const ghw11::Ghw11PublicKey*)pk;
+  const auto pols = strs(policies, n_policies);
+  const auto lang = lang_of(language);
+  return pipeline::produce(h->engines_if(key_buf != nullptr), h->rng(), n_items, pipeline::GROUP_ONLY,
+                           [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
+    return ghw11::encaps_packed(eng, r, key, pols, lang, hi - lo, item_policy + lo, out, cap, off, key_buf ? key_buf + KEM_KEY * lo : nullptr);
+  }, hdr_buf, hdr_cap, hdr_off) ? 0 : 1;
+  GUARD_END(h)
+}
+int32_t rabe_ghw11_decaps_out_packed(rabe_host* h, const void* rk, size_t n_items, const uint8_t* tct_buf, uint32_t flags, int32_t* status,
+                                     uint8_t* key_buf) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  const auto& key = *(const ghw11::Ghw11RetrieveKey*)rk;
+  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
+  pipeline::for_blocks(h->engines_if(tct_buf && status && key_buf), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
+    ghw11::decaps_out_packed(eng, key, hi - lo, tct_buf ? tct_buf + 768 * lo : nullptr, trusted, status ? status + lo : nullptr,
+                             key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
+    return true;
+  }, &errors);
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
+int32_t rabe_ghw11_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
+                                 int32_t* status, uint8_t* key_buf) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  const auto& key = *(const ghw11::Ghw11SecretKey*)sk;
+  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
+  pipeline::for_blocks(h->engines_if(ct_off && status && key_buf), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
+    ghw11::decaps_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
+                         key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
+    return true;
+  }, &errors);
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
 int32_t rabe_ghw11_decrypt(rabe_host* h, const void* sk, const void* ct, uint8_t** plaintext, size_t* len) {
   GUARD_BEGIN
   return give_bytes(ghw11::decrypt(h->eng, *(const ghw11::Ghw11SecretKey*)sk, *(const ghw11::Ghw11Ciphertext*)ct), plaintext, len);

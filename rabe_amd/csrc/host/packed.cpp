@@ -1929,9 +1929,13 @@ void destroy_keys(void* h) { rhip_ghw11_keys_destroy((rhip_ghw11_keys*)h); }
 // reference (:195-197) and the object API, an empty plaintext is encrypted.  Record = Ghw11Ciphertext:
 //   policy text, language, c, c1, row count, per row (name_col, C_i = g1_a * share - (g1 * h(name)) * t_i, D_i = g1 * t_i), sealed data.
 // The rows are one lane each (k_ghw11_enc_rows): share, both walks of C on one accumulator, D, one inversion per block.
-bool encrypt_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
-                    const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  Timer tm("ghw11::encrypt_packed");
+// key_buf != nullptr is the key encapsulation (encaps_packed below): no plaintexts, no nonce draw, records that end in the length field of an
+// empty sealed part, and per item the content key SHA3-256(bytes(msg)) instead of a payload sealed under it.
+static bool encrypt_core(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                         const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off,
+                         uint8_t* key_buf) {
+  const bool kem = key_buf != nullptr;
+  Timer tm(kem ? "ghw11::encaps_packed" : "ghw11::encrypt_packed");
   Engine::ArenaScope arena(eng);
   ShareTrees st;
   for (const auto& p : policies) st.add(p, language);
@@ -1939,7 +1943,7 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::
   std::vector<size_t> fixed(policies.size());
   for (size_t p = 0; p < policies.size(); p++)
     fixed[p] = 4 + policies[p].size() + 1 + 384 + 64 + 4 + pols[p]->leaf_name.size() * (4 + 64 + 64) + pols[p]->names_bytes + 4;
-  if (!record_offsets("ghw11::encrypt_packed", "item_policy", n, item_policy, policies.size(), fixed, pt_off, out_buf, out_cap, out_off)) return false;
+  if (!record_offsets("ghw11::encrypt_packed", "item_policy", n, item_policy, policies.size(), fixed, kem ? nullptr : pt_off, out_buf, out_cap, out_off)) return false;
   st.place(n, item_policy, 1);
   const std::vector<uint32_t>&leaf_off = st.leaf_off, &coef_off = st.coef_off;
   const size_t total = st.total, total_coef = st.total_coef;
@@ -1957,7 +1961,7 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::
     memcpy(h_rho + 32 * i, rho.l, 32);
     for (uint32_t c = coef_off[i]; c < coef_off[i + 1]; c++) { Fr a = r.next_fr(); memcpy(h_coef + 32 * (size_t)c, a.l, 32); }
     for (uint32_t y = leaf_off[i]; y < leaf_off[i + 1]; y++) { Fr t = r.next_fr(); memcpy(h_t + 32 * (size_t)y, t.l, 32); }
-    r.fill(nonces[i].data(), 12);
+    if (!kem) r.fill(nonces[i].data(), 12);
   });
   tm.lap("draws");
   rhip_ctx* cx = eng.ctx();
@@ -1987,13 +1991,35 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::
       L.src(2, (uint32_t)(128 * y), 128);          // C | D, adjacent in the row kernel's output as in the record
     }
     if (L.bytes() + 4 != fixed[p_]) throw RabeError("ghw11::encrypt_packed: record layout and size disagree");
+    if (kem) L.u32(0);          // the length field of an empty sealed part; no sealed source
   }
   std::vector<uint64_t> src_off(3 * n);
   for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * i; src_off[n + i] = 64ull * i; src_off[2 * n + i] = 128ull * leaf_off[i]; }
+  if (kem) {          // headers from the template alone, keys straight out of the msg array: no seal kernel is launched
+    DBuf d_keys(&eng, n * 32 + 4);
+    eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
+    eng.check(rhip_gt_kdf_batch(cx, n, d_msg.as<rhip_gt>(), nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
+    emit_plain_records(eng, layouts, n, item_policy, {d_c.ptr(), d_c1.ptr(), d_cd.ptr()}, src_off, out_off, out_buf);
+    if (n) eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
+    tm.lap("device: group arithmetic, headers, keys; two copies out");
+    return true;
+  }
   emit_sealed_records(eng, layouts, n, item_policy, {d_c.ptr(), d_c1.ptr(), d_cd.ptr()}, src_off, d_msg.ptr(), (const uint8_t*)nonces.data(),
                       pt_blob, pt_off, out_off, out_buf);
   tm.lap("device: group arithmetic, records, sealing; one copy out");
   return true;
+}
+bool encrypt_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                    const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  return encrypt_core(eng, rng, pk, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off, nullptr);
+}
+// n key encapsulations: record i is the Ghw11Ciphertext header encrypt_packed writes for the same draws with an empty sealed part (its draws
+// minus the AES nonce), key_buf + 32 i = SHA3-256(bytes(msg_i)).  Headers pass through transform_packed, which never reads the sealed part.
+bool encaps_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                   const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  if (n && !key_buf) throw RabeError("ghw11::encaps_packed: null input");
+  if (!n) { out_off[0] = 0; return true; }
+  return encrypt_core(eng, rng, pk, policies, language, n, item_policy, nullptr, nullptr, out_buf, out_cap, out_off, key_buf);
 }
 
 // n calls of ghw11::decrypt_out (ghw11/mod.rs:297-305) under ONE retrieve key -- the client's half after transform_packed.  Item i: the
@@ -2265,13 +2291,17 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
 // verdicts come back.  Failures stay with their item, with transform_packed's error texts (bounds, a malformed record, a policy the key does
 // not satisfy, a missing row name, a non-member unless trusted) or decrypt_out_packed's (trailing bytes, a tag that does not verify): status
 // -1 and an EMPTY plaintext slot.  pt_cap below the sealed lengths of the well-formed records: returns false with that size in pt_off[n].
-bool decrypt_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                    int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
-  Timer tm("ghw11::decrypt_packed");
+// key_buf != nullptr is the key decapsulation (decaps_packed below): the same launch set up to msg = c * t_1^-1, then the KDF behind the verdict
+// mask (records.h: derive_keys) instead of the open; pt_buf / pt_cap / pt_off are unused, the sealed part is skipped by its length field and never
+// read -- headers (an empty sealed part) and full records give the same key.
+static bool decrypt_core(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                         int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors, uint8_t* key_buf) {
+  const bool kem = key_buf != nullptr;
+  Timer tm(kem ? "ghw11::decaps_packed" : "ghw11::decrypt_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
-  if (!ct_off || !pt_off || (n && (!ct_blob || !status))) throw RabeError("ghw11::decrypt_packed: null input");
-  if (!n) { pt_off[0] = 0; return true; }
+  if (!ct_off || (!kem && !pt_off) || (n && (!ct_blob || !status))) throw RabeError("ghw11::decrypt_packed: null input");
+  if (!n) { if (!kem) pt_off[0] = 0; return true; }
   (void)check_offsets(n, ct_off, ct_len, errors);
   BlobGather gather(eng, ct_blob, ct_len);          // the blob starts for the device now, beside the parsing below (records.h)
   CtBatch b;
@@ -2279,7 +2309,7 @@ bool decrypt_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8
   tm.lap("parse + plan");
   uint64_t need = 0;
   for (size_t i = 0; i < n; i++) if (b.parsed[i]) need += b.sealed[i].len;
-  if (!pt_buf || pt_cap < need) { pt_off[n] = need; return false; }
+  if (!kem && (!pt_buf || pt_cap < need)) { pt_off[n] = need; return false; }
   b.select(n, *errors);
   const Selection& sel = b.sel;
   const std::vector<size_t>& live = sel.live;
@@ -2330,6 +2360,11 @@ bool decrypt_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8
         if (!ok_c1[j] || !ok_ci[j] || !ok_di[j] || !ok_c[j]) (*errors)[live[j]] = "deserialize: a ciphertext element is not a group member (FieldError::NotMember)";
     }
   }
+  if (kem) {
+    derive_keys(eng, n, live, d_msg.ptr(), status, key_buf, *errors);
+    tm.lap(trusted ? "device: gather, pairings, keys" : "device: gather, pairings, keys; membership beside");
+    return true;
+  }
   // KDF + AES-GCM open on the device: msg never leaves HBM; plaintext bytes come back in one copy
   open_sealed_records(eng, n, live, d_msg.ptr(), gather.dev_blob(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
   // a tag that did not verify leaves a zeroed slot behind: close it up, so that every failed item has an empty one
@@ -2347,6 +2382,77 @@ bool decrypt_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8
   }
   tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
   return true;
+}
+bool decrypt_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                    int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
+  return decrypt_core(eng, sk, n, ct_blob, ct_len, ct_off, trusted, status, pt_buf, pt_cap, pt_off, errors, nullptr);
+}
+void decaps_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                   int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
+  if (n && (!status || !key_buf)) throw RabeError("ghw11::decaps_packed: null input");
+  uint8_t none = 0;          // n = 0: nothing is written
+  decrypt_core(eng, sk, n, ct_blob, ct_len, ct_off, trusted, status, nullptr, 0, nullptr, errors, key_buf ? key_buf : &none);
+}
+// n key decapsulations of a thin client under ONE retrieve key: item i is the Ghw11TransformCiphertext record c | t at tct + 768 i and nothing
+// else -- no ciphertext blob.  key_buf + 32 i = SHA3-256(bytes(c_i * t_i^-z)), the KDF of what decrypt_out_gt returns.  On the device: ONE
+// rhip_gt_pow_rows call over the live records (one item, every row under the one z uploaded once, mul = c, the inverse a conjugation), then
+// the KDF behind the verdict mask.  An item fails alone (status -1, 32 zero bytes): an all-zero tct record (transform_packed's failure mark);
+// c or t not in Gt unless trusted -- with trusted a non-member's key is unspecified (the power's split assumes the order-r subgroup).
+void decaps_out_packed(Engine& eng, const Ghw11RetrieveKey& rk, size_t n, const uint8_t* tct, bool trusted, int32_t* status, uint8_t* key_buf,
+                       std::vector<std::string>* errors) {
+  Timer tm("ghw11::decaps_out_packed");
+  Engine::ArenaScope arena(eng);
+  errors->assign(n, "");
+  if (n && (!tct || !status || !key_buf)) throw RabeError("ghw11::decaps_out_packed: null input");
+  if (!n) return;
+  std::vector<size_t> live;
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t* rec = tct + 768 * i;
+    bool zero = true;
+    for (size_t b = 0; b < 768 && zero; b++) zero = rec[b] == 0;
+    if (zero) (*errors)[i] = "ghw11::decaps_out_packed: no transformed ciphertext for this item (transform failed)";
+    else live.push_back(i);
+  }
+  const size_t m = live.size();
+  if (m > 0xFFFFFFF0ull) throw RabeError("ghw11::decaps_out_packed: more than 2^32 records in one call");
+  DBuf d_msg(&eng, m * 384 + 4);
+  if (m) {
+    eng.scrub_when_done();          // z and the messages pass through the staging buffers
+    rhip_ctx* cx = eng.ctx();
+    uint8_t* h = eng.pinned(0, m * 768 + 32);          // c of the live items | t of the live items | z
+    uint8_t* h_t = h + m * 384;
+    uint8_t* h_k = h + m * 768;
+    parallel_for(m, [&](size_t j) {
+      const uint8_t* rec = tct + 768 * live[j];
+      memcpy(h + 384 * j, rec, 384);
+      memcpy(h_t + 384 * j, rec + 384, 384);
+    });
+    memcpy(h_k, rk.z.l, 32);
+    tm.lap("pack");
+    const std::vector<uint32_t> row_off{0, (uint32_t)m};          // one item: every record under the one z
+    DBuf d_ct(&eng, m * 768), d_k(&eng, 32), d_off = up32(eng, row_off);
+    eng.check(rhip_upload_async(cx, d_ct.ptr(), h, m * 768), "upload");
+    eng.check(rhip_upload_async(cx, d_k.ptr(), h_k, 32), "upload");
+    const rhip_gt* d_c = d_ct.as<rhip_gt>();
+    const rhip_gt* d_t = d_c + m;
+    std::unique_ptr<MemberChecks> mc;
+    if (!trusted) {
+      mc.reset(new MemberChecks(eng));
+      mc->add(3, d_c, m);
+      mc->add(3, d_t, m);
+    }
+    eng.check(rhip_gt_pow_rows(cx, m, d_off.as<uint32_t>(), d_t, 1, d_k.as<rhip_fr>(), d_c, RHIP_GT_POW_INVERT, d_msg.as<rhip_gt>()), "rhip_gt_pow_rows");
+    if (mc) {
+      mc->collect();
+      const auto &ok_c = mc->ok(0), &ok_t = mc->ok(1);
+      for (size_t j = 0; j < m; j++) {
+        if (!ok_c[j]) (*errors)[live[j]] = "deserialize: c is not a member of Gt (FieldError::NotMember)";
+        else if (!ok_t[j]) (*errors)[live[j]] = "deserialize: t is not a member of Gt (FieldError::NotMember)";
+      }
+    }
+  }
+  derive_keys(eng, n, live, d_msg.ptr(), status, key_buf, *errors);
+  tm.lap(trusted ? "device: power, keys" : "device: power, keys; membership beside");
 }
 // n calls of ghw11::keygen (ghw11/mod.rs:123-152) under one master key.  Item i gets the attribute list sets[item_set[i]]; draw order: one r
 // per item, in item order (:130).  Record = Ghw11SecretKey: k, l, rows (name, k_x).  Every element is a fixed-base multiple (the hash to G2

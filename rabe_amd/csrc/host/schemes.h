@@ -236,6 +236,15 @@ bool decrypt_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8
                     int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors);
 Gt decrypt_out_gt(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11RetrieveKey& rk);
 Bytes decrypt_out(Engine& eng, const Ghw11TransformCiphertext& pct, const Ghw11RetrieveKey& rk, const Bytes& data);
+// key encapsulation (packed.cpp; include/rabe_host.h: rabe_ghw11_{encaps,decaps_out,decaps}_packed): encrypt_packed's records with an empty
+// sealed part and the content keys SHA3-256(bytes(msg)); the thin client's half over 768-byte c | t records alone (one Gt power over a
+// four-way split per item, rhip_gt_pow_rows); the key holder's own decaps (decrypt_packed's launch set up to c * t_1^-1, then the KDF)
+bool encaps_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                   const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf);
+void decaps_out_packed(Engine& eng, const Ghw11RetrieveKey& rk, size_t n, const uint8_t* tct, bool trusted, int32_t* status, uint8_t* key_buf,
+                       std::vector<std::string>* errors);
+void decaps_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                   int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors);
 }  // namespace ghw11
 
 namespace dnfabe {

@@ -267,6 +267,29 @@ class Engine:
     def gt_pow(self, a, k): return self._elem("rhip_gt_pow", len(a), [a, k], GT)
     def pairing(self, p, q): return self._elem("rhip_pairing", len(p), [p, q], GT)
 
+    def gt_pow_rows(self, a, item_row_off, scalars, mul=None, invert=False):
+        """out[t] = (mul[t] if mul else 1) * a[t]^(+-scalars[i]) for the rows t of item i, minus with invert (rhip_gt_pow_rows: one four-way
+        split over the Frobenius map per scalar, one joint chain of at most 66 squarings per row); item_row_off: len(scalars) + 1
+        non-decreasing offsets ending at len(a).  The elements of `a` must be members of Gt.  Same bytes as gt_pow + gt_inv / gt_mul."""
+        n_rows, n_items = len(a), len(scalars)
+        if len(item_row_off) != n_items + 1 or item_row_off[0] != 0 or item_row_off[-1] != n_rows:
+            raise ValueError("gt_pow_rows: item_row_off must run from 0 to len(a) in len(scalars) + 1 entries")
+        if any(item_row_off[i] > item_row_off[i + 1] for i in range(n_items)):
+            raise ValueError("gt_pow_rows: item_row_off must not decrease")
+        if mul is not None and len(mul) != n_rows:
+            raise ValueError("gt_pow_rows: one mul element per row")
+        if not n_rows:
+            self._check(self.lib.rhip_gt_pow_rows(self.ctx, ctypes.c_size_t(0), None, None, ctypes.c_size_t(n_items), None, None,
+                                                  ctypes.c_uint32(1 if invert else 0), None))
+            return []
+        da, dk, doff = self.upload(b"".join(a)), self.upload(b"".join(scalars)), self.upload_u32(item_row_off)
+        dm = self.upload(b"".join(mul)) if mul is not None else None
+        out = self.alloc(n_rows * GT)
+        self._check(self.lib.rhip_gt_pow_rows(self.ctx, ctypes.c_size_t(n_rows), doff.ptr, da.ptr, ctypes.c_size_t(n_items), dk.ptr,
+                                              dm.ptr if dm is not None else None, ctypes.c_uint32(1 if invert else 0), out.ptr))
+        raw = self.download(out, n_rows * GT)
+        return [raw[i * GT:(i + 1) * GT] for i in range(n_rows)]
+
     def g1_on_curve(self, p):
         return [int.from_bytes(x, "little") for x in self._elem("rhip_g1_on_curve", len(p), [p], 4)]
 

@@ -124,6 +124,38 @@ def decrypt_out_packed(host, rk, tct, ct_blob, ct_off, trusted=False):
     return buf[:int(po[n])], po, status[:n]
 
 
+# ---- key encapsulation (rabe_ghw11_{encaps,decaps_out,decaps}_packed): the packed service without payloads
+def encaps_packed(host, pk, policies, item_policy, language=JSON_POLICY, out=None):
+    """n key encapsulations (rabe_ghw11_encaps_packed): header i is the Ghw11Ciphertext record encrypt_packed writes for the same draws
+    with an empty sealed part; transform_packed takes the headers as they are.  Returns (hdr_blob, hdr_off uint64 [n+1], keys uint8 [n, 32])."""
+    from ..hostlib import packed_encaps
+    return packed_encaps(host, "rabe_ghw11_encaps_packed", (pk.ptr,), policies, item_policy, language, out)
+
+
+def decaps_out_packed(host, rk, tct, trusted=False):
+    """the thin client's half (rabe_ghw11_decaps_out_packed): `tct` = the [n, 768] array transform_packed returns (or its bytes) and nothing
+    else -- no ciphertext blob.  Row i of the result = SHA3-256(bytes(c_i * t_i^-z)): the KDF of decrypt_out_gt.  Returns (keys uint8
+    [n, 32] -- zeros where status is -1 --, status int32 [n]).  With trusted=True a non-member's key is unspecified."""
+    import numpy as np
+    from ..hostlib import PACKED_TRUSTED, _as_u8, _np_ptr
+    t = np.ascontiguousarray(_as_u8(tct) if not isinstance(tct, np.ndarray) else tct, dtype=np.uint8).reshape(-1)
+    if t.size % 768:
+        raise ValueError("decaps_out_packed: tct holds %d bytes, not a whole number of 768-byte records" % t.size)
+    n = t.size // 768
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    keys = np.full((max(n, 1), 32), 0xEE, dtype=np.uint8)
+    host.call("rabe_ghw11_decaps_out_packed", rk.ptr, ctypes.c_size_t(n), _np_ptr(t), ctypes.c_uint32(PACKED_TRUSTED if trusted else 0),
+              _np_ptr(status), _np_ptr(keys))
+    return keys[:n], status[:n]
+
+
+def decaps_packed(host, sk, ct_blob, ct_off, trusted=False):
+    """the key holder's own decapsulation, no proxy (rabe_ghw11_decaps_packed): headers from encaps_packed or full records from
+    encrypt_packed; the sealed part is skipped, never read.  Returns (keys uint8 [n, 32] -- zeros where status is -1 --, status int32 [n])."""
+    from ..hostlib import packed_decaps
+    return packed_decaps(host, "rabe_ghw11_decaps_packed", (sk.ptr,), ct_blob, ct_off, trusted)
+
+
 def keygen_packed(host, pk, msk, attr_sets, item_set, out=None):
     """n keys under one master key (rabe_ghw11_keygen_packed): attr_sets = distinct attribute lists, item_set[i] indexes them.
     Returns (sk_blob: numpy uint8 view of the Ghw11SecretKey records, sk_off: numpy uint64 [n+1])."""
