@@ -500,6 +500,20 @@ int32_t rhip_lsw_decrypt_batch_one_sk(rhip_ctx* ctx, size_t n_items, size_t max_
                                       const rhip_gt* dev_ct_e1 /*[n_items]*/, const rhip_g2* dev_ct_e2 /*[n_items]*/,
                                       const rhip_g1* dev_ct_e1j /*[ct attribute rows]: ej.1*/, const uint32_t* dev_ct_attr_off /*[n_items+1]*/,
                                       const rhip_g1* dev_sk_d1 /*[the key's leaf rows]*/, const rhip_g2_lines* sk_d2_lines, rhip_gt* dev_out /*[n_items]*/);
+/* The attribute rows of n_items calls of lsw::encrypt (lsw/mod.rs:201-208), one lane per row (k_lsw_enc_rows).  The four tables are window
+ * tables with 16-bit windows (rhip_g1_table_add_w16) of the public key's g1, g1_b, g1_b2 and h_b.  Item i owns rows
+ * [item_row_off[i], item_row_off[i+1]); row t of it has the attribute hash h = dev_hash[item_hash_off[i] + t - item_row_off[i]] (items with
+ * the same attribute list share their hashes) and the scalar dev_sx[t], which the caller supplies as the reference's loop leaves it (:197-200:
+ * the first row's loses sx[i], not the new element -- zero for a list of one attribute).  The products h secret and sx h are formed on the device.
+ *   out[3 t] = e3 = g1 * (h secret_i)     out[3 t + 1] = e4 = g1_b * sx     out[3 t + 2] = e5 = g1_b2 * (sx h) + h_b * sx
+ * e5 is two walks on one accumulator; the three conversions of a row share one inversion, and a block its rows'.  An element that is the
+ * identity (sx = 0, h secret = 0, or the two halves of e5 cancelling) is 64 zero bytes, and its neighbours in the row are unaffected.  The
+ * bytes are those of rhip_g1_table_mul over host-formed products followed by rhip_g1_add.  The item-level elements (e1, e2) are not
+ * computed here. */
+int32_t rhip_lsw_encrypt_rows(rhip_ctx* ctx, const rhip_g1_table* g1, const rhip_g1_table* g1_b, const rhip_g1_table* g1_b2, const rhip_g1_table* h_b,
+                              size_t n_items, size_t total_rows, const uint32_t* dev_item_row_off /*[n_items+1]*/,
+                              const uint32_t* dev_item_hash_off /*[n_items]*/, const rhip_fr* dev_hash, const rhip_fr* dev_secret /*[n_items]*/,
+                              const rhip_fr* dev_sx /*[total_rows]*/, rhip_g1* dev_out /*[3 total_rows]: e3, e4, e5 per row*/);
 
 /* ---- Level B: GHW11 outsourced decryption (src/schemes/ghw11/mod.rs:227-295) ----------------------
  * Group arithmetic of n_items calls of ghw11::transform under ONE transform key.  tk_lines = rhip_g2_lines_prepare over the key's G2

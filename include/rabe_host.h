@@ -47,6 +47,7 @@ int32_t rabe_host_create(int32_t device, rabe_host** out);
  *   AC17 KP: rabe_ac17_kp_encrypt_packed, rabe_ac17_kp_decrypt_packed;
  *   the KEM pair of both schemes: rabe_ac17_cp_encaps_packed, rabe_ac17_cp_decaps_packed, rabe_bsw_encaps_packed, rabe_bsw_decaps_packed;
  *   the GHW11 KEM: rabe_ghw11_encaps_packed, rabe_ghw11_decaps_out_packed, rabe_ghw11_decaps_packed;
+ *   the key-policy KEMs: rabe_ac17_kp_encaps_packed, rabe_ac17_kp_decaps_packed, rabe_lsw_decaps_packed;
  *   the GHW11 service: rabe_ghw11_encrypt_packed, rabe_ghw11_transform_packed, rabe_ghw11_decrypt_out_packed, rabe_ghw11_decrypt_packed,
  *     rabe_ghw11_keygen_packed, rabe_ghw11_provision_packed;
  *   the DNF schemes' encrypt: rabe_bdabe_encrypt_packed, rabe_mke08_encrypt_packed.
@@ -63,7 +64,7 @@ int32_t rabe_host_create(int32_t device, rabe_host** out);
  * sealed parts (every block is handed the slice its records span); see the calls' own comments.
  * NOT sharded, on devices[0]: rabe_ghw11_tkgen_packed (what it draws depends on which records decode on the host; the call is
  * host-bound), the bulk keygen_packed calls of ac17 / bsw / aw11 / bdabe / mke08, the request_*_sk_packed pair, rabe_bsw_delegate_packed,
- * rabe_lsw_encrypt_packed, rabe_{bdabe,mke08}_decrypt_packed, the object API and the submission queue.
+ * rabe_lsw_encrypt_packed, rabe_lsw_encaps_packed, rabe_{bdabe,mke08}_decrypt_packed, the object API and the submission queue.
  * Status: as rabe_host_create_checked. */
 int32_t rabe_host_open_group_checked(int32_t abi_version, size_t n_devices, const int32_t* devices, rabe_host** out);
 #define rabe_host_open_group(n_devices, devices, out) rabe_host_open_group_checked(RABE_HOST_ABI_VERSION, (n_devices), (devices), (out))
@@ -180,7 +181,7 @@ int32_t rabe_ac17_cp_decrypt_packed(rabe_host* h, const void* sk, size_t n_items
 /* ---- key encapsulation: the packed pair WITHOUT payloads.  A caller that seals large objects where they live (files, streams, rows) wants per
  * item the ciphertext HEADER and the 32-byte content key the reference's kdf derives (src/utils/aes/mod.rs:47-55), and on the other side the same
  * 32 bytes back from the header and a secret key.  Not functions of the reference but compositions of functions that are (as
- * rabe_ghw11_provision_packed is).  Built for ac17 (CP) and bsw; all four calls are sharded over a device group (a block's headers at their
+ * rabe_ghw11_provision_packed is).  Built for ac17 (CP) and bsw here, for ac17 (KP), lsw and ghw11 below; all four calls are sharded over a device group (a block's headers at their
  * offsets, its keys and verdicts at key_buf + 32 lo and status + lo).
  *   key = SHA3-256(bytes(Gt)): bytes(Gt) is the byte form the reference's kdf hashes -- the 12 coefficients in wire order, each as 32 BIG-endian
  *   bytes -- i.e. exactly the AES key rabe_encrypt_symmetric / rabe_decrypt_symmetric derive from that Gt.
@@ -231,6 +232,15 @@ int32_t rabe_ac17_kp_encrypt_packed(rabe_host* h, const void* pk, const char* co
 int32_t rabe_ac17_kp_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
                                     const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* pt_buf, size_t pt_cap,
                                     uint64_t* pt_off /*[n_items+1]*/);
+/* Key encapsulation for the KP pair: everything said at rabe_ac17_cp_{encaps,decaps}_packed, with Ac17KpCiphertext records,
+ * rabe_ac17_kp_encrypt_packed / rabe_ac17_kp_decrypt_packed as the calls composed (their arguments minus the payloads, plus key_buf) and
+ * rabe_ac17_kp_decrypt_gt as the definition of X.  ENCAPS DRAW ORDER: rabe_ac17_kp_encrypt_packed's minus the AES nonce -- per item s0, s1,
+ * msg.  The kernels are the CP pair's.  Both calls are cut over a device group where the calls they compose are cut. */
+int32_t rabe_ac17_kp_encaps_packed(rabe_host* h, const void* pk, const char* const* attributes, const size_t* counts, size_t n_sets, size_t n_items,
+                                   const uint32_t* item_set /*[n_items]*/, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off /*[n_items+1]*/,
+                                   uint8_t* key_buf /*32 n_items*/);
+int32_t rabe_ac17_kp_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
+                                   const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* key_buf /*32 n_items*/);
 /* n independent kp_encrypt / kp_decrypt calls in one launch set; item i's attributes are the next counts[i] entries of `attributes` */
 int32_t rabe_ac17_kp_encrypt_batch(rabe_host* h, const void* pk, size_t n, const char* const* attributes, const size_t* counts,
                                    const uint8_t* const* datas, const size_t* lens, void** cts);
@@ -322,6 +332,23 @@ int32_t rabe_lsw_decrypt_packed(rabe_host* h, const void* ct, size_t n_items, co
 int32_t rabe_lsw_decrypt_one_sk_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
                                        const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/,
                                        uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off /*[n_items+1]*/);
+/* Key encapsulation for lsw: everything said at rabe_ac17_cp_{encaps,decaps}_packed about the format, the key, the failure of an item alone,
+ * RABE_PACKED_TRUSTED, the bounds and the scrubbed staging, with KpAbeCiphertext records and rabe_lsw_decrypt_gt as the definition of X.
+ * ENCAPS: arguments of rabe_lsw_encrypt_packed minus the payloads, plus key_buf.  Header i is the record rabe_lsw_encrypt_packed writes for the
+ *   same draws with a sealed part of length zero.  DRAW ORDER: rabe_lsw_encrypt_packed's minus the AES nonce -- per item secret, one sx per
+ *   attribute, the msg exponent.  The attribute rows come from ONE fused kernel (rhip_lsw_encrypt_rows: one lane per row, the products
+ *   h secret and sx h formed on the device, 32 uploaded bytes per row, one inversion per block) where rabe_lsw_encrypt_packed runs four table
+ *   launches and an addition; the bytes are the same.  e1 and e2 keep their table calls; no AES kernel is launched.  Like
+ *   rabe_lsw_encrypt_packed the call is NOT cut over a device group: it runs on the group's first device.
+ * DECAPS: ONE key of the holder's own against n_items records, arguments of rabe_lsw_decrypt_one_sk_packed with key_buf in place of the
+ *   plaintext buffers.  Headers and full records are both valid input.  The launch set is rabe_lsw_decrypt_one_sk_packed's up to the final Gt
+ *   (shared plans per list of row names, the key's prepared lines, the membership checks), then the KDF behind the verdict mask and one
+ *   download of 32 n_items bytes.  A selected negative attribute fails the item.  Cut over a device group as rabe_lsw_decrypt_one_sk_packed is. */
+int32_t rabe_lsw_encaps_packed(rabe_host* h, const void* pk, const char* const* attributes, const size_t* counts, size_t n_sets, size_t n_items,
+                               const uint32_t* item_set /*[n_items]*/, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off /*[n_items+1]*/,
+                               uint8_t* key_buf /*32 n_items*/);
+int32_t rabe_lsw_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
+                               const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* key_buf /*32 n_items*/);
 
 /* ---- aw11 (src/schemes/aw11/mod.rs:100-390) */
 int32_t rabe_aw11_setup(rabe_host* h, void** gk);

@@ -2,12 +2,14 @@
 // share a scalar (four-way split over the twist endomorphism, bn254/gls4.h), which serves ghw11::tkgen; the user-key row kernels of
 // BDABE / MKE08 (fixed-base) and the variable-base G1 multiplication over rows that share a scalar (GLV, bn254/curve.h), which with the G2
 // one serves their secret attribute keys; GHW11's fused keygen + tkgen for an authority that knows r and z (fixed-base again: an Fr kernel
-// that inverts the z of a block together, and a row kernel over a third window table).
+// that inverts the z of a block together, and a row kernel over a third window table); the LSW ciphertext rows (fixed-base: three elements
+// per lane, four walks, one inversion per block -- bn254/lsw_rows.h).
 //
 // A translation unit of its own: docs/rr29.md records that adding a kernel to a unit can move its neighbours' register allocation, and
 // engine_jobs.hip holds the kernels BASELINE configs 3 - 5 time.
 #include "engine_internal.h"
 #include "bn254/gls4.h"
+#include "bn254/lsw_rows.h"
 #include <mutex>
 
 // Montgomery records are 128 bytes and 16-byte aligned: 128-bit accesses
@@ -602,5 +604,65 @@ extern "C" int32_t rhip_dnf_keygen_batch(rhip_ctx* ctx, const rhip_dnf_keys* key
           (const G1M*)keys->g1->dev16, (const rhip_g1*)keys->a1, n_rows, r, out_g1);
   KLAUNCH(ctx, "k_dnf_keygen_g2", k_dnf_keygen_g2, dim3(blocks_for(n_rows, 128)), dim3(128), 0, ctx->stream, (const G2M*)keys->p2->dev16,
           (const G2M*)keys->g2->dev16, (const rhip_g2*)keys->a2, n_rows, r, out_g2);
+  return RHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ LSW ciphertext rows
+// the lane routine and the three-point conversion are host + device code (bn254/lsw_rows.h): the CPU check runs the same text
+struct W16Table {
+  const G1M* t;
+  __device__ __forceinline__ G1Aff entry(int w, uint32_t d) const { return ld_g1_m(t + (size_t)w * TBL16_DIGITS + (d - 1)); }
+};
+// one lane per ciphertext row (lsw/mod.rs:201-208); row t belongs to the item i with item_row_off[i] <= t < item_row_off[i+1], its
+// attribute hash is h = hash[item_hash_off[i] + t - item_row_off[i]], its scalar sx[t]:
+//   out[3 t]     = e3 = g1 * (h secret_i)
+//   out[3 t + 1] = e4 = g1_b * sx
+//   out[3 t + 2] = e5 = g1_b2 * (sx h) + h_b * sx          both walks on ONE accumulator (no point buffer, no separate addition)
+// The two products are formed in the lane.  ONE accumulator is live at a time: e3 and e4 are PARKED, as Jacobian Montgomery values, in the
+// row's own output slots (3 x 64 B of affine output = 2 x 96 B) while the next element is walked, and read back into registers before the
+// first affine point is stored over them.  The three conversions of a lane share one inversion, and the block's lanes share theirs: ONE
+// field inversion per block.  An element that is the identity -- sx = 0 (the row of a one-attribute list, as the reference's loop is written),
+// h secret = 0, or the two halves of e5 cancelling -- enters the shared product as one and is stored as 64 zero bytes (bn254/lsw_rows.h).
+__global__ void __launch_bounds__(RB_ROWS_BLOCK, 2) k_lsw_enc_rows(const G1M* g1_tbl, const G1M* g1b_tbl, const G1M* g1b2_tbl, const G1M* hb_tbl, size_t n_items,
+                                                                   size_t total_rows, const uint32_t* item_row_off, const uint32_t* item_hash_off,
+                                                                   const rhip_fr* hash, const rhip_fr* secret, const rhip_fr* sx, rhip_g1* out) {
+  __shared__ uint32_t sh[2 * 8 * RB_ROWS_BLOCK];
+  size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool active = t < total_rows;
+  if (!active) t = total_rows - 1;          // inactive lanes shadow the last row (no stores) and still join the block inversion
+  const size_t item = owner_of(item_row_off, n_items, t);
+  const rhip_fr* hp = hash + ((size_t)item_hash_off[item] + (t - item_row_off[item]));
+  G1Jac* park = (G1Jac*)(out + 3 * t);
+  G1Jac r = lsw_row_e3(W16Table{g1_tbl}, load_fr(hp->l), load_fr(secret[item].l));
+  if (active) park[0] = r;
+  uint32_t kk[8];
+  ld_scalar(kk, sx + t);
+  r = lsw_row_e4(W16Table{g1b_tbl}, kk);
+  if (active) park[1] = r;
+  r = lsw_row_e5(W16Table{g1b2_tbl}, W16Table{hb_tbl}, load_fr(hp->l), kk);
+  G1Jac a = jac_inf<Fp>(), b = jac_inf<Fp>();
+  if (active) { a = park[0]; b = park[1]; }
+  G1Three z;
+  const Fp abc = g1_three_product(z, a, b, r);
+  const Fp inv_abc = block_batch_inverse_n<RB_ROWS_BLOCK>(sh, active ? abc : one<FpParams>());
+  if (!active) return;
+  G1Aff e[3];
+  g1_three_to_aff(z, inv_abc, a, b, r, e);
+  store_g1(out[3 * t].l, e[0]);
+  store_g1(out[3 * t + 1].l, e[1]);
+  store_g1(out[3 * t + 2].l, e[2]);
+}
+static_assert(2 * sizeof(G1Jac) == 3 * sizeof(rhip_g1), "two parked Jacobian points fill a row's three output records");
+extern "C" int32_t rhip_lsw_encrypt_rows(rhip_ctx* ctx, const rhip_g1_table* g1, const rhip_g1_table* g1_b, const rhip_g1_table* g1_b2, const rhip_g1_table* h_b,
+                                         size_t n_items, size_t total_rows, const uint32_t* item_row_off, const uint32_t* item_hash_off, const rhip_fr* hash,
+                                         const rhip_fr* secret, const rhip_fr* sx, rhip_g1* out) {
+  NEED(ctx);
+  if (!g1 || !g1_b || !g1_b2 || !h_b) return RHIP_ERR_ARG;
+  if (!n_items || !total_rows) return RHIP_OK;
+  if (!item_row_off || !item_hash_off || !hash || !secret || !sx || !out) return RHIP_ERR_ARG;
+  if (!g1->dev16 || !g1_b->dev16 || !g1_b2->dev16 || !h_b->dev16)
+    return fail(ctx, hipErrorInvalidValue, "rhip_lsw_encrypt_rows: the G1 tables have no 16-bit windows (rhip_g1_table_add_w16)");
+  KLAUNCH(ctx, "k_lsw_enc_rows", k_lsw_enc_rows, dim3(blocks_for(total_rows, RB_ROWS_BLOCK)), dim3(RB_ROWS_BLOCK), 0, ctx->stream, (const G1M*)g1->dev16,
+          (const G1M*)g1_b->dev16, (const G1M*)g1_b2->dev16, (const G1M*)h_b->dev16, n_items, total_rows, item_row_off, item_hash_off, hash, secret, sx, out);
   return RHIP_OK;
 }

@@ -1271,6 +1271,37 @@ int32_t rabe_ac17_kp_decrypt_packed(rabe_host* h, const void* sk, size_t n_items
   return 0;
   GUARD_END(h)
 }
+// key encapsulation over the KP pair: cut over a device group where rabe_ac17_kp_{encrypt,decrypt}_packed are cut
+int32_t rabe_ac17_kp_encaps_packed(rabe_host* h, const void* pk, const char* const* attributes, const size_t* counts, size_t n_sets, size_t n_items,
+                                   const uint32_t* item_set, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {
+  GUARD_BEGIN
+  if (!item_set || !hdr_off) throw RabeError("kp_encaps_packed: null input");
+  std::vector<std::vector<std::string>> sets(n_sets);
+  size_t at = 0;
+  for (size_t s = 0; s < n_sets; s++)
+    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
+  const auto& key = *(const ac17::Ac17PublicKey*)pk;
+  return pipeline::produce(h->engines_if(key_buf != nullptr), h->rng(), n_items, pipeline::GROUP_ONLY,
+                           [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
+    return ac17::kp_encaps_packed(eng, r, key, sets, hi - lo, item_set + lo, out, cap, off, key_buf ? key_buf + KEM_KEY * lo : nullptr);
+  }, hdr_buf, hdr_cap, hdr_off) ? 0 : 1;
+  GUARD_END(h)
+}
+int32_t rabe_ac17_kp_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
+                                   uint32_t flags, int32_t* status, uint8_t* key_buf) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  const auto& key = *(const ac17::Ac17KpSecretKey*)sk;
+  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
+  pipeline::for_blocks(h->engines_if(ct_off && status && key_buf), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
+    ac17::kp_decaps_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
+                           key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
+    return true;
+  }, &errors);
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
 int32_t rabe_bsw_keygen_packed(rabe_host* h, const void* pk, const void* msk, const char* const* attributes, const size_t* counts, size_t n_sets,
                                size_t n_items, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off) {
   GUARD_BEGIN
@@ -1371,6 +1402,34 @@ int32_t rabe_lsw_decrypt_one_sk_packed(rabe_host* h, const void* sk, size_t n_it
         return lsw::decrypt_one_sk_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
       }, status, pt_buf, pt_cap, pt_off, &errors))
     return 1;
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
+// key encapsulation over the LSW pair.  Encaps runs on the group's first device, as rabe_lsw_encrypt_packed does; decaps is cut where
+// rabe_lsw_decrypt_one_sk_packed is cut, a block's 32-byte key slots written straight to key_buf + 32 lo.
+int32_t rabe_lsw_encaps_packed(rabe_host* h, const void* pk, const char* const* attributes, const size_t* counts, size_t n_sets, size_t n_items,
+                               const uint32_t* item_set, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {
+  GUARD_BEGIN
+  if (!item_set || !hdr_off) throw RabeError("lsw::encaps_packed: null input");
+  std::vector<std::vector<std::string>> sets(n_sets);
+  size_t at = 0;
+  for (size_t s = 0; s < n_sets; s++)
+    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
+  return lsw::encaps_packed(h->eng, h->rng(), *(const lsw::KpAbePublicKey*)pk, sets, n_items, item_set, hdr_buf, hdr_cap, hdr_off, key_buf) ? 0 : 1;
+  GUARD_END(h)
+}
+int32_t rabe_lsw_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
+                               int32_t* status, uint8_t* key_buf) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  const auto& key = *(const lsw::KpAbeSecretKey*)sk;
+  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
+  pipeline::for_blocks(h->engines_if(ct_off && status && key_buf), n_items, CHUNK_LSW, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
+    lsw::decaps_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
+                       key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
+    return true;
+  }, &errors);
   for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
   return 0;
   GUARD_END(h)

@@ -1176,6 +1176,98 @@ bool encrypt_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::
   return true;
 }
 
+// n key encapsulations (include/rabe_host.h: rabe_lsw_encaps_packed): record i is the KpAbeCiphertext header encrypt_packed writes for the same
+// draws with a sealed part of length zero, key_buf + 32 i = SHA3-256(bytes(msg_i)).  Draw order per item: encrypt_packed's without the nonce --
+// secret, one sx per attribute (the same index quirk), the message exponent.  The rows are one lane each (k_lsw_enc_rows): the host uploads
+// sx as it computes it (32 bytes per row), one secret per item and one hash per (list, position); h secret and sx h are formed on the device,
+// e5 is two walks on one accumulator and a row's three conversions share one inversion.  e1 and e2 keep their table calls.  No AES kernel.
+bool encaps_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
+                   uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  Timer tm("lsw::encaps_packed");
+  Engine::ArenaScope arena(eng);
+  if (n && (!item_set || !key_buf)) throw RabeError("lsw::encaps_packed: null input");
+  if (!out_off) throw RabeError("lsw::encaps_packed: null input");
+  std::vector<size_t> fixed(sets.size());
+  std::vector<uint32_t> set_hash_off(sets.size() + 1, 0);
+  std::vector<Fr> hashes;
+  for (size_t s = 0; s < sets.size(); s++) {
+    if (sets[s].empty()) throw RabeError("attributes or data empty");
+    fixed[s] = 384 + 128 + 4 + 4;
+    for (const auto& a : sets[s]) { fixed[s] += 4 + a.size() + 3 * 64; hashes.push_back(sha3_hash_fr(a)); }
+    set_hash_off[s + 1] = (uint32_t)hashes.size();
+  }
+  if (!record_offsets("lsw::encaps_packed", "item_set", n, item_set, sets.size(), fixed, nullptr, out_buf, out_cap, out_off)) return false;
+  if (!n) return true;
+  std::vector<uint32_t> row_off(n + 1, 0), hash_off(n);
+  for (size_t i = 0; i < n; i++) {
+    row_off[i + 1] = row_off[i] + (uint32_t)sets[item_set[i]].size();
+    hash_off[i] = set_hash_off[item_set[i]];
+  }
+  const size_t total = row_off[n];
+  eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
+  // scalars: per item secret | msg exponent; per row sx
+  uint8_t* h_k = eng.pinned(0, (2 * n + total) * 32 + 32);
+  uint8_t* h_sec = h_k;
+  uint8_t* h_rho = h_sec + n * 32;
+  uint8_t* h_sx = h_rho + n * 32;
+  draw_items(rng, n, [&](Rng& r, size_t i) {
+    const Fr secret = r.next_fr();
+    const size_t rows = row_off[i + 1] - row_off[i];
+    std::vector<Fr> sx{secret};
+    for (size_t y = 0; y < rows; y++) {
+      sx.push_back(r.next_fr());
+      sx[0] = fr_sub(sx[0], sx[y]);                 // :197-200 as it is written
+    }
+    for (size_t y = 0; y < rows; y++) memcpy(h_sx + 32 * (row_off[i] + y), sx[y].l, 32);
+    const Fr rho = r.next_fr();
+    memcpy(h_sec + 32 * i, secret.l, 32);
+    memcpy(h_rho + 32 * i, rho.l, 32);
+  });
+  tm.lap("draws + scalars");
+  const EncTables* tb;
+  {
+    std::string key((const char*)pk.g1.data(), 64);
+    key.append((const char*)pk.g2.data(), 128).append((const char*)pk.g1_b.data(), 64).append((const char*)pk.g1_b2.data(), 64).append((const char*)pk.h_b.data(), 64);
+    key.append((const char*)pk.e_gg_alpha.data(), 384);
+    tb = (const EncTables*)eng.aux("lsw_enc_tables", key, make_enc_tables, &pk, destroy_enc_tables, 2);
+  }
+  rhip_gt_table* gen = eng.gt_generator_table();
+  rhip_ctx* cx = eng.ctx();
+  DBuf d_k(&eng, (2 * n + total) * 32 + 4), d_msg(&eng, n * 384), d_pw(&eng, n * 384), d_e1(&eng, n * 384), d_e2(&eng, n * 128), d_rows(&eng, total * 192 + 4),
+      d_keys(&eng, n * 32 + 4), d_row_off = up32(eng, row_off), d_hash_off = up32(eng, hash_off), d_hash = up_bytes(eng, flatten_fr(hashes));
+  eng.check(rhip_upload_async(cx, d_k.ptr(), h_k, (2 * n + total) * 32), "upload");
+  const rhip_fr* k_sec = d_k.as<rhip_fr>();
+  const rhip_fr* k_rho = k_sec + n;
+  const rhip_fr* k_sx = k_rho + n;
+  eng.check(rhip_gt_table_pow(cx, gen, n, k_rho, d_msg.as<rhip_gt>()), "rhip_gt_table_pow");                 // rng.gen::<Gt>() = e(g1, g2)^rho
+  eng.check(rhip_gt_table_pow(cx, tb->egg, n, k_sec, d_pw.as<rhip_gt>()), "rhip_gt_table_pow");
+  eng.check(rhip_gt_mul(cx, n, d_pw.as<rhip_gt>(), d_msg.as<rhip_gt>(), d_e1.as<rhip_gt>()), "rhip_gt_mul");
+  eng.check(rhip_g2_table_mul(cx, tb->g2, n, k_sec, d_e2.as<rhip_g2>()), "rhip_g2_table_mul");
+  eng.check(rhip_lsw_encrypt_rows(cx, tb->g1, tb->g1_b, tb->g1_b2, tb->h_b, n, total, d_row_off.as<uint32_t>(), d_hash_off.as<uint32_t>(), d_hash.as<rhip_fr>(),
+                                  k_sec, k_sx, d_rows.as<rhip_g1>()), "rhip_lsw_encrypt_rows");
+  // headers from the template alone (records.h), keys straight out of the msg array: no seal kernel is launched
+  std::vector<RecordLayout> layouts(sets.size());
+  for (size_t p_ = 0; p_ < sets.size(); p_++) {
+    RecordLayout& L = layouts[p_];
+    L.src(0, 0, 384);
+    L.src(1, 0, 128);
+    L.u32((uint32_t)sets[p_].size());
+    for (size_t y = 0; y < sets[p_].size(); y++) {
+      L.str(sets[p_][y]);
+      L.src(2, (uint32_t)(192 * y), 192);
+    }
+    if (L.bytes() + 4 != fixed[p_]) throw RabeError("lsw::encaps_packed: record layout and size disagree");
+    L.u32(0);          // the length field of an empty sealed part; no sealed source
+  }
+  std::vector<uint64_t> src_off(3 * n);
+  for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * i; src_off[n + i] = 128ull * i; src_off[2 * n + i] = 192ull * row_off[i]; }
+  eng.check(rhip_gt_kdf_batch(cx, n, d_msg.as<rhip_gt>(), nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
+  emit_plain_records(eng, layouts, n, item_set, {d_e1.ptr(), d_e2.ptr(), d_rows.ptr()}, src_off, out_off, out_buf);
+  eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
+  tm.lap("device: group arithmetic, headers, keys; two copies out");
+  return true;
+}
+
 // n calls of lsw::keygen (lsw/mod.rs:121-170).  Draw order per item: the gate coefficients of gen_shares_policy(alpha1), then one
 // `random` per share (:136).  Record = KpAbeSecretKey: policy text, language, leaf count, per leaf (name, d1, d2, d3, d4, d5) with
 // d3..d5 the identity for positive leaves and d1, d2 the identity for negative ones ("!x", :137-146: rhip_lsw_keygen_batch_signed).
@@ -1418,12 +1510,15 @@ void* make_sk_d2_lines(Engine& eng, const void* arg) {          // arg: d2 of ev
 // G2 argument of an item is its own e2, whose walk gives its membership verdict.  The whole rows (e1, e2, e3 of every attribute) are gathered
 // and checked as a decoder would; row r's E1 is element 3 r of that array.  pt_cap below the sealed lengths of the well-formed records:
 // returns false with that size in pt_off[n].
-bool decrypt_one_sk_packed(Engine& eng, const KpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                           int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
-  Timer tm("lsw::decrypt_one_sk_packed");
+// key_buf != nullptr is the key decapsulation (decaps_packed below): the same launch set up to the final Gt, then the KDF behind the verdict mask
+// (records.h: derive_keys) instead of the open; pt_buf / pt_cap / pt_off are unused, the sealed part is skipped by its length field and never read.
+static bool decrypt_one_sk_core(Engine& eng, const KpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                                int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors, uint8_t* key_buf) {
+  const bool kem = key_buf != nullptr;
+  Timer tm(kem ? "lsw::decaps_packed" : "lsw::decrypt_one_sk_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
-  if (!ct_off || !pt_off || (n && !ct_blob)) throw RabeError("lsw::decrypt_one_sk_packed: null input");
+  if (!ct_off || (!kem && !pt_off) || (n && !ct_blob)) throw RabeError("lsw::decrypt_one_sk_packed: null input");
   (void)check_offsets(n, ct_off, ct_len, errors);
   BlobGather gather(eng, ct_blob, ct_len);          // the blob starts for the device now, beside the parsing below (records.h)
   const std::shared_ptr<const FlatPolicy> flat = flat_policy(sk.policy.first, sk.policy.second);
@@ -1481,7 +1576,7 @@ bool decrypt_one_sk_packed(Engine& eng, const KpAbeSecretKey& sk, size_t n, cons
   tm.lap("parse + plan");
   uint64_t need = 0;
   for (size_t i = 0; i < n; i++) if (parsed[i]) need += sealed[i].len;
-  if (!pt_buf || pt_cap < need) { pt_off[n] = need; return false; }
+  if (!kem && (!pt_buf || pt_cap < need)) { pt_off[n] = need; return false; }
   // every record is in the standard layout of ITS list of names; the records of one list are one selection group of the kernel
   Selection sel(1, 1);
   std::vector<uint32_t> attr_off{0}, group_off{0}, item_group;
@@ -1558,11 +1653,29 @@ bool decrypt_one_sk_packed(Engine& eng, const KpAbeSecretKey& sk, size_t n, cons
       ws.fail(live, {ws.k_alone}, "deserialize: e2 is not a member of G2 (FieldError::NotMember)", errors);
     }
   }
+  if (kem) {
+    ws.fail_walked(live, "deserialize: e2 is not a member of G2 (FieldError::NotMember)", errors);
+    derive_keys(eng, n, live, d_out.ptr(), status, key_buf, *errors);
+    tm.lap(trusted ? "device: gather, pairings, keys" : "device: gather, pairings, keys; membership beside");
+    return true;
+  }
   // KDF + AES-GCM open on the device: the decrypted Gt never leaves HBM; plaintext bytes come back in one copy
   open_sealed_records(eng, n, live, d_out.ptr(), gather.dev_blob(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
   ws.retract(live, "deserialize: e2 is not a member of G2 (FieldError::NotMember)", status, pt_buf, pt_off, errors);
   tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
   return true;
+}
+bool decrypt_one_sk_packed(Engine& eng, const KpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                           int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
+  return decrypt_one_sk_core(eng, sk, n, ct_blob, ct_len, ct_off, trusted, status, pt_buf, pt_cap, pt_off, errors, nullptr);
+}
+// n key decapsulations under ONE key (include/rabe_host.h: rabe_lsw_decaps_packed): key_buf + 32 i = SHA3-256(bytes(Gt)) of what decrypt_gt
+// returns for record i; input may be headers or full records
+void decaps_packed(Engine& eng, const KpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                   int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
+  if (n && (!status || !key_buf)) throw RabeError("lsw::decaps_packed: null input");
+  uint8_t none = 0;          // n = 0: nothing is written
+  decrypt_one_sk_core(eng, sk, n, ct_blob, ct_len, ct_off, trusted, status, nullptr, 0, nullptr, errors, key_buf ? key_buf : &none);
 }
 }  // namespace lsw
 

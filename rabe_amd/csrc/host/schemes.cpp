@@ -1284,12 +1284,22 @@ bool kp_encrypt_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std
   for (const auto& a : sets) pols.push_back(enc_attr_set(a));
   return encrypt_packed_core(eng, rng, pk, pols, nullptr, PolicyLanguage::JsonPolicy, n, item_set, pt_blob, pt_off, out_buf, out_cap, out_off);
 }
+// Key encapsulation over the KP pair (include/rabe_host.h: rabe_ac17_kp_encaps_packed): kp_encrypt_packed's records with a sealed part of length
+// zero and the content keys, as cp_encaps_packed
+bool kp_encaps_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
+                      uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  if (n && !key_buf) throw RabeError("kp_encaps_packed: null input");
+  if (!n) { out_off[0] = 0; return true; }
+  std::vector<std::shared_ptr<const EncPolicy>> pols;
+  for (const auto& a : sets) pols.push_back(enc_attr_set(a));
+  return encrypt_packed_core(eng, rng, pk, pols, nullptr, PolicyLanguage::JsonPolicy, n, item_set, nullptr, nullptr, out_buf, out_cap, out_off, key_buf);
+}
 static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::shared_ptr<const EncPolicy>>& pols,
                                 const std::vector<std::string>* policies, PolicyLanguage language, size_t n,
                                 const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off,
                                 uint8_t* key_buf) {
   const bool kem = key_buf != nullptr;
-  StageTimer tm(kem ? "ac17::cp_encaps_packed" : policies ? "ac17::cp_encrypt_packed" : "ac17::kp_encrypt_packed");
+  StageTimer tm(kem ? (policies ? "ac17::cp_encaps_packed" : "ac17::kp_encaps_packed") : policies ? "ac17::cp_encrypt_packed" : "ac17::kp_encrypt_packed");
   Engine::ArenaScope arena(eng);
   if (pk.h_a.size() != 3 || pk.e_gh_ka.size() != 2) throw RabeError("malformed Ac17PublicKey");
   std::vector<uint32_t> a_off{0};
@@ -1468,11 +1478,19 @@ bool kp_decrypt_packed(Engine& eng, const Ac17KpSecretKey& sk, size_t n, const u
   if (!(sk.sk.k_p.empty() || sk.sk.k_p.size() == 3)) throw RabeError("malformed Ac17KpSecretKey");
   return decrypt_packed_core(eng, DecKey{sk.sk, nullptr, &sk.policy}, n, ct_blob, ct_len, ct_off, trusted, status, pt_buf, pt_cap, pt_off, errors);
 }
+// Key decapsulation over the KP pair (include/rabe_host.h: rabe_ac17_kp_decaps_packed), as cp_decaps_packed: kp_decrypt_packed up to the final Gt
+void kp_decaps_packed(Engine& eng, const Ac17KpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                      int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
+  if (!(sk.sk.k_p.empty() || sk.sk.k_p.size() == 3)) throw RabeError("malformed Ac17KpSecretKey");
+  if (n && (!status || !key_buf)) throw RabeError("kp_decaps_packed: null input");
+  uint8_t none = 0;          // n = 0: nothing is written
+  decrypt_packed_core(eng, DecKey{sk.sk, nullptr, &sk.policy}, n, ct_blob, ct_len, ct_off, trusted, status, nullptr, 0, nullptr, errors, key_buf ? key_buf : &none);
+}
 static bool decrypt_packed_core(Engine& eng, const DecKey& key, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                                 int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors, uint8_t* key_buf) {
   const bool kp = key.kp_policy != nullptr, kem = key_buf != nullptr;
   const Ac17SecretKey& core = key.sk;
-  StageTimer tm(kem ? "ac17::cp_decaps_packed" : kp ? "ac17::kp_decrypt_packed" : "ac17::cp_decrypt_packed");
+  StageTimer tm(kem ? (kp ? "ac17::kp_decaps_packed" : "ac17::cp_decaps_packed") : kp ? "ac17::kp_decrypt_packed" : "ac17::cp_decrypt_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
   if (!ct_off || (n && !ct_blob)) throw RabeError("cp_decrypt_packed: null input");

@@ -72,6 +72,11 @@ bool kp_encrypt_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std
                        const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
 bool kp_decrypt_packed(Engine& eng, const Ac17KpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                        int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors);
+// key encapsulation over the KP pair (include/rabe_host.h: rabe_ac17_kp_{encaps,decaps}_packed), as cp_{encaps,decaps}_packed
+bool kp_encaps_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
+                      uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf);
+void kp_decaps_packed(Engine& eng, const Ac17KpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                      int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors);
 std::vector<DecryptResult> kp_decrypt_batch(Engine& eng, const std::vector<const Ac17KpSecretKey*>& sks, const std::vector<const Ac17KpCiphertext*>& cts);
 }  // namespace ac17
 
@@ -146,6 +151,12 @@ bool decrypt_packed(Engine& eng, const KpAbeCiphertext& ct, size_t n, const uint
 // ONE key against n ciphertexts (a blob of KpAbeCiphertext records, as encrypt_packed writes them) over rhip_lsw_decrypt_batch_one_sk
 bool decrypt_one_sk_packed(Engine& eng, const KpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                            int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors);
+// key encapsulation (include/rabe_host.h: rabe_lsw_{encaps,decaps}_packed): encrypt_packed's headers (records with an empty sealed part) +
+// 32-byte content keys out, rows from rhip_lsw_encrypt_rows; content keys back under ONE key; status[i] = -1 and 32 zero bytes for an item that fails
+bool encaps_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
+                   uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf);
+void decaps_packed(Engine& eng, const KpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                   int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors);
 }  // namespace lsw
 
 namespace aw11 {

@@ -681,6 +681,14 @@ def lsw_decrypt_one_sk_dev(eng, n_items, max_pairs, total_pairs, n_sel, d_pair_o
                                                      _p(sk_d2_lines), _p(d_out)))
 
 
+def lsw_encrypt_rows_dev(eng, g1_tbl, g1_b_tbl, g1_b2_tbl, h_b_tbl, n_items, total_rows, d_item_row_off, d_item_hash_off, d_hash, d_secret, d_sx,
+                         d_out):
+    """rhip_lsw_encrypt_rows: the attribute rows of n_items lsw::encrypt calls, one lane per row (k_lsw_enc_rows).  The four tables are
+    Engine.g1_table objects with 16-bit windows (add_w16) of g1, g1_b, g1_b2 and h_b; d_out takes e3, e4, e5 of every row (3 x 64 bytes)"""
+    eng._check(eng.lib.rhip_lsw_encrypt_rows(eng.ctx, g1_tbl.h, g1_b_tbl.h, g1_b2_tbl.h, h_b_tbl.h, _sz(n_items), _sz(total_rows), _p(d_item_row_off),
+                                             _p(d_item_hash_off), _p(d_hash), _p(d_secret), _p(d_sx), _p(d_out)))
+
+
 class Aw11Pk:
     def __init__(self, eng, g1, g2, egg_alpha, g2_y):
         self.eng = eng

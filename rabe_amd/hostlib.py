@@ -460,6 +460,28 @@ def packed_encaps(host, fn, head_args, policies, item_policy, language, out=None
     return buf[:int(ho[n])], ho, keys[:n]
 
 
+def packed_encaps_sets(host, fn, head_args, attr_sets, item_set, out=None):
+    """key encapsulation of the key-policy schemes: calls `fn(host, *head_args, attributes, counts, n_sets, n, item_set, hdr_buf, hdr_cap, hdr_off,
+    key_buf)` -- item i under the attribute list attr_sets[item_set[i]] -- growing the header buffer once when the library reports the size it
+    needs (that first call draws nothing).  Returns (hdr_blob view, hdr_off uint64 [n+1], keys uint8 [n, 32])."""
+    import numpy as np
+    n = len(item_set)
+    arr, _ = _strs([a for s_ in attr_sets for a in s_])
+    counts = (ctypes.c_size_t * max(len(attr_sets), 1))(*[len(s_) for s_ in attr_sets])
+    it = np.ascontiguousarray(item_set, dtype=np.uint32)
+    ho = np.zeros(n + 1, dtype=np.uint64)
+    keys = np.zeros((max(n, 1), 32), dtype=np.uint8)
+    buf = out if out is not None else np.empty(0, dtype=np.uint8)
+    for _ in range(2):
+        rc = getattr(host.lib, fn)(host.h, *head_args, arr, counts, ctypes.c_size_t(len(attr_sets)), ctypes.c_size_t(n), _np_ptr(it), _np_ptr(buf),
+                                   ctypes.c_size_t(buf.size), _np_ptr(ho), _np_ptr(keys))
+        if rc != 1:
+            break
+        buf = np.empty(int(ho[n]), dtype=np.uint8)
+    _check(rc, host.h)
+    return buf[:int(ho[n])], ho, keys[:n]
+
+
 def packed_decaps(host, fn, head_args, blob, off, trusted=False):
     """key decapsulation: calls `fn(host, *head_args, n, blob, len, off, flags, status, key_buf)`.
     Returns (keys uint8 [n, 32] -- zeros where status is -1, status int32 [n])."""

@@ -227,3 +227,17 @@ def cp_decaps_packed(host, sk, ct_blob, ct_off, trusted=False):
     has status -1 and 32 zero bytes.  The sealed parts are neither read nor authenticated."""
     from ..hostlib import packed_decaps
     return packed_decaps(host, "rabe_ac17_cp_decaps_packed", (sk.ptr,), ct_blob, ct_off, trusted)
+
+
+def kp_encaps_packed(host, pk, attr_sets, item_set, out=None):
+    """the same over the KP pair (rabe_ac17_kp_encaps_packed): item i under the attribute list attr_sets[item_set[i]]; headers are
+    Ac17KpCiphertext records with an empty sealed part.  Returns (hdr_blob view, hdr_off uint64 [n+1], keys uint8 [n, 32])."""
+    from ..hostlib import packed_encaps_sets
+    return packed_encaps_sets(host, "rabe_ac17_kp_encaps_packed", (pk.ptr,), attr_sets, item_set, out)
+
+
+def kp_decaps_packed(host, sk, ct_blob, ct_off, trusted=False):
+    """the content keys of n Ac17KpCiphertext records (headers or full ciphertexts) under one KP key (rabe_ac17_kp_decaps_packed).
+    Returns (keys uint8 [n, 32], status int32 [n]); a failed item has status -1 and 32 zero bytes."""
+    from ..hostlib import packed_decaps
+    return packed_decaps(host, "rabe_ac17_kp_decaps_packed", (sk.ptr,), ct_blob, ct_off, trusted)

@@ -84,3 +84,19 @@ def encrypt_packed(host, pk, attr_sets, item_set, pt_blob, pt_off, out=None):
         buf = np.empty(int(co[n]), dtype=np.uint8)
     _check(rc, host.h)
     return buf[:int(co[n])], co
+
+
+# ---- key encapsulation (rabe_lsw_{encaps,decaps}_packed): the packed pair without payloads
+def encaps_packed(host, pk, attr_sets, item_set, out=None):
+    """n key encapsulations (rabe_lsw_encaps_packed): header i is the KpAbeCiphertext record encrypt_packed writes for the same draws with an
+    empty sealed part (its draws minus the nonce), key i = SHA3-256(bytes(msg_i)); the rows come from the fused row kernel.
+    Returns (hdr_blob view, hdr_off uint64 [n+1], keys uint8 [n, 32])."""
+    from ..hostlib import packed_encaps_sets
+    return packed_encaps_sets(host, "rabe_lsw_encaps_packed", (pk.ptr,), attr_sets, item_set, out)
+
+
+def decaps_packed(host, sk, ct_blob, ct_off, trusted=False):
+    """ONE key against n headers or full records (rabe_lsw_decaps_packed): key i = SHA3-256(bytes(decrypt_gt(sk, record i))).
+    Returns (keys uint8 [n, 32] -- zeros where status is -1, status int32 [n])."""
+    from ..hostlib import packed_decaps
+    return packed_decaps(host, "rabe_lsw_decaps_packed", (sk.ptr,), ct_blob, ct_off, trusted)
