@@ -132,6 +132,10 @@ enum { RHIP_FR_ADD = 0, RHIP_FR_SUB = 1, RHIP_FR_MUL = 2, RHIP_FR_NEG = 3, RHIP_
 int32_t rhip_fr_op(rhip_ctx* ctx, int32_t op, size_t n, const rhip_fr* dev_a, const rhip_fr* dev_b, rhip_fr* dev_out);
 /* `Fr::from_slice` of n 32-byte BIG-endian digests: integer mod r */
 int32_t rhip_fr_from_be32_reduce(rhip_ctx* ctx, size_t n, const uint8_t* dev_digests, rhip_fr* dev_out);
+/* Diagnostic: out[i] = a0[i] b0[i] + a1[i] b1[i] in the BASE field (canonical 32-byte records < p, the coordinate encoding of rhip_g1),
+ * through the two-term dot product under one reduction that closes the G1 mixed addition (bn254/fp.h: mont_dot2_raw). */
+int32_t rhip_fp_dot2(rhip_ctx* ctx, size_t n, const rhip_fr* dev_a0, const rhip_fr* dev_b0, const rhip_fr* dev_a1, const rhip_fr* dev_b1,
+                     rhip_fr* dev_out);
 
 int32_t rhip_g1_add(rhip_ctx* ctx, size_t n, const rhip_g1* dev_a, const rhip_g1* dev_b, rhip_g1* dev_out);
 int32_t rhip_g1_neg(rhip_ctx* ctx, size_t n, const rhip_g1* dev_a, rhip_g1* dev_out);

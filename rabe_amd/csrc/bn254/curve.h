@@ -111,7 +111,8 @@ RB_MID Jac<F> jac_add_aff(const Jac<F>& p, const Aff<F>& q) {
 // forms take 11 products, this one 7 additive steps instead of 14.  The point is the same, its representative is not: Z3 is half of
 // jac_add_aff's (X3 a quarter, Y3 an eighth).  Every consumer converts to affine through 1/Z, so every stored byte is unchanged.
 // The 11 field products are expanded in place (no call, so nothing has to sit in callee-saved registers around them) and issued
-// as 1 + 5 interleaved pairs of independent products.  Same special cases as jac_add_aff, in the same places.
+// as 1 + 4 interleaved pairs of independent products and, for Y3, one dot product of two terms: r (V - X3) + (-Y1) HHH is reduced
+// once, so the addition has ten Montgomery reductions for its eleven products.  Same special cases as jac_add_aff, in the same places.
 // The doubling case of the mixed addition (never taken with honest inputs) as a function that passes and returns FIELD elements
 // in registers, one coordinate per call: a call that takes the accumulator by reference, or returns a point through a memory
 // slot, pins the caller's accumulator to the stack -- a store and a reload of the whole point in every loop iteration of the
@@ -140,9 +141,9 @@ RB_HD Jac<Fp> g1_madd_inl(const Jac<Fp>& p, const Aff<Fp>& q) {
   Fp R2;
   mul2_inl(R2, r.z, rr, rr, p.z, H);
   r.x = sub(sub(R2, HHH), dbl(V));
-  Fp A, B;
-  mul2_inl(A, B, rr, sub(V, r.x), p.y, HHH);
-  r.y = sub(A, B);
+  // Y3 = r (V - X3) + (p - Y1) HHH: the sum of the two 512-bit products under ONE reduction (fp.h: mont_dot2_raw).  neg(0) is 0, so
+  // every operand stays below p
+  r.y = dot2_inl(rr, sub(V, r.x), neg(p.y), HHH);
   return r;
 }
 

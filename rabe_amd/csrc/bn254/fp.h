@@ -300,12 +300,14 @@ struct ColumnPlan {
   // column to be in the safe set).  `top2` tells how much of the budget the top-limb products of the a*b part take.
   uint16_t safe[16];
   uint16_t last_safe;
-  constexpr ColumnPlan(bool with_ab, uint32_t top_a, uint32_t top_b) : safe{}, last_safe(0) {
+  // n_terms: how many a*b products of reduced operands are summed under the one reduction (mont_dot2: 2) -- every term brings its own
+  // top-limb products into a column, and they come out of the same budget.
+  constexpr ColumnPlan(bool with_ab, uint32_t top_a, uint32_t top_b, int n_terms = 1) : safe{}, last_safe(0) {
     constexpr uint64_t LIMIT = 0xFFFFFF00ull;     // sum of the bounding limbs, in units of 2^32; 2^8 units of slack cover the
                                                   // incoming < 2^37 and the one plain 32-bit addend of redc2
     for (int k = 0; k < 16; k++) {
       uint64_t used = 0;
-      if (with_ab && k >= 7 && k <= 14) used = (k == 14) ? (uint64_t)top_a : (uint64_t)top_a + top_b;   // a7 b(k-7) [+ a(k-7) b7]
+      if (with_ab && k >= 7 && k <= 14) used = (uint64_t)n_terms * ((k == 14) ? (uint64_t)top_a : (uint64_t)top_a + top_b);   // a7 b(k-7) [+ a(k-7) b7]
       const int lo = k < 8 ? 0 : k - 7, hi = k < 8 ? k - 1 : 7;        // i range of the m_i * mod(k-i) products, m_k * mod(0) excluded
       bool taken[8] = {false, false, false, false, false, false, false, false};
       int n_taken = 0;
@@ -332,6 +334,9 @@ template <class M> RB_HD constexpr bool plan_redc_safe(int k, int i) { constexpr
 template <class M> RB_HD constexpr bool plan_redc_last_safe(int k) { constexpr ColumnPlan<M> t(false, 0, 0); return (t.last_safe >> k) & 1; }
 template <class M> RB_HD constexpr bool plan_mul_safe(int k, int i) { constexpr ColumnPlan<M> t(true, M::mod(7) + 1, M::mod(7) + 1); return (t.safe[k] >> i) & 1; }
 template <class M> RB_HD constexpr bool plan_mul_last_safe(int k) { constexpr ColumnPlan<M> t(true, M::mod(7) + 1, M::mod(7) + 1); return (t.last_safe >> k) & 1; }
+// plan of a sum of two products of operands < mod under one reduction (mont_dot2_raw): up to four top-limb products in a column
+template <class M> RB_HD constexpr bool plan_dot2_safe(int k, int i) { constexpr ColumnPlan<M> t(true, M::mod(7) + 1, M::mod(7) + 1, 2); return (t.safe[k] >> i) & 1; }
+template <class M> RB_HD constexpr bool plan_dot2_last_safe(int k) { constexpr ColumnPlan<M> t(true, M::mod(7) + 1, M::mod(7) + 1, 2); return (t.last_safe >> k) & 1; }
 // a_i * b_(k-i) is a top-limb product of column k
 RB_HD constexpr bool ab_top(int k, int i) { return k >= 7 && (i == 7 || k - i == 7); }
 
@@ -697,6 +702,65 @@ RB_HD void mont_mul_raw(uint32_t* r, const A& a, const B& b) {
 }
 #endif
 
+// ---- Montgomery dot product of two terms: r = (a0 b0 + a1 b1) / 2^256 mod m, ONE reduction for the sum of the two 512-bit
+// products.  Operands < mod, so the sum is below 2 mod^2 < mod * 2^256: the reduced value is below 2 mod and one conditional
+// subtraction finishes it, as for a single product.  Against two products and an addition this saves the second reduction (64
+// m*p multiply-adds, 8 m products, their captures).  A column now carries up to 16 a*b products -- up to FOUR of them top-limb
+// products -- so the set of reduction products that issue without a capture is a plan of its own (plan_dot2_*; the bounds are
+// proved in tests/test_mac_plan_dot2.py).
+// The loop form below is written over plain 64-bit integers and FOLLOWS the plan: a product the plan takes as safe is added
+// without looking at the carry, exactly as the generated device routine issues it, so a wrong plan gives wrong results here too.
+// It serves the host builds and every instantiation but the device's Fp, which is the generated mont_dot2_fp.
+template <class M, class A>
+RB_HD void mont_dot2_generic(uint32_t* r, const A& a0, const A& b0, const A& a1, const A& b1) {
+  uint32_t m[8];
+  uint64_t acc = 0;
+#pragma unroll
+  for (int k = 0; k < 16; k++) {
+    uint32_t ovf = 0;
+    bool have = false;
+    const int lo = k < 8 ? 0 : k - 7, hi = k < 8 ? k : 7;
+    // products that cannot carry first
+#pragma unroll
+    for (int i = lo; i <= hi; i++)
+      if (ab_top(k, i)) { acc += (uint64_t)a0[i] * b0[k - i]; acc += (uint64_t)a1[i] * b1[k - i]; }
+#pragma unroll
+    for (int i = lo; i <= hi; i++)
+      if (!(k < 8 && i == k) && plan_dot2_safe<M>(k, i)) acc += (uint64_t)m[i] * M::mod(k - i);
+    // the carry-banked rest
+#pragma unroll
+    for (int i = lo; i <= hi; i++)
+      if (!ab_top(k, i)) {
+        const uint64_t x = (uint64_t)a0[i] * b0[k - i], y = (uint64_t)a1[i] * b1[k - i];
+        acc += x; ovf += acc < x;
+        acc += y; ovf += acc < y;
+        have = true;
+      }
+#pragma unroll
+    for (int i = lo; i <= hi; i++)
+      if (!(k < 8 && i == k) && !plan_dot2_safe<M>(k, i)) { const uint64_t x = (uint64_t)m[i] * M::mod(k - i); acc += x; ovf += acc < x; have = true; }
+    if (k < 8) {
+      m[k] = (uint32_t)acc * M::INV;
+      const uint64_t x = (uint64_t)m[k] * M::mod(0);
+      acc += x;
+      if (have || !plan_dot2_last_safe<M>(k)) ovf += acc < x;
+    } else {
+      r[k - 8] = (uint32_t)acc;
+    }
+    acc = (acc >> 32) | ((uint64_t)ovf << 32);
+  }
+  // value < 2*mod < 2^255: nothing left in acc
+  cond_sub_mod<M>(r, 0);
+}
+template <class M, class A>
+RB_HD void mont_dot2_raw(uint32_t* r, const A& a0, const A& b0, const A& a1, const A& b1) {
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(RB_NO_GEN_MUL2)
+  if constexpr (IsFp<M>::value) mont_dot2_fp(r, a0, b0, a1, b1);
+  else
+#endif
+    mont_dot2_generic<M>(r, a0, b0, a1, b1);
+}
+
 // Host-only instrumentation for the roofline's algorithmic work count (tests/hostsim builds with
 // -DRB_COUNT_MULS; never defined for device code): every Montgomery multiplication bumps a counter.
 #if defined(RB_COUNT_MULS) && !defined(__HIP_DEVICE_COMPILE__)
@@ -733,6 +797,17 @@ RB_HD void mul3_inl(Mont<M>& r0, Mont<M>& r1, Mont<M>& r2, const Mont<M>& a0, co
   mont_mul3_raw<M>(t0, t1, t2, a0.v, b0.v, a1.v, b1.v, a2.v, b2.v);
 #pragma unroll
   for (int i = 0; i < 8; i++) { r0.v[i] = t0[i]; r1.v[i] = t1[i]; r2.v[i] = t2[i]; }
+}
+// a0 b0 + a1 b1 with one reduction (mont_dot2_raw); counted as the two products it stands for
+template <class M>
+RB_HD Mont<M> dot2_inl(const Mont<M>& a0, const Mont<M>& b0, const Mont<M>& a1, const Mont<M>& b1) {
+  RB_COUNT_ONE_MUL(); RB_COUNT_ONE_MUL();
+  uint32_t t[8];
+  mont_dot2_raw<M>(t, a0.v, b0.v, a1.v, b1.v);
+  Mont<M> r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = t[i];
+  return r;
 }
 // out-of-line form: operands and result travel in VGPRs
 template <class M>

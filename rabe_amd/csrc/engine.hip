@@ -369,6 +369,13 @@ __global__ void __launch_bounds__(256, RB_MIN_WAVES) k_fr_op(int op, size_t n, c
   }
   store_fr(out[i].l, r);
 }
+// diagnostic: the two-term dot product of the G1 mixed addition (fp.h: mont_dot2_raw) on base-field records
+__global__ void __launch_bounds__(256, RB_MIN_WAVES) k_fp_dot2(size_t n, const rhip_fr* a0, const rhip_fr* b0, const rhip_fr* a1, const rhip_fr* b1,
+                                                               rhip_fr* out) {
+  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  store_fp(out[i].l, dot2_inl(load_fp(a0[i].l), load_fp(b0[i].l), load_fp(a1[i].l), load_fp(b1[i].l)));
+}
 __global__ void __launch_bounds__(256, RB_MIN_WAVES) k_fr_from_be32(size_t n, const uint8_t* dig, rhip_fr* out) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1106,6 +1113,12 @@ extern "C" int32_t rhip_fr_from_be32_reduce(rhip_ctx* ctx, size_t n, const uint8
   NEED(ctx);
   if (!n) return RHIP_OK;
   KLAUNCH(ctx, "k_fr_from_be32", k_fr_from_be32, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, n, dig, out);
+  return RHIP_OK;
+}
+extern "C" int32_t rhip_fp_dot2(rhip_ctx* ctx, size_t n, const rhip_fr* a0, const rhip_fr* b0, const rhip_fr* a1, const rhip_fr* b1, rhip_fr* out) {
+  NEED(ctx);
+  if (!n) return RHIP_OK;
+  KLAUNCH(ctx, "k_fp_dot2", k_fp_dot2, dim3(blocks_for(n, 256)), dim3(256), 0, ctx->stream, n, a0, b0, a1, b1, out);
   return RHIP_OK;
 }
 extern "C" int32_t rhip_g1_add(rhip_ctx* ctx, size_t n, const rhip_g1* a, const rhip_g1* b, rhip_g1* out) {

@@ -171,6 +171,10 @@ class Engine:
     def fr_from_be32_reduce(self, digests):
         return self._elem("rhip_fr_from_be32_reduce", len(digests), [digests], FR)
 
+    def fp_dot2(self, a0, b0, a1, b1):
+        """diagnostic: a0 b0 + a1 b1 over the base field through the device's two-term dot product (canonical 32-byte records < p)"""
+        return self._elem("rhip_fp_dot2", len(a0), [a0, b0, a1, b1], FR)
+
     def g1_add(self, a, b): return self._elem("rhip_g1_add", len(a), [a, b], G1)
     def g1_neg(self, a): return self._elem("rhip_g1_neg", len(a), [a], G1)
     def g1_mul(self, p, k): return self._elem("rhip_g1_mul", len(p), [p, k], G1)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Generates rabe_amd/csrc/bn254/fp_gfx950_gen.h: the straight-line gfx950 forms of the three multiplication routines the
 pairing kernels live in -- wide_mul3 (three 256x256 products in lockstep), redc2 (two Montgomery reductions in lockstep) and
-mont_mul2_raw over Fp (two Montgomery products in lockstep).
+mont_mul2_raw over Fp (two Montgomery products in lockstep) -- and of mont_dot2_fp, the two-term dot product under one reduction
+that closes the G1 mixed addition (one chain: those kernels hide its latency with four waves per SIMD).
 
 Why generated: hipcc pads every `asm` statement with one wait state before the next VALU instruction that touches its outputs
 (cdna_hip_programming.md 5.7 item 2), and a kernel that runs one wave per SIMD pays each of them (tools/ubench_mac.hip: ~1.7
@@ -28,13 +29,13 @@ def fp_mod():
     return [int(x.strip().rstrip("u"), 16) for x in m.group(1).split(",")]
 
 
-def column_plan(mod, with_ab, top_a, top_b):
+def column_plan(mod, with_ab, top_a, top_b, n_terms=1):
     """fp.h: ColumnPlan -- the same greedy rule"""
     safe, last_safe = [0] * 16, 0
     for k in range(16):
         used = 0
         if with_ab and 7 <= k <= 14:
-            used = top_a if k == 14 else top_a + top_b
+            used = n_terms * (top_a if k == 14 else top_a + top_b)
         lo, hi = (0, k - 1) if k < 8 else (k - 7, 7)
         taken = set()
         while True:
@@ -269,16 +270,54 @@ def gen_mul2(out, mod, safe, last_safe):
     out.append("}")
 
 
+def gen_dot2(out, mod, safe, last_safe):
+    out.append("// Montgomery dot product of two terms over Fp, (a0 b0 + a1 b1) / 2^256 mod p with ONE reduction; operands < p, result < p.")
+    out.append("// One chain: a column takes the (up to four) top-limb products and the plan's safe reduction products without a capture,")
+    out.append("// then the other a*b products of both terms and the rest of the reduction products, each with its capture.")
+    out.append("template <class A>")
+    out.append("RB_HD void mont_dot2_fp(uint32_t* r, const A& a0, const A& b0, const A& a1, const A& b1) {")
+    out.append("  uint64_t acc0 = 0, c0_;")
+    out.append("  uint32_t ovf0;")
+    for j in range(8):
+        out.append("  const uint32_t p%d = 0x%08xu;" % (j, mod[j]))
+    out.append("  const uint32_t inv_ = FpParams::INV;")
+    for i in range(8):
+        out.append("  const uint32_t x0_%d = a0[%d], y0_%d = b0[%d], x1_%d = a1[%d], y1_%d = b1[%d];" % ((i,) * 8))
+    accs, ovfs, cars = ["acc0"], ["ovf0"], ["c0_"]
+    for k in range(16):
+        lo, hi = (0, k) if k < 8 else (k - 7, 7)
+        tops = [i for i in range(lo, hi + 1) if k >= 7 and (i == 7 or k - i == 7)]
+        mp = [i for i in range(lo, hi + 1) if not (k < 8 and i == k)]
+        macs = [(["x%d_%d" % (t, i)], ["y%d_%d" % (t, k - i)], "v", False) for i in tops for t in (0, 1)]
+        macs += [(["m_%d" % i], "p%d" % (k - i), "s", False) for i in sorted([i for i in mp if (safe[k] >> i) & 1], key=lambda i: mod[k - i])]
+        macs += [(["x%d_%d" % (t, i)], ["y%d_%d" % (t, k - i)], "v", True) for i in range(lo, hi + 1) if i not in tops for t in (0, 1)]
+        macs += [(["m_%d" % i], "p%d" % (k - i), "s", True) for i in mp if not (safe[k] >> i) & 1]
+        have = [False]
+        out.append("  // column %d" % k)
+        pack(out, 1, macs, accs, ovfs, cars, have)
+        if k < 8:
+            out.append("  const uint32_t m_%d = (uint32_t)acc0 * inv_;" % k)
+            closing_safe = (not have[0]) and ((last_safe >> k) & 1)
+            pack(out, 1, [(["m_%d" % k], "p0", "s", not closing_safe)], accs, ovfs, cars, have)
+        else:
+            out.append("  r[%d] = (uint32_t)acc0;" % (k - 8))
+        shift(out, 1, have[0])
+    out.append("  cond_sub_mod<FpParams>(r, 0);")
+    out.append("}")
+
+
 def main():
     mod = fp_mod()
     top = mod[7] + 1
     redc_safe, redc_last = column_plan(mod, False, 0, 0)
     mul_safe, mul_last = column_plan(mod, True, top, top)
+    dot2_safe, dot2_last = column_plan(mod, True, top, top, 2)
     out = ["// GENERATED by tools/gen_fp_asm.py -- do not edit; regenerate with `python tools/gen_fp_asm.py`.",
            "// Straight-line gfx950 forms of wide_mul3 / redc2 / mont_mul2_raw over Fp (see the generator's header for the why).",
            "// Included by fp.h inside its device-only block.", ""]
     out.append("// the plan these statements were laid out for is the one ColumnPlan computes (fp.h; tests/test_mac_plan.py proves its bounds)")
-    for name, safe, last, args in (("redc", redc_safe, redc_last, "false, 0, 0"), ("mul", mul_safe, mul_last, "true, FpParams::mod(7) + 1, FpParams::mod(7) + 1")):
+    for name, safe, last, args in (("redc", redc_safe, redc_last, "false, 0, 0"), ("mul", mul_safe, mul_last, "true, FpParams::mod(7) + 1, FpParams::mod(7) + 1"),
+                                   ("dot2", dot2_safe, dot2_last, "true, FpParams::mod(7) + 1, FpParams::mod(7) + 1, 2")):
         out.append("namespace gen_check_%s {" % name)
         out.append("constexpr ColumnPlan<FpParams> plan(%s);" % args)
         out.append("static_assert(" + " && ".join("plan.safe[%d] == 0x%x" % (k, safe[k]) for k in range(16)) + ", \"regenerate fp_gfx950_gen.h\");")
@@ -292,6 +331,8 @@ def main():
     gen_redc2(out, mod, redc_safe, redc_last)
     out.append("")
     gen_mul2(out, mod, mul_safe, mul_last)
+    out.append("")
+    gen_dot2(out, mod, dot2_safe, dot2_last)
     out.append("")
     path = os.path.join(ROOT, "rabe_amd", "csrc", "bn254", "fp_gfx950_gen.h")
     with open(path, "w") as f:

@@ -40,7 +40,7 @@ def listing():
 
 lines = listing().split('\n')
 start = next(i for i, l in enumerate(lines) if re.match(r'^[0-9a-f]+ <_Z\d+%s[A-Z]\S*>:' % kname, l))
-end = next(i for i in range(start + 1, len(lines)) if re.match(r'^[0-9a-f]+ <[^L]\S*>:', lines[i]))
+end = next((i for i in range(start + 1, len(lines)) if re.match(r'^[0-9a-f]+ <[^L]\S*>:', lines[i])), len(lines))   # the unit's last kernel
 ins, labels = [], {}
 for l in lines[start + 1:end]:
     l = l.split('//')[0].strip()
