@@ -219,6 +219,21 @@ int32_t rhip_gt_pow(rhip_ctx* ctx, size_t n, const rhip_gt* dev_a, const rhip_fr
 int32_t rhip_gt_pow_rows(rhip_ctx* ctx, size_t n_rows, const uint32_t* dev_item_row_off /*[n_items+1]*/, const rhip_gt* dev_a /*[n_rows]*/,
                          size_t n_items, const rhip_fr* dev_k /*[n_items]*/, const rhip_gt* dev_mul /*[n_rows] or NULL*/, uint32_t flags,
                          rhip_gt* dev_out /*[n_rows]*/);
+/* Gt multi-exponentiation per item: out[i] = (dev_mul ? mul[i] : 1) * prod over the rows t in [item_row_off[i], item_row_off[i+1]) of
+ * a[t]^(+-k[t]), minus with RHIP_GT_POW_INVERT; offsets as rhip_gt_pow_rows (an item without rows gives mul[i] or 1).  The shape of AW11's
+ * leading factor c_0 * prod C1_e^(-c_e) (aw11/mod.rs:320-352).  Any 256-bit scalar word is accepted and brought below r where it is
+ * loaded; zero and multiples of r give a factor of 1.  Every scalar is recoded on the device into width-4 signed odd digits (+-1, +-3, +-5,
+ * +-7; 128 bytes of staging per scalar), every row gets the table a, a^3, a^5, a^7 in a work arena of the context (4 x 384 = 1536 bytes
+ * per row), and lane (chunk, item) walks its chunk of at most C rows on ONE chain of cyclotomic squarings: a non-zero digit costs a table
+ * load, a conjugation when it is negative and one multiplication (~51 per 254-bit scalar against ~85 over the plain NAF); a finish lane
+ * per item multiplies the L partial products and mul[i].  chunk_terms = 0 lets the engine choose (L, C) from the compute-unit count and the
+ * longest item; another value forces C.  The offsets are read back once for that (the call synchronises its stream).
+ * The elements a[t] must be members of Gt (rhip_gt_is_member): the routine squares cyclotomically and inverts by conjugation, so for
+ * anything else rhip_gt_pow + rhip_gt_product is the route; mul[i] may be any field element.  dev_out may be dev_mul.  Same bytes as
+ * rhip_gt_pow -> (rhip_gt_inv) -> rhip_gt_product -> rhip_gt_mul.  The digit staging is zeroed when the call's kernels are done. */
+int32_t rhip_gt_multiexp_rows(rhip_ctx* ctx, size_t n_rows, const uint32_t* dev_item_row_off /*[n_items+1]*/, const rhip_gt* dev_a /*[n_rows]*/,
+                              const rhip_fr* dev_k /*[n_rows]*/, size_t n_items, const rhip_gt* dev_mul /*[n_items] or NULL*/, uint32_t flags,
+                              uint32_t chunk_terms /*0 = the engine's choice*/, rhip_gt* dev_out /*[n_items]*/);
 
 /* n independent pairings e(p_i, q_i) */
 int32_t rhip_pairing(rhip_ctx* ctx, size_t n, const rhip_g1* dev_p, const rhip_g2* dev_q, rhip_gt* dev_out);
@@ -657,6 +672,17 @@ int32_t rhip_aw11_decrypt_batch(rhip_ctx* ctx, size_t n_items, size_t max_pairs,
                                 const uint32_t* dev_ct_row_off /*[n_items+1]*/, const rhip_g1* dev_sk_hash /*[n_sk]*/, const rhip_g1* dev_sk_k,
                                 const uint32_t* dev_sk_attr_off /*[n_sk+1]*/, const uint32_t* dev_sk_idx /*[n_items] or NULL*/,
                                 rhip_gt* dev_out /*[n_items]*/);
+/* The same call, same arguments, same bytes, with the leading factor c_0 * prod_e C1_e^(-c_e) over width-4 signed windows (the routine of
+ * rhip_gt_multiexp_rows: k_gtmexp4_digits, k_gtmexp4_table, k_gt_mexp4_partial, k_gt_mexp4_finish) in place of k_gt_multiexp_partial +
+ * k_gt_lead; every other launch is rhip_aw11_decrypt_batch's.  Measured slower on AW11's own coefficients (docs/tried.md): no call of the host
+ * layer takes it unless RABE_AW11_LEAD_W4 is set (rabe_aw11_decaps_packed, tools/bench_aw11_kem.py). */
+int32_t rhip_aw11_decrypt_batch_w4(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel,
+                                   const uint32_t* dev_pair_off /*[n_items+1]*/, const uint32_t* dev_sel_start /*[n_items]*/,
+                                   const uint32_t* dev_sel_ct_row, const uint32_t* dev_sel_sk_attr, const rhip_fr* dev_sel_coeff,
+                                   const rhip_gt* dev_ct_c0 /*[n_items]*/, const rhip_gt* dev_ct_c1, const rhip_g2* dev_ct_c2, const rhip_g2* dev_ct_c3,
+                                   const uint32_t* dev_ct_row_off /*[n_items+1]*/, const rhip_g1* dev_sk_hash /*[n_sk]*/, const rhip_g1* dev_sk_k,
+                                   const uint32_t* dev_sk_attr_off /*[n_sk+1]*/, const uint32_t* dev_sk_idx /*[n_items] or NULL*/,
+                                   rhip_gt* dev_out /*[n_items]*/);
 
 /* ---- Level S: the KEM -> DEM step and label hashing on the device (rabe_amd/csrc/engine_sym.hip) ------------------------------
  * Replaces, for batches, src/utils/aes/mod.rs:10-55 (`encrypt_symmetric` :10, `decrypt_symmetric` :29, `kdf` :47: key = SHA3-256(bytes(Gt)),

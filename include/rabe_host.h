@@ -48,6 +48,7 @@ int32_t rabe_host_create(int32_t device, rabe_host** out);
  *   the KEM pair of both schemes: rabe_ac17_cp_encaps_packed, rabe_ac17_cp_decaps_packed, rabe_bsw_encaps_packed, rabe_bsw_decaps_packed;
  *   the GHW11 KEM: rabe_ghw11_encaps_packed, rabe_ghw11_decaps_out_packed, rabe_ghw11_decaps_packed;
  *   the key-policy KEMs: rabe_ac17_kp_encaps_packed, rabe_ac17_kp_decaps_packed, rabe_lsw_decaps_packed;
+ *   the AW11 KEM: rabe_aw11_encaps_packed, rabe_aw11_decaps_packed;
  *   the GHW11 service: rabe_ghw11_encrypt_packed, rabe_ghw11_transform_packed, rabe_ghw11_decrypt_out_packed, rabe_ghw11_decrypt_packed,
  *     rabe_ghw11_keygen_packed, rabe_ghw11_provision_packed;
  *   the DNF schemes' encrypt: rabe_bdabe_encrypt_packed, rabe_mke08_encrypt_packed.
@@ -379,6 +380,25 @@ int32_t rabe_aw11_encrypt_packed(rabe_host* h, const void* gk, const void* const
 int32_t rabe_aw11_decrypt_packed(rabe_host* h, const void* gk, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
                                  const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* pt_buf, size_t pt_cap,
                                  uint64_t* pt_off /*[n_items+1]*/);
+/* Key encapsulation for aw11: everything said at rabe_ac17_cp_{encaps,decaps}_packed about the format, the key, the failure of an item alone
+ * (status -1 and 32 zero bytes: bounds, membership unless RABE_PACKED_TRUSTED, a key that lacks the attributes), the bounds and the scrubbed
+ * staging, with Aw11Ciphertext records and rabe_aw11_decrypt_gt as the definition of X.  Compositions: the reference has neither function.
+ * ENCAPS: arguments of rabe_aw11_encrypt_packed minus the payloads, plus key_buf.  Header i is the record rabe_aw11_encrypt_packed writes for
+ *   the same draws with a sealed part of length zero; key i = SHA3-256(bytes(msg_i)).  DRAW ORDER: rabe_aw11_encrypt_packed's minus the AES
+ *   nonce -- per item s, the gate coefficients of the s-shares then of the 0-shares, msg, one r_x per share.  No AES kernel is launched.
+ * DECAPS: ONE key against n_items records, arguments of rabe_aw11_decrypt_packed with key_buf in place of the plaintext buffers.  Headers and
+ *   full records are both valid input; the sealed part is neither read nor authenticated.  The launch set is rabe_aw11_decrypt_packed's up to
+ *   the final Gt -- parsing, membership passes, selection, k_aw11_dec_pairs, the G2 sum, the leading factor and the pairings unchanged -- then
+ *   the KDF behind the verdict mask and one download of 32 n_items bytes.  No Gt element crosses PCIe.  The leading factor
+ *   c_0 * prod C1_e^(-c_e) over width-4 windows (rhip_aw11_decrypt_batch_w4, the kernels of rhip_gt_multiexp_rows) was built for this call and
+ *   measured SLOWER on this scheme's coefficients (products of 2 and -1: docs/tried.md), so k_gt_multiexp_partial + k_gt_lead stay; the
+ *   environment variable RABE_AW11_LEAD_W4 puts the windowed routine in their place for measurements (same keys).
+ * Both calls are cut over a device group where the calls they compose are cut. */
+int32_t rabe_aw11_encaps_packed(rabe_host* h, const void* gk, const void* const* pks, size_t n_pks, const char* const* policies, size_t n_policies,
+                                int32_t language, size_t n_items, const uint32_t* item_policy /*[n_items]*/, uint8_t* hdr_buf, size_t hdr_cap,
+                                uint64_t* hdr_off /*[n_items+1]*/, uint8_t* key_buf /*32 n_items*/);
+int32_t rabe_aw11_decaps_packed(rabe_host* h, const void* gk, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
+                                const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* key_buf /*32 n_items*/);
 
 /* ---- ghw11, CP-ABE with outsourced decryption (src/schemes/ghw11/mod.rs:92-305): `transform` is the server's part
  * (m + 2 pairings per ciphertext), `decrypt_out` the client's (one Gt power) */

@@ -47,7 +47,7 @@ struct rhip_ctx {
   void* fe_ws = nullptr;
   size_t fe_ws_bytes = 0;
   // grow-only work arenas of the job kernels (engine_jobs.hip: pair lists, running G2 points, scalars)
-  enum { N_WORK = 19 };          // 18: the masks of rhip_g1_mul_rows (engine_keys.hip); 16, 17: the masks and the point images of rhip_g2_mul_rows (engine_keys.hip); 15: the table pointers of a DNF encrypt that spans several term sets (engine_jobs.hip: rhip_dnf_encrypt_batch); 12, 13: the cross-check mode's second result buffer and its snapshot of an in-place factor (engine_jobs.hip); 14: the two-lane Miller kernel's workspace (its own slot: in the cross-check mode it alternates with the one-lane kernel's, and a grow-only slot shared by two sizes would be re-allocated -- a device-wide hipFree -- on every launch)
+  enum { N_WORK = 22 };          // 19, 20, 21: the digits, the odd-power tables and the partial products of the windowed Gt multi-exponentiation (engine_gtpow.hip); 18: the masks of rhip_g1_mul_rows (engine_keys.hip); 16, 17: the masks and the point images of rhip_g2_mul_rows (engine_keys.hip); 15: the table pointers of a DNF encrypt that spans several term sets (engine_jobs.hip: rhip_dnf_encrypt_batch); 12, 13: the cross-check mode's second result buffer and its snapshot of an in-place factor (engine_jobs.hip); 14: the two-lane Miller kernel's workspace (its own slot: in the cross-check mode it alternates with the one-lane kernel's, and a grow-only slot shared by two sizes would be re-allocated -- a device-wide hipFree -- on every launch)
   void* work[N_WORK] = {};
   size_t work_bytes[N_WORK] = {};
   // optional per-kernel timing (HIP events on the launch stream), for bench.py's roofline leg
@@ -250,6 +250,11 @@ int32_t rhip_build_w16_g2(rhip_ctx* ctx, const G2M* t8, G2M* t16);
 int32_t rhip_launch_final_exp(rhip_ctx* ctx, size_t n_items, const uint32_t* off, uint32_t stride, const GtM* mill, const rhip_gt* mul_in,
                               rhip_gt* out);
 #define launch_final_exp rhip_launch_final_exp
+// engine_gtpow.hip: out[i] = (mul ? mul[i] : 1) * prod_j base[term_off[i] + j]^(+-k[k_start[i] + j]) over width-4 signed windows (the body of
+// rhip_gt_multiexp_rows).  The bases come in wire form (a_wire) or in Montgomery form (a_mont), one of the two NULL; k_start NULL: the
+// scalars are per term (k_start = term_off).  max_terms >= every item's term count; chunk_terms 0: rb_gtmexp4_chunks decides.
+int32_t rhip_gt_mexp4_run(rhip_ctx* ctx, size_t n_items, size_t max_terms, size_t n_terms, const uint32_t* term_off, const rhip_gt* a_wire, const GtM* a_mont,
+                          size_t n_k, const rhip_fr* k, const uint32_t* k_start, const rhip_gt* mul, uint32_t flags, uint32_t chunk_terms, rhip_gt* out);
 // ------------------------------------------------------------------------------------------------
 // fixed-base tables: T[w][d-1] = (d * 256^w) * base, d = 1..255, w = 0..31, affine Montgomery.
 #define TBL_WINDOWS 32

@@ -2063,11 +2063,13 @@ __global__ void __launch_bounds__(64, RB_MIN_WAVES) k_gt_lead(size_t n_items, ui
   for (uint32_t c = 0; c < L; c++) acc = fp12_mul_fn(acc, ld_gt_m(part + i * L + c));
   store_gt(lead[i].l, acc);
 }
-extern "C" int32_t rhip_aw11_decrypt_batch(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
-                                           const uint32_t* sel_start, const uint32_t* sel_ct_row, const uint32_t* sel_sk_attr, const rhip_fr* sel_coeff,
-                                           const rhip_gt* ct_c0, const rhip_gt* ct_c1, const rhip_g2* ct_c2, const rhip_g2* ct_c3,
-                                           const uint32_t* ct_row_off, const rhip_g1* sk_hash, const rhip_g1* sk_k, const uint32_t* sk_attr_off,
-                                           const uint32_t* sk_idx, rhip_gt* out) {
+// lead_w4: the leading factor from the windowed routine of engine_gtpow.hip (rhip_aw11_decrypt_batch_w4) instead of the NAF walk; every other
+// launch is the same
+static int32_t aw11_decrypt_body(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
+                                 const uint32_t* sel_start, const uint32_t* sel_ct_row, const uint32_t* sel_sk_attr, const rhip_fr* sel_coeff,
+                                 const rhip_gt* ct_c0, const rhip_gt* ct_c1, const rhip_g2* ct_c2, const rhip_g2* ct_c3,
+                                 const uint32_t* ct_row_off, const rhip_g1* sk_hash, const rhip_g1* sk_k, const uint32_t* sk_attr_off,
+                                 const uint32_t* sk_idx, rhip_gt* out, bool lead_w4) {
   NEED(ctx);
   if (!n_items) return RHIP_OK;
   if (!total_pairs || !pair_off || !n_sel) return RHIP_ERR_ARG;
@@ -2106,10 +2108,32 @@ extern "C" int32_t rhip_aw11_decrypt_batch(rhip_ctx* ctx, size_t n_items, size_t
           (const uint32_t*)w_off, sel_start, (const G2M*)t_c3, (const uint32_t*)w_masks, 0, p_g2);
   KLAUNCH(ctx, "k_msm_finish_g2", k_msm_finish_g2, dim3(blocks_for(n_items, 128)), dim3(128), 0, ctx->stream, n_items, L, (const G2JM*)p_g2, pair_off,
           pl.Q, pl.qref);
-  KLAUNCH(ctx, "k_gt_multiexp_partial", k_gt_multiexp_partial, dim3(blocks_for(n_items * L, 64)), dim3(64), 0, ctx->stream, n_items, L, C,
-          (const uint32_t*)w_off, sel_start, (const GtM*)t_c1, (const uint32_t*)w_masks, 1, p_gt);
-  KLAUNCH(ctx, "k_gt_lead", k_gt_lead, dim3(blocks_for(n_items, 64)), dim3(64), 0, ctx->stream, n_items, L, ct_c0, (const GtM*)p_gt, lead);
+  if (lead_w4) {
+    rc = rhip_gt_mexp4_run(ctx, n_items, max_pairs - 1, total_terms, (const uint32_t*)w_off, nullptr, (const GtM*)t_c1, n_sel, sel_coeff, sel_start, ct_c0,
+                           RHIP_GT_POW_INVERT, 0, lead);
+    if (rc) return rc;
+  } else {
+    KLAUNCH(ctx, "k_gt_multiexp_partial", k_gt_multiexp_partial, dim3(blocks_for(n_items * L, 64)), dim3(64), 0, ctx->stream, n_items, L, C,
+            (const uint32_t*)w_off, sel_start, (const GtM*)t_c1, (const uint32_t*)w_masks, 1, p_gt);
+    KLAUNCH(ctx, "k_gt_lead", k_gt_lead, dim3(blocks_for(n_items, 64)), dim3(64), 0, ctx->stream, n_items, L, ct_c0, (const GtM*)p_gt, lead);
+  }
   return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, (const LineM*)nullptr, (const void*)nullptr, (const rhip_gt*)lead, out);
+}
+extern "C" int32_t rhip_aw11_decrypt_batch(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
+                                           const uint32_t* sel_start, const uint32_t* sel_ct_row, const uint32_t* sel_sk_attr, const rhip_fr* sel_coeff,
+                                           const rhip_gt* ct_c0, const rhip_gt* ct_c1, const rhip_g2* ct_c2, const rhip_g2* ct_c3,
+                                           const uint32_t* ct_row_off, const rhip_g1* sk_hash, const rhip_g1* sk_k, const uint32_t* sk_attr_off,
+                                           const uint32_t* sk_idx, rhip_gt* out) {
+  return aw11_decrypt_body(ctx, n_items, max_pairs, total_pairs, n_sel, pair_off, sel_start, sel_ct_row, sel_sk_attr, sel_coeff, ct_c0, ct_c1, ct_c2, ct_c3,
+                           ct_row_off, sk_hash, sk_k, sk_attr_off, sk_idx, out, false);
+}
+extern "C" int32_t rhip_aw11_decrypt_batch_w4(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
+                                              const uint32_t* sel_start, const uint32_t* sel_ct_row, const uint32_t* sel_sk_attr, const rhip_fr* sel_coeff,
+                                              const rhip_gt* ct_c0, const rhip_gt* ct_c1, const rhip_g2* ct_c2, const rhip_g2* ct_c3,
+                                              const uint32_t* ct_row_off, const rhip_g1* sk_hash, const rhip_g1* sk_k, const uint32_t* sk_attr_off,
+                                              const uint32_t* sk_idx, rhip_gt* out) {
+  return aw11_decrypt_body(ctx, n_items, max_pairs, total_pairs, n_sel, pair_off, sel_start, sel_ct_row, sel_sk_attr, sel_coeff, ct_c0, ct_c1, ct_c2, ct_c3,
+                           ct_row_off, sk_hash, sk_k, sk_attr_off, sk_idx, out, true);
 }
 
 // ------------------------------------------------------------------------------------------------ BDABE / MKE08 encrypt (DNF policies)

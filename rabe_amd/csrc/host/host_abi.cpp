@@ -1476,6 +1476,40 @@ int32_t rabe_aw11_decrypt_packed(rabe_host* h, const void* gk, const void* sk, s
   return 0;
   GUARD_END(h)
 }
+// key encapsulation over the AW11 pair: both calls are cut over a device group where rabe_aw11_{encrypt,decrypt}_packed are cut, a block's
+// 32-byte key slots written straight to key_buf + 32 lo
+int32_t rabe_aw11_encaps_packed(rabe_host* h, const void* gk, const void* const* pks, size_t n_pks, const char* const* policies, size_t n_policies,
+                                int32_t language, size_t n_items, const uint32_t* item_policy, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off,
+                                uint8_t* key_buf) {
+  GUARD_BEGIN
+  if (!item_policy || !hdr_off) throw RabeError("aw11::encaps_packed: null input");
+  std::vector<const aw11::Aw11PublicKey*> p;
+  for (size_t i = 0; i < n_pks; i++) p.push_back((const aw11::Aw11PublicKey*)pks[i]);
+  const auto& g = *(const aw11::Aw11GlobalKey*)gk;
+  const auto pols = strs(policies, n_policies);
+  const auto lang = lang_of(language);
+  return pipeline::produce(h->engines_if(key_buf != nullptr), h->rng(), n_items, CHUNK_AW11,
+                           [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
+    return aw11::encaps_packed(eng, r, g, p, pols, lang, hi - lo, item_policy + lo, out, cap, off, key_buf ? key_buf + KEM_KEY * lo : nullptr);
+  }, hdr_buf, hdr_cap, hdr_off) ? 0 : 1;
+  GUARD_END(h)
+}
+int32_t rabe_aw11_decaps_packed(rabe_host* h, const void* gk, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
+                                uint32_t flags, int32_t* status, uint8_t* key_buf) {
+  GUARD_BEGIN
+  std::vector<std::string> errors;
+  const auto& g = *(const aw11::Aw11GlobalKey*)gk;
+  const auto& key = *(const aw11::Aw11SecretKey*)sk;
+  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
+  pipeline::for_blocks(h->engines_if(ct_off && status && key_buf), n_items, CHUNK_AW11, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
+    aw11::decaps_packed(eng, g, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
+                        key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
+    return true;
+  }, &errors);
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  return 0;
+  GUARD_END(h)
+}
 int32_t rabe_ac17_cp_decrypt_batch(rabe_host* h, size_t n, const void* const* sks, const void* const* cts, int32_t* status,
                                    uint8_t** plaintexts, size_t* lens) {
   GUARD_BEGIN

@@ -1704,10 +1704,13 @@ void destroy_pk(void* h) { rhip_aw11_pk_destroy((rhip_aw11_pk*)h); }
 // coefficients of the s-shares then of the 0-shares (:259-260), msg (:262), one r_x per share (:267), the nonce.  Record =
 // Aw11Ciphertext: policy, c_0, row count, per row (NAME_COL upper-cased, c1, c2, c3), sealed data.  A leaf whose attribute no
 // authority key lists is silently dropped by the reference (:269-271); here it is an error (use rabe_aw11_encrypt for that case).
-bool encrypt_packed(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::vector<const Aw11PublicKey*>& pks, const std::vector<std::string>& policies,
-                    PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf,
-                    size_t out_cap, uint64_t* out_off) {
-  Timer tm("aw11::encrypt_packed");
+// key_buf != nullptr is the key encapsulation (encaps_packed below): no plaintexts, no nonce draw, records that end in the length field of an
+// empty sealed part, and per item the content key SHA3-256(bytes(msg)) instead of a payload sealed under it.
+static bool encrypt_core(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::vector<const Aw11PublicKey*>& pks, const std::vector<std::string>& policies,
+                         PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf,
+                         size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  const bool kem = key_buf != nullptr;
+  Timer tm(kem ? "aw11::encaps_packed" : "aw11::encrypt_packed");
   Engine::ArenaScope arena(eng);
   PkArg arg{&gk, {}};
   std::string key((const char*)gk.g1.data(), 64);
@@ -1732,7 +1735,7 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::v
       fixed[p] += 4 + up.size() + 384 + 128 + 128;
     }
   }
-  if (!record_offsets("aw11::encrypt_packed", "item_policy", n, item_policy, policies.size(), fixed, pt_off, out_buf, out_cap, out_off)) return false;
+  if (!record_offsets("aw11::encrypt_packed", "item_policy", n, item_policy, policies.size(), fixed, kem ? nullptr : pt_off, out_buf, out_cap, out_off)) return false;
   st.place(n, item_policy, 2);          // the s-shares' coefficients, then the 0-shares'
   std::vector<uint32_t> n_coef(n);
   for (size_t i = 0; i < n; i++) n_coef[i] = st.pols[item_policy[i]]->n_coef;
@@ -1751,7 +1754,7 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::v
     Fr rho = r.next_fr();
     memcpy(h_rho + 32 * i, rho.l, 32);
     for (uint32_t y = row_off[i]; y < row_off[i + 1]; y++) { Fr a = r.next_fr(); memcpy(h_rand + 32 * (size_t)y, a.l, 32); }
-    r.fill(nonces[i].data(), 12);
+    if (!kem) r.fill(nonces[i].data(), 12);
   });
   tm.lap("policies + draws");
   rhip_ctx* cx = eng.ctx();
@@ -1779,13 +1782,39 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::v
       L.src(2, (uint32_t)(128 * y), 128);
       L.src(3, (uint32_t)(128 * y), 128);
     }
+    if (kem) {
+      if (L.bytes() + 4 != fixed[p_]) throw RabeError("aw11::encaps_packed: record layout and size disagree");
+      L.u32(0);          // the length field of an empty sealed part; no sealed source
+    }
   }
   std::vector<uint64_t> src_off(4 * n);
   for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * i; src_off[n + i] = 384ull * row_off[i]; src_off[2 * n + i] = src_off[3 * n + i] = 128ull * row_off[i]; }
+  if (kem) {          // headers from the template alone, keys straight out of the msg array: no seal kernel is launched
+    DBuf d_keys(&eng, n * 32 + 4);
+    eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
+    eng.check(rhip_gt_kdf_batch(cx, n, d_msg.as<rhip_gt>(), nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
+    emit_plain_records(eng, layouts, n, item_policy, {d_c0.ptr(), d_c1.ptr(), d_c2.ptr(), d_c3.ptr()}, src_off, out_off, out_buf);
+    if (n) eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
+    tm.lap("device: group arithmetic, headers, keys; two copies out");
+    return true;
+  }
   emit_sealed_records(eng, layouts, n, item_policy, {d_c0.ptr(), d_c1.ptr(), d_c2.ptr(), d_c3.ptr()}, src_off, d_msg.ptr(), (const uint8_t*)nonces.data(),
                       pt_blob, pt_off, out_off, out_buf);
   tm.lap("device: group arithmetic, records, sealing; one copy out");
   return true;
+}
+bool encrypt_packed(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::vector<const Aw11PublicKey*>& pks, const std::vector<std::string>& policies,
+                    PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf,
+                    size_t out_cap, uint64_t* out_off) {
+  return encrypt_core(eng, rng, gk, pks, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off, nullptr);
+}
+// n key encapsulations (include/rabe_host.h: rabe_aw11_encaps_packed): header i is the Aw11Ciphertext record encrypt_packed writes for the same
+// draws with a sealed part of length zero, key_buf + 32 i = SHA3-256(bytes(msg_i)).  Draw order: encrypt_packed's minus the nonce.
+bool encaps_packed(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::vector<const Aw11PublicKey*>& pks, const std::vector<std::string>& policies,
+                   PolicyLanguage language, size_t n, const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  if (n && !key_buf) throw RabeError("aw11::encaps_packed: null input");
+  if (!n) { out_off[0] = 0; return true; }
+  return encrypt_core(eng, rng, gk, pks, policies, language, n, item_policy, nullptr, nullptr, out_buf, out_cap, out_off, key_buf);
 }
 
 namespace {
@@ -1872,14 +1901,17 @@ bool keygen_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11MasterKey& ms
 // n calls of aw11::decrypt (aw11/mod.rs:298-366) with one key.  Per distinct policy: traverse_policy, calc_pruned, and per pruned
 // (name, name_col) the FIRST key attribute named `name`, the FIRST ciphertext row named name_col (literal spelling, :325-333) and the
 // FIRST coefficient named name_col.
-bool decrypt_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
-                    bool trusted, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
-  Timer tm("aw11::decrypt_packed");
+// key_buf != nullptr is the key decapsulation (decaps_packed below): the same launch set up to the final Gt, then the KDF behind the verdict
+// mask (records.h: derive_keys) instead of the open; pt_buf / pt_cap / pt_off are unused, the sealed part is skipped by its length field and never read.
+static bool decrypt_core(Engine& eng, const Aw11GlobalKey& gk, const Aw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
+                         bool trusted, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors, uint8_t* key_buf) {
+  const bool kem = key_buf != nullptr;
+  Timer tm(kem ? "aw11::decaps_packed" : "aw11::decrypt_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
   if (!ct_off || (n && !ct_blob)) throw RabeError("aw11::decrypt_packed: null input");
   const uint64_t span = check_offsets(n, ct_off, ct_len, errors);
-  if (!pt_buf || pt_cap < span) return false;
+  if (!kem && (!pt_buf || pt_cap < span)) return false;
   BlobGather gather(eng, ct_blob, ct_len);          // the blob starts for the device now, beside the parsing below (records.h)
   std::vector<std::string> str_attr;
   for (const auto& a : sk.attr) str_attr.push_back(a.first);
@@ -1989,7 +2021,10 @@ bool decrypt_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11SecretKey& s
       ws.check_g2(eng, walk_checks(), sel, total, d_row_off.as<uint32_t>(), 1);
     }
     if (ws.walked) ws.walked->arm();
-    int32_t rc = rhip_aw11_decrypt_batch(cx, m_items, sel.max_pairs, sel.pair_off[m_items], sel.sel_rec.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
+    // measured (docs/tried.md): the windowed leading factor loses to the NAF walk on this scheme's coefficients, so the decaps keeps the
+    // decrypt's kernels; RABE_AW11_LEAD_W4=1 puts the windowed routine in its place (tools/bench_aw11_kem.py alternates the two)
+    const bool lead_w4 = kem && getenv("RABE_AW11_LEAD_W4") != nullptr;
+    int32_t rc = (lead_w4 ? rhip_aw11_decrypt_batch_w4 : rhip_aw11_decrypt_batch)(cx, m_items, sel.max_pairs, sel.pair_off[m_items], sel.sel_rec.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
                                          d_sel_ct.as<uint32_t>(), d_sel_sk.as<uint32_t>(), d_sel_z.as<rhip_fr>(), d_c0.as<rhip_gt>(), d_c1.as<rhip_gt>(),
                                          d_c2.as<rhip_g2>(), d_c3.as<rhip_g2>(), d_row_off.as<uint32_t>(), d_hash.as<rhip_g1>(), d_kk.as<rhip_g1>(),
                                          d_sk_attr_off.as<uint32_t>(), d_sk_idx.as<uint32_t>(), d_out.as<rhip_gt>());
@@ -1999,11 +2034,29 @@ bool decrypt_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11SecretKey& s
       ws.fail(live, {0, 1, 2, ws.k_alone}, "deserialize: a ciphertext element is not a group member (FieldError::NotMember)", errors);
     }
   }
+  if (kem) {
+    ws.fail_walked(live, "deserialize: a ciphertext element is not a group member (FieldError::NotMember)", errors);
+    derive_keys(eng, n, live, d_out.ptr(), status, key_buf, *errors);
+    tm.lap(trusted ? "device: gather, pairings, keys" : "device: gather, pairings, keys; membership beside");
+    return true;
+  }
   // KDF + AES-GCM open on the device: the decrypted Gt never leaves HBM; plaintext bytes come back in one copy
   open_sealed_records(eng, n, live, d_out.ptr(), gather.dev_blob(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
   ws.retract(live, "deserialize: a ciphertext element is not a group member (FieldError::NotMember)", status, pt_buf, pt_off, errors);
   tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
   return true;
+}
+bool decrypt_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
+                    bool trusted, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
+  return decrypt_core(eng, gk, sk, n, ct_blob, ct_len, ct_off, trusted, status, pt_buf, pt_cap, pt_off, errors, nullptr);
+}
+// n key decapsulations under ONE key (include/rabe_host.h: rabe_aw11_decaps_packed): key_buf + 32 i = SHA3-256(bytes(Gt)) of what decrypt_gt
+// returns for record i; input may be headers or full records
+void decaps_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
+                   bool trusted, int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
+  if (n && (!status || !key_buf)) throw RabeError("aw11::decaps_packed: null input");
+  uint8_t none = 0;          // n = 0: nothing is written
+  decrypt_core(eng, gk, sk, n, ct_blob, ct_len, ct_off, trusted, status, nullptr, 0, nullptr, errors, key_buf ? key_buf : &none);
 }
 }  // namespace aw11
 

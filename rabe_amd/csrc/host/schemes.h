@@ -193,6 +193,13 @@ bool encrypt_packed(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::v
                     size_t out_cap, uint64_t* out_off);
 bool decrypt_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
                     bool trusted, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors);
+// key encapsulation (include/rabe_host.h: rabe_aw11_{encaps,decaps}_packed): encrypt_packed's headers (records with an empty sealed part) +
+// 32-byte content keys out; content keys back under ONE key (decrypt_packed's launch set up to the final Gt, then the masked KDF);
+// status[i] = -1 and 32 zero bytes for an item that fails
+bool encaps_packed(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::vector<const Aw11PublicKey*>& pks, const std::vector<std::string>& policies,
+                   PolicyLanguage language, size_t n, const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf);
+void decaps_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
+                   bool trusted, int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors);
 }  // namespace aw11
 
 namespace ghw11 {

@@ -294,6 +294,33 @@ class Engine:
         raw = self.download(out, n_rows * GT)
         return [raw[i * GT:(i + 1) * GT] for i in range(n_rows)]
 
+    def gt_multiexp_rows(self, a, item_row_off, scalars, mul=None, invert=False, chunk_terms=0):
+        """out[i] = (mul[i] if mul else 1) * prod of a[t]^(+-scalars[t]) over the rows t of item i, minus with invert (rhip_gt_multiexp_rows:
+        width-4 signed digits per scalar, the table a, a^3, a^5, a^7 per row, lane (chunk, item) on one chain of cyclotomic squarings);
+        item_row_off: n_items + 1 non-decreasing offsets from 0 to len(a); chunk_terms 0 lets the engine choose the chunking, another value
+        forces the rows per lane.  The elements of `a` must be members of Gt.  Same bytes as gt_pow + gt_inv + gt_product + gt_mul."""
+        n_rows, n_items = len(a), len(item_row_off) - 1
+        if len(scalars) != n_rows:
+            raise ValueError("gt_multiexp_rows: one scalar per row")
+        if n_items < 0 or item_row_off[0] != 0 or item_row_off[-1] != n_rows:
+            raise ValueError("gt_multiexp_rows: item_row_off must run from 0 to len(a)")
+        if any(item_row_off[i] > item_row_off[i + 1] for i in range(n_items)):
+            raise ValueError("gt_multiexp_rows: item_row_off must not decrease")
+        if mul is not None and len(mul) != n_items:
+            raise ValueError("gt_multiexp_rows: one mul element per item")
+        if not n_items:
+            return []
+        doff = self.upload_u32(item_row_off)
+        da = self.upload(b"".join(a)) if n_rows else None
+        dk = self.upload(b"".join(scalars)) if n_rows else None
+        dm = self.upload(b"".join(mul)) if mul is not None else None
+        out = self.alloc(n_items * GT)
+        self._check(self.lib.rhip_gt_multiexp_rows(self.ctx, ctypes.c_size_t(n_rows), doff.ptr, da.ptr if da is not None else None,
+                                                   dk.ptr if dk is not None else None, ctypes.c_size_t(n_items), dm.ptr if dm is not None else None,
+                                                   ctypes.c_uint32(1 if invert else 0), ctypes.c_uint32(chunk_terms), out.ptr))
+        raw = self.download(out, n_items * GT)
+        return [raw[i * GT:(i + 1) * GT] for i in range(n_items)]
+
     def g1_on_curve(self, p):
         return [int.from_bytes(x, "little") for x in self._elem("rhip_g1_on_curve", len(p), [p], 4)]
 
@@ -715,7 +742,9 @@ def aw11_encrypt_dev(eng, pk, n_items, total_rows, d_item_row_off, d_item_tree_l
 
 
 def aw11_decrypt_dev(eng, n_items, max_pairs, total_pairs, n_sel, d_pair_off, d_sel_start, d_sel_ct_row, d_sel_sk_attr, d_sel_coeff, d_ct_c0,
-                     d_ct_c1, d_ct_c2, d_ct_c3, d_ct_row_off, d_sk_hash, d_sk_k, d_sk_attr_off, d_sk_idx, d_out):
-    eng._check(eng.lib.rhip_aw11_decrypt_batch(eng.ctx, _sz(n_items), _sz(max_pairs), _sz(total_pairs), _sz(n_sel), _p(d_pair_off), _p(d_sel_start),
-                                               _p(d_sel_ct_row), _p(d_sel_sk_attr), _p(d_sel_coeff), _p(d_ct_c0), _p(d_ct_c1), _p(d_ct_c2),
-                                               _p(d_ct_c3), _p(d_ct_row_off), _p(d_sk_hash), _p(d_sk_k), _p(d_sk_attr_off), _p(d_sk_idx), _p(d_out)))
+                     d_ct_c1, d_ct_c2, d_ct_c3, d_ct_row_off, d_sk_hash, d_sk_k, d_sk_attr_off, d_sk_idx, d_out, w4=False):
+    """rhip_aw11_decrypt_batch; w4: rhip_aw11_decrypt_batch_w4, the same call with the leading factor over width-4 windows"""
+    fn = eng.lib.rhip_aw11_decrypt_batch_w4 if w4 else eng.lib.rhip_aw11_decrypt_batch
+    eng._check(fn(eng.ctx, _sz(n_items), _sz(max_pairs), _sz(total_pairs), _sz(n_sel), _p(d_pair_off), _p(d_sel_start),
+                  _p(d_sel_ct_row), _p(d_sel_sk_attr), _p(d_sel_coeff), _p(d_ct_c0), _p(d_ct_c1), _p(d_ct_c2),
+                  _p(d_ct_c3), _p(d_ct_row_off), _p(d_sk_hash), _p(d_sk_k), _p(d_sk_attr_off), _p(d_sk_idx), _p(d_out)))

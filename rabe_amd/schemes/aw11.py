@@ -95,3 +95,20 @@ def keygen_packed(host, gk, msk, gids, attr_sets, item_set, out=None):
         buf = np.empty(int(so[n]), dtype=np.uint8)
     _check(rc, host.h)
     return buf[:int(so[n])], so
+
+
+# ---- key encapsulation (rabe_aw11_{encaps,decaps}_packed): the packed pair without payloads
+def encaps_packed(host, gk, pks, policies, item_policy, language=JSON_POLICY, out=None):
+    """n headers (Aw11Ciphertext records with an empty sealed part: encrypt_packed's for the same draws minus the nonce) + n 32-byte content
+    keys SHA3-256(bytes(msg)).  Returns (hdr_blob view, hdr_off uint64 [n+1], keys uint8 [n, 32])."""
+    from ..hostlib import packed_encaps
+    arr = (ctypes.c_void_p * max(1, len(pks)))(*[p.ptr for p in pks])
+    return packed_encaps(host, "rabe_aw11_encaps_packed", (gk.ptr, arr, ctypes.c_size_t(len(pks))), policies, item_policy, language, out)
+
+
+def decaps_packed(host, gk, sk, ct_blob, ct_off, trusted=False):
+    """the content keys of n records (headers or full ciphertexts) under one key: key i = SHA3-256(bytes(decrypt_gt(sk, record i))); the
+    launch set is decrypt_packed's up to the final Gt.  Returns (keys uint8 [n, 32], status int32 [n]); a failed item has
+    status -1 and 32 zero bytes.  The sealed parts are neither read nor authenticated."""
+    from ..hostlib import packed_decaps
+    return packed_decaps(host, "rabe_aw11_decaps_packed", (gk.ptr, sk.ptr), ct_blob, ct_off, trusted)
