@@ -8,28 +8,15 @@
 // (the device reads its window tables in HBM, the CPU check computes the entry it is asked for).
 #pragma once
 #include "io.h"
+#include "table_walk.h"
 
 namespace rabe { namespace bn254 {
 
-// acc + tbl * k: one mixed addition (g1_madd_inl: the Z3 = Z1*H form, with its doubling and cancelling cases) per non-zero digit
+// acc + tbl * k: the 16-bit walk of table_walk.h with one mixed addition (g1_madd_inl: the Z3 = Z1*H form, with its doubling and
+// cancelling cases) per non-zero digit
 template <class TBL>
 RB_HD G1Jac lsw_walk16(G1Jac acc, const TBL& tbl, const uint32_t k[8]) {
-#pragma unroll 1
-  for (int w = 0; w < 16; w++) {
-    uint32_t word;
-    switch (w >> 1) {
-      case 0: word = k[0]; break;
-      case 1: word = k[1]; break;
-      case 2: word = k[2]; break;
-      case 3: word = k[3]; break;
-      case 4: word = k[4]; break;
-      case 5: word = k[5]; break;
-      case 6: word = k[6]; break;
-      default: word = k[7]; break;
-    }
-    const uint32_t d = (w & 1) ? (word >> 16) : (word & 0xffffu);
-    if (d) acc = g1_madd_inl(acc, tbl.entry(w, d));
-  }
+  walk16(k, [&](int w, uint32_t d) { acc = g1_madd_inl(acc, tbl.entry(w, d)); });
   return acc;
 }
 // the three elements, one at a time: the scalar of a walk is formed just before it (the two products h secret and sx h in Montgomery form,

@@ -255,23 +255,7 @@ __global__ void __launch_bounds__(64, RB_C6_WAVES) C6K(k_gt_table_pow_c6)(const 
     if (active) ld_scalar(kk, k + item * kstride + t);
 #pragma unroll 1
     for (int w = 0; w < n_win; w++) {
-      uint32_t d;
-      if (w16) {
-        uint32_t word;
-        switch (w >> 1) {
-          case 0: word = kk[0]; break;
-          case 1: word = kk[1]; break;
-          case 2: word = kk[2]; break;
-          case 3: word = kk[3]; break;
-          case 4: word = kk[4]; break;
-          case 5: word = kk[5]; break;
-          case 6: word = kk[6]; break;
-          default: word = kk[7]; break;
-        }
-        d = (w & 1) ? (word >> 16) : (word & 0xffffu);
-      } else {
-        d = scalar_byte(kk, w);
-      }
+      const uint32_t d = w16 ? digit16(kk, w) : digit8(kk, w);
       Fp2 e = fp2_zero();
       if (d) e = ld_fp2_m((tbl + (size_t)w * (w16 ? TBL16_DIGITS : TBL_DIGITS) + (d - 1))->l + 16 * ti);
       c6_put(cx, C6_B, e);

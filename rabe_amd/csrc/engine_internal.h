@@ -11,6 +11,7 @@
 
 #include "../../include/rabe_hip.h"
 #include "bn254/io.h"
+#include "bn254/table_walk.h"
 #include "bn254/coop3.h"
 
 using namespace rabe::bn254;
@@ -261,19 +262,13 @@ int32_t rhip_gt_mexp4_run(rhip_ctx* ctx, size_t n_items, size_t max_terms, size_
 #define TBL_DIGITS 255
 #define TBL16_WINDOWS 16
 #define TBL16_DIGITS 65535
-// dev: 8-bit windows; dev16: optional 16-bit windows; wide: optional signed w-bit windows (17 <= w <= 27)
+static_assert(TBL_WINDOWS == WALK8_WINDOWS && TBL16_WINDOWS == WALK16_WINDOWS, "the tables have the windows bn254/table_walk.h walks");
+// dev: 8-bit windows; dev16: optional 16-bit windows; wide: optional signed w-bit windows (17 <= w <= 27; geometry: bn254/table_walk.h)
 struct rhip_g1_table { rhip_ctx* ctx; G1M* dev; G1M* dev16; G1M* wide; int wide_bits; };
-// signed w-bit windows: k = sum_i d_i 2^(w i), -2^(w-1) < d_i <= 2^(w-1); T[i][|d|-1] = (|d| 2^(w i)) * base, the sign is
-// applied to y on the fly.  n = ceil(254 / w) windows of 2^(w-1) entries (the top one only needs 2^(254-w(n-1)) of them).
-__host__ __device__ inline int wide_windows(int w) { return (254 + w - 1) / w; }
-__host__ __device__ inline size_t wide_count(int w, int i) {
-  const int n = wide_windows(w);
-  return (i < n - 1) ? ((size_t)1 << (w - 1)) : ((size_t)1 << (254 - w * (n - 1)));
-}
-__host__ __device__ inline size_t wide_offset(int w, int i) { return (size_t)i << (w - 1); }   // windows below the top are full
 struct rhip_g2_table { rhip_ctx* ctx; G2M* dev; G2M* dev16; };   // dev16: optional 16-bit windows (134 MB)
 struct rhip_gt_table { rhip_ctx* ctx; GtM* dev; GtM* dev16; };   // dev16: optional 16-bit windows (402 MB)
 
+// The walks below bind a loop of bn254/table_walk.h (8-bit, 16-bit or signed w-bit digits) to a table load and a group operation.
 // ---- fixed-base Gt powers on the lane's home value (LdsHome above): home *= entry for every non-zero window digit.
 // `started` false: the first entry is copied instead of multiplied (and stays false when the scalar is 0).
 struct GtMOperand {
@@ -294,45 +289,42 @@ __device__ __forceinline__ void home_take_signed(bool& started, const GtM* e, bo
   if (started) facc_mul(LdsHome{}, GtMOperand{e, inverse});
   else { facc_set(LdsHome{}, GtMOperand{e, inverse}); started = true; }
 }
+static __device__ __noinline__ void home_table_pow_gt(bool& started, const GtM* tbl, const uint32_t k[8]) {
+  walk8(k, [&](int w, uint32_t d) { home_take(started, tbl + w * TBL_DIGITS + (d - 1)); });
+}
 static __device__ __noinline__ void home_table_pow_gt_w16(bool& started, const GtM* tbl, const uint32_t k[8]) {
+  walk16(k, [&](int w, uint32_t d) { home_take(started, tbl + (size_t)w * TBL16_DIGITS + (d - 1)); });
+}
+// signed windows of w bits (8 <= w <= 14, sgn_windows(w) full windows): a negative digit takes the entry's conjugate
+static __device__ __noinline__ void home_table_pow_gt_signed(bool& started, const GtM* tbl, const uint32_t k[8], int w) {
+  const int n = sgn_windows(w);
+  SignedRecoder rec(w);
 #pragma unroll 1
-  for (int w = 0; w < TBL16_WINDOWS; w++) {
-    uint32_t word;
-    switch (w >> 1) {
-      case 0: word = k[0]; break;
-      case 1: word = k[1]; break;
-      case 2: word = k[2]; break;
-      case 3: word = k[3]; break;
-      case 4: word = k[4]; break;
-      case 5: word = k[5]; break;
-      case 6: word = k[6]; break;
-      default: word = k[7]; break;
-    }
-    const uint32_t d = (w & 1) ? (word >> 16) : (word & 0xffffu);
-    if (d) home_take(started, tbl + (size_t)w * TBL16_DIGITS + (d - 1));
+  for (int i = 0; i < n; i++) {
+    const uint32_t mag = rec.next(scalar_bits(k, w * i, w));
+    if (mag) home_take_signed(started, tbl + ((size_t)i << (w - 1)) + (mag - 1), rec.carry != 0);
   }
 }
-__device__ __forceinline__ uint32_t scalar_byte(const uint32_t k[8], int w) {
-  uint32_t word;
-  switch (w >> 2) {
-    case 0: word = k[0]; break;
-    case 1: word = k[1]; break;
-    case 2: word = k[2]; break;
-    case 3: word = k[3]; break;
-    case 4: word = k[4]; break;
-    case 5: word = k[5]; break;
-    case 6: word = k[6]; break;
-    default: word = k[7]; break;
-  }
-  return (word >> (8 * (w & 3))) & 255u;
+// the value forms (64-thread blocks only: they go through the home)
+__device__ __forceinline__ Fp12 home_result(bool started) { return started ? facc_get(LdsHome{}) : fp12_one(); }
+__device__ __forceinline__ void home_put(const Fp12& v) {
+  const LdsHome h{};
+  h.st_f6(0, v.c0);
+  h.st_f6(1, v.c1);
+  h.fence();
 }
+// ---- G1: one mixed addition per non-zero digit.  The table_mul_* forms start from infinity; the table_madd_* forms take a RUNNING
+// accumulator: a sum of two fixed-base products is two walks on one accumulator and costs the additions of both and nothing else.
+// (Both are kept where kernels use both: a start from infinity written as table_madd_*(jac_inf, ...) changes the generated code of
+// the kernels that had the other form -- docs/kernels.md, "The window walks".)
 // sum of <= 32 table entries selected by the bytes of the canonical scalar k
 static __device__ __noinline__ G1Jac table_mul_g1(const G1M* tbl, const uint32_t k[8]) {
   G1Jac acc = jac_inf<Fp>();
-  for (int w = 0; w < TBL_WINDOWS; w++) {
-    uint32_t d = scalar_byte(k, w);
-    if (d) acc = jac_add_aff(acc, ld_g1_m(tbl + w * TBL_DIGITS + (d - 1)));
-  }
+  walk8(k, [&](int w, uint32_t d) { acc = jac_add_aff(acc, ld_g1_m(tbl + w * TBL_DIGITS + (d - 1))); });
+  return acc;
+}
+static __device__ __forceinline__ G1Jac table_madd_g1_inl(G1Jac acc, const G1M* tbl, const uint32_t k[8]) {
+  walk8(k, [&](int w, uint32_t d) { acc = g1_madd_inl(acc, ld_g1_m(tbl + w * TBL_DIGITS + (d - 1))); });
   return acc;
 }
 // 16-bit digits: 16 mixed additions.  The entry is fetched where it is used: holding the next entry across the addition (a
@@ -343,137 +335,60 @@ static __device__ __noinline__ G1Jac table_mul_g1(const G1M* tbl, const uint32_t
 // written per window (profiles/r02k_pmc_traffic.txt: 14 GB of write-back per launch of k_ac17_enc_rows, 22 x its results).
 static __device__ __forceinline__ G1Jac table_mul_g1_w16_inl(const G1M* tbl, const uint32_t k[8]) {
   G1Jac acc = jac_inf<Fp>();
-#pragma unroll 1
-  for (int w = 0; w < TBL16_WINDOWS; w++) {
-    uint32_t word;
-    switch (w >> 1) {
-      case 0: word = k[0]; break;
-      case 1: word = k[1]; break;
-      case 2: word = k[2]; break;
-      case 3: word = k[3]; break;
-      case 4: word = k[4]; break;
-      case 5: word = k[5]; break;
-      case 6: word = k[6]; break;
-      default: word = k[7]; break;
-    }
-    const uint32_t d = (w & 1) ? (word >> 16) : (word & 0xffffu);
-    if (d) acc = g1_madd_inl(acc, ld_g1_m(tbl + (size_t)w * TBL16_DIGITS + (d - 1)));
-  }
+  walk16(k, [&](int w, uint32_t d) { acc = g1_madd_inl(acc, ld_g1_m(tbl + (size_t)w * TBL16_DIGITS + (d - 1))); });
+  return acc;
+}
+static __device__ __forceinline__ G1Jac table_madd_g1_w16_inl(G1Jac acc, const G1M* tbl, const uint32_t k[8]) {
+  walk16(k, [&](int w, uint32_t d) { acc = g1_madd_inl(acc, ld_g1_m(tbl + (size_t)w * TBL16_DIGITS + (d - 1))); });
   return acc;
 }
 static __device__ __noinline__ G1Jac table_mul_g1_w16(const G1M* tbl, const uint32_t k[8]) { return table_mul_g1_w16_inl(tbl, k); }
-// signed w-bit digits: ceil(254/w) mixed additions (11 for w = 24, 10 for w = 26); the digit's sign flips y
-__device__ __forceinline__ uint32_t scalar_bits(const uint32_t k[8], int b, int w) {
-  const int word = b >> 5, sh = b & 31;
-  uint32_t lo, hi;
-  switch (word) {
-    case 0: lo = k[0]; hi = k[1]; break;
-    case 1: lo = k[1]; hi = k[2]; break;
-    case 2: lo = k[2]; hi = k[3]; break;
-    case 3: lo = k[3]; hi = k[4]; break;
-    case 4: lo = k[4]; hi = k[5]; break;
-    case 5: lo = k[5]; hi = k[6]; break;
-    case 6: lo = k[6]; hi = k[7]; break;
-    default: lo = k[7]; hi = 0; break;
-  }
-  const uint64_t v = (((uint64_t)hi << 32) | lo) >> sh;
-  return (uint32_t)v & ((1u << w) - 1u);
-}
+// signed w-bit digits of the wide table: ceil(254/w) mixed additions (11 for w = 24, 10 for w = 26); the digit's sign flips y
+// (the loop is written out around the shared recoder, as in the G2 and Gt signed walks: docs/tried.md, "one signed loop with a step")
 static __device__ __forceinline__ G1Jac table_mul_g1_wide_inl(const G1M* tbl, const uint32_t k[8], int w) {
   const int n = wide_windows(w);
-  const uint32_t half = 1u << (w - 1);
   G1Jac acc = jac_inf<Fp>();
-  uint32_t carry = 0;
+  SignedRecoder rec(w);
 #pragma unroll 1
   for (int i = 0; i < n; i++) {
-    const uint32_t raw = scalar_bits(k, w * i, w) + carry;
-    carry = raw > half ? 1u : 0u;
-    const uint32_t mag = carry ? (1u << w) - raw : raw;
+    const uint32_t mag = rec.next(scalar_bits(k, w * i, w));
     if (mag) {
-      G1Aff e = ld_g1_m(tbl + wide_offset(w, i) + (mag - 1));        // fetched where it is used (see table_mul_g1_w16)
-      if (carry) e.y = neg(e.y);
+      G1Aff e = ld_g1_m(tbl + wide_offset(w, i) + (mag - 1));        // fetched where it is used (see table_mul_g1_w16_inl)
+      if (rec.carry) e.y = neg(e.y);
       acc = g1_madd_inl(acc, e);
     }
   }
   return acc;
 }
 static __device__ __noinline__ G1Jac table_mul_g1_wide(const G1M* tbl, const uint32_t k[8], int w) { return table_mul_g1_wide_inl(tbl, k, w); }
-// The same signed w-bit recoding for tables with FULL windows (8 <= w <= 14; per-attribute bases of AW11): n = sgn_windows(w) windows
-// of 2^(w-1) entries each, T[i][|d|-1] = (|d| 2^(w i)) * base.  n w >= 255, so the last carry always lands in a window.
-__host__ __device__ inline int sgn_windows(int w) { return (255 + w - 1) / w; }
-__host__ __device__ inline size_t sgn_entries(int w) { return (size_t)sgn_windows(w) << (w - 1); }
+// ---- G2: the same on jac_add_aff.  The inlined forms are for kernels that walk two tables in a row: the out-of-line forms return
+// the point through a stack slot.
+static __device__ __forceinline__ G2Jac table_mul_g2_inl(const G2M* tbl, const uint32_t k[8]) {
+  G2Jac acc = jac_inf<Fp2>();
+  walk8(k, [&](int w, uint32_t d) { acc = jac_add_aff(acc, ld_g2_m(tbl + w * TBL_DIGITS + (d - 1))); });
+  return acc;
+}
+static __device__ __forceinline__ G2Jac table_mul_g2_w16_inl(const G2M* tbl, const uint32_t k[8]) {
+  G2Jac acc = jac_inf<Fp2>();
+  walk16(k, [&](int w, uint32_t d) { acc = jac_add_aff(acc, ld_g2_m(tbl + (size_t)w * TBL16_DIGITS + (d - 1))); });
+  return acc;
+}
+static __device__ __noinline__ G2Jac table_mul_g2(const G2M* tbl, const uint32_t k[8]) { return table_mul_g2_inl(tbl, k); }
+static __device__ __noinline__ G2Jac table_mul_g2_w16(const G2M* tbl, const uint32_t k[8]) { return table_mul_g2_w16_inl(tbl, k); }
+// signed windows of w bits (8 <= w <= 14, sgn_windows(w) full windows; per-attribute bases of AW11): a negative digit negates y
 static __device__ __noinline__ G2Jac table_mul_g2_signed(G2Jac acc, const G2M* tbl, const uint32_t k[8], int w) {
   const int n = sgn_windows(w);
-  const uint32_t half = 1u << (w - 1);
-  uint32_t carry = 0;
+  SignedRecoder rec(w);
 #pragma unroll 1
   for (int i = 0; i < n; i++) {
-    const int bit = w * i;
-    const uint32_t raw = scalar_bits(k, bit, w) + carry;          // bit <= w (n - 1) < 255; bits past 255 read as zero
-    carry = raw > half ? 1u : 0u;
-    const uint32_t mag = carry ? (1u << w) - raw : raw;
+    const uint32_t mag = rec.next(scalar_bits(k, w * i, w));
     if (mag) {
       G2Aff e = ld_g2_m(tbl + ((size_t)i << (w - 1)) + (mag - 1));
-      if (carry) e.y = fp2_neg(e.y);
+      if (rec.carry) e.y = fp2_neg(e.y);
       acc = jac_add_aff(acc, e);
     }
   }
   return acc;
-}
-static __device__ __noinline__ G2Jac table_mul_g2(const G2M* tbl, const uint32_t k[8]) {
-  G2Jac acc = jac_inf<Fp2>();
-  for (int w = 0; w < TBL_WINDOWS; w++) {
-    uint32_t d = scalar_byte(k, w);
-    if (d) acc = jac_add_aff(acc, ld_g2_m(tbl + w * TBL_DIGITS + (d - 1)));
-  }
-  return acc;
-}
-static __device__ __noinline__ G2Jac table_mul_g2_w16(const G2M* tbl, const uint32_t k[8]) {
-  G2Jac acc = jac_inf<Fp2>();
-#pragma unroll 1
-  for (int w = 0; w < TBL16_WINDOWS; w++) {
-    uint32_t word;
-    switch (w >> 1) {
-      case 0: word = k[0]; break;
-      case 1: word = k[1]; break;
-      case 2: word = k[2]; break;
-      case 3: word = k[3]; break;
-      case 4: word = k[4]; break;
-      case 5: word = k[5]; break;
-      case 6: word = k[6]; break;
-      default: word = k[7]; break;
-    }
-    const uint32_t d = (w & 1) ? (word >> 16) : (word & 0xffffu);
-    if (d) acc = jac_add_aff(acc, ld_g2_m(tbl + (size_t)w * TBL16_DIGITS + (d - 1)));
-  }
-  return acc;
-}
-static __device__ __noinline__ void home_table_pow_gt(bool& started, const GtM* tbl, const uint32_t k[8]) {
-#pragma unroll 1
-  for (int w = 0; w < TBL_WINDOWS; w++) {
-    const uint32_t d = scalar_byte(k, w);
-    if (d) home_take(started, tbl + w * TBL_DIGITS + (d - 1));
-  }
-}
-static __device__ __noinline__ void home_table_pow_gt_signed(bool& started, const GtM* tbl, const uint32_t k[8], int w) {
-  const int n = sgn_windows(w);
-  const uint32_t half = 1u << (w - 1);
-  uint32_t carry = 0;
-#pragma unroll 1
-  for (int i = 0; i < n; i++) {
-    const uint32_t raw = scalar_bits(k, w * i, w) + carry;
-    carry = raw > half ? 1u : 0u;
-    const uint32_t mag = carry ? (1u << w) - raw : raw;
-    if (mag) home_take_signed(started, tbl + ((size_t)i << (w - 1)) + (mag - 1), carry != 0);
-  }
-}
-// the value forms (64-thread blocks only: they go through the home)
-__device__ __forceinline__ Fp12 home_result(bool started) { return started ? facc_get(LdsHome{}) : fp12_one(); }
-__device__ __forceinline__ void home_put(const Fp12& v) {
-  const LdsHome h{};
-  h.st_f6(0, v.c0);
-  h.st_f6(1, v.c1);
-  h.fence();
 }
 // ---- batched inversion across a 256-thread block (Montgomery's trick over LDS + one wave-level scan).
 // Every thread of the block contributes one non-zero Fp value and gets its inverse back; the block pays ONE

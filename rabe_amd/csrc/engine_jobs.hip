@@ -836,27 +836,6 @@ extern "C" int32_t rhip_ghw11_pk_create(rhip_ctx* ctx, const rhip_g1* g1, const 
   *out = pk;
   return RHIP_OK;
 }
-// the 16-bit walk of table_mul_g1_w16_inl (engine_internal.h) onto a RUNNING accumulator: a sum of two fixed-base products costs
-// the additions of both walks and nothing else
-static __device__ __forceinline__ G1Jac table_madd_g1_w16_inl(G1Jac acc, const G1M* tbl, const uint32_t k[8]) {
-#pragma unroll 1
-  for (int w = 0; w < TBL16_WINDOWS; w++) {
-    uint32_t word;
-    switch (w >> 1) {
-      case 0: word = k[0]; break;
-      case 1: word = k[1]; break;
-      case 2: word = k[2]; break;
-      case 3: word = k[3]; break;
-      case 4: word = k[4]; break;
-      case 5: word = k[5]; break;
-      case 6: word = k[6]; break;
-      default: word = k[7]; break;
-    }
-    const uint32_t d = (w & 1) ? (word >> 16) : (word & 0xffffu);
-    if (d) acc = g1_madd_inl(acc, ld_g1_m(tbl + (size_t)w * TBL16_DIGITS + (d - 1)));
-  }
-  return acc;
-}
 // two Jacobian points -> affine canonical with ONE field inversion per block.  The first point is PARKED, as a Jacobian Montgomery
 // value, in the row's own output slots (2 x 64 B of affine output >= 96 B) by the lane that computed it; the second arrives in
 // registers.  Both are read into registers before the first affine point is stored over the parked data (store3_g1_block_parked's
@@ -1902,29 +1881,28 @@ __global__ void __launch_bounds__(128, RB_G2_WAVES) k_aw11_enc_c3(size_t total_r
   ld_scalar(kr, rand + t);
   ld_scalar(kw, omg + t);
   G2Jac acc = jac_inf<Fp2>();
+  // (the loops are written out on the shared cutters: as walk16 / walk8 / walk*_two calls this kernel compiled to 15 more instructions)
   if (w16 > 1) {         // attribute base: signed w16-bit windows; g2: its 16-bit table (g2_tbl) or, without one, its 8-bit table
     acc = table_mul_g2_signed(acc, attr_tbl + (size_t)a * sgn_entries(w16), kr, w16);
     if (g2_is_w16) {
 #pragma unroll 1
       for (int w = 0; w < TBL16_WINDOWS; w++) {
-        const uint32_t word = word_sel8(kw, w >> 1);
-        const uint32_t d = (w & 1) ? (word >> 16) : (word & 0xffffu);
+        const uint32_t d = digit16(kw, w);
         if (d) acc = jac_add_aff(acc, ld_g2_m(g2_tbl + (size_t)w * TBL16_DIGITS + (d - 1)));
       }
     } else {
 #pragma unroll 1
       for (int w = 0; w < TBL_WINDOWS; w++) {
-        const uint32_t d = scalar_byte(kw, w);
+        const uint32_t d = digit8(kw, w);
         if (d) acc = jac_add_aff(acc, ld_g2_m(g2_tbl + w * TBL_DIGITS + (d - 1)));
       }
     }
-  } else if (w16) {      // both tables with 16-bit windows: 2 x 16 entries
+  } else if (w16) {
     const G2M* ta = attr_tbl + (size_t)a * TBL16_WINDOWS * TBL16_DIGITS;
 #pragma unroll 1
     for (int w = 0; w < 2 * TBL16_WINDOWS; w++) {
       const int ww = w & (TBL16_WINDOWS - 1);
-      const uint32_t word = word_sel8(w < TBL16_WINDOWS ? kr : kw, ww >> 1);
-      const uint32_t d = (ww & 1) ? (word >> 16) : (word & 0xffffu);
+      const uint32_t d = digit16(w < TBL16_WINDOWS ? kr : kw, ww);
       if (d) acc = jac_add_aff(acc, ld_g2_m((w < TBL16_WINDOWS ? ta : g2_tbl) + (size_t)ww * TBL16_DIGITS + (d - 1)));
     }
   } else {
@@ -1932,7 +1910,7 @@ __global__ void __launch_bounds__(128, RB_G2_WAVES) k_aw11_enc_c3(size_t total_r
 #pragma unroll 1
     for (int w = 0; w < 2 * TBL_WINDOWS; w++) {
       const int ww = w & (TBL_WINDOWS - 1);
-      const uint32_t d = scalar_byte(w < TBL_WINDOWS ? kr : kw, ww);
+      const uint32_t d = digit8(w < TBL_WINDOWS ? kr : kw, ww);
       if (d) acc = jac_add_aff(acc, ld_g2_m((w < TBL_WINDOWS ? ta : g2_tbl) + ww * TBL_DIGITS + (d - 1)));
     }
   }
@@ -2229,46 +2207,6 @@ extern "C" int32_t rhip_dnf_terms_create(rhip_ctx* ctx, size_t n_terms, uint32_t
   if (he != hipSuccess) { rhip_dnf_terms_destroy(t); return fail(ctx, he, "rhip_dnf_terms_create"); }
   *out = t;
   return RHIP_OK;
-}
-// 8-bit walk of a term's G1 table onto a running accumulator, inlined like table_madd_g1_w16_inl
-static __device__ __forceinline__ G1Jac table_madd_g1_inl(G1Jac acc, const G1M* tbl, const uint32_t k[8]) {
-#pragma unroll 1
-  for (int w = 0; w < TBL_WINDOWS; w++) {
-    const uint32_t d = scalar_byte(k, w);
-    if (d) acc = g1_madd_inl(acc, ld_g1_m(tbl + w * TBL_DIGITS + (d - 1)));
-  }
-  return acc;
-}
-// the G2 walks of table_mul_g2 / table_mul_g2_w16 (engine_internal.h), inlined: their out-of-line forms return the point through a
-// stack slot
-static __device__ __forceinline__ G2Jac table_mul_g2_inl(const G2M* tbl, const uint32_t k[8]) {
-  G2Jac acc = jac_inf<Fp2>();
-#pragma unroll 1
-  for (int w = 0; w < TBL_WINDOWS; w++) {
-    const uint32_t d = scalar_byte(k, w);
-    if (d) acc = jac_add_aff(acc, ld_g2_m(tbl + w * TBL_DIGITS + (d - 1)));
-  }
-  return acc;
-}
-static __device__ __forceinline__ G2Jac table_mul_g2_w16_inl(const G2M* tbl, const uint32_t k[8]) {
-  G2Jac acc = jac_inf<Fp2>();
-#pragma unroll 1
-  for (int w = 0; w < TBL16_WINDOWS; w++) {
-    uint32_t word;
-    switch (w >> 1) {
-      case 0: word = k[0]; break;
-      case 1: word = k[1]; break;
-      case 2: word = k[2]; break;
-      case 3: word = k[3]; break;
-      case 4: word = k[4]; break;
-      case 5: word = k[5]; break;
-      case 6: word = k[6]; break;
-      default: word = k[7]; break;
-    }
-    const uint32_t d = (w & 1) ? (word >> 16) : (word & 0xffffu);
-    if (d) acc = jac_add_aff(acc, ld_g2_m(tbl + (size_t)w * TBL16_DIGITS + (d - 1)));
-  }
-  return acc;
 }
 // store2_g1_block_parked for G2 (128-thread blocks): the first point is parked as a Jacobian value in the row's two output records
 // (192 B of 256), the second arrives in registers; ONE Fp inversion per block covers both, through the norms of their z's

@@ -213,28 +213,11 @@ __global__ void __launch_bounds__(128, RB_MIN_WAVES) k_ghw11_tk_scalars(size_t n
   store_fr(zinv[i].l, zi);
   store_fr(rz[i].l, mul(load_fr(r[i].l), zi));
 }
-// two fixed-base products on one accumulator: tbl1 * k1 + tbl2 * k2 over the 16-bit windows of both tables (table_mul_g2_w16 twice, without
-// leaving Jacobian form in between); a lane with k2 = 0 adds nothing in the second half
+// two fixed-base products on one accumulator: tbl1 * k1 + tbl2 * k2 over the 16-bit windows of both tables, without leaving Jacobian form
+// in between and with ONE call site of the G2 addition; a lane with k2 = 0 adds nothing in the second half
 __device__ __forceinline__ G2Jac table_mul2_g2_w16(const G2M* tbl1, const uint32_t k1[8], const G2M* tbl2, const uint32_t k2[8]) {
   G2Jac acc = jac_inf<Fp2>();
-#pragma unroll 1
-  for (int s = 0; s < 2 * TBL16_WINDOWS; s++) {
-    const bool second = s >= TBL16_WINDOWS;
-    const int w = s & (TBL16_WINDOWS - 1);
-    uint32_t word;
-    switch (w >> 1) {
-      case 0: word = second ? k2[0] : k1[0]; break;
-      case 1: word = second ? k2[1] : k1[1]; break;
-      case 2: word = second ? k2[2] : k1[2]; break;
-      case 3: word = second ? k2[3] : k1[3]; break;
-      case 4: word = second ? k2[4] : k1[4]; break;
-      case 5: word = second ? k2[5] : k1[5]; break;
-      case 6: word = second ? k2[6] : k1[6]; break;
-      default: word = second ? k2[7] : k1[7]; break;
-    }
-    const uint32_t d = (w & 1) ? (word >> 16) : (word & 0xffffu);
-    if (d) acc = jac_add_aff(acc, ld_g2_m((second ? tbl2 : tbl1) + (size_t)w * TBL16_DIGITS + (d - 1)));
-  }
+  walk16_two(k1, k2, [&](bool second, int w, uint32_t d) { acc = jac_add_aff(acc, ld_g2_m((second ? tbl2 : tbl1) + (size_t)w * TBL16_DIGITS + (d - 1))); });
   return acc;
 }
 // one lane per transform-key element (ghw11/mod.rs:156-178 on the elements of :123-152), rows as in k_ghw11_keygen_rows; with
