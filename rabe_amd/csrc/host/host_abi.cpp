@@ -18,6 +18,7 @@
 #include <thread>
 
 #include "../../../include/rabe_host.h"
+#include "abi_helpers.h"
 #include "predraw.h"
 #include "schemes.h"
 
@@ -682,6 +683,18 @@ int32_t queue_call(rabe_host* h, T* t, void** obj, uint8_t** out, size_t* len) {
 }
 }  // namespace
 
+// ---- small pieces every packed entry point shares
+using abi::attr_sets;
+using abi::key_ptrs;
+using abi::record_span;
+static bool trusted_of(uint32_t flags) { return (flags & RABE_PACKED_TRUSTED) != 0; }
+// the call's error text: the first item that failed says why (the others are in their status)
+static void first_error(rabe_host* h, const std::vector<std::string>& errors) {
+  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+}
+// null arrays an entry point refuses itself: -1 with `text`
+static void require(bool arrays_given, const char* text) { if (!arrays_given) throw RabeError(text); }
+
 // ---- packed decrypts of the DNF schemes: the records of a blob become objects (all cores), the membership pass runs once per group over
 // every element of the blob, the objects go through the schemes' batch decrypt (one pairing-job launch set, sealed parts opened on the device)
 template <class CT>
@@ -740,7 +753,7 @@ template <class CT, class UK, class BATCH>
 static int32_t dnf_decrypt_packed(rabe_host* h, int32_t kind, const void* uk, size_t n, const uint8_t* blob, size_t len, const uint64_t* off, uint32_t flags,
                                   int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, BATCH batch) {
   std::vector<std::string> errors;
-  auto objs = parse_blob<CT>(h, kind, n, blob, len, off, (flags & RABE_PACKED_TRUSTED) != 0, &errors);
+  auto objs = parse_blob<CT>(h, kind, n, blob, len, off, trusted_of(flags), &errors);
   std::vector<const UK*> sks;
   std::vector<const CT*> cts;
   std::vector<size_t> who;
@@ -759,7 +772,81 @@ static int32_t dnf_decrypt_packed(rabe_host* h, int32_t kind, const void* uk, si
     status[i] = pt[i] ? 0 : -1;
     if (pt[i] && !pt[i]->empty()) memcpy(pt_buf + pt_off[i], pt[i]->data(), pt[i]->size());
   }
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  first_error(h, errors);
+  return 0;
+}
+
+// ---- the call shapes of the packed entry points.  An entry point is one of the three shapes below over pipeline.cpp, or a direct call of its
+// scheme function on the host's own engine.  What differs between two entry points of one shape is stated where the shape is called: the
+// engines the items are cut over (engines(), or engines_if(...) where a missing array must reach the uncut call, which refuses it), the
+// fewest items of a chunk (CHUNK_*, or GROUP_ONLY), whether a decrypt announces its record span first, and which null arrays it refuses
+// itself (`require`, before or after its strings are converted).  docs/multi_gpu.md lists every entry point's choices.
+static const size_t KEM_KEY = 32;          // a content key of the encaps / decaps calls
+static const size_t TCT = 768;             // a Ghw11TransformCiphertext record
+
+// PRODUCE (encrypt, encaps, keygen): block [lo, hi) draws from `rng` in item order and writes records.  `item` / `pt_off` / `keys` are the
+// caller's arrays at the block's first item (a null one stays null); encaps has no pt_off, encrypt and keygen no keys.
+struct ProduceBlock { Engine& eng; Rng& rng; size_t n; const uint32_t* item; const uint64_t* pt_off; uint8_t* out; size_t cap; uint64_t* off; uint8_t* keys; };
+template <class F>
+static int32_t produce_shape(rabe_host* h, const std::vector<Engine*>& engines, size_t min_chunk, size_t n_items, const uint32_t* item, const uint64_t* pt_off,
+                             uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf, F call) {
+  return pipeline::produce(engines, h->rng(), n_items, min_chunk, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
+    return call(ProduceBlock{eng, r, hi - lo, item ? item + lo : nullptr, pt_off ? pt_off + lo : nullptr, out, cap, off, key_buf ? key_buf + KEM_KEY * lo : nullptr});
+  }, out_buf, out_cap, out_off) ? 0 : 1;
+}
+// CONSUME (decrypt): block [lo, hi) reads the records at in_off + lo and writes plaintexts, which `consume` closes up.  announce_span: the size
+// the plaintext buffer must have is left in pt_off[n_items] before anything else happens (where both offset arrays are there).
+struct ConsumeBlock { Engine& eng; size_t lo, n; const uint64_t* in_off; int32_t* status; uint8_t* pt; size_t cap; uint64_t* pt_off; std::vector<std::string>* errors; };
+template <class F>
+static int32_t consume_shape(rabe_host* h, const std::vector<Engine*>& engines, size_t min_chunk, bool announce_span, size_t n_items, const uint64_t* in_off,
+                             size_t in_len, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, F call) {
+  std::vector<std::string> errors;
+  if (announce_span && in_off && pt_off) pt_off[n_items] = record_span(n_items, in_off, in_len);
+  if (!pipeline::consume(engines, n_items, min_chunk, in_off, in_len, [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off,
+                                                                        std::vector<std::string>* errs) {
+        return call(ConsumeBlock{eng, lo, hi - lo, in_off ? in_off + lo : nullptr, st, pt, cap, off, errs});
+      }, status, pt_buf, pt_cap, pt_off, &errors))
+    return 1;
+  first_error(h, errors);
+  return 0;
+}
+// DECAPS: block [lo, hi) writes its verdicts at status + lo and its 32-byte keys at key_buf + 32 lo -- fixed slots, nothing to close up, no size
+// to refuse.  `in_off`: the offsets of a record blob, or null for the fixed-size records of rabe_ghw11_decaps_out_packed (cut by b.lo).
+struct DecapsBlock { Engine& eng; size_t lo, n; const uint64_t* in_off; int32_t* status; uint8_t* keys; std::vector<std::string>* errors; };
+template <class F>
+static int32_t decaps_shape(rabe_host* h, const std::vector<Engine*>& engines, size_t min_chunk, size_t n_items, const uint64_t* in_off, int32_t* status,
+                            uint8_t* key_buf, F call) {
+  std::vector<std::string> errors;
+  pipeline::for_blocks(engines, n_items, min_chunk, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
+    call(DecapsBlock{eng, lo, hi - lo, in_off ? in_off + lo : nullptr, status ? status + lo : nullptr, key_buf ? key_buf + KEM_KEY * lo : nullptr, errs});
+    return true;
+  }, &errors);
+  first_error(h, errors);
+  return 0;
+}
+// the twins BDABE / MKE08: one body per call, the scheme's types and function handed in (as dnf_decrypt_packed above)
+template <class PK, class APK, class F>
+static int32_t dnf_encrypt_packed(rabe_host* h, const char* null_text, const void* pk, const void* const* attr_pks, size_t n_pks, const char* const* policies,
+                                  size_t n_policies, int32_t language, size_t n_items, const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off,
+                                  uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off, F encrypt) {
+  const auto v = key_ptrs<APK>(attr_pks, n_pks);
+  const auto& key = *(const PK*)pk;
+  const auto pols = strs(policies, n_policies);
+  const auto lang = lang_of(language);
+  require(item_policy && pt_off && ct_off, null_text);
+  return produce_shape(h, h->engines(), CHUNK_DNF, n_items, item_policy, pt_off, ct_buf, ct_cap, ct_off, nullptr, [&](const ProduceBlock& b) {
+    return encrypt(b.eng, b.rng, key, v, pols, lang, b.n, b.item, pt_blob, b.pt_off, b.out, b.cap, b.off);
+  });
+}
+template <class SKA, class F>
+static int32_t dnf_request_sk_packed(rabe_host* h, const void* ska, const char* const* attributes, const size_t* counts, size_t n_sets, size_t n_items,
+                                     const uint32_t* item_set, const uint8_t* upk_blob, size_t upk_len, const uint64_t* upk_off, uint32_t flags, int32_t* status,
+                                     uint8_t* out_buf, size_t out_cap, uint64_t* out_off, F request) {
+  std::vector<std::string> errors;
+  if (!request(h->eng, *(const SKA*)ska, attr_sets(attributes, counts, n_sets), n_items, item_set, upk_blob, upk_len, upk_off, trusted_of(flags), status, out_buf,
+               out_cap, out_off, &errors))
+    return 1;
+  first_error(h, errors);
   return 0;
 }
 extern "C" {
@@ -1137,228 +1224,136 @@ int32_t rabe_ac17_cp_encrypt_batch(rabe_host* h, const void* pk, size_t n, const
   return give_objects(h, ts, RABE_AC17_CP_CT, cts);
   GUARD_END(h)
 }
-// What a batch cut over a device group asks of the plaintext buffer (pipeline.cpp: consume): the total size of the well-formed records.  The
-// decrypt-shaped entry points leave it in pt_off[n_items] before they start; the uncut call states its own, never larger, size when it refuses.
-static uint64_t record_span(size_t n, const uint64_t* off, size_t len) {
-  uint64_t span = 0;
-  for (size_t i = 0; i < n; i++) if (off[i] <= off[i + 1] && off[i + 1] <= len) span += off[i + 1] - off[i];
-  return span;
-}
-int32_t rabe_ac17_cp_encrypt_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
-                                    const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* ct_buf, size_t ct_cap,
-                                    uint64_t* ct_off) {
-  GUARD_BEGIN
-  const auto& key = *(const ac17::Ac17PublicKey*)pk;
-  const auto pols = strs(policies, n_policies);
-  const auto lang = lang_of(language);
-  if (!item_policy || !pt_off || !ct_off) throw RabeError("cp_encrypt_packed: null input");
-  return pipeline::produce(h->engines(), h->rng(), n_items, CHUNK_AC17, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return ac17::cp_encrypt_packed(eng, r, key, pols, lang, hi - lo, item_policy + lo, pt_blob, pt_off + lo, out, cap, off);
-  }, ct_buf, ct_cap, ct_off) ? 0 : 1;
-  GUARD_END(h)
-}
+// ---------------------------------------------------------------- packed entry points (the shapes: above `extern "C"`)
+// Where several entry points share one C signature, the signature and the body are written once, as a macro (a template cannot give a
+// function a C name), and every entry point is one line that names its choices: key type, scheme function, engines, chunk, span, null text.
+// The header's prototypes hold each expansion to its declared signature.
+#define ENCRYPT_BY_POLICY_PACKED(NAME, KEY, FN, CHUNK, NULL_TEXT) /* all engines; the arrays are checked after the strings are converted */ \
+  int32_t NAME(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,               \
+               const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off) { \
+    GUARD_BEGIN                                                                                                                            \
+    const auto& key = *(const KEY*)pk;                                                                                                     \
+    const auto pols = strs(policies, n_policies);                                                                                          \
+    const auto lang = lang_of(language);                                                                                                   \
+    require(item_policy && pt_off && ct_off, NULL_TEXT);                                                                                   \
+    return produce_shape(h, h->engines(), CHUNK, n_items, item_policy, pt_off, ct_buf, ct_cap, ct_off, nullptr, [&](const ProduceBlock& b) { \
+      return FN(b.eng, b.rng, key, pols, lang, b.n, b.item, pt_blob, b.pt_off, b.out, b.cap, b.off);                                       \
+    });                                                                                                                                    \
+    GUARD_END(h)                                                                                                                           \
+  }
+ENCRYPT_BY_POLICY_PACKED(rabe_ac17_cp_encrypt_packed, ac17::Ac17PublicKey, ac17::cp_encrypt_packed, CHUNK_AC17, "cp_encrypt_packed: null input")
+ENCRYPT_BY_POLICY_PACKED(rabe_bsw_encrypt_packed, bsw::CpAbePublicKey, bsw::encrypt_packed, CHUNK_BSW, "bsw::encrypt_packed: null input")
+ENCRYPT_BY_POLICY_PACKED(rabe_ghw11_encrypt_packed, ghw11::Ghw11PublicKey, ghw11::encrypt_packed, CHUNK_GHW11, "ghw11::encrypt_packed: null input")
+// key encapsulation: the packed pair without payloads (include/rabe_host.h).  Over a device group: the headers through `produce`, a block's
+// 32-byte key slots straight to key_buf + 32 lo (the sizing pass returns before a key is written); decaps through `for_blocks`.
+#define ENCAPS_BY_POLICY_PACKED(NAME, KEY, FN, NULL_TEXT) /* all engines if key_buf; GROUP_ONLY; the arrays are checked before the strings */ \
+  int32_t NAME(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,               \
+               const uint32_t* item_policy, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {                       \
+    GUARD_BEGIN                                                                                                                            \
+    require(item_policy && hdr_off, NULL_TEXT);                                                                                            \
+    const auto& key = *(const KEY*)pk;                                                                                                     \
+    const auto pols = strs(policies, n_policies);                                                                                          \
+    const auto lang = lang_of(language);                                                                                                   \
+    return produce_shape(h, h->engines_if(key_buf != nullptr), pipeline::GROUP_ONLY, n_items, item_policy, nullptr, hdr_buf, hdr_cap, hdr_off, key_buf, \
+                         [&](const ProduceBlock& b) { return FN(b.eng, b.rng, key, pols, lang, b.n, b.item, b.out, b.cap, b.off, b.keys); }); \
+    GUARD_END(h)                                                                                                                           \
+  }
+ENCAPS_BY_POLICY_PACKED(rabe_ac17_cp_encaps_packed, ac17::Ac17PublicKey, ac17::cp_encaps_packed, "cp_encaps_packed: null input")
+ENCAPS_BY_POLICY_PACKED(rabe_bsw_encaps_packed, bsw::CpAbePublicKey, bsw::encaps_packed, "bsw::encaps_packed: null input")
+ENCAPS_BY_POLICY_PACKED(rabe_ghw11_encaps_packed, ghw11::Ghw11PublicKey, ghw11::encaps_packed, "ghw11::encaps_packed: null input")
+// records under ONE key (lsw_decrypt: keys under one ciphertext).  ENGINES: the engines the items are cut over; SPAN: whether pt_off[n_items]
+// announces the record span first; REFUSE: the entry point's own null check, or nothing
+#define DECRYPT_PACKED(NAME, KEY, FN, ENGINES, CHUNK, SPAN, REFUSE)                                                                        \
+  int32_t NAME(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,  \
+               int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {                                                        \
+    GUARD_BEGIN                                                                                                                            \
+    const auto& key = *(const KEY*)sk;                                                                                                     \
+    REFUSE;                                                                                                                                \
+    return consume_shape(h, ENGINES, CHUNK, SPAN, n_items, ct_off, ct_len, status, pt_buf, pt_cap, pt_off, [&](const ConsumeBlock& b) {    \
+      return FN(b.eng, key, b.n, ct_blob, ct_len, b.in_off, trusted_of(flags), b.status, b.pt, b.cap, b.pt_off, b.errors);                 \
+    });                                                                                                                                    \
+    GUARD_END(h)                                                                                                                           \
+  }
+#define NO_REFUSAL (void)0
+DECRYPT_PACKED(rabe_ac17_cp_decrypt_packed, ac17::Ac17CpSecretKey, ac17::cp_decrypt_packed, h->engines(), CHUNK_AC17, false, NO_REFUSAL)
+DECRYPT_PACKED(rabe_ac17_kp_decrypt_packed, ac17::Ac17KpSecretKey, ac17::kp_decrypt_packed, h->engines_if(pt_off && status), pipeline::GROUP_ONLY, true, NO_REFUSAL)
+DECRYPT_PACKED(rabe_bsw_decrypt_packed, bsw::CpAbeSecretKey, bsw::decrypt_packed, h->engines(), CHUNK_BSW, false, NO_REFUSAL)
+DECRYPT_PACKED(rabe_lsw_decrypt_packed, lsw::KpAbeCiphertext, lsw::decrypt_packed, h->engines(), CHUNK_LSW, false, NO_REFUSAL)
+DECRYPT_PACKED(rabe_lsw_decrypt_one_sk_packed, lsw::KpAbeSecretKey, lsw::decrypt_one_sk_packed, h->engines(), CHUNK_LSW, true,
+               require(ct_off && pt_off, "lsw::decrypt_one_sk_packed: null input"))
+DECRYPT_PACKED(rabe_ghw11_decrypt_packed, ghw11::Ghw11SecretKey, ghw11::decrypt_packed, h->engines_if(pt_off && status), pipeline::GROUP_ONLY, true, NO_REFUSAL)
+// every one: all engines if (ct_off, status, key_buf), the uncut call refusing what is missing
+#define DECAPS_PACKED(NAME, KEY, FN, CHUNK)                                                                                                \
+  int32_t NAME(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,  \
+               int32_t* status, uint8_t* key_buf) {                                                                                        \
+    GUARD_BEGIN                                                                                                                            \
+    const auto& key = *(const KEY*)sk;                                                                                                     \
+    return decaps_shape(h, h->engines_if(ct_off && status && key_buf), CHUNK, n_items, ct_off, status, key_buf, [&](const DecapsBlock& b) { \
+      FN(b.eng, key, b.n, ct_blob, ct_len, b.in_off, trusted_of(flags), b.status, b.keys, b.errors);                                       \
+    });                                                                                                                                    \
+    GUARD_END(h)                                                                                                                           \
+  }
+DECAPS_PACKED(rabe_ac17_cp_decaps_packed, ac17::Ac17CpSecretKey, ac17::cp_decaps_packed, pipeline::GROUP_ONLY)
+DECAPS_PACKED(rabe_ac17_kp_decaps_packed, ac17::Ac17KpSecretKey, ac17::kp_decaps_packed, pipeline::GROUP_ONLY)
+DECAPS_PACKED(rabe_bsw_decaps_packed, bsw::CpAbeSecretKey, bsw::decaps_packed, pipeline::GROUP_ONLY)
+DECAPS_PACKED(rabe_lsw_decaps_packed, lsw::KpAbeSecretKey, lsw::decaps_packed, CHUNK_LSW)
+DECAPS_PACKED(rabe_ghw11_decaps_packed, ghw11::Ghw11SecretKey, ghw11::decaps_packed, pipeline::GROUP_ONLY)
+// ---- the entry points with a signature of their own
 int32_t rabe_ac17_cp_keygen_packed(rabe_host* h, const void* msk, const char* const* attributes, const size_t* counts, size_t n_sets, size_t n_items,
                                    const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off) {
   GUARD_BEGIN
-  std::vector<std::vector<std::string>> sets(n_sets);
-  size_t at = 0;
-  for (size_t s = 0; s < n_sets; s++)
-    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
-  return ac17::cp_keygen_packed(h->eng, h->rng(), *(const ac17::Ac17MasterKey*)msk, sets, n_items, item_set, sk_buf, sk_cap, sk_off) ? 0 : 1;
+  return ac17::cp_keygen_packed(h->eng, h->rng(), *(const ac17::Ac17MasterKey*)msk, attr_sets(attributes, counts, n_sets), n_items, item_set, sk_buf, sk_cap,
+                                sk_off) ? 0 : 1;
   GUARD_END(h)
 }
-int32_t rabe_ac17_cp_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
-                                    uint32_t flags, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
+int32_t rabe_ac17_kp_keygen_packed(rabe_host* h, const void* msk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
+                                   const uint32_t* item_policy, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off) {
   GUARD_BEGIN
-  std::vector<std::string> errors;
-  const auto& key = *(const ac17::Ac17CpSecretKey*)sk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  if (!pipeline::consume(h->engines(), n_items, CHUNK_AC17, ct_off, ct_len, [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off,
-                                                                           std::vector<std::string>* errs) {
-        return ac17::cp_decrypt_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
-      }, status, pt_buf, pt_cap, pt_off, &errors))
-    return 1;
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
-  GUARD_END(h)
-}
-// key encapsulation: the packed pair without payloads (include/rabe_host.h).  Over a device group: the headers through `produce`, a block's
-// 32-byte key slots straight to key_buf + 32 lo (the sizing pass returns before a key is written); decaps through `for_blocks`.
-static const size_t KEM_KEY = 32;
-int32_t rabe_ac17_cp_encaps_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
-                                   const uint32_t* item_policy, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {
-  GUARD_BEGIN
-  if (!item_policy || !hdr_off) throw RabeError("cp_encaps_packed: null input");
-  const auto& key = *(const ac17::Ac17PublicKey*)pk;
-  const auto pols = strs(policies, n_policies);
-  const auto lang = lang_of(language);
-  return pipeline::produce(h->engines_if(key_buf != nullptr), h->rng(), n_items, pipeline::GROUP_ONLY,
-                           [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return ac17::cp_encaps_packed(eng, r, key, pols, lang, hi - lo, item_policy + lo, out, cap, off, key_buf ? key_buf + KEM_KEY * lo : nullptr);
-  }, hdr_buf, hdr_cap, hdr_off) ? 0 : 1;
-  GUARD_END(h)
-}
-int32_t rabe_ac17_cp_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
-                                   uint32_t flags, int32_t* status, uint8_t* key_buf) {
-  GUARD_BEGIN
-  std::vector<std::string> errors;
-  const auto& key = *(const ac17::Ac17CpSecretKey*)sk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  pipeline::for_blocks(h->engines_if(ct_off && status && key_buf), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
-    ac17::cp_decaps_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
-                           key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
-    return true;
-  }, &errors);
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
-  GUARD_END(h)
-}
-int32_t rabe_bsw_encaps_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
-                               const uint32_t* item_policy, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {
-  GUARD_BEGIN
-  if (!item_policy || !hdr_off) throw RabeError("bsw::encaps_packed: null input");
-  const auto& key = *(const bsw::CpAbePublicKey*)pk;
-  const auto pols = strs(policies, n_policies);
-  const auto lang = lang_of(language);
-  return pipeline::produce(h->engines_if(key_buf != nullptr), h->rng(), n_items, pipeline::GROUP_ONLY,
-                           [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return bsw::encaps_packed(eng, r, key, pols, lang, hi - lo, item_policy + lo, out, cap, off, key_buf ? key_buf + KEM_KEY * lo : nullptr);
-  }, hdr_buf, hdr_cap, hdr_off) ? 0 : 1;
-  GUARD_END(h)
-}
-int32_t rabe_bsw_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
-                               int32_t* status, uint8_t* key_buf) {
-  GUARD_BEGIN
-  std::vector<std::string> errors;
-  const auto& key = *(const bsw::CpAbeSecretKey*)sk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  pipeline::for_blocks(h->engines_if(ct_off && status && key_buf), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
-    bsw::decaps_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
-                       key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
-    return true;
-  }, &errors);
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
+  return ac17::kp_keygen_packed(h->eng, h->rng(), *(const ac17::Ac17MasterKey*)msk, strs(policies, n_policies), lang_of(language), n_items, item_policy, sk_buf,
+                                sk_cap, sk_off) ? 0 : 1;
   GUARD_END(h)
 }
 int32_t rabe_ac17_kp_encrypt_packed(rabe_host* h, const void* pk, const char* const* attributes, const size_t* counts, size_t n_sets, size_t n_items,
                                     const uint32_t* item_set, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off) {
   GUARD_BEGIN
-  if (!item_set || !pt_off || !ct_off) throw RabeError("kp_encrypt_packed: null input");
-  std::vector<std::vector<std::string>> sets(n_sets);
-  size_t at = 0;
-  for (size_t s = 0; s < n_sets; s++)
-    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
+  require(item_set && pt_off && ct_off, "kp_encrypt_packed: null input");
+  const auto sets = attr_sets(attributes, counts, n_sets);
   const auto& key = *(const ac17::Ac17PublicKey*)pk;
-  return pipeline::produce(h->engines(), h->rng(), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return ac17::kp_encrypt_packed(eng, r, key, sets, hi - lo, item_set + lo, pt_blob, pt_off + lo, out, cap, off);
-  }, ct_buf, ct_cap, ct_off) ? 0 : 1;
-  GUARD_END(h)
-}
-int32_t rabe_ac17_kp_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
-                                    uint32_t flags, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
-  GUARD_BEGIN
-  std::vector<std::string> errors;
-  const auto& key = *(const ac17::Ac17KpSecretKey*)sk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  if (ct_off && pt_off) pt_off[n_items] = record_span(n_items, ct_off, ct_len);
-  if (!pipeline::consume(h->engines_if(pt_off && status), n_items, pipeline::GROUP_ONLY, ct_off, ct_len,
-                         [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off, std::vector<std::string>* errs) {
-        return ac17::kp_decrypt_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
-      }, status, pt_buf, pt_cap, pt_off, &errors))
-    return 1;
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
+  return produce_shape(h, h->engines(), pipeline::GROUP_ONLY, n_items, item_set, pt_off, ct_buf, ct_cap, ct_off, nullptr, [&](const ProduceBlock& b) {
+    return ac17::kp_encrypt_packed(b.eng, b.rng, key, sets, b.n, b.item, pt_blob, b.pt_off, b.out, b.cap, b.off);
+  });
   GUARD_END(h)
 }
 // key encapsulation over the KP pair: cut over a device group where rabe_ac17_kp_{encrypt,decrypt}_packed are cut
 int32_t rabe_ac17_kp_encaps_packed(rabe_host* h, const void* pk, const char* const* attributes, const size_t* counts, size_t n_sets, size_t n_items,
                                    const uint32_t* item_set, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {
   GUARD_BEGIN
-  if (!item_set || !hdr_off) throw RabeError("kp_encaps_packed: null input");
-  std::vector<std::vector<std::string>> sets(n_sets);
-  size_t at = 0;
-  for (size_t s = 0; s < n_sets; s++)
-    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
+  require(item_set && hdr_off, "kp_encaps_packed: null input");
+  const auto sets = attr_sets(attributes, counts, n_sets);
   const auto& key = *(const ac17::Ac17PublicKey*)pk;
-  return pipeline::produce(h->engines_if(key_buf != nullptr), h->rng(), n_items, pipeline::GROUP_ONLY,
-                           [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return ac17::kp_encaps_packed(eng, r, key, sets, hi - lo, item_set + lo, out, cap, off, key_buf ? key_buf + KEM_KEY * lo : nullptr);
-  }, hdr_buf, hdr_cap, hdr_off) ? 0 : 1;
-  GUARD_END(h)
-}
-int32_t rabe_ac17_kp_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
-                                   uint32_t flags, int32_t* status, uint8_t* key_buf) {
-  GUARD_BEGIN
-  std::vector<std::string> errors;
-  const auto& key = *(const ac17::Ac17KpSecretKey*)sk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  pipeline::for_blocks(h->engines_if(ct_off && status && key_buf), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
-    ac17::kp_decaps_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
-                           key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
-    return true;
-  }, &errors);
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
+  return produce_shape(h, h->engines_if(key_buf != nullptr), pipeline::GROUP_ONLY, n_items, item_set, nullptr, hdr_buf, hdr_cap, hdr_off, key_buf,
+                       [&](const ProduceBlock& b) { return ac17::kp_encaps_packed(b.eng, b.rng, key, sets, b.n, b.item, b.out, b.cap, b.off, b.keys); });
   GUARD_END(h)
 }
 int32_t rabe_bsw_keygen_packed(rabe_host* h, const void* pk, const void* msk, const char* const* attributes, const size_t* counts, size_t n_sets,
                                size_t n_items, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off) {
   GUARD_BEGIN
-  std::vector<std::vector<std::string>> sets(n_sets);
-  size_t at = 0;
-  for (size_t s = 0; s < n_sets; s++)
-    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
-  return bsw::keygen_packed(h->eng, h->rng(), *(const bsw::CpAbePublicKey*)pk, *(const bsw::CpAbeMasterKey*)msk, sets, n_items, item_set, sk_buf, sk_cap,
-                            sk_off) ? 0 : 1;
+  return bsw::keygen_packed(h->eng, h->rng(), *(const bsw::CpAbePublicKey*)pk, *(const bsw::CpAbeMasterKey*)msk, attr_sets(attributes, counts, n_sets), n_items,
+                            item_set, sk_buf, sk_cap, sk_off) ? 0 : 1;
   GUARD_END(h)
 }
 int32_t rabe_bsw_delegate_packed(rabe_host* h, const void* pk, const void* sk, const char* const* attributes, const size_t* counts, size_t n_subsets,
                                  size_t n_items, const uint32_t* item_subset, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off) {
   GUARD_BEGIN
-  std::vector<std::vector<std::string>> sets(n_subsets);
-  size_t at = 0;
-  for (size_t s = 0; s < n_subsets; s++)
-    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
-  return bsw::delegate_packed(h->eng, h->rng(), *(const bsw::CpAbePublicKey*)pk, *(const bsw::CpAbeSecretKey*)sk, sets, n_items, item_subset, sk_buf, sk_cap,
-                              sk_off) ? 0 : 1;
-  GUARD_END(h)
-}
-int32_t rabe_bsw_encrypt_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
-                                const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off) {
-  GUARD_BEGIN
-  const auto& key = *(const bsw::CpAbePublicKey*)pk;
-  const auto pols = strs(policies, n_policies);
-  const auto lang = lang_of(language);
-  if (!item_policy || !pt_off || !ct_off) throw RabeError("bsw::encrypt_packed: null input");
-  return pipeline::produce(h->engines(), h->rng(), n_items, CHUNK_BSW, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return bsw::encrypt_packed(eng, r, key, pols, lang, hi - lo, item_policy + lo, pt_blob, pt_off + lo, out, cap, off);
-  }, ct_buf, ct_cap, ct_off) ? 0 : 1;
-  GUARD_END(h)
-}
-int32_t rabe_bsw_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
-                                int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
-  GUARD_BEGIN
-  std::vector<std::string> errors;
-  const auto& key = *(const bsw::CpAbeSecretKey*)sk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  if (!pipeline::consume(h->engines(), n_items, CHUNK_BSW, ct_off, ct_len, [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off,
-                                                                          std::vector<std::string>* errs) {
-        return bsw::decrypt_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
-      }, status, pt_buf, pt_cap, pt_off, &errors))
-    return 1;
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
+  return bsw::delegate_packed(h->eng, h->rng(), *(const bsw::CpAbePublicKey*)pk, *(const bsw::CpAbeSecretKey*)sk, attr_sets(attributes, counts, n_subsets), n_items,
+                              item_subset, sk_buf, sk_cap, sk_off) ? 0 : 1;
   GUARD_END(h)
 }
 int32_t rabe_lsw_encrypt_packed(rabe_host* h, const void* pk, const char* const* attributes, const size_t* counts, size_t n_sets, size_t n_items,
                                 const uint32_t* item_set, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off) {
   GUARD_BEGIN
-  std::vector<std::vector<std::string>> sets(n_sets);
-  size_t at = 0;
-  for (size_t s = 0; s < n_sets; s++)
-    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
-  return lsw::encrypt_packed(h->eng, h->rng(), *(const lsw::KpAbePublicKey*)pk, sets, n_items, item_set, pt_blob, pt_off, ct_buf, ct_cap, ct_off) ? 0 : 1;
+  return lsw::encrypt_packed(h->eng, h->rng(), *(const lsw::KpAbePublicKey*)pk, attr_sets(attributes, counts, n_sets), n_items, item_set, pt_blob, pt_off, ct_buf,
+                             ct_cap, ct_off) ? 0 : 1;
   GUARD_END(h)
 }
 int32_t rabe_lsw_keygen_packed(rabe_host* h, const void* pk, const void* msk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
@@ -1368,79 +1363,26 @@ int32_t rabe_lsw_keygen_packed(rabe_host* h, const void* pk, const void* msk, co
   const auto& master = *(const lsw::KpAbeMasterKey*)msk;
   const auto pols = strs(policies, n_policies);
   const auto lang = lang_of(language);
-  if (!item_policy || !sk_off) throw RabeError("lsw::keygen_packed: null input");
-  return pipeline::produce(h->engines(), h->rng(), n_items, CHUNK_LSW, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return lsw::keygen_packed(eng, r, key, master, pols, lang, hi - lo, item_policy + lo, out, cap, off);
-  }, sk_buf, sk_cap, sk_off) ? 0 : 1;
-  GUARD_END(h)
-}
-int32_t rabe_lsw_decrypt_packed(rabe_host* h, const void* ct, size_t n_items, const uint8_t* sk_blob, size_t sk_len, const uint64_t* sk_off, uint32_t flags,
-                                int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
-  GUARD_BEGIN
-  std::vector<std::string> errors;
-  const auto& c = *(const lsw::KpAbeCiphertext*)ct;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  if (!pipeline::consume(h->engines(), n_items, CHUNK_LSW, sk_off, sk_len, [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off,
-                                                                          std::vector<std::string>* errs) {
-        return lsw::decrypt_packed(eng, c, hi - lo, sk_blob, sk_len, sk_off + lo, trusted, st, pt, cap, off, errs);
-      }, status, pt_buf, pt_cap, pt_off, &errors))
-    return 1;
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
-  GUARD_END(h)
-}
-int32_t rabe_lsw_decrypt_one_sk_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
-                                       int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
-  GUARD_BEGIN
-  std::vector<std::string> errors;
-  const auto& key = *(const lsw::KpAbeSecretKey*)sk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  if (!ct_off || !pt_off) throw RabeError("lsw::decrypt_one_sk_packed: null input");
-  pt_off[n_items] = record_span(n_items, ct_off, ct_len);
-  if (!pipeline::consume(h->engines(), n_items, CHUNK_LSW, ct_off, ct_len, [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off,
-                                                                          std::vector<std::string>* errs) {
-        return lsw::decrypt_one_sk_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
-      }, status, pt_buf, pt_cap, pt_off, &errors))
-    return 1;
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
+  require(item_policy && sk_off, "lsw::keygen_packed: null input");
+  return produce_shape(h, h->engines(), CHUNK_LSW, n_items, item_policy, nullptr, sk_buf, sk_cap, sk_off, nullptr, [&](const ProduceBlock& b) {
+    return lsw::keygen_packed(b.eng, b.rng, key, master, pols, lang, b.n, b.item, b.out, b.cap, b.off);
+  });
   GUARD_END(h)
 }
 // key encapsulation over the LSW pair.  Encaps runs on the group's first device, as rabe_lsw_encrypt_packed does; decaps is cut where
-// rabe_lsw_decrypt_one_sk_packed is cut, a block's 32-byte key slots written straight to key_buf + 32 lo.
+// rabe_lsw_decrypt_one_sk_packed is cut.
 int32_t rabe_lsw_encaps_packed(rabe_host* h, const void* pk, const char* const* attributes, const size_t* counts, size_t n_sets, size_t n_items,
                                const uint32_t* item_set, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {
   GUARD_BEGIN
-  if (!item_set || !hdr_off) throw RabeError("lsw::encaps_packed: null input");
-  std::vector<std::vector<std::string>> sets(n_sets);
-  size_t at = 0;
-  for (size_t s = 0; s < n_sets; s++)
-    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
-  return lsw::encaps_packed(h->eng, h->rng(), *(const lsw::KpAbePublicKey*)pk, sets, n_items, item_set, hdr_buf, hdr_cap, hdr_off, key_buf) ? 0 : 1;
-  GUARD_END(h)
-}
-int32_t rabe_lsw_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
-                               int32_t* status, uint8_t* key_buf) {
-  GUARD_BEGIN
-  std::vector<std::string> errors;
-  const auto& key = *(const lsw::KpAbeSecretKey*)sk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  pipeline::for_blocks(h->engines_if(ct_off && status && key_buf), n_items, CHUNK_LSW, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
-    lsw::decaps_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
-                       key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
-    return true;
-  }, &errors);
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
+  require(item_set && hdr_off, "lsw::encaps_packed: null input");
+  return lsw::encaps_packed(h->eng, h->rng(), *(const lsw::KpAbePublicKey*)pk, attr_sets(attributes, counts, n_sets), n_items, item_set, hdr_buf, hdr_cap, hdr_off,
+                            key_buf) ? 0 : 1;
   GUARD_END(h)
 }
 int32_t rabe_aw11_keygen_packed(rabe_host* h, const void* gk, const void* msk, const char* const* gids, const char* const* attributes, const size_t* counts,
                                 size_t n_sets, size_t n_items, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off) {
   GUARD_BEGIN
-  std::vector<std::vector<std::string>> sets(n_sets);
-  size_t at = 0;
-  for (size_t s = 0; s < n_sets; s++)
-    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
+  const auto sets = attr_sets(attributes, counts, n_sets);
   return aw11::keygen_packed(h->eng, *(const aw11::Aw11GlobalKey*)gk, *(const aw11::Aw11MasterKey*)msk, strs(gids, n_items), sets, n_items, item_set, sk_buf,
                              sk_cap, sk_off) ? 0 : 1;
   GUARD_END(h)
@@ -1449,65 +1391,48 @@ int32_t rabe_aw11_encrypt_packed(rabe_host* h, const void* gk, const void* const
                                  int32_t language, size_t n_items, const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off,
                                  uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off) {
   GUARD_BEGIN
-  std::vector<const aw11::Aw11PublicKey*> p;
-  for (size_t i = 0; i < n_pks; i++) p.push_back((const aw11::Aw11PublicKey*)pks[i]);
+  const auto p = key_ptrs<aw11::Aw11PublicKey>(pks, n_pks);
   const auto& g = *(const aw11::Aw11GlobalKey*)gk;
   const auto pols = strs(policies, n_policies);
   const auto lang = lang_of(language);
-  if (!item_policy || !pt_off || !ct_off) throw RabeError("aw11::encrypt_packed: null input");
-  return pipeline::produce(h->engines(), h->rng(), n_items, CHUNK_AW11, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return aw11::encrypt_packed(eng, r, g, p, pols, lang, hi - lo, item_policy + lo, pt_blob, pt_off + lo, out, cap, off);
-  }, ct_buf, ct_cap, ct_off) ? 0 : 1;
+  require(item_policy && pt_off && ct_off, "aw11::encrypt_packed: null input");
+  return produce_shape(h, h->engines(), CHUNK_AW11, n_items, item_policy, pt_off, ct_buf, ct_cap, ct_off, nullptr, [&](const ProduceBlock& b) {
+    return aw11::encrypt_packed(b.eng, b.rng, g, p, pols, lang, b.n, b.item, pt_blob, b.pt_off, b.out, b.cap, b.off);
+  });
   GUARD_END(h)
 }
 int32_t rabe_aw11_decrypt_packed(rabe_host* h, const void* gk, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
                                  uint32_t flags, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
   GUARD_BEGIN
-  std::vector<std::string> errors;
   const auto& g = *(const aw11::Aw11GlobalKey*)gk;
   const auto& key = *(const aw11::Aw11SecretKey*)sk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  if (!pipeline::consume(h->engines(), n_items, CHUNK_AW11, ct_off, ct_len, [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off,
-                                                                           std::vector<std::string>* errs) {
-        return aw11::decrypt_packed(eng, g, key, hi - lo, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
-      }, status, pt_buf, pt_cap, pt_off, &errors))
-    return 1;
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
+  return consume_shape(h, h->engines(), CHUNK_AW11, false, n_items, ct_off, ct_len, status, pt_buf, pt_cap, pt_off, [&](const ConsumeBlock& b) {
+    return aw11::decrypt_packed(b.eng, g, key, b.n, ct_blob, ct_len, b.in_off, trusted_of(flags), b.status, b.pt, b.cap, b.pt_off, b.errors);
+  });
   GUARD_END(h)
 }
-// key encapsulation over the AW11 pair: both calls are cut over a device group where rabe_aw11_{encrypt,decrypt}_packed are cut, a block's
-// 32-byte key slots written straight to key_buf + 32 lo
+// key encapsulation over the AW11 pair: both calls are cut over a device group where rabe_aw11_{encrypt,decrypt}_packed are cut
 int32_t rabe_aw11_encaps_packed(rabe_host* h, const void* gk, const void* const* pks, size_t n_pks, const char* const* policies, size_t n_policies,
                                 int32_t language, size_t n_items, const uint32_t* item_policy, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off,
                                 uint8_t* key_buf) {
   GUARD_BEGIN
-  if (!item_policy || !hdr_off) throw RabeError("aw11::encaps_packed: null input");
-  std::vector<const aw11::Aw11PublicKey*> p;
-  for (size_t i = 0; i < n_pks; i++) p.push_back((const aw11::Aw11PublicKey*)pks[i]);
+  require(item_policy && hdr_off, "aw11::encaps_packed: null input");
+  const auto p = key_ptrs<aw11::Aw11PublicKey>(pks, n_pks);
   const auto& g = *(const aw11::Aw11GlobalKey*)gk;
   const auto pols = strs(policies, n_policies);
   const auto lang = lang_of(language);
-  return pipeline::produce(h->engines_if(key_buf != nullptr), h->rng(), n_items, CHUNK_AW11,
-                           [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return aw11::encaps_packed(eng, r, g, p, pols, lang, hi - lo, item_policy + lo, out, cap, off, key_buf ? key_buf + KEM_KEY * lo : nullptr);
-  }, hdr_buf, hdr_cap, hdr_off) ? 0 : 1;
+  return produce_shape(h, h->engines_if(key_buf != nullptr), CHUNK_AW11, n_items, item_policy, nullptr, hdr_buf, hdr_cap, hdr_off, key_buf,
+                       [&](const ProduceBlock& b) { return aw11::encaps_packed(b.eng, b.rng, g, p, pols, lang, b.n, b.item, b.out, b.cap, b.off, b.keys); });
   GUARD_END(h)
 }
 int32_t rabe_aw11_decaps_packed(rabe_host* h, const void* gk, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
                                 uint32_t flags, int32_t* status, uint8_t* key_buf) {
   GUARD_BEGIN
-  std::vector<std::string> errors;
   const auto& g = *(const aw11::Aw11GlobalKey*)gk;
   const auto& key = *(const aw11::Aw11SecretKey*)sk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  pipeline::for_blocks(h->engines_if(ct_off && status && key_buf), n_items, CHUNK_AW11, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
-    aw11::decaps_packed(eng, g, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
-                        key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
-    return true;
-  }, &errors);
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
+  return decaps_shape(h, h->engines_if(ct_off && status && key_buf), CHUNK_AW11, n_items, ct_off, status, key_buf, [&](const DecapsBlock& b) {
+    aw11::decaps_packed(b.eng, g, key, b.n, ct_blob, ct_len, b.in_off, trusted_of(flags), b.status, b.keys, b.errors);
+  });
   GUARD_END(h)
 }
 int32_t rabe_ac17_cp_decrypt_batch(rabe_host* h, size_t n, const void* const* sks, const void* const* cts, int32_t* status,
@@ -1525,13 +1450,6 @@ int32_t rabe_ac17_kp_keygen(rabe_host* h, const void* msk, const char* policy, i
   GUARD_BEGIN
   *sk = new ac17::Ac17KpSecretKey(ac17::kp_keygen(h->eng, h->rng(), *(const ac17::Ac17MasterKey*)msk, policy, lang_of(language)));
   return 0;
-  GUARD_END(h)
-}
-int32_t rabe_ac17_kp_keygen_packed(rabe_host* h, const void* msk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
-                                   const uint32_t* item_policy, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off) {
-  GUARD_BEGIN
-  return ac17::kp_keygen_packed(h->eng, h->rng(), *(const ac17::Ac17MasterKey*)msk, strs(policies, n_policies), lang_of(language), n_items, item_policy, sk_buf,
-                                sk_cap, sk_off) ? 0 : 1;
   GUARD_END(h)
 }
 int32_t rabe_ac17_kp_encrypt(rabe_host* h, const void* pk, const char* const* attributes, size_t n, const uint8_t* data, size_t len, void** ct) {
@@ -1854,6 +1772,7 @@ int32_t rabe_bdabe_decrypt_batch(rabe_host* h, size_t n, const void* const* uks,
   return 0;
   GUARD_END(h)
 }
+// ---- bdabe, mke08: packed entry points, each pair through one body (dnf_*_packed above `extern "C"`)
 int32_t rabe_bdabe_decrypt_packed(rabe_host* h, const void* uk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
                                   int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
   GUARD_BEGIN
@@ -1874,39 +1793,19 @@ int32_t rabe_bdabe_encrypt_packed(rabe_host* h, const void* pk, const void* cons
                                   int32_t language, size_t n_items, const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off,
                                   uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off) {
   GUARD_BEGIN
-  std::vector<const bdabe::BdabePublicAttributeKey*> v;
-  for (size_t i = 0; i < n_pks; i++) v.push_back((const bdabe::BdabePublicAttributeKey*)attr_pks[i]);
-  const auto& key = *(const bdabe::BdabePublicKey*)pk;
-  const auto pols = strs(policies, n_policies);
-  const auto lang = lang_of(language);
-  if (!item_policy || !pt_off || !ct_off) throw RabeError("bdabe::encrypt_packed: null input");
-  return pipeline::produce(h->engines(), h->rng(), n_items, CHUNK_DNF, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return bdabe::encrypt_packed(eng, r, key, v, pols, lang, hi - lo, item_policy + lo, pt_blob, pt_off + lo, out, cap, off);
-  }, ct_buf, ct_cap, ct_off) ? 0 : 1;
+  return dnf_encrypt_packed<bdabe::BdabePublicKey, bdabe::BdabePublicAttributeKey>(
+      h, "bdabe::encrypt_packed: null input", pk, attr_pks, n_pks, policies, n_policies, language, n_items, item_policy, pt_blob, pt_off, ct_buf, ct_cap, ct_off,
+      [](auto&&... a) { return bdabe::encrypt_packed(a...); });
   GUARD_END(h)
 }
 int32_t rabe_mke08_encrypt_packed(rabe_host* h, const void* pk, const void* const* attr_pks, size_t n_pks, const char* const* policies, size_t n_policies,
                                   int32_t language, size_t n_items, const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off,
                                   uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off) {
   GUARD_BEGIN
-  std::vector<const mke08::Mke08PublicAttributeKey*> v;
-  for (size_t i = 0; i < n_pks; i++) v.push_back((const mke08::Mke08PublicAttributeKey*)attr_pks[i]);
-  const auto& key = *(const mke08::Mke08PublicKey*)pk;
-  const auto pols = strs(policies, n_policies);
-  const auto lang = lang_of(language);
-  if (!item_policy || !pt_off || !ct_off) throw RabeError("mke08::encrypt_packed: null input");
-  return pipeline::produce(h->engines(), h->rng(), n_items, CHUNK_DNF, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return mke08::encrypt_packed(eng, r, key, v, pols, lang, hi - lo, item_policy + lo, pt_blob, pt_off + lo, out, cap, off);
-  }, ct_buf, ct_cap, ct_off) ? 0 : 1;
+  return dnf_encrypt_packed<mke08::Mke08PublicKey, mke08::Mke08PublicAttributeKey>(
+      h, "mke08::encrypt_packed: null input", pk, attr_pks, n_pks, policies, n_policies, language, n_items, item_policy, pt_blob, pt_off, ct_buf, ct_cap, ct_off,
+      [](auto&&... a) { return mke08::encrypt_packed(a...); });
   GUARD_END(h)
-}
-// attribute lists of a bulk call: flat names + per-list counts (as rabe_ghw11_keygen_packed)
-static std::vector<std::vector<std::string>> attr_sets(const char* const* attributes, const size_t* counts, size_t n_sets) {
-  std::vector<std::vector<std::string>> sets(n_sets);
-  size_t at = 0;
-  for (size_t s = 0; s < n_sets; s++)
-    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
-  return sets;
 }
 int32_t rabe_bdabe_keygen_packed(rabe_host* h, const void* pk, const void* ska, const char* const* names, size_t n_items, uint8_t* uk_buf, size_t uk_cap,
                                  uint64_t* uk_off) {
@@ -1926,24 +1825,16 @@ int32_t rabe_bdabe_request_attribute_sk_packed(rabe_host* h, const void* ska, co
                                                size_t n_items, const uint32_t* item_set, const uint8_t* upk_blob, size_t upk_len, const uint64_t* upk_off,
                                                uint32_t flags, int32_t* status, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
   GUARD_BEGIN
-  std::vector<std::string> errors;
-  if (!bdabe::request_attribute_sk_packed(h->eng, *(const bdabe::BdabeSecretAuthorityKey*)ska, attr_sets(attributes, counts, n_sets), n_items, item_set,
-                                          upk_blob, upk_len, upk_off, (flags & RABE_PACKED_TRUSTED) != 0, status, out_buf, out_cap, out_off, &errors))
-    return 1;
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
+  return dnf_request_sk_packed<bdabe::BdabeSecretAuthorityKey>(h, ska, attributes, counts, n_sets, n_items, item_set, upk_blob, upk_len, upk_off, flags, status,
+                                                               out_buf, out_cap, out_off, [](auto&&... a) { return bdabe::request_attribute_sk_packed(a...); });
   GUARD_END(h)
 }
 int32_t rabe_mke08_request_authority_sk_packed(rabe_host* h, const void* ska, const char* const* attributes, const size_t* counts, size_t n_sets,
                                                size_t n_items, const uint32_t* item_set, const uint8_t* upk_blob, size_t upk_len, const uint64_t* upk_off,
                                                uint32_t flags, int32_t* status, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
   GUARD_BEGIN
-  std::vector<std::string> errors;
-  if (!mke08::request_authority_sk_packed(h->eng, *(const mke08::Mke08SecretAuthorityKey*)ska, attr_sets(attributes, counts, n_sets), n_items, item_set,
-                                          upk_blob, upk_len, upk_off, (flags & RABE_PACKED_TRUSTED) != 0, status, out_buf, out_cap, out_off, &errors))
-    return 1;
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
+  return dnf_request_sk_packed<mke08::Mke08SecretAuthorityKey>(h, ska, attributes, counts, n_sets, n_items, item_set, upk_blob, upk_len, upk_off, flags, status,
+                                                               out_buf, out_cap, out_off, [](auto&&... a) { return mke08::request_authority_sk_packed(a...); });
   GUARD_END(h)
 }
 int32_t rabe_mke08_setup(rabe_host* h, void** pk, void** msk) {
@@ -2063,150 +1954,61 @@ int32_t rabe_ghw11_transform_batch(rabe_host* h, size_t n, const void* const* ct
   return 0;
   GUARD_END(h)
 }
+// ---- ghw11: packed entry points
 int32_t rabe_ghw11_transform_packed(rabe_host* h, const void* tk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
                                     int32_t* status, uint8_t* tct_buf, size_t tct_cap) {
   GUARD_BEGIN
   std::vector<std::string> errors;
   const auto& key = *(const ghw11::Ghw11TransformKey*)tk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  const size_t TCT = 768;
   // fixed slots: block [lo, hi) writes its records at tct_buf + 768 lo and its verdicts at status + lo, where the uncut call puts them
   const bool room = tct_buf && tct_cap >= n_items * TCT;
   if (!pipeline::for_blocks(h->engines_if(ct_off && status && room), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
     const bool whole = hi - lo == n_items;          // the uncut call judges the caller's own capacity
-    return ghw11::transform_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
+    return ghw11::transform_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted_of(flags), status ? status + lo : nullptr,
                                    tct_buf ? tct_buf + TCT * lo : nullptr, whole ? tct_cap : TCT * (hi - lo), errs);
   }, &errors))
     return 1;
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  first_error(h, errors);
   return 0;
-  GUARD_END(h)
-}
-int32_t rabe_ghw11_encrypt_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
-                                  const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off) {
-  GUARD_BEGIN
-  const auto& key = *(const ghw11::Ghw11PublicKey*)pk;
-  const auto pols = strs(policies, n_policies);
-  const auto lang = lang_of(language);
-  if (!item_policy || !pt_off || !ct_off) throw RabeError("ghw11::encrypt_packed: null input");
-  return pipeline::produce(h->engines(), h->rng(), n_items, CHUNK_GHW11, [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return ghw11::encrypt_packed(eng, r, key, pols, lang, hi - lo, item_policy + lo, pt_blob, pt_off + lo, out, cap, off);
-  }, ct_buf, ct_cap, ct_off) ? 0 : 1;
   GUARD_END(h)
 }
 int32_t rabe_ghw11_decrypt_out_packed(rabe_host* h, const void* rk, size_t n_items, const uint8_t* tct_buf, const uint8_t* ct_blob, size_t ct_len,
                                       const uint64_t* ct_off, uint32_t flags, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
   GUARD_BEGIN
-  std::vector<std::string> errors;
   const auto& key = *(const ghw11::Ghw11RetrieveKey*)rk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  if (ct_off && pt_off) pt_off[n_items] = record_span(n_items, ct_off, ct_len);
   // two inputs cut at the same item boundaries: the 768-byte tct slots and the records of the blob
-  if (!pipeline::consume(h->engines_if(pt_off && status && tct_buf), n_items, pipeline::GROUP_ONLY, ct_off, ct_len,
-                         [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off, std::vector<std::string>* errs) {
-        return ghw11::decrypt_out_packed(eng, key, hi - lo, tct_buf ? tct_buf + 768 * lo : nullptr, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
-      }, status, pt_buf, pt_cap, pt_off, &errors))
-    return 1;
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
-  GUARD_END(h)
-}
-int32_t rabe_ghw11_decrypt_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
-                                  int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off) {
-  GUARD_BEGIN
-  std::vector<std::string> errors;
-  const auto& key = *(const ghw11::Ghw11SecretKey*)sk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  if (ct_off && pt_off) pt_off[n_items] = record_span(n_items, ct_off, ct_len);
-  if (!pipeline::consume(h->engines_if(pt_off && status), n_items, pipeline::GROUP_ONLY, ct_off, ct_len,
-                         [&](Engine& eng, size_t lo, size_t hi, int32_t* st, uint8_t* pt, size_t cap, uint64_t* off, std::vector<std::string>* errs) {
-        return ghw11::decrypt_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off + lo, trusted, st, pt, cap, off, errs);
-      }, status, pt_buf, pt_cap, pt_off, &errors))
-    return 1;
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
-  GUARD_END(h)
-}
-// key encapsulation (include/rabe_host.h).  Over a device group, as the AC17 / BSW pair: the headers through `produce`, a block's 32-byte
-// key slots and verdicts in place through `for_blocks`.
-int32_t rabe_ghw11_encaps_packed(rabe_host* h, const void* pk, const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
-                                 const uint32_t* item_policy, uint8_t* hdr_buf, size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {
-  GUARD_BEGIN
-  if (!item_policy || !hdr_off) throw RabeError("ghw11::encaps_packed: null input");
-  const auto& key = *(const ghw11::Ghw11PublicKey*)pk;
-  const auto pols = strs(policies, n_policies);
-  const auto lang = lang_of(language);
-  return pipeline::produce(h->engines_if(key_buf != nullptr), h->rng(), n_items, pipeline::GROUP_ONLY,
-                           [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return ghw11::encaps_packed(eng, r, key, pols, lang, hi - lo, item_policy + lo, out, cap, off, key_buf ? key_buf + KEM_KEY * lo : nullptr);
-  }, hdr_buf, hdr_cap, hdr_off) ? 0 : 1;
+  return consume_shape(h, h->engines_if(pt_off && status && tct_buf), pipeline::GROUP_ONLY, true, n_items, ct_off, ct_len, status, pt_buf, pt_cap, pt_off,
+                       [&](const ConsumeBlock& b) {
+    return ghw11::decrypt_out_packed(b.eng, key, b.n, tct_buf ? tct_buf + TCT * b.lo : nullptr, ct_blob, ct_len, b.in_off, trusted_of(flags), b.status, b.pt, b.cap,
+                                     b.pt_off, b.errors);
+  });
   GUARD_END(h)
 }
 int32_t rabe_ghw11_decaps_out_packed(rabe_host* h, const void* rk, size_t n_items, const uint8_t* tct_buf, uint32_t flags, int32_t* status,
                                      uint8_t* key_buf) {
   GUARD_BEGIN
-  std::vector<std::string> errors;
   const auto& key = *(const ghw11::Ghw11RetrieveKey*)rk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  pipeline::for_blocks(h->engines_if(tct_buf && status && key_buf), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
-    ghw11::decaps_out_packed(eng, key, hi - lo, tct_buf ? tct_buf + 768 * lo : nullptr, trusted, status ? status + lo : nullptr,
-                             key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
-    return true;
-  }, &errors);
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
-  GUARD_END(h)
-}
-int32_t rabe_ghw11_decaps_packed(rabe_host* h, const void* sk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, uint32_t flags,
-                                 int32_t* status, uint8_t* key_buf) {
-  GUARD_BEGIN
-  std::vector<std::string> errors;
-  const auto& key = *(const ghw11::Ghw11SecretKey*)sk;
-  const bool trusted = (flags & RABE_PACKED_TRUSTED) != 0;
-  pipeline::for_blocks(h->engines_if(ct_off && status && key_buf), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
-    ghw11::decaps_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted, status ? status + lo : nullptr,
-                         key_buf ? key_buf + KEM_KEY * lo : nullptr, errs);
-    return true;
-  }, &errors);
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
-  return 0;
-  GUARD_END(h)
-}
-int32_t rabe_ghw11_decrypt(rabe_host* h, const void* sk, const void* ct, uint8_t** plaintext, size_t* len) {
-  GUARD_BEGIN
-  return give_bytes(ghw11::decrypt(h->eng, *(const ghw11::Ghw11SecretKey*)sk, *(const ghw11::Ghw11Ciphertext*)ct), plaintext, len);
-  GUARD_END(h)
-}
-int32_t rabe_ghw11_decrypt_gt(rabe_host* h, const void* sk, const void* ct, uint8_t out_gt[384]) {
-  GUARD_BEGIN
-  Gt g = ghw11::decrypt_gt(h->eng, *(const ghw11::Ghw11SecretKey*)sk, *(const ghw11::Ghw11Ciphertext*)ct);
-  memcpy(out_gt, g.data(), 384);
-  return 0;
+  return decaps_shape(h, h->engines_if(tct_buf && status && key_buf), pipeline::GROUP_ONLY, n_items, nullptr, status, key_buf, [&](const DecapsBlock& b) {
+    ghw11::decaps_out_packed(b.eng, key, b.n, tct_buf ? tct_buf + TCT * b.lo : nullptr, trusted_of(flags), b.status, b.keys, b.errors);
+  });
   GUARD_END(h)
 }
 int32_t rabe_ghw11_keygen_packed(rabe_host* h, const void* pk, const void* msk, const char* const* attributes, const size_t* counts, size_t n_sets,
                                  size_t n_items, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off) {
   GUARD_BEGIN
-  std::vector<std::vector<std::string>> sets(n_sets);
-  size_t at = 0;
-  for (size_t s = 0; s < n_sets; s++)
-    for (size_t k = 0; k < counts[s]; k++) sets[s].push_back(attributes[at++]);
+  const auto sets = attr_sets(attributes, counts, n_sets);
   const auto& key = *(const ghw11::Ghw11PublicKey*)pk;
   const auto& master = *(const ghw11::Ghw11MasterKey*)msk;
-  return pipeline::produce(h->engines_if(sk_off && item_set), h->rng(), n_items, pipeline::GROUP_ONLY,
-                           [&](Engine& eng, size_t lo, size_t hi, Rng& r, uint8_t* out, size_t cap, uint64_t* off) {
-    return ghw11::keygen_packed(eng, r, key, master, sets, hi - lo, item_set ? item_set + lo : nullptr, out, cap, off);
-  }, sk_buf, sk_cap, sk_off) ? 0 : 1;
+  return produce_shape(h, h->engines_if(sk_off && item_set), pipeline::GROUP_ONLY, n_items, item_set, nullptr, sk_buf, sk_cap, sk_off, nullptr,
+                       [&](const ProduceBlock& b) { return ghw11::keygen_packed(b.eng, b.rng, key, master, sets, b.n, b.item, b.out, b.cap, b.off); });
   GUARD_END(h)
 }
 int32_t rabe_ghw11_tkgen_packed(rabe_host* h, size_t n_items, const uint8_t* sk_blob, size_t sk_len, const uint64_t* sk_off, uint32_t flags, int32_t* status,
                                 uint8_t* tk_buf, size_t tk_cap, uint64_t* tk_off, uint8_t* rk_buf) {
   GUARD_BEGIN
   std::vector<std::string> errors;
-  if (!ghw11::tkgen_packed(h->eng, h->rng(), n_items, sk_blob, sk_len, sk_off, (flags & RABE_PACKED_TRUSTED) != 0, status, tk_buf, tk_cap, tk_off, rk_buf,
-                           &errors))
-    return 1;
-  for (const auto& e : errors) if (!e.empty()) { set_err(h, e); break; }
+  if (!ghw11::tkgen_packed(h->eng, h->rng(), n_items, sk_blob, sk_len, sk_off, trusted_of(flags), status, tk_buf, tk_cap, tk_off, rk_buf, &errors)) return 1;
+  first_error(h, errors);
   return 0;
   GUARD_END(h)
 }
@@ -2245,6 +2047,18 @@ int32_t rabe_ghw11_provision_packed(rabe_host* h, const void* pk, const void* ms
       throw RabeError("ghw11::provision_packed: a block's records do not have the announced size");
     return true;
   }, nullptr);
+  return 0;
+  GUARD_END(h)
+}
+int32_t rabe_ghw11_decrypt(rabe_host* h, const void* sk, const void* ct, uint8_t** plaintext, size_t* len) {
+  GUARD_BEGIN
+  return give_bytes(ghw11::decrypt(h->eng, *(const ghw11::Ghw11SecretKey*)sk, *(const ghw11::Ghw11Ciphertext*)ct), plaintext, len);
+  GUARD_END(h)
+}
+int32_t rabe_ghw11_decrypt_gt(rabe_host* h, const void* sk, const void* ct, uint8_t out_gt[384]) {
+  GUARD_BEGIN
+  Gt g = ghw11::decrypt_gt(h->eng, *(const ghw11::Ghw11SecretKey*)sk, *(const ghw11::Ghw11Ciphertext*)ct);
+  memcpy(out_gt, g.data(), 384);
   return 0;
   GUARD_END(h)
 }
