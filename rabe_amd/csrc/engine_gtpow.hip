@@ -82,10 +82,10 @@ extern "C" int32_t rhip_gt_pow_rows(rhip_ctx* ctx, size_t n_rows, const uint32_t
   void* masks = nullptr;
   void* img = nullptr;
   const size_t mask_bytes = n_items * 24 * sizeof(uint32_t);
-  int32_t rc = rhip_ensure_work(ctx, 16, mask_bytes, &masks);
+  int32_t rc = rhip_ensure_work(ctx, WORK_ROWS_MASKS, mask_bytes, &masks);
   if (rc) return rc;
   const size_t stride = ((n_rows < RB_GT_ROWS_CHUNK ? n_rows : RB_GT_ROWS_CHUNK) + 63) / 64 * 64;
-  rc = rhip_ensure_work(ctx, 17, stride * 4 * sizeof(GtM), &img);
+  rc = rhip_ensure_work(ctx, WORK_ROWS_IMAGES, stride * 4 * sizeof(GtM), &img);
   if (rc) return rc;
   KLAUNCH(ctx, "k_gtpow4_masks", k_gtpow4_masks, dim3(blocks_for(n_items, 256)), dim3(256), 0, ctx->stream, n_items, k, flags & RHIP_GT_POW_INVERT,
           (uint32_t*)masks);
@@ -169,9 +169,9 @@ int32_t rhip_gt_mexp4_run(rhip_ctx* ctx, size_t n_items, size_t max_terms, size_
   }
   void *dg = nullptr, *tbl = nullptr, *part = nullptr;
   const size_t dg_bytes = (n_k ? n_k : 1) * RB_GTMEXP4_WORDS * sizeof(uint32_t);
-  int32_t rc = rhip_ensure_work(ctx, 19, dg_bytes, &dg);
-  if (!rc) rc = rhip_ensure_work(ctx, 20, (n_terms ? n_terms : 1) * RB_GTMEXP4_TABLE * sizeof(GtM), &tbl);
-  if (!rc) rc = rhip_ensure_work(ctx, 21, n_items * L * sizeof(GtM), &part);
+  int32_t rc = rhip_ensure_work(ctx, WORK_GTMEXP4_DIGITS, dg_bytes, &dg);
+  if (!rc) rc = rhip_ensure_work(ctx, WORK_GTMEXP4_TABLES, (n_terms ? n_terms : 1) * RB_GTMEXP4_TABLE * sizeof(GtM), &tbl);
+  if (!rc) rc = rhip_ensure_work(ctx, WORK_GTMEXP4_PARTS, n_items * L * sizeof(GtM), &part);
   if (rc) return rc;
   if (n_k)
     KLAUNCH(ctx, "k_gtmexp4_digits", k_gtmexp4_digits, dim3(blocks_for(n_k, 256)), dim3(256), 0, ctx->stream, n_k, k, flags & RHIP_GT_POW_INVERT, (uint32_t*)dg);

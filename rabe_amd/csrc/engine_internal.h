@@ -33,6 +33,32 @@ using namespace rabe::bn254;
 #ifndef RB_G2_WAVES
 #define RB_G2_WAVES 2
 #endif
+// grow-only work arenas of a context (rhip_ctx::work, rhip_ensure_work), by name.  One line per slot: who uses it, with whom it is shared, from whom it must stay apart.  A slot is grow-only; two users of one slot in
+// the same launch set overwrite each other, and two sizes alternating in one slot re-allocate (a device-wide hipFree) on every launch.
+enum rhip_work_slot {
+  WORK_PAIR_P = 0,           // pair lists, G1 arguments (engine_jobs.hip: alloc_pair_lists); live until the final exponentiation
+  WORK_PAIR_Q = 1,           // pair lists, walked G2 arguments
+  WORK_PAIR_QREF = 2,        // pair lists, walk / skip / prepared-line block of every pair
+  WORK_MILLER_WS = 3,        // running G2 points of the Miller kernels on 8 x 32-bit limbs, planned and (L, C) geometry alike
+  WORK_SUM_TERMS = 4,        // shared-doubling sum: bases.  Three layouts: G1M terms; AW11 [G2M terms | GtM terms | lead]; outside a decrypt the Fr scalars of the encrypt / keygen entry points
+  WORK_SUM_MASKS = 5,        // shared-doubling sum: NAF masks per selection entry
+  WORK_SUM_PARTS = 6,        // shared-doubling sum: partial sums, G1JM; AW11 [G2JM | GtM partial products]
+  WORK_SUM_OFF = 7,          // shared-doubling sum: term offsets per item; rhip_pairing_jobs keeps its combined pair offsets here
+  WORK_ENTRY_POINTS = 8,     // G1M[n] | uint8_t inf[n]: BSW / LSW one-ciphertext scaled selection entries, LSW one-key group sums (one of them per entry point)
+  WORK_MILLER_PLAN = 9,      // plan | histogram | chunk offsets | work list of a device-planned Miller launch
+  WORK_TILE_OFF = 10,        // tile table of a ragged gather launch (gather_lanes)
+  WORK_RR_WS = 11,           // reduced-radix Miller workspace (engine_rr.hip)
+  WORK_XCHECK_OUT = 12,      // cross-check mode: the forced families' result and the flag word
+  WORK_XCHECK_FACTOR = 13,   // cross-check mode: snapshot of an in-place leading factor
+  WORK_RR2_WS = 14,          // two-lane Miller workspace (engine_rr2.hip).  Its own slot: in the cross-check mode it alternates with the one-lane kernel's, and one slot for both sizes would re-allocate on every launch
+  WORK_DNF_TABLES = 15,      // table pointers of a DNF encrypt that spans several term sets (rhip_dnf_encrypt_batch)
+  WORK_ROWS_MASKS = 16,      // masks of rhip_g2_mul_rows, z^-1 | r z^-1 of rhip_ghw11_provision_batch (engine_keys.hip); digits of rhip_gt_pow_rows (engine_gtpow.hip): key issuing and Gt powers never share a launch set
+  WORK_ROWS_IMAGES = 17,     // point images of rhip_g2_mul_rows; Gt images of rhip_gt_pow_rows (shared as 16 is)
+  WORK_G1_ROWS_MASKS = 18,   // masks of rhip_g1_mul_rows (engine_keys.hip)
+  WORK_GTMEXP4_DIGITS = 19,  // windowed Gt multi-exponentiation (engine_gtpow.hip): digits.  19 .. 21 stay apart from 4 .. 7: aw11_decrypt_body calls rhip_gt_mexp4_run while its sum's arenas are live
+  WORK_GTMEXP4_TABLES = 20,  // ... odd-power tables
+  WORK_GTMEXP4_PARTS = 21,   // ... partial products
+};
 // ------------------------------------------------------------------------------------------------
 // context
 struct rhip_ctx {
@@ -48,7 +74,7 @@ struct rhip_ctx {
   void* fe_ws = nullptr;
   size_t fe_ws_bytes = 0;
   // grow-only work arenas of the job kernels (engine_jobs.hip: pair lists, running G2 points, scalars)
-  enum { N_WORK = 22 };          // 19, 20, 21: the digits, the odd-power tables and the partial products of the windowed Gt multi-exponentiation (engine_gtpow.hip); 18: the masks of rhip_g1_mul_rows (engine_keys.hip); 16, 17: the masks and the point images of rhip_g2_mul_rows (engine_keys.hip); 15: the table pointers of a DNF encrypt that spans several term sets (engine_jobs.hip: rhip_dnf_encrypt_batch); 12, 13: the cross-check mode's second result buffer and its snapshot of an in-place factor (engine_jobs.hip); 14: the two-lane Miller kernel's workspace (its own slot: in the cross-check mode it alternates with the one-lane kernel's, and a grow-only slot shared by two sizes would be re-allocated -- a device-wide hipFree -- on every launch)
+  enum { N_WORK = 22 };          // one per rhip_work_slot, above
   void* work[N_WORK] = {};
   size_t work_bytes[N_WORK] = {};
   // optional per-kernel timing (HIP events on the launch stream), for bench.py's roofline leg
@@ -68,6 +94,7 @@ struct rhip_ctx {
   struct Pending { std::string name; hipEvent_t e0, e1; };
   std::vector<Pending> pending;
 };
+static_assert(rhip_ctx::N_WORK == WORK_GTMEXP4_PARTS + 1, "N_WORK follows the last work slot");
 // defined in engine.hip
 void rhip_ktime_begin(rhip_ctx* ctx, const char* name);
 void rhip_ktime_end(rhip_ctx* ctx);
@@ -86,7 +113,7 @@ struct RhipOnFork {
 };
 int32_t rhip_ensure_scratch(rhip_ctx* ctx, size_t bytes);
 int32_t rhip_ensure_fe_ws(rhip_ctx* ctx, size_t bytes);
-int32_t rhip_ensure_work(rhip_ctx* ctx, int slot, size_t bytes, void** out);
+int32_t rhip_ensure_work(rhip_ctx* ctx, int slot /* rhip_work_slot */, size_t bytes, void** out);
 bool rhip_use_c3(const rhip_ctx* ctx, size_t n_pairs);
 #define ktime_begin rhip_ktime_begin
 #define ktime_end rhip_ktime_end

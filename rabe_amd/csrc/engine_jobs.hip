@@ -16,6 +16,8 @@
 // There is no CPU fallback anywhere in this file.
 #include "engine_internal.h"
 #include "msm_chunks.h"
+#include "miller_plan.h"
+#define RC_TRY(call) do { const int32_t rc__ = (call); if (rc__) return rc__; } while (0)          // a failed step ends the entry point with its code
 
 // ------------------------------------------------------------------------------------------------ small device helpers
 __device__ __forceinline__ Fp ld_fp_q(const uint4* p) {
@@ -81,17 +83,22 @@ struct PairLists {
   uint32_t* qref;
 };
 static int32_t alloc_pair_lists(rhip_ctx* ctx, size_t total_pairs, PairLists* pl) {
-  void* p = nullptr;
-  int32_t rc = rhip_ensure_work(ctx, 0, total_pairs * sizeof(G1M), &p);
-  if (rc) return rc;
-  pl->P = (G1M*)p;
-  rc = rhip_ensure_work(ctx, 1, total_pairs * sizeof(G2M), &p);
-  if (rc) return rc;
-  pl->Q = (G2M*)p;
-  rc = rhip_ensure_work(ctx, 2, total_pairs * sizeof(uint32_t), &p);
-  if (rc) return rc;
-  pl->qref = (uint32_t*)p;
+  void *p = nullptr, *q = nullptr, *r = nullptr;
+  RC_TRY(rhip_ensure_work(ctx, WORK_PAIR_P, total_pairs * sizeof(G1M), &p));
+  RC_TRY(rhip_ensure_work(ctx, WORK_PAIR_Q, total_pairs * sizeof(G2M), &q));
+  RC_TRY(rhip_ensure_work(ctx, WORK_PAIR_QREF, total_pairs * sizeof(uint32_t), &r));
+  *pl = PairLists{(G1M*)p, (G2M*)q, (uint32_t*)r};
   return RHIP_OK;
+}
+// One G1 point per selection entry or group, computed once and copied into the pairs that use it: pts[n] | inf[n] (1: the point at infinity,
+// pts[e] is not written).  One such buffer per launch set.
+struct EntryPoints { G1M* pts; uint8_t* inf; };
+static int32_t alloc_entry_points(rhip_ctx* ctx, size_t n, EntryPoints* ep) {
+  void* w = nullptr;
+  const int32_t rc = rhip_ensure_work(ctx, WORK_ENTRY_POINTS, n * (sizeof(G1M) + 1) + 64, &w);
+  ep->pts = (G1M*)w;
+  ep->inf = (uint8_t*)(ep->pts + n);
+  return rc;
 }
 
 // k * base (or k * -base), affine Montgomery, one field inversion per 256-thread block.  All threads must call this.
@@ -190,7 +197,7 @@ static int32_t gather_lanes(rhip_ctx* ctx, size_t n_items, size_t max_pairs, siz
   const size_t n_tiles = (n_items + 63) / 64;
   if (n_tiles * 64 * max_pairs >= ((size_t)1 << 32)) return RHIP_OK;          // the table holds 32-bit lane numbers
   void* w = nullptr;
-  const int32_t rc = rhip_ensure_work(ctx, 10, (n_tiles + 1) * sizeof(uint32_t), &w);
+  const int32_t rc = rhip_ensure_work(ctx, WORK_TILE_OFF, (n_tiles + 1) * sizeof(uint32_t), &w);
   if (rc) return rc;
   KLAUNCH(ctx, "k_tile_offsets", k_tile_offsets, dim3(1), dim3(1024), 0, ctx->stream, n_items, pair_off, (uint32_t*)w);
   *tile_off = (const uint32_t*)w;
@@ -516,9 +523,6 @@ __global__ void __launch_bounds__(256) k_plan_fill(size_t n_items, const uint32_
     }
   }
 }
-// Miller values of all items' pairs + final exponentiation: out[i] = mul_in[i] * FE(prod_j ML(P_j, Q_j))
-static int32_t run_pair_lists_mode(rhip_ctx* ctx, size_t n_items, const uint32_t* pair_off, size_t max_pairs, size_t total_pairs, const PairLists& pl,
-                                   const LineM* lines, const void* lines29, const rhip_gt* mul_in, rhip_gt* out);
 // ---- pairing mode 99, the cross-check: the launch runs as "auto" would run it (that result is the one the caller gets, walk verdicts and early
 // releases included), then AGAIN with each family of pairing kernels forced -- one lane per accumulator on 8 x 32-bit limbs (1), six lanes (6),
 // reduced radix (29), reduced radix with a unit on two lanes (58): Miller loops AND final exponentiation of that family -- on the same pair lists, and every result is compared with the
@@ -534,20 +538,91 @@ __global__ void __launch_bounds__(256) k_xcheck_compare(size_t n_quads, const ui
   const uint4 x = a[t];
   if (x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w) atomicOr(flag, bit);
 }
+// The geometry of a Miller launch: which lane owns which (item, chunk).  Fixed: lane = chunk * n_items + item, L chunks of at most C pairs for
+// every item, Miller values at mill[item * L + c].  Planned (a ragged batch): lane = entry of the device-made work list -- the chunks that exist,
+// C chosen on the device from [c_lo, c_hi] -- Miller values at the compact mill[chunk_off[item] + c].
+struct MillerGeometry {
+  uint32_t L, C;                 // planned: 0, 0 (the kernels read them from the plan)
+  uint32_t c_max;                // the most pairs a lane can hold: C, planned c_hi
+  size_t lanes;                  // n_items * L; planned: the bound w_max of the work list
+  const MillerPlan* plan; const uint2* work; const uint32_t* chunk_off;          // planned only, like the next line
+  size_t plan_pairs; uint32_t plan_c_lo;          // the batch's pairs and the plan's c_lo: the two-lane launcher sizes its columns from them
+  void* ws; size_t ws_bytes;          // running G2 points of the walked pairs
+};
+// the Miller loops of the family the launch calls for, the walk verdicts where they were asked for, the final exponentiation
+static int32_t run_miller_and_final_exp(rhip_ctx* ctx, const MillerGeometry& g, size_t n_items, const uint32_t* pair_off, size_t max_pairs, const PairLists& pl,
+                                        const LineM* lines, const void* lines29, const rhip_gt* mul_in, rhip_gt* out) {
+  GtM* mill = (GtM*)ctx->scratch;          // g.lanes Miller values: ensured by the caller, where it sized the workspace
+  // rhip_ctx_release_when_miller_resident: the waiter goes on beside the reduced-radix Miller loops already.  The fixed geometry alone takes
+  // one; a planned launch takes none (its waiter is released as without the request, in front of the final exponentiation).
+  const bool early = ctx->early_release && !g.plan;
+  uint32_t* started = nullptr;
+  if (rhip_use_c6(ctx, n_items, max_pairs)) {       // six lanes per (item, chunk): engine_coop.hip; same (item, chunk) map and workspace layout, so the walk verdicts below apply unchanged
+    RC_TRY(rhip_launch_miller_c6(ctx, n_items, g.L, g.C, pair_off, (uint32_t)max_pairs, pl.P, pl.Q, pl.qref, lines, g.ws, mill, g.plan, g.work, g.chunk_off, g.lanes));
+  } else if (rhip_use_rr2(ctx, g.c_max)) {          // one unit on two lanes, two waves per SIMD (engine_rr2.hip)
+    if (early) RC_TRY(rhip_take_waiter(ctx, blocks_for(2 * g.lanes, RB_MILLER_BLOCK), &started));
+    RC_TRY(rhip_launch_miller_rr2(ctx, n_items, g.L, g.C, g.c_max, pair_off, (uint32_t)max_pairs, pl.P, pl.Q, pl.qref, lines, lines29, g.ws, mill, g.plan, g.work, g.chunk_off,
+                                  g.lanes, started, g.plan_pairs, g.plan_c_lo));
+  } else if (rhip_use_rr(ctx)) {
+    if (early) RC_TRY(rhip_take_waiter(ctx, blocks_for(g.lanes, RB_MILLER_BLOCK), &started));
+    RC_TRY(rhip_launch_miller_rr(ctx, n_items, g.L, g.C, pair_off, (uint32_t)max_pairs, pl.P, pl.Q, pl.qref, lines, lines29, g.ws, g.ws_bytes, mill, g.plan, g.work, g.chunk_off,
+                                 g.lanes, started));
+  } else
+    KLAUNCH(ctx, "k_miller_multi", k_miller_multi, dim3(blocks_for(g.lanes, RB_MILLER_BLOCK)), dim3(RB_MILLER_BLOCK), 0, ctx->stream, n_items, g.L, g.C, pair_off,
+            (uint32_t)max_pairs, (const G1M*)pl.P, (const G2M*)pl.Q, (const uint32_t*)pl.qref, lines, (uint4*)g.ws, (size_t)64, mill, g.plan, g.work, g.chunk_off);
+  if (ctx->walk_fail) {
+    KLAUNCH(ctx, "k_walk_verdicts", k_walk_verdicts, dim3(blocks_for(g.lanes, 256)), dim3(256), 0, ctx->stream, n_items, g.L, g.C, pair_off, (uint32_t)max_pairs,
+            (const G2M*)pl.Q, (const uint32_t*)pl.qref, (const uint4*)g.ws, g.plan, g.work, ctx->walk_fail, ctx->walk_count);
+    ctx->walk_fail = ctx->walk_count = nullptr;
+  }
+  return launch_final_exp(ctx, n_items, g.chunk_off, g.plan ? 1u : g.L, (const GtM*)mill, mul_in, out);
+}
+// Miller values of all items' pairs + final exponentiation: out[i] = mul_in[i] * FE(prod_j ML(P_j, Q_j)).  pair_off == NULL: every item owns max_pairs pairs
+static int32_t run_pair_lists_mode(rhip_ctx* ctx, size_t n_items, const uint32_t* pair_off, size_t max_pairs, size_t total_pairs, const PairLists& pl,
+                                   const LineM* lines, const void* lines29, const rhip_gt* mul_in, rhip_gt* out) {
+  MillerGeometry g{};
+  if (pair_off && total_pairs && total_pairs < n_items * max_pairs && !getenv("RABE_NO_MILLER_PLAN")) {
+    // ragged: plan on the device; the bounds of what the plan may choose and the buffers for the worst of the range: miller_plan.h
+    const rb_miller_plan_sizes b = rb_miller_plan_bounds((size_t)ctx->n_cu, RB_MILLER_BLOCK, sizeof(MillerPlan), n_items, max_pairs, total_pairs);
+    void* pb = nullptr;
+    RC_TRY(rhip_ensure_work(ctx, WORK_MILLER_PLAN, b.plan_bytes, &pb));
+    MillerPlan* plan = (MillerPlan*)pb;
+    uint32_t* hist = (uint32_t*)pb + b.plan_words;
+    uint32_t* chunk_off = hist + b.hist_words;
+    uint2* work = (uint2*)(chunk_off + b.off_words);
+    RC_TRY(rhip_ensure_work(ctx, WORK_MILLER_WS, b.ws_bytes, &g.ws));
+    RC_TRY(ensure_scratch(ctx, b.w_max * sizeof(GtM)));
+    HIP_TRY(ctx, hipMemsetAsync(hist, 0, b.hist_words * 4, ctx->stream));
+    KLAUNCH(ctx, "k_plan_hist", k_plan_hist, dim3(blocks_for(n_items, 256)), dim3(256), 0, ctx->stream, n_items, pair_off, (uint32_t)max_pairs, hist);
+    KLAUNCH(ctx, "k_plan_choose", k_plan_choose, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)hist, (uint32_t)max_pairs, (uint32_t)n_items, (uint32_t)b.c_lo,
+            (uint32_t)b.c_hi, (uint32_t)ctx->n_cu, plan);
+    KLAUNCH(ctx, "k_plan_scan", k_plan_scan, dim3(1), dim3(1024), 0, ctx->stream, n_items, pair_off, (const MillerPlan*)plan, chunk_off);
+    KLAUNCH(ctx, "k_plan_fill", k_plan_fill, dim3(ctx->n_cu * 4), dim3(256), 0, ctx->stream, n_items, pair_off, plan, work);
+    g.c_max = (uint32_t)b.c_hi, g.lanes = b.w_max, g.ws_bytes = b.ws_bytes;
+    g.plan = plan, g.work = work, g.chunk_off = chunk_off, g.plan_pairs = total_pairs, g.plan_c_lo = (uint32_t)b.c_lo;
+  } else {
+    if (rhip_use_c6(ctx, n_items, max_pairs)) rhip_choose_chunks_c6(ctx, n_items, max_pairs, &g.L, &g.C);
+    else choose_chunks(ctx, n_items, max_pairs, pair_off ? total_pairs : 0, &g.L, &g.C);
+    g.c_max = g.C, g.lanes = n_items * g.L, g.ws_bytes = (g.lanes + 63) / 64 * 64 * g.C * 12 * sizeof(uint4);
+    RC_TRY(rhip_ensure_work(ctx, WORK_MILLER_WS, g.ws_bytes, &g.ws));
+    RC_TRY(ensure_scratch(ctx, g.lanes * sizeof(GtM)));
+  }
+  return run_miller_and_final_exp(ctx, g, n_items, pair_off, max_pairs, pl, lines, lines29, mul_in, out);
+}
 static int32_t run_pair_lists(rhip_ctx* ctx, size_t n_items, const uint32_t* pair_off, size_t max_pairs, size_t total_pairs, const PairLists& pl,
                               const LineM* lines, const void* lines29, const rhip_gt* mul_in, rhip_gt* out) {
   if (ctx->pairing_mode != 99) return run_pair_lists_mode(ctx, n_items, pair_off, max_pairs, total_pairs, pl, lines, lines29, mul_in, out);
   struct Restore { rhip_ctx* c; ~Restore() { c->pairing_mode = 99; } } restore{ctx};
   const size_t bytes = n_items * sizeof(rhip_gt);
   void* tmp = nullptr;
-  int32_t rc = rhip_ensure_work(ctx, 12, bytes + 256, &tmp);
+  int32_t rc = rhip_ensure_work(ctx, WORK_XCHECK_OUT, bytes + 256, &tmp);
   if (rc) return rc;
   uint32_t* flag = (uint32_t*)((uint8_t*)tmp + bytes);
   HIP_TRY(ctx, hipMemsetAsync(flag, 0, 4, ctx->stream));
   const rhip_gt* factor = mul_in;
   if (mul_in && (const void*)mul_in == (const void*)out) {          // in place: the other families need the factor as it was
     void* keep = nullptr;
-    rc = rhip_ensure_work(ctx, 13, bytes, &keep);
+    rc = rhip_ensure_work(ctx, WORK_XCHECK_FACTOR, bytes, &keep);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(keep, mul_in, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     factor = (const rhip_gt*)keep;
@@ -573,103 +648,6 @@ static int32_t run_pair_lists(rhip_ctx* ctx, size_t n_items, const uint32_t* pai
     return RHIP_ERR_HIP;
   }
   return RHIP_OK;
-}
-static int32_t run_pair_lists_mode(rhip_ctx* ctx, size_t n_items, const uint32_t* pair_off, size_t max_pairs, size_t total_pairs, const PairLists& pl,
-                              const LineM* lines, const void* lines29, const rhip_gt* mul_in, rhip_gt* out) {          // pair_off == NULL: every item owns max_pairs pairs
-  if (pair_off && total_pairs && total_pairs < n_items * max_pairs && !getenv("RABE_NO_MILLER_PLAN")) {
-    // ragged: plan on the device.  Bounds of what the plan may choose: no fewer pairs per chunk than four rounds' worth of lanes need
-    // (more lanes only add shared squarings), no more than 64; the buffers are sized for the worst of the range.
-    const size_t R = (size_t)ctx->n_cu * RB_MILLER_BLOCK;
-    size_t c_lo = total_pairs / (4 * R);
-    if (c_lo < 1) c_lo = 1;
-    size_t c_hi = max_pairs < 64 ? max_pairs : 64;
-    if (c_lo > c_hi) c_lo = c_hi;
-    const size_t w_max = total_pairs / c_lo + n_items + 64;
-    const size_t hist_words = (max_pairs + 2 + 3) / 4 * 4;
-    const size_t plan_words = (sizeof(MillerPlan) / 4 + 3) / 4 * 4;
-    const size_t off_words = (n_items + 1 + 3) / 4 * 4;
-    void* pb = nullptr;
-    int32_t rc = rhip_ensure_work(ctx, 9, (plan_words + hist_words + off_words) * 4 + w_max * sizeof(uint2), &pb);
-    if (rc) return rc;
-    MillerPlan* plan = (MillerPlan*)pb;
-    uint32_t* hist = (uint32_t*)pb + plan_words;
-    uint32_t* chunk_off = hist + hist_words;
-    uint2* work = (uint2*)(chunk_off + off_words);
-    void* ws = nullptr;
-    const size_t ws_bytes = (total_pairs + n_items * (c_hi - 1) + 64 * c_hi + 64) * 12 * sizeof(uint4);
-    rc = rhip_ensure_work(ctx, 3, ws_bytes, &ws);
-    if (rc) return rc;
-    rc = ensure_scratch(ctx, w_max * sizeof(GtM));
-    if (rc) return rc;
-    GtM* mill = (GtM*)ctx->scratch;
-    HIP_TRY(ctx, hipMemsetAsync(hist, 0, hist_words * 4, ctx->stream));
-    KLAUNCH(ctx, "k_plan_hist", k_plan_hist, dim3(blocks_for(n_items, 256)), dim3(256), 0, ctx->stream, n_items, pair_off, (uint32_t)max_pairs, hist);
-    KLAUNCH(ctx, "k_plan_choose", k_plan_choose, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)hist, (uint32_t)max_pairs, (uint32_t)n_items, (uint32_t)c_lo,
-            (uint32_t)c_hi, (uint32_t)ctx->n_cu, plan);
-    KLAUNCH(ctx, "k_plan_scan", k_plan_scan, dim3(1), dim3(1024), 0, ctx->stream, n_items, pair_off, (const MillerPlan*)plan, chunk_off);
-    KLAUNCH(ctx, "k_plan_fill", k_plan_fill, dim3(ctx->n_cu * 4), dim3(256), 0, ctx->stream, n_items, pair_off, plan, work);
-    if (rhip_use_c6(ctx, n_items, max_pairs)) {
-      rc = rhip_launch_miller_c6(ctx, n_items, 0u, 0u, pair_off, (uint32_t)max_pairs, pl.P, pl.Q, pl.qref, lines, ws, mill, plan, work, chunk_off, w_max);
-      if (rc) return rc;
-    } else if (rhip_use_rr2(ctx, (uint32_t)c_hi)) {          // one unit on two lanes, two waves per SIMD (engine_rr2.hip)
-      rc = rhip_launch_miller_rr2(ctx, n_items, 0u, 0u, (uint32_t)c_hi, pair_off, (uint32_t)max_pairs, pl.P, pl.Q, pl.qref, lines, lines29, ws, mill, plan, work, chunk_off, w_max,
-                                  nullptr, total_pairs, (uint32_t)c_lo);
-      if (rc) return rc;
-    } else if (rhip_use_rr(ctx)) {
-      rc = rhip_launch_miller_rr(ctx, n_items, 0u, 0u, pair_off, (uint32_t)max_pairs, pl.P, pl.Q, pl.qref, lines, lines29, ws, ws_bytes, mill, plan, work, chunk_off, w_max);
-      if (rc) return rc;
-    } else
-    KLAUNCH(ctx, "k_miller_multi", k_miller_multi, dim3(blocks_for(w_max, RB_MILLER_BLOCK)), dim3(RB_MILLER_BLOCK), 0, ctx->stream, n_items, 0u, 0u, pair_off, (uint32_t)max_pairs,
-            (const G1M*)pl.P, (const G2M*)pl.Q, (const uint32_t*)pl.qref, lines, (uint4*)ws, (size_t)64, mill, (const MillerPlan*)plan, (const uint2*)work,
-            (const uint32_t*)chunk_off);
-    if (ctx->walk_fail) {
-      KLAUNCH(ctx, "k_walk_verdicts", k_walk_verdicts, dim3(blocks_for(w_max, 256)), dim3(256), 0, ctx->stream, n_items, 0u, 0u, pair_off, (uint32_t)max_pairs, (const G2M*)pl.Q,
-              (const uint32_t*)pl.qref, (const uint4*)ws, (const MillerPlan*)plan, (const uint2*)work, ctx->walk_fail, ctx->walk_count);
-      ctx->walk_fail = ctx->walk_count = nullptr;
-    }
-    return launch_final_exp(ctx, n_items, (const uint32_t*)chunk_off, 1u, (const GtM*)mill, mul_in, out);
-  }
-  uint32_t L, C;
-  const bool c6 = rhip_use_c6(ctx, n_items, max_pairs);
-  if (c6) rhip_choose_chunks_c6(ctx, n_items, max_pairs, &L, &C);
-  else choose_chunks(ctx, n_items, max_pairs, pair_off ? total_pairs : 0, &L, &C);
-  const size_t lanes = n_items * L;
-  const size_t lanes_pad = (lanes + 63) / 64 * 64;
-  void* ws = nullptr;
-  const size_t ws_bytes = lanes_pad * C * 12 * sizeof(uint4);
-  int32_t rc = rhip_ensure_work(ctx, 3, ws_bytes, &ws);
-  if (rc) return rc;
-  rc = ensure_scratch(ctx, lanes * sizeof(GtM));
-  if (rc) return rc;
-  GtM* mill = (GtM*)ctx->scratch;
-  if (c6) {       // six lanes per (item, chunk): engine_coop.hip; same (item, chunk) map and workspace layout, so the walk verdicts below apply unchanged
-    rc = rhip_launch_miller_c6(ctx, n_items, L, C, pair_off, (uint32_t)max_pairs, pl.P, pl.Q, pl.qref, lines, ws, mill, nullptr, nullptr, nullptr, lanes);
-    if (rc) return rc;
-  } else if (rhip_use_rr2(ctx, C)) {          // one unit on two lanes, two waves per SIMD (engine_rr2.hip)
-    uint32_t* started = nullptr;
-    if (ctx->early_release) {          // rhip_ctx_release_when_miller_resident: the waiter goes on beside the Miller loops already
-      rc = rhip_take_waiter(ctx, blocks_for(2 * lanes, RB_MILLER_BLOCK), &started);
-      if (rc) return rc;
-    }
-    rc = rhip_launch_miller_rr2(ctx, n_items, L, C, C, pair_off, (uint32_t)max_pairs, pl.P, pl.Q, pl.qref, lines, lines29, ws, mill, nullptr, nullptr, nullptr, lanes, started, 0, 0u);
-    if (rc) return rc;
-  } else if (rhip_use_rr(ctx)) {
-    uint32_t* started = nullptr;
-    if (ctx->early_release) {          // rhip_ctx_release_when_miller_resident: the waiter goes on beside the Miller loops already
-      rc = rhip_take_waiter(ctx, blocks_for(lanes, RB_MILLER_BLOCK), &started);
-      if (rc) return rc;
-    }
-    rc = rhip_launch_miller_rr(ctx, n_items, L, C, pair_off, (uint32_t)max_pairs, pl.P, pl.Q, pl.qref, lines, lines29, ws, ws_bytes, mill, nullptr, nullptr, nullptr, lanes, started);
-    if (rc) return rc;
-  } else
-  KLAUNCH(ctx, "k_miller_multi", k_miller_multi, dim3(blocks_for(lanes, RB_MILLER_BLOCK)), dim3(RB_MILLER_BLOCK), 0, ctx->stream, n_items, L, C, pair_off, (uint32_t)max_pairs, (const G1M*)pl.P,
-          (const G2M*)pl.Q, (const uint32_t*)pl.qref, lines, (uint4*)ws, (size_t)64, mill, (const MillerPlan*)nullptr, (const uint2*)nullptr, (const uint32_t*)nullptr);
-  if (ctx->walk_fail) {
-    KLAUNCH(ctx, "k_walk_verdicts", k_walk_verdicts, dim3(blocks_for(lanes, 256)), dim3(256), 0, ctx->stream, n_items, L, C, pair_off, (uint32_t)max_pairs, (const G2M*)pl.Q,
-            (const uint32_t*)pl.qref, (const uint4*)ws, (const MillerPlan*)nullptr, (const uint2*)nullptr, ctx->walk_fail, ctx->walk_count);
-    ctx->walk_fail = ctx->walk_count = nullptr;
-  }
-  return launch_final_exp(ctx, n_items, (const uint32_t*)nullptr, L, (const GtM*)mill, mul_in, out);
 }
 
 // ------------------------------------------------------------------------------------------------ share generation
@@ -787,7 +765,7 @@ extern "C" int32_t rhip_bsw_encrypt_batch(rhip_ctx* ctx, const rhip_bsw_pk* pk, 
   if (!pk) return RHIP_ERR_ARG;
   if (!n_items) return RHIP_OK;
   void* w = nullptr;
-  int32_t rc = rhip_ensure_work(ctx, 4, (total_leaves ? total_leaves : 1) * 2 * sizeof(rhip_fr), &w);
+  int32_t rc = rhip_ensure_work(ctx, WORK_SUM_TERMS, (total_leaves ? total_leaves : 1) * 2 * sizeof(rhip_fr), &w);
   if (rc) return rc;
   rhip_fr* kq = (rhip_fr*)w;
   rhip_fr* khq = kq + total_leaves;
@@ -1052,7 +1030,34 @@ static int32_t bsw_decrypt_impl(rhip_ctx* ctx, size_t n_items, size_t max_pairs,
                                 const rhip_fr* sel_coeff, const rhip_g1* ct_c, const rhip_gt* ct_cp, const rhip_g1* ct_cy_g1,
                                 const rhip_g2* ct_cy_g2, const uint32_t* ct_leaf_off, const rhip_g2* sk_d, const rhip_g1* sk_dj_g1,
                                 const rhip_g2* sk_dj_g2, const uint32_t* sk_attr_off, const uint32_t* sk_idx,
-                                const rhip_bsw_sk_lines* sk_lines, rhip_gt* out);
+                                const rhip_bsw_sk_lines* sk_lines, rhip_gt* out) {
+  NEED(ctx);
+  if (!n_items) return RHIP_OK;
+  if (!total_pairs || !pair_off) return RHIP_ERR_ARG;
+  PairLists pl;
+  int32_t rc = alloc_pair_lists(ctx, total_pairs, &pl);
+  if (rc) return rc;
+  const uint32_t ppi = uniform_ppi(n_items, max_pairs, total_pairs);
+  EntryPoints psel{nullptr, nullptr};
+  if (!sk_idx && n_sel && 2 * n_sel < total_pairs - n_items) {     // one key and shared entries: its scaled Dj.g1 once per entry
+    RC_TRY(alloc_entry_points(ctx, n_sel, &psel));
+    KLAUNCH(ctx, "k_bsw_scale_entries", k_bsw_scale_entries, dim3(blocks_for(n_sel, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_sel, sel_sk_attr, sel_coeff,
+            sk_dj_g1, psel.pts, psel.inf);
+  }
+  const int compact = (psel.pts && ppi >= 3) ? 1 : 0;        // uniform batch: the odd pairs are copies (k_bsw_entry_pairs), the others get the lanes
+  size_t lanes = 0;
+  const uint32_t* tile_off = nullptr;
+  if (compact) lanes = pair_lanes(n_items, n_items * (size_t)((ppi + 1) / 2), (ppi + 1) / 2);
+  else if ((rc = gather_lanes(ctx, n_items, max_pairs, total_pairs, pair_off, ppi, &tile_off, &lanes)) != RHIP_OK) return rc;
+  KLAUNCH(ctx, "k_bsw_dec_pairs", k_bsw_dec_pairs, dim3(blocks_for(lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items,
+          total_pairs, pair_off, ppi, tile_off, sel_start, sel_ct_leaf, sel_sk_attr, sel_coeff, ct_c, ct_cy_g1, ct_cy_g2, ct_leaf_off, sk_d, sk_dj_g1, sk_dj_g2,
+          sk_attr_off, sk_idx, (uint32_t)(sk_lines ? sk_lines->total_attrs : 0), sk_lines ? 1 : 0,
+          (const uint8_t*)(sk_lines ? sk_lines->l->q_inf : nullptr), pl.P, pl.Q, pl.qref, (const G1M*)psel.pts, (const uint8_t*)psel.inf, compact);
+  if (compact)
+    KLAUNCH(ctx, "k_bsw_entry_pairs", k_bsw_entry_pairs, dim3(blocks_for(n_items * (size_t)((ppi - 1) / 2), 256)), dim3(256), 0, ctx->stream, n_items, ppi, sel_start,
+            sel_ct_leaf, ct_cy_g2, ct_leaf_off, (const G1M*)psel.pts, (const uint8_t*)psel.inf, pl.P, pl.Q, pl.qref);
+  return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, sk_lines ? (const LineM*)sk_lines->l->lines : (const LineM*)nullptr, sk_lines ? sk_lines->l->lines29 : nullptr, ct_cp, out);
+}
 extern "C" int32_t rhip_bsw_decrypt_batch(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, const uint32_t* pair_off,
                                           const uint32_t* sel_start, const uint32_t* sel_ct_leaf, const uint32_t* sel_sk_attr,
                                           const rhip_fr* sel_coeff, const rhip_g1* ct_c, const rhip_gt* ct_cp, const rhip_g1* ct_cy_g1,
@@ -1070,44 +1075,6 @@ extern "C" int32_t rhip_bsw_decrypt_batch_one_sk(rhip_ctx* ctx, size_t n_items, 
                                                  const rhip_g2* sk_dj_g2, const uint32_t* sk_attr_off, const rhip_bsw_sk_lines* sk_lines, rhip_gt* out) {
   return bsw_decrypt_impl(ctx, n_items, max_pairs, total_pairs, n_sel, pair_off, sel_start, sel_ct_leaf, sel_sk_attr, sel_coeff, ct_c, ct_cp, ct_cy_g1, ct_cy_g2,
                           ct_leaf_off, sk_d, sk_dj_g1, sk_dj_g2, sk_attr_off, (const uint32_t*)nullptr, sk_lines, out);
-}
-static int32_t bsw_decrypt_impl(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
-                                const uint32_t* sel_start, const uint32_t* sel_ct_leaf, const uint32_t* sel_sk_attr,
-                                const rhip_fr* sel_coeff, const rhip_g1* ct_c, const rhip_gt* ct_cp, const rhip_g1* ct_cy_g1,
-                                const rhip_g2* ct_cy_g2, const uint32_t* ct_leaf_off, const rhip_g2* sk_d, const rhip_g1* sk_dj_g1,
-                                const rhip_g2* sk_dj_g2, const uint32_t* sk_attr_off, const uint32_t* sk_idx,
-                                const rhip_bsw_sk_lines* sk_lines, rhip_gt* out) {
-  NEED(ctx);
-  if (!n_items) return RHIP_OK;
-  if (!total_pairs || !pair_off) return RHIP_ERR_ARG;
-  PairLists pl;
-  int32_t rc = alloc_pair_lists(ctx, total_pairs, &pl);
-  if (rc) return rc;
-  const uint32_t ppi = uniform_ppi(n_items, max_pairs, total_pairs);
-  G1M* psel = nullptr;
-  uint8_t* psel_inf = nullptr;
-  if (!sk_idx && n_sel && 2 * n_sel < total_pairs - n_items) {     // one key and shared entries: its scaled Dj.g1 once per entry
-    void* w_sel = nullptr;
-    rc = rhip_ensure_work(ctx, 8, n_sel * (sizeof(G1M) + 1) + 64, &w_sel);
-    if (rc) return rc;
-    psel = (G1M*)w_sel;
-    psel_inf = (uint8_t*)(psel + n_sel);
-    KLAUNCH(ctx, "k_bsw_scale_entries", k_bsw_scale_entries, dim3(blocks_for(n_sel, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_sel, sel_sk_attr, sel_coeff,
-            sk_dj_g1, psel, psel_inf);
-  }
-  const int compact = (psel && ppi >= 3) ? 1 : 0;        // uniform batch: the odd pairs are copies (k_bsw_entry_pairs), the others get the lanes
-  size_t lanes = 0;
-  const uint32_t* tile_off = nullptr;
-  if (compact) lanes = pair_lanes(n_items, n_items * (size_t)((ppi + 1) / 2), (ppi + 1) / 2);
-  else if ((rc = gather_lanes(ctx, n_items, max_pairs, total_pairs, pair_off, ppi, &tile_off, &lanes)) != RHIP_OK) return rc;
-  KLAUNCH(ctx, "k_bsw_dec_pairs", k_bsw_dec_pairs, dim3(blocks_for(lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items,
-          total_pairs, pair_off, ppi, tile_off, sel_start, sel_ct_leaf, sel_sk_attr, sel_coeff, ct_c, ct_cy_g1, ct_cy_g2, ct_leaf_off, sk_d, sk_dj_g1, sk_dj_g2,
-          sk_attr_off, sk_idx, (uint32_t)(sk_lines ? sk_lines->total_attrs : 0), sk_lines ? 1 : 0,
-          (const uint8_t*)(sk_lines ? sk_lines->l->q_inf : nullptr), pl.P, pl.Q, pl.qref, (const G1M*)psel, (const uint8_t*)psel_inf, compact);
-  if (compact)
-    KLAUNCH(ctx, "k_bsw_entry_pairs", k_bsw_entry_pairs, dim3(blocks_for(n_items * (size_t)((ppi - 1) / 2), 256)), dim3(256), 0, ctx->stream, n_items, ppi, sel_start,
-            sel_ct_leaf, ct_cy_g2, ct_leaf_off, (const G1M*)psel, (const uint8_t*)psel_inf, pl.P, pl.Q, pl.qref);
-  return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, sk_lines ? (const LineM*)sk_lines->l->lines : (const LineM*)nullptr, sk_lines ? sk_lines->l->lines29 : nullptr, ct_cp, out);
 }
 
 // ------------------------------------------------------------------------------------------------ shared-doubling sums
@@ -1247,7 +1214,7 @@ extern "C" int32_t rhip_lsw_keygen_batch(rhip_ctx* ctx, const rhip_lsw_pk* pk, s
   if (!pk) return RHIP_ERR_ARG;
   if (!n_items || !total_leaves) return RHIP_OK;
   void* w = nullptr;
-  int32_t rc = rhip_ensure_work(ctx, 4, total_leaves * sizeof(rhip_fr), &w);
+  int32_t rc = rhip_ensure_work(ctx, WORK_SUM_TERMS, total_leaves * sizeof(rhip_fr), &w);
   if (rc) return rc;
   const TreeTables tt{path_off, path_gate, path_x, gate_k, gate_coef_off};
   KLAUNCH(ctx, "k_lsw_keygen_scalars", k_lsw_keygen_scalars, dim3(blocks_for(total_leaves, 256)), dim3(256), 0, ctx->stream, n_items, total_leaves,
@@ -1301,7 +1268,7 @@ extern "C" int32_t rhip_lsw_keygen_batch_signed(rhip_ctx* ctx, const rhip_lsw_pk
   if (!pk || !host_h_g1) return RHIP_ERR_ARG;
   if (!n_items || !total_leaves) return RHIP_OK;
   void* w = nullptr;
-  int32_t rc = rhip_ensure_work(ctx, 4, total_leaves * (6 * sizeof(rhip_fr) + sizeof(rhip_g1)), &w);
+  int32_t rc = rhip_ensure_work(ctx, WORK_SUM_TERMS, total_leaves * (6 * sizeof(rhip_fr) + sizeof(rhip_g1)), &w);
   if (rc) return rc;
   rhip_fr* k = (rhip_fr*)w;
   rhip_g1* tmp = (rhip_g1*)(k + 6 * total_leaves);
@@ -1381,6 +1348,47 @@ __global__ void __launch_bounds__(256, RB_MIN_WAVES) k_term_off(size_t n_items, 
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i <= n_items) term_off[i] = pair_off[i] - other * (uint32_t)i;          // `other`: pairs of an item that are not terms of its sum
 }
+// ---- the shared-doubling sum stage of a decrypt launch set: n sums (one per item, or per selection group) of terms sum_j c_j B_j.  The stage owns
+// arenas WORK_SUM_TERMS .. WORK_SUM_OFF and the (L, C) cut of a sum into L lanes of at most C terms; the caller's fill kernel writes the
+// bases into `terms` between the two halves.  What differs between the callers is an argument here, never a default: the sizes (some
+// guard an empty batch with (n ? n : 1), some cannot see one), the pairs of an item that are no terms, the orientation of the masks.
+struct SumStage {
+  rhip_ctx* ctx;
+  size_t n;
+  uint32_t L = 1, C = 1;
+  void *terms = nullptr, *masks = nullptr, *parts = nullptr, *off = nullptr;
+  // the arenas, in the order 4, 5, 6, 7 (term_offsets false: no arena 7 -- the offsets are the caller's)
+  int32_t prepare(size_t max_terms, size_t terms_bytes, size_t n_masks, size_t part_bytes, bool term_offsets) {
+    choose_msm_chunks(ctx, n, max_terms, &L, &C);
+    int32_t rc = rhip_ensure_work(ctx, WORK_SUM_TERMS, terms_bytes, &terms);
+    if (!rc) rc = rhip_ensure_work(ctx, WORK_SUM_MASKS, n_masks * 16 * sizeof(uint32_t), &masks);
+    if (!rc) rc = rhip_ensure_work(ctx, WORK_SUM_PARTS, n * L * part_bytes, &parts);
+    if (!rc && term_offsets) rc = rhip_ensure_work(ctx, WORK_SUM_OFF, (n + 1) * sizeof(uint32_t), &off);
+    return rc;
+  }
+  int32_t naf_masks(size_t n_coeff, const rhip_fr* coeff) {          // n_coeff != 0
+    KLAUNCH(ctx, "k_naf_masks", k_naf_masks, dim3(blocks_for(n_coeff, 256)), dim3(256), 0, ctx->stream, n_coeff, coeff, (uint32_t*)masks);
+    return RHIP_OK;
+  }
+  int32_t term_offsets(const uint32_t* pair_off, uint32_t other) {          // off[i] = pair_off[i] - other * i
+    KLAUNCH(ctx, "k_term_off", k_term_off, dim3(blocks_for(n + 1, 256)), dim3(256), 0, ctx->stream, n, pair_off, (uint32_t*)off, other);
+    return RHIP_OK;
+  }
+  // lane (chunk, sum): sum i's terms start at term_off[i] in `terms`, their masks at mask_start[i]; flip: the sum of the negated terms
+  template <class F, class AFFM, class JACM>
+  int32_t partial(const char* name, const uint32_t* term_off, const uint32_t* mask_start, int flip) {
+    KLAUNCH(ctx, name, (k_msm_partial<F, AFFM, JACM>), dim3(blocks_for(n * L, 64)), dim3(64), 0, ctx->stream, n, L, C, term_off, mask_start, (const AFFM*)terms,
+            (const uint32_t*)masks, flip, (JACM*)parts);
+    return RHIP_OK;
+  }
+  int32_t partial_g1(const uint32_t* term_off, const uint32_t* mask_start, int flip) { return partial<Fp, G1M, G1JM>("k_msm_partial_g1", term_off, mask_start, flip); }
+  // sum i -> the G1 argument of item i's last pair (or a skipped pair)
+  int32_t finish_g1(const uint32_t* pair_off, const PairLists& pl) {
+    KLAUNCH(ctx, "k_msm_finish_g1", k_msm_finish_g1, dim3(blocks_for(n, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n, L, (const G1JM*)parts, pair_off, pl.P,
+            pl.qref);
+    return RHIP_OK;
+  }
+};
 // one ciphertext for the whole batch: the scaled G1 arguments depend on the selection entry alone -- entry e: c_e * E1[sel_ct_attr[e]]
 __global__ void __launch_bounds__(RB_PAIRS_BLOCK, 2) k_lsw_scale_entries(size_t n_sel, const uint32_t* sel_ct_attr, const rhip_fr* sel_coeff, const rhip_g1* ct_e1j,
                                                                         G1M* psel, uint8_t* psel_inf) {
@@ -1398,7 +1406,35 @@ static int32_t lsw_decrypt_impl(rhip_ctx* ctx, size_t n_items, size_t max_pairs,
                                 const uint32_t* sel_start, const uint32_t* sel_sk_leaf, const uint32_t* sel_ct_attr, const rhip_fr* sel_coeff,
                                 const rhip_gt* ct_e1, const rhip_g2* ct_e2, const rhip_g1* ct_e1j, const uint32_t* ct_attr_off,
                                 const uint32_t* ct_idx, const rhip_g1* sk_d1, const rhip_g2* sk_d2, const uint32_t* sk_leaf_off,
-                                const uint32_t* sk_idx, const rhip_g2_lines* ct_e2_lines, rhip_gt* out, bool one_ct);
+                                const uint32_t* sk_idx, const rhip_g2_lines* ct_e2_lines, rhip_gt* out, bool one_ct) {
+  NEED(ctx);
+  if (!n_items) return RHIP_OK;
+  if (!total_pairs || !pair_off || !n_sel) return RHIP_ERR_ARG;
+  PairLists pl;
+  int32_t rc = alloc_pair_lists(ctx, total_pairs, &pl);
+  if (rc) return rc;
+  const size_t total_terms = total_pairs - n_items;
+  SumStage sum{ctx, n_items};
+  RC_TRY(sum.prepare(max_pairs - 1, (total_terms ? total_terms : 1) * sizeof(G1M), n_sel, sizeof(G1JM), true));
+  RC_TRY(sum.naf_masks(n_sel, sel_coeff));          // n_sel != 0: checked above
+  RC_TRY(sum.term_offsets(pair_off, 1));          // the pair with e2 is no term
+  const uint32_t ppi = uniform_ppi(n_items, max_pairs, total_pairs);
+  EntryPoints psel{nullptr, nullptr};
+  if (one_ct && n_sel < total_pairs - n_items) {          // fewer entries than pairs: items share entries, scale per entry
+    RC_TRY(alloc_entry_points(ctx, n_sel, &psel));
+    KLAUNCH(ctx, "k_lsw_scale_entries", k_lsw_scale_entries, dim3(blocks_for(n_sel, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_sel, sel_ct_attr, sel_coeff,
+            ct_e1j, psel.pts, psel.inf);
+  }
+  size_t g_lanes = 0;
+  const uint32_t* tile_off = nullptr;
+  if ((rc = gather_lanes(ctx, n_items, max_pairs, total_pairs, pair_off, ppi, &tile_off, &g_lanes)) != RHIP_OK) return rc;
+  KLAUNCH(ctx, "k_lsw_dec_pairs", k_lsw_dec_pairs, dim3(blocks_for(g_lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items, total_pairs,
+          pair_off, ppi, tile_off, sel_start, sel_sk_leaf, sel_ct_attr, sel_coeff, ct_e2, ct_e1j, ct_attr_off, ct_idx, sk_d1, sk_d2, sk_leaf_off, sk_idx,
+          (const uint8_t*)(ct_e2_lines ? ct_e2_lines->q_inf : nullptr), pl.P, pl.Q, pl.qref, (G1M*)sum.terms, (const G1M*)psel.pts, (const uint8_t*)psel.inf, one_ct ? 1 : 0);
+  RC_TRY(sum.partial_g1((const uint32_t*)sum.off, sel_start, 1));          // flipped: sum -c_e D1_e
+  RC_TRY(sum.finish_g1(pair_off, pl));
+  return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, ct_e2_lines ? (const LineM*)ct_e2_lines->lines : (const LineM*)nullptr, ct_e2_lines ? ct_e2_lines->lines29 : nullptr, ct_e1, out);
+}
 extern "C" int32_t rhip_lsw_decrypt_batch(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
                                           const uint32_t* sel_start, const uint32_t* sel_sk_leaf, const uint32_t* sel_ct_attr, const rhip_fr* sel_coeff,
                                           const rhip_gt* ct_e1, const rhip_g2* ct_e2, const rhip_g1* ct_e1j, const uint32_t* ct_attr_off,
@@ -1414,52 +1450,6 @@ extern "C" int32_t rhip_lsw_decrypt_batch_one_ct(rhip_ctx* ctx, size_t n_items, 
                                                  const rhip_g2_lines* ct_e2_lines, rhip_gt* out) {
   return lsw_decrypt_impl(ctx, n_items, max_pairs, total_pairs, n_sel, pair_off, sel_start, sel_sk_leaf, sel_ct_attr, sel_coeff, ct_e1, ct_e2, ct_e1j,
                           (const uint32_t*)nullptr, (const uint32_t*)nullptr, sk_d1, sk_d2, sk_leaf_off, sk_idx, ct_e2_lines, out, true);
-}
-static int32_t lsw_decrypt_impl(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
-                                const uint32_t* sel_start, const uint32_t* sel_sk_leaf, const uint32_t* sel_ct_attr, const rhip_fr* sel_coeff,
-                                const rhip_gt* ct_e1, const rhip_g2* ct_e2, const rhip_g1* ct_e1j, const uint32_t* ct_attr_off,
-                                const uint32_t* ct_idx, const rhip_g1* sk_d1, const rhip_g2* sk_d2, const uint32_t* sk_leaf_off,
-                                const uint32_t* sk_idx, const rhip_g2_lines* ct_e2_lines, rhip_gt* out, bool one_ct) {
-  NEED(ctx);
-  if (!n_items) return RHIP_OK;
-  if (!total_pairs || !pair_off || !n_sel) return RHIP_ERR_ARG;
-  PairLists pl;
-  int32_t rc = alloc_pair_lists(ctx, total_pairs, &pl);
-  if (rc) return rc;
-  const size_t total_terms = total_pairs - n_items;
-  void *w_terms = nullptr, *w_masks = nullptr, *w_part = nullptr, *w_off = nullptr;
-  rc = rhip_ensure_work(ctx, 4, (total_terms ? total_terms : 1) * sizeof(G1M), &w_terms);
-  if (!rc) rc = rhip_ensure_work(ctx, 5, n_sel * 16 * sizeof(uint32_t), &w_masks);
-  uint32_t L, C;
-  choose_msm_chunks(ctx, n_items, max_pairs - 1, &L, &C);
-  if (!rc) rc = rhip_ensure_work(ctx, 6, n_items * L * sizeof(G1JM), &w_part);
-  if (!rc) rc = rhip_ensure_work(ctx, 7, (n_items + 1) * sizeof(uint32_t), &w_off);
-  if (rc) return rc;
-  KLAUNCH(ctx, "k_naf_masks", k_naf_masks, dim3(blocks_for(n_sel, 256)), dim3(256), 0, ctx->stream, n_sel, sel_coeff, (uint32_t*)w_masks);
-  KLAUNCH(ctx, "k_term_off", k_term_off, dim3(blocks_for(n_items + 1, 256)), dim3(256), 0, ctx->stream, n_items, pair_off, (uint32_t*)w_off);
-  const uint32_t ppi = uniform_ppi(n_items, max_pairs, total_pairs);
-  G1M* psel = nullptr;
-  uint8_t* psel_inf = nullptr;
-  if (one_ct && n_sel < total_pairs - n_items) {          // fewer entries than pairs: items share entries, scale per entry
-    void* w_sel = nullptr;
-    rc = rhip_ensure_work(ctx, 8, n_sel * (sizeof(G1M) + 1) + 64, &w_sel);
-    if (rc) return rc;
-    psel = (G1M*)w_sel;
-    psel_inf = (uint8_t*)(psel + n_sel);
-    KLAUNCH(ctx, "k_lsw_scale_entries", k_lsw_scale_entries, dim3(blocks_for(n_sel, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_sel, sel_ct_attr, sel_coeff,
-            ct_e1j, psel, psel_inf);
-  }
-  size_t g_lanes = 0;
-  const uint32_t* tile_off = nullptr;
-  if ((rc = gather_lanes(ctx, n_items, max_pairs, total_pairs, pair_off, ppi, &tile_off, &g_lanes)) != RHIP_OK) return rc;
-  KLAUNCH(ctx, "k_lsw_dec_pairs", k_lsw_dec_pairs, dim3(blocks_for(g_lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items, total_pairs,
-          pair_off, ppi, tile_off, sel_start, sel_sk_leaf, sel_ct_attr, sel_coeff, ct_e2, ct_e1j, ct_attr_off, ct_idx, sk_d1, sk_d2, sk_leaf_off, sk_idx,
-          (const uint8_t*)(ct_e2_lines ? ct_e2_lines->q_inf : nullptr), pl.P, pl.Q, pl.qref, (G1M*)w_terms, (const G1M*)psel, (const uint8_t*)psel_inf, one_ct ? 1 : 0);
-  KLAUNCH(ctx, "k_msm_partial_g1", (k_msm_partial<Fp, G1M, G1JM>), dim3(blocks_for(n_items * L, 64)), dim3(64), 0, ctx->stream, n_items, L, C,
-          (const uint32_t*)w_off, sel_start, (const G1M*)w_terms, (const uint32_t*)w_masks, 1, (G1JM*)w_part);
-  KLAUNCH(ctx, "k_msm_finish_g1", k_msm_finish_g1, dim3(blocks_for(n_items, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items, L,
-          (const G1JM*)w_part, pair_off, pl.P, pl.qref);
-  return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, ct_e2_lines ? (const LineM*)ct_e2_lines->lines : (const LineM*)nullptr, ct_e2_lines ? ct_e2_lines->lines29 : nullptr, ct_e1, out);
 }
 
 // decrypt of many ciphertexts under ONE key (the mirror image of the one-ciphertext form): every D2 is the key's, so the m key-side
@@ -1528,29 +1518,23 @@ extern "C" int32_t rhip_lsw_decrypt_batch_one_sk(rhip_ctx* ctx, size_t n_items, 
   PairLists pl;
   int32_t rc = alloc_pair_lists(ctx, total_pairs, &pl);
   if (rc) return rc;
-  void *w_terms = nullptr, *w_masks = nullptr, *w_part = nullptr, *w_sum = nullptr;
-  rc = rhip_ensure_work(ctx, 4, n_sel * sizeof(G1M), &w_terms);
-  if (!rc) rc = rhip_ensure_work(ctx, 5, n_sel * 16 * sizeof(uint32_t), &w_masks);
-  uint32_t L, C;
-  choose_msm_chunks(ctx, n_groups, max_pairs - 1, &L, &C);
-  if (!rc) rc = rhip_ensure_work(ctx, 6, n_groups * L * sizeof(G1JM), &w_part);
-  if (!rc) rc = rhip_ensure_work(ctx, 8, n_groups * (sizeof(G1M) + 1) + 64, &w_sum);
-  if (rc) return rc;
-  G1M* gsum = (G1M*)w_sum;
-  uint8_t* gsum_inf = (uint8_t*)(gsum + n_groups);
-  // the sums, over the groups as the MSM's "items": group g's terms and masks are its entries [group_off[g], group_off[g+1])
-  KLAUNCH(ctx, "k_naf_masks", k_naf_masks, dim3(blocks_for(n_sel, 256)), dim3(256), 0, ctx->stream, n_sel, sel_coeff, (uint32_t*)w_masks);
-  KLAUNCH(ctx, "k_lsw_entry_terms", k_lsw_entry_terms, dim3(blocks_for(n_sel, 256)), dim3(256), 0, ctx->stream, n_sel, sel_sk_leaf, sk_d1, (G1M*)w_terms);
-  KLAUNCH(ctx, "k_msm_partial_g1", (k_msm_partial<Fp, G1M, G1JM>), dim3(blocks_for(n_groups * L, 64)), dim3(64), 0, ctx->stream, n_groups, L, C, group_off, group_off,
-          (const G1M*)w_terms, (const uint32_t*)w_masks, 1, (G1JM*)w_part);
-  KLAUNCH(ctx, "k_msm_finish_groups_g1", k_msm_finish_groups_g1, dim3(blocks_for(n_groups, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_groups, L,
-          (const G1JM*)w_part, gsum, gsum_inf);
+  // the sums, over the groups as the stage's "items": group g's terms and masks are its entries [group_off[g], group_off[g+1]).  n_sel != 0
+  // (checked above): no size is guarded.  The finish is this entry point's own: it writes the groups' buffer, not a pair list.
+  SumStage sum{ctx, n_groups};
+  RC_TRY(sum.prepare(max_pairs - 1, n_sel * sizeof(G1M), n_sel, sizeof(G1JM), false));
+  EntryPoints gsum;
+  RC_TRY(alloc_entry_points(ctx, n_groups, &gsum));
+  RC_TRY(sum.naf_masks(n_sel, sel_coeff));
+  KLAUNCH(ctx, "k_lsw_entry_terms", k_lsw_entry_terms, dim3(blocks_for(n_sel, 256)), dim3(256), 0, ctx->stream, n_sel, sel_sk_leaf, sk_d1, (G1M*)sum.terms);
+  RC_TRY(sum.partial_g1(group_off, group_off, 1));
+  KLAUNCH(ctx, "k_msm_finish_groups_g1", k_msm_finish_groups_g1, dim3(blocks_for(n_groups, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_groups, sum.L,
+          (const G1JM*)sum.parts, gsum.pts, gsum.inf);
   const uint32_t ppi = uniform_ppi(n_items, max_pairs, total_pairs);
   size_t g_lanes = 0;
   const uint32_t* tile_off = nullptr;
   if ((rc = gather_lanes(ctx, n_items, max_pairs, total_pairs, pair_off, ppi, &tile_off, &g_lanes)) != RHIP_OK) return rc;
   KLAUNCH(ctx, "k_lsw_dec_pairs_one_sk", k_lsw_dec_pairs_one_sk, dim3(blocks_for(g_lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items, total_pairs,
-          pair_off, ppi, tile_off, sel_start, sel_sk_leaf, sel_ct_attr, sel_coeff, item_group, (const G1M*)gsum, (const uint8_t*)gsum_inf, ct_e2, ct_e1j, ct_attr_off,
+          pair_off, ppi, tile_off, sel_start, sel_sk_leaf, sel_ct_attr, sel_coeff, item_group, (const G1M*)gsum.pts, (const uint8_t*)gsum.inf, ct_e2, ct_e1j, ct_attr_off,
           (const uint8_t*)sk_d2_lines->q_inf, pl.P, pl.Q, pl.qref);
   return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, (const LineM*)sk_d2_lines->lines, sk_d2_lines->lines29, ct_e1, out);
 }
@@ -1608,17 +1592,12 @@ static int32_t ghw11_pairs_batch(rhip_ctx* ctx, bool inv, size_t n_items, size_t
   PairLists pl;
   int32_t rc = alloc_pair_lists(ctx, total_pairs, &pl);
   if (rc) return rc;
+  // a batch of empty selections is served (n_sel = 0, two pairs per item): both sizes are guarded and the masks are not launched
   const size_t total_terms = total_pairs - 2 * n_items;
-  void *w_terms = nullptr, *w_masks = nullptr, *w_part = nullptr, *w_off = nullptr;
-  rc = rhip_ensure_work(ctx, 4, (total_terms ? total_terms : 1) * sizeof(G1M), &w_terms);
-  if (!rc) rc = rhip_ensure_work(ctx, 5, (n_sel ? n_sel : 1) * 16 * sizeof(uint32_t), &w_masks);
-  uint32_t L, C;
-  choose_msm_chunks(ctx, n_items, max_pairs - 2, &L, &C);
-  if (!rc) rc = rhip_ensure_work(ctx, 6, n_items * L * sizeof(G1JM), &w_part);
-  if (!rc) rc = rhip_ensure_work(ctx, 7, (n_items + 1) * sizeof(uint32_t), &w_off);
-  if (rc) return rc;
-  if (n_sel) KLAUNCH(ctx, "k_naf_masks", k_naf_masks, dim3(blocks_for(n_sel, 256)), dim3(256), 0, ctx->stream, n_sel, sel_coeff, (uint32_t*)w_masks);
-  KLAUNCH(ctx, "k_term_off", k_term_off, dim3(blocks_for(n_items + 1, 256)), dim3(256), 0, ctx->stream, n_items, pair_off, (uint32_t*)w_off, 2u);
+  SumStage sum{ctx, n_items};
+  RC_TRY(sum.prepare(max_pairs - 2, (total_terms ? total_terms : 1) * sizeof(G1M), n_sel ? n_sel : 1, sizeof(G1JM), true));
+  if (n_sel) RC_TRY(sum.naf_masks(n_sel, sel_coeff));
+  RC_TRY(sum.term_offsets(pair_off, 2));          // the pairs with k_z and l_z are no terms
   const uint32_t ppi = uniform_ppi(n_items, max_pairs, total_pairs);
   size_t g_lanes = 0;
   const uint32_t* tile_off = nullptr;
@@ -1626,16 +1605,14 @@ static int32_t ghw11_pairs_batch(rhip_ctx* ctx, bool inv, size_t n_items, size_t
   if (inv)
     KLAUNCH(ctx, "k_ghw11_pairs_inv", k_ghw11_pairs<true>, dim3(blocks_for(g_lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items,
             total_pairs, pair_off, ppi, tile_off, sel_start, sel_ct_row, sel_tk_attr, sel_coeff, ct_c1, ct_c, ct_d, ct_row_off, (const uint8_t*)tk_lines->q_inf, pl.P,
-            pl.qref, (G1M*)w_terms);
+            pl.qref, (G1M*)sum.terms);
   else
     KLAUNCH(ctx, "k_ghw11_pairs", k_ghw11_pairs<false>, dim3(blocks_for(g_lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items,
             total_pairs, pair_off, ppi, tile_off, sel_start, sel_ct_row, sel_tk_attr, sel_coeff, ct_c1, ct_c, ct_d, ct_row_off, (const uint8_t*)tk_lines->q_inf, pl.P,
-            pl.qref, (G1M*)w_terms);
+            pl.qref, (G1M*)sum.terms);
   // the sum's sign is the masks' orientation: flipped (sum_e (-w_e) C_e) for t, as they are (sum_e w_e C_e) for t^-1
-  KLAUNCH(ctx, "k_msm_partial_g1", (k_msm_partial<Fp, G1M, G1JM>), dim3(blocks_for(n_items * L, 64)), dim3(64), 0, ctx->stream, n_items, L, C,
-          (const uint32_t*)w_off, sel_start, (const G1M*)w_terms, (const uint32_t*)w_masks, inv ? 0 : 1, (G1JM*)w_part);
-  KLAUNCH(ctx, "k_msm_finish_g1", k_msm_finish_g1, dim3(blocks_for(n_items, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items, L,
-          (const G1JM*)w_part, pair_off, pl.P, pl.qref);
+  RC_TRY(sum.partial_g1((const uint32_t*)sum.off, sel_start, inv ? 0 : 1));
+  RC_TRY(sum.finish_g1(pair_off, pl));
   return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, (const LineM*)tk_lines->lines, tk_lines->lines29, lead, out);
 }
 extern "C" int32_t rhip_ghw11_transform_batch(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
@@ -1930,7 +1907,7 @@ extern "C" int32_t rhip_aw11_encrypt_batch(rhip_ctx* ctx, const rhip_aw11_pk* pk
           (const GtM*)(et->dev16 ? et->dev16 : et->dev), et->dev16 ? 1 : 0, n_items, s, msg, c0);
   if (!total_rows) return RHIP_OK;
   void* w = nullptr;
-  int32_t rc = rhip_ensure_work(ctx, 4, total_rows * 2 * sizeof(rhip_fr), &w);
+  int32_t rc = rhip_ensure_work(ctx, WORK_SUM_TERMS, total_rows * 2 * sizeof(rhip_fr), &w);
   if (rc) return rc;
   rhip_fr* lam = (rhip_fr*)w;
   rhip_fr* omg = lam + total_rows;
@@ -2055,23 +2032,20 @@ static int32_t aw11_decrypt_body(rhip_ctx* ctx, size_t n_items, size_t max_pairs
   int32_t rc = alloc_pair_lists(ctx, total_pairs, &pl);
   if (rc) return rc;
   const size_t total_terms = total_pairs - n_items;
-  uint32_t L, C;
-  choose_msm_chunks(ctx, n_items, max_pairs - 1, &L, &C);
-  // arena 4: [C3 terms (G2M)][C1 terms (GtM)][lead (rhip_gt per item)];  5: masks;  6: [G2 partials][Gt partials];  7: term offsets
-  void *w4 = nullptr, *w_masks = nullptr, *w6 = nullptr, *w_off = nullptr;
+  // terms: [C3 terms (G2M)][C1 terms (GtM)][lead (rhip_gt per item)];  parts: [G2 partials][Gt partials] -- the Gt product shares the sum's
+  // masks, offsets and (L, C).  n_sel != 0 (checked above); the term count is guarded: every selection may be empty.
   const size_t nt = total_terms ? total_terms : 1;
-  rc = rhip_ensure_work(ctx, 4, nt * (sizeof(G2M) + sizeof(GtM)) + n_items * sizeof(rhip_gt), &w4);
-  if (!rc) rc = rhip_ensure_work(ctx, 5, n_sel * 16 * sizeof(uint32_t), &w_masks);
-  if (!rc) rc = rhip_ensure_work(ctx, 6, n_items * L * (sizeof(G2JM) + sizeof(GtM)), &w6);
-  if (!rc) rc = rhip_ensure_work(ctx, 7, (n_items + 1) * sizeof(uint32_t), &w_off);
-  if (rc) return rc;
-  G2M* t_c3 = (G2M*)w4;
+  SumStage sum{ctx, n_items};
+  RC_TRY(sum.prepare(max_pairs - 1, nt * (sizeof(G2M) + sizeof(GtM)) + n_items * sizeof(rhip_gt), n_sel, sizeof(G2JM) + sizeof(GtM), true));
+  const uint32_t L = sum.L, C = sum.C;
+  const uint32_t* w_off = (const uint32_t*)sum.off;
+  G2M* t_c3 = (G2M*)sum.terms;
   GtM* t_c1 = (GtM*)(t_c3 + nt);
   rhip_gt* lead = (rhip_gt*)(t_c1 + nt);
-  G2JM* p_g2 = (G2JM*)w6;
+  G2JM* p_g2 = (G2JM*)sum.parts;
   GtM* p_gt = (GtM*)(p_g2 + n_items * L);
-  KLAUNCH(ctx, "k_naf_masks", k_naf_masks, dim3(blocks_for(n_sel, 256)), dim3(256), 0, ctx->stream, n_sel, sel_coeff, (uint32_t*)w_masks);
-  KLAUNCH(ctx, "k_term_off", k_term_off, dim3(blocks_for(n_items + 1, 256)), dim3(256), 0, ctx->stream, n_items, pair_off, (uint32_t*)w_off);
+  RC_TRY(sum.naf_masks(n_sel, sel_coeff));
+  RC_TRY(sum.term_offsets(pair_off, 1));          // the pair with H(gid) is no term
   const uint32_t ppi = uniform_ppi(n_items, max_pairs, total_pairs);
   size_t g_lanes = 0;
   const uint32_t* tile_off = nullptr;
@@ -2081,18 +2055,17 @@ static int32_t aw11_decrypt_body(rhip_ctx* ctx, size_t n_items, size_t max_pairs
           pl.qref);
   if (total_terms)
     KLAUNCH(ctx, "k_aw11_gather_terms", k_aw11_gather_terms, dim3(blocks_for(total_terms, 64)), dim3(64), 0, ctx->stream, n_items, total_terms,
-            (const uint32_t*)w_off, sel_start, sel_ct_row, ct_row_off, ct_c1, ct_c3, t_c3, t_c1);
-  KLAUNCH(ctx, "k_msm_partial_g2", (k_msm_partial<Fp2, G2M, G2JM>), dim3(blocks_for(n_items * L, 64)), dim3(64), 0, ctx->stream, n_items, L, C,
-          (const uint32_t*)w_off, sel_start, (const G2M*)t_c3, (const uint32_t*)w_masks, 0, p_g2);
+            w_off, sel_start, sel_ct_row, ct_row_off, ct_c1, ct_c3, t_c3, t_c1);
+  RC_TRY((sum.partial<Fp2, G2M, G2JM>("k_msm_partial_g2", w_off, sel_start, 0)));          // instantiated here, where the parent launched it: the code object keeps its order
   KLAUNCH(ctx, "k_msm_finish_g2", k_msm_finish_g2, dim3(blocks_for(n_items, 128)), dim3(128), 0, ctx->stream, n_items, L, (const G2JM*)p_g2, pair_off,
           pl.Q, pl.qref);
   if (lead_w4) {
-    rc = rhip_gt_mexp4_run(ctx, n_items, max_pairs - 1, total_terms, (const uint32_t*)w_off, nullptr, (const GtM*)t_c1, n_sel, sel_coeff, sel_start, ct_c0,
+    rc = rhip_gt_mexp4_run(ctx, n_items, max_pairs - 1, total_terms, w_off, nullptr, (const GtM*)t_c1, n_sel, sel_coeff, sel_start, ct_c0,
                            RHIP_GT_POW_INVERT, 0, lead);
     if (rc) return rc;
   } else {
     KLAUNCH(ctx, "k_gt_multiexp_partial", k_gt_multiexp_partial, dim3(blocks_for(n_items * L, 64)), dim3(64), 0, ctx->stream, n_items, L, C,
-            (const uint32_t*)w_off, sel_start, (const GtM*)t_c1, (const uint32_t*)w_masks, 1, p_gt);
+            w_off, sel_start, (const GtM*)t_c1, (const uint32_t*)sum.masks, 1, p_gt);
     KLAUNCH(ctx, "k_gt_lead", k_gt_lead, dim3(blocks_for(n_items, 64)), dim3(64), 0, ctx->stream, n_items, L, ct_c0, (const GtM*)p_gt, lead);
   }
   return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, (const LineM*)nullptr, (const void*)nullptr, (const rhip_gt*)lead, out);
@@ -2285,7 +2258,7 @@ extern "C" int32_t rhip_dnf_encrypt_batch(rhip_ctx* ctx, const rhip_dnf_pk* pk, 
     size_t total = 0;
     for (size_t s = 0; s < n_sets; s++) total += sets[s]->n_terms;
     void* w = nullptr;
-    const int32_t rc = rhip_ensure_work(ctx, 15, total * stride * sizeof(void*), &w);
+    const int32_t rc = rhip_ensure_work(ctx, WORK_DNF_TABLES, total * stride * sizeof(void*), &w);
     if (rc) return rc;
     size_t at = 0;
     for (size_t s = 0; s < n_sets; s++) {
@@ -2492,28 +2465,25 @@ extern "C" int32_t rhip_pairing_jobs(rhip_ctx* ctx, size_t n_items, size_t max_p
   PairLists pl;
   int32_t rc = alloc_pair_lists(ctx, total, &pl);
   if (rc) return rc;
-  void *w_terms = nullptr, *w_masks = nullptr, *w_part = nullptr, *w_off = nullptr;
-  uint32_t L = 1, C = 1;
-  if (with_sum) choose_msm_chunks(ctx, n_items, max_terms ? max_terms : 1, &L, &C);
-  rc = rhip_ensure_work(ctx, 7, (n_items + 1) * sizeof(uint32_t), &w_off);
-  if (!rc && with_sum) rc = rhip_ensure_work(ctx, 4, (n_terms ? n_terms : 1) * sizeof(G1M), &w_terms);
-  if (!rc && with_sum) rc = rhip_ensure_work(ctx, 5, (n_terms ? n_terms : 1) * 16 * sizeof(uint32_t), &w_masks);
-  if (!rc && with_sum) rc = rhip_ensure_work(ctx, 6, n_items * L * sizeof(G1JM), &w_part);
+  // the combined pair offsets live in the sum's offsets arena and are asked for first; the sum's own offsets are the caller's sum_off.
+  // One mask per term; an empty sum list is served: both sizes are guarded, masks and bases are not launched.
+  void* w_off = nullptr;
+  rc = rhip_ensure_work(ctx, WORK_SUM_OFF, (n_items + 1) * sizeof(uint32_t), &w_off);
   if (rc) return rc;
+  SumStage sum{ctx, n_items};
+  if (with_sum) RC_TRY(sum.prepare(max_terms ? max_terms : 1, (n_terms ? n_terms : 1) * sizeof(G1M), n_terms ? n_terms : 1, sizeof(G1JM), false));
   uint32_t* cpo = (uint32_t*)w_off;
   KLAUNCH(ctx, "k_cpair_off", k_cpair_off, dim3(blocks_for(n_items + 1, 256)), dim3(256), 0, ctx->stream, n_items, pair_off, with_sum ? 1 : 0, cpo);
   KLAUNCH(ctx, "k_jobs_pairs", k_jobs_pairs, dim3(blocks_for(total, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items, total,
           (const uint32_t*)cpo, pair_off, base, scal, q, s_q, pl.P, pl.Q, pl.qref);
   if (with_sum) {
     if (n_terms) {
-      KLAUNCH(ctx, "k_naf_masks", k_naf_masks, dim3(blocks_for(n_terms, 256)), dim3(256), 0, ctx->stream, n_terms, s_scal, (uint32_t*)w_masks);
-      KLAUNCH(ctx, "k_g1_to_mont", k_g1_to_mont, dim3(blocks_for(n_terms, 256)), dim3(256), 0, ctx->stream, n_terms, s_base, (G1M*)w_terms);
+      RC_TRY(sum.naf_masks(n_terms, s_scal));
+      KLAUNCH(ctx, "k_g1_to_mont", k_g1_to_mont, dim3(blocks_for(n_terms, 256)), dim3(256), 0, ctx->stream, n_terms, s_base, (G1M*)sum.terms);
     }
-    // every item's terms start at sum_off[i] in the term arrays AND in the mask array (one mask per term)
-    KLAUNCH(ctx, "k_msm_partial_g1", (k_msm_partial<Fp, G1M, G1JM>), dim3(blocks_for(n_items * L, 64)), dim3(64), 0, ctx->stream, n_items, L, C,
-            sum_off, sum_off, (const G1M*)w_terms, (const uint32_t*)w_masks, 0, (G1JM*)w_part);
-    KLAUNCH(ctx, "k_msm_finish_g1", k_msm_finish_g1, dim3(blocks_for(n_items, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items, L,
-            (const G1JM*)w_part, (const uint32_t*)cpo, pl.P, pl.qref);
+    // every item's terms start at sum_off[i] in the term arrays AND in the mask array (one mask per term); the masks as they are
+    RC_TRY(sum.partial_g1(sum_off, sum_off, 0));
+    RC_TRY(sum.finish_g1((const uint32_t*)cpo, pl));
   }
   return run_pair_lists(ctx, n_items, (const uint32_t*)cpo, max_pairs + (with_sum ? 1 : 0), total, pl, (const LineM*)nullptr, (const void*)nullptr, lead, out);
 }

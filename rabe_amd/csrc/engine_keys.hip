@@ -272,7 +272,7 @@ extern "C" int32_t rhip_ghw11_provision_batch(rhip_ctx* ctx, rhip_ghw11_keys* ke
   // z^-1 | r z^-1 per item: the per-item slot of rhip_g2_mul_rows (both are scratch of key issuing, in stream order on this context),
   // zeroed behind the row kernel -- the pair is the retrieve key and the key's r in another form
   void* work = nullptr;
-  const int32_t rc = rhip_ensure_work(ctx, 16, 2 * n_items * sizeof(rhip_fr), &work);
+  const int32_t rc = rhip_ensure_work(ctx, WORK_ROWS_MASKS, 2 * n_items * sizeof(rhip_fr), &work);
   if (rc) return rc;
   rhip_fr* zinv = (rhip_fr*)work;
   rhip_fr* rz = zinv + n_items;
@@ -331,10 +331,10 @@ extern "C" int32_t rhip_g2_mul_rows(rhip_ctx* ctx, size_t n_rows, const uint32_t
   if (!n_items || !item_row_off || !p || !k || !out) return RHIP_ERR_ARG;
   void* masks = nullptr;
   void* img = nullptr;
-  int32_t rc = rhip_ensure_work(ctx, 16, n_items * 24 * sizeof(uint32_t), &masks);
+  int32_t rc = rhip_ensure_work(ctx, WORK_ROWS_MASKS, n_items * 24 * sizeof(uint32_t), &masks);
   if (rc) return rc;
   const size_t stride = ((n_rows < RB_G2_ROWS_CHUNK ? n_rows : RB_G2_ROWS_CHUNK) + 127) / 128 * 128;
-  rc = rhip_ensure_work(ctx, 17, stride * 4 * sizeof(G2M), &img);
+  rc = rhip_ensure_work(ctx, WORK_ROWS_IMAGES, stride * 4 * sizeof(G2M), &img);
   if (rc) return rc;
   KLAUNCH(ctx, "k_gls4_masks", k_gls4_masks, dim3(blocks_for(n_items, 256)), dim3(256), 0, ctx->stream, n_items, k, (uint32_t*)masks);
   for (size_t row0 = 0; row0 < n_rows; row0 += RB_G2_ROWS_CHUNK) {
@@ -395,10 +395,10 @@ extern "C" int32_t rhip_g2_mul_rows_at(rhip_ctx* ctx, size_t n_rows, const uint3
   if (!n_items || !item_row_off || !p || !row_src || !k || !row_dst || !out) return RHIP_ERR_ARG;
   void* masks = nullptr;
   void* img = nullptr;
-  int32_t rc = rhip_ensure_work(ctx, 16, n_items * 24 * sizeof(uint32_t), &masks);
+  int32_t rc = rhip_ensure_work(ctx, WORK_ROWS_MASKS, n_items * 24 * sizeof(uint32_t), &masks);
   if (rc) return rc;
   const size_t stride = ((n_rows < RB_G2_ROWS_CHUNK ? n_rows : RB_G2_ROWS_CHUNK) + 127) / 128 * 128;
-  rc = rhip_ensure_work(ctx, 17, stride * 4 * sizeof(G2M), &img);
+  rc = rhip_ensure_work(ctx, WORK_ROWS_IMAGES, stride * 4 * sizeof(G2M), &img);
   if (rc) return rc;
   KLAUNCH(ctx, "k_gls4_masks", k_gls4_masks, dim3(blocks_for(n_items, 256)), dim3(256), 0, ctx->stream, n_items, k, (uint32_t*)masks);
   for (size_t row0 = 0; row0 < n_rows; row0 += RB_G2_ROWS_CHUNK) {
@@ -480,7 +480,7 @@ __global__ void __launch_bounds__(256, RB_G1_WAVES) k_g1_mul_rows(size_t n_rows,
 static int32_t g1_mul_rows(rhip_ctx* ctx, size_t n_rows, const uint32_t* item_row_off, const rhip_g1* p, const uint32_t* row_src, size_t n_items,
                            const rhip_fr* k, const uint32_t* row_dst, rhip_g1* out) {
   void* masks = nullptr;
-  const int32_t rc = rhip_ensure_work(ctx, 18, n_items * RB_GLV_MASK_WORDS * sizeof(uint32_t), &masks);
+  const int32_t rc = rhip_ensure_work(ctx, WORK_G1_ROWS_MASKS, n_items * RB_GLV_MASK_WORDS * sizeof(uint32_t), &masks);
   if (rc) return rc;
   KLAUNCH(ctx, "k_glv_masks", k_glv_masks, dim3(blocks_for(n_items, 256)), dim3(256), 0, ctx->stream, n_items, k, (uint32_t*)masks);
   KLAUNCH(ctx, "k_g1_mul_rows", k_g1_mul_rows, dim3(blocks_for(n_rows, 256)), dim3(256), 0, ctx->stream, n_rows, n_items, item_row_off, p, row_src,

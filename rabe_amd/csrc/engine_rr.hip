@@ -518,7 +518,7 @@ int32_t rhip_launch_miller_rr(rhip_ctx* ctx, size_t n_items, uint32_t L, uint32_
     return RHIP_ERR_ARG;
   }
   void* ws29 = nullptr;
-  const int32_t rc = rhip_ensure_work(ctx, 11, ws_bytes / 12 * RR_SLOT_QUADS, &ws29);
+  const int32_t rc = rhip_ensure_work(ctx, WORK_RR_WS, ws_bytes / 12 * RR_SLOT_QUADS, &ws29);
   if (rc) return rc;
   KLAUNCH(ctx, "k_miller_multi_rr", k_miller_multi_rr, dim3(blocks_for(lanes, RB_MILLER_BLOCK)), dim3(RB_MILLER_BLOCK), 0, ctx->stream, n_items, L, C, pair_off, uniform,
           (const G1M*)P, (const G2M*)Q, qref, (const uint4*)lines29, (uint4*)ws, (uint4*)ws29, (GtM*)mill, plan, (const uint2*)work, chunk_off, started);
