@@ -7,6 +7,7 @@
 #include <set>
 #include <atomic>
 #include <array>
+#include <chrono>
 #include <functional>
 #include <map>
 #include <memory>
@@ -14,17 +15,15 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include <stdio.h>
+#include <stdlib.h>
 
 #include "../../../include/rabe_hip.h"
 #include "aes_gcm.h"
+#include "bytes.h"
 #include "policy.h"
 
 namespace rabe {
-
-// src/error.rs:19-28
-struct RabeError : std::runtime_error {
-  explicit RabeError(const std::string& details) : std::runtime_error(details) {}
-};
 
 typedef std::vector<uint8_t> Bytes;
 typedef std::array<uint8_t, 64> G1;
@@ -49,6 +48,20 @@ inline G2 g2_generator() {
   memcpy(g.data(), L, 128);
   return g;
 }
+
+// RABE_HOST_TIMING=1: stage timings of the batch entry points on stderr (development aid)
+struct StageTimer {
+  bool on;
+  const char* what;
+  std::chrono::steady_clock::time_point t0;
+  explicit StageTimer(const char* w) : on(getenv("RABE_HOST_TIMING") != nullptr), what(w), t0(std::chrono::steady_clock::now()) {}
+  void lap(const char* stage) {
+    if (!on) return;
+    auto t1 = std::chrono::steady_clock::now();
+    fprintf(stderr, "[host-timing] %s: %s %.1f ms\n", what, stage, std::chrono::duration<double, std::milli>(t1 - t0).count());
+    t0 = t1;
+  }
+};
 
 // ---------------------------------------------------------------------------------------------- randomness
 // Stands where the reference uses rand::thread_rng() (ac17/mod.rs:143,201,281; bsw/mod.rs:227;

@@ -1,21 +1,24 @@
 // Packed batch entry points (include/rabe_host.h: rabe_*_packed): n independent calls of one of the reference's scheme functions with ONE blob
 // of canonical records + offsets on each side of the boundary, fed to the device-resident Level B paths (rhip_*_batch, include/rabe_hip.h)
-// instead of the per-object pairing jobs.  In file order: AC17 bulk keygen; BSW keygen / delegate / encrypt / decrypt; LSW encrypt / keygen /
-// decrypt (n keys, one ciphertext) / decrypt (n ciphertexts, one key); AW11 encrypt / keygen / decrypt; GHW11 encrypt / decrypt_out /
-// transform / decrypt / keygen / tkgen / provision; BDABE and MKE08 (one body, dnfabe) encrypt / keygen / secret attribute keys.  AC17's
-// packed encrypt, decrypt and KP keygen are in schemes.cpp.  The key-encapsulation forms (rabe_{ac17_cp,bsw}_{encaps,decaps}_packed) are a mode of
-// the encrypt / decrypt bodies: same caches, plans and launch sets, another ending.
+// instead of the per-object pairing jobs.  In file order: AC17 bulk keygen (CP, KP) / encrypt / decrypt (CP and KP: one body each); BSW keygen /
+// delegate / encrypt / decrypt; LSW encrypt / keygen / decrypt (n keys, one ciphertext) / decrypt (n ciphertexts, one key); AW11 encrypt /
+// keygen / decrypt; GHW11 encrypt / decrypt_out / transform / decrypt / keygen / tkgen / provision; BDABE and MKE08 (one body, dnfabe) encrypt /
+// keygen / secret attribute keys.  The key-encapsulation forms (rabe_{ac17_cp,ac17_kp,bsw,...}_{encaps,decaps}_packed) are a mode of the encrypt /
+// decrypt bodies: same caches, plans and launch sets, another ending.
 // What stays on the host is what the reference does with strings and bytes: policy parsing, flattening the tree into the index tables the
 // share kernels walk, traverse / calc_pruned / calc_coefficients per distinct policy, the selection tables, record layouts.  Records are the
 // byte form rabe_obj_serialize gives the corresponding struct (host_abi.cpp), so packed and object APIs interoperate.
-// The six "many records under one key" decrypts (bsw, lsw x 2, aw11, ghw11 transform and decrypt) are top-to-bottom functions -- parse body,
-// plan body, buffers, launch, messages -- over the helpers of the anonymous namespace below: PlanCache, for_each_record, Selection,
-// WalkScope, gather_record.  The issuers size their output with record_offsets (records.h), and the four that walk share trees (bsw / ghw11 /
-// aw11 encrypt, lsw keygen) keep them in a ShareTrees.
+// The seven "many records under one key" decrypts (ac17, bsw, lsw x 2, aw11, ghw11 transform and decrypt) are top-to-bottom functions -- bounds,
+// parse + plan, lists, shapes, buffers, checks, launch, verdicts -- over check_offsets / Cursor / same (ac17_record.h, with AC17's record reader)
+// and the helpers of the anonymous namespace below: PlanCache, for_each_record, Selection, WalkScope, gather_record.  AC17 differs in two
+// places: its plans are kept ACROSS calls (Ac17PlanCache: a PlanCache per key fingerprint), and its selection is two plain index lists copied
+// on all cores instead of a Selection.  The issuers size their output with record_offsets (records.h), and the four that walk share trees (bsw /
+// ghw11 / aw11 encrypt, lsw keygen) keep them in a ShareTrees.
 #include "schemes.h"
 #include "records.h"
+#include "ac17_record.h"
 
-#include <chrono>
+#include <algorithm>
 #include <functional>
 #include <mutex>
 #include <shared_mutex>
@@ -31,22 +34,6 @@ void parallel_for(size_t n, const std::function<void(size_t)>& fn);             
 
 namespace schemes {
 namespace {
-
-inline void put_u32(uint8_t* p, uint32_t v) { for (int i = 0; i < 4; i++) p[i] = (uint8_t)(v >> (8 * i)); }
-inline uint32_t get_u32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-
-struct Timer {
-  bool on;
-  const char* what;
-  std::chrono::steady_clock::time_point t0;
-  explicit Timer(const char* w) : on(getenv("RABE_HOST_TIMING") != nullptr), what(w), t0(std::chrono::steady_clock::now()) {}
-  void lap(const char* stage) {
-    if (!on) return;
-    auto t1 = std::chrono::steady_clock::now();
-    fprintf(stderr, "[host-timing] %s: %s %.1f ms\n", what, stage, std::chrono::duration<double, std::milli>(t1 - t0).count());
-    t0 = t1;
-  }
-};
 
 // A policy text as the device-level paths want it (include/rabe_hip.h, "Flattened policy trees"): leaves in DFS order -- the order
 // gen_shares_policy emits shares (src/utils/secretsharing/mod.rs:82-122) -- each with its root-to-leaf path of (gate, 1-based child
@@ -175,25 +162,6 @@ struct ShareTrees {
 template <class DRAW>
 void draw_items(Rng& rng, size_t n, DRAW draw) { rabe::draw_items(rng, n, 256, 16, draw); }
 
-// bounds of the records of an untrusted blob: monotone, inside [0, len); span = total size of the well-formed ones
-uint64_t check_offsets(size_t n, const uint64_t* off, size_t len, std::vector<std::string>* errors) {
-  uint64_t span = 0;
-  for (size_t i = 0; i < n; i++) {
-    if (off[i] > off[i + 1] || off[i + 1] > len) (*errors)[i] = "deserialize: record offsets are not monotone inside the blob";
-    else span += off[i + 1] - off[i];
-  }
-  return span;
-}
-struct Cursor {
-  const uint8_t* p;
-  const uint8_t* end;
-  void need(size_t k) const { if ((size_t)(end - p) < k) throw RabeError("deserialize: truncated input"); }
-  uint32_t u32() { need(4); uint32_t v = get_u32(p); p += 4; return v; }
-  const uint8_t* raw(size_t k) { need(k); const uint8_t* q = p; p += k; return q; }
-  std::pair<const char*, uint32_t> str() { uint32_t l = u32(); return {(const char*)raw(l), l}; }
-};
-inline bool same(const std::pair<const char*, uint32_t>& a, const std::string& b) { return a.second == b.size() && memcmp(a.first, b.data(), b.size()) == 0; }
-
 // The plans of one call by (language, key text), looked up WITHOUT copying the text and without serialising the readers: every item of a
 // batch asks for its policy's plan, the texts are kilobytes (a 200-leaf policy: ~10 KB), and a mutex around a std::map of strings made the
 // parse stage of a 4096-item call 8 ms long.  A miss runs `make(plan, text, lang)` under plans_mu -- once per distinct key, so no plan is
@@ -217,15 +185,28 @@ class PlanCache {
     }
     std::unique_lock<std::shared_mutex> w(mu_);
     tab_[h].push_back(Entry{std::move(text), lang, pl});
+    n_++;
     return pl;
   }
+  // the same for a caller that keeps the cache itself alive for as long as it uses the plans (a cache kept across calls): a plain pointer,
+  // no reference count that every thread of the parse stage would touch once per record
+  template <class MAKE>
+  Plan* get_kept(const char* txt, size_t len, PolicyLanguage lang, MAKE make) {
+    { std::shared_lock<std::shared_mutex> g(mu_); if (const auto* hit = at(hash(txt, len, lang), txt, len, lang)) return hit->get(); }
+    return get(txt, len, lang, make).get();
+  }
+  size_t size() const { return n_.load(); }          // plans made so far (a cache kept across calls is bounded by it)
  private:
   struct Entry { std::string text; PolicyLanguage lang; std::shared_ptr<Plan> plan; };
   std::shared_ptr<Plan> find(uint64_t h, const char* txt, size_t len, PolicyLanguage lang) {
     std::shared_lock<std::shared_mutex> g(mu_);
+    const auto* hit = at(h, txt, len, lang);
+    return hit ? *hit : nullptr;
+  }
+  const std::shared_ptr<Plan>* at(uint64_t h, const char* txt, size_t len, PolicyLanguage lang) const {          // under mu_
     auto it = tab_.find(h);
     if (it != tab_.end())
-      for (const auto& e : it->second) if (e.lang == lang && e.text.size() == len && memcmp(e.text.data(), txt, len) == 0) return e.plan;
+      for (const auto& e : it->second) if (e.lang == lang && e.text.size() == len && memcmp(e.text.data(), txt, len) == 0) return &e.plan;
     return nullptr;
   }
   static uint64_t hash(const char* txt, size_t len, PolicyLanguage lang) {
@@ -237,6 +218,7 @@ class PlanCache {
   std::mutex plans_mu;          // the makers, one at a time
   std::shared_mutex mu_;
   std::unordered_map<uint64_t, std::vector<Entry>> tab_;
+  std::atomic<size_t> n_{0};
 };
 
 // fn(i) for every record that has no error yet, on the host's cores; what it throws is that record's error
@@ -419,7 +401,7 @@ void msk_tables(Engine& eng, const Ac17MasterKey& msk, rhip_g1_table** g, rhip_g
 // Level B kernels (the label hashes of a list are computed once); the window tables of the master key's g and h are kept across calls.
 bool cp_keygen_packed(Engine& eng, Rng& rng, const Ac17MasterKey& msk, const std::vector<std::vector<std::string>>& sets, size_t n,
                       const uint32_t* item_set, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  Timer tm("ac17::cp_keygen_packed");
+  StageTimer tm("ac17::cp_keygen_packed");
   Engine::ArenaScope arena(eng);
   eng.scrub_when_done();          // master-key-derived scalars pass through the staging buffers
   if (msk.a.size() != 2 || msk.b.size() != 2 || msk.g_k.size() != 3) throw RabeError("malformed Ac17MasterKey: a, b must have 2 and g_k 3 elements");
@@ -529,6 +511,552 @@ bool cp_keygen_packed(Engine& eng, Rng& rng, const Ac17MasterKey& msk, const std
   tm.lap("assembly");
   return true;
 }
+
+// n calls of ac17::kp_keygen (:439-547) under one master key: item i's policy = policies[item_policy[i]].  Draw order per item as above.
+// The Fr half runs on all host cores; the group half is ONE fixed-base launch per group (window tables of msk.g / msk.h, kept across
+// calls), one batched addition for the rows whose first MSP column is +/-1 (+/- g_k), and the records are written on the device.
+// Record = Ac17KpSecretKey: policy text, language, k_0 (3 G2), rows (name, 3 G1), an empty k_p.  Buffers as cp_keygen_packed.
+bool kp_keygen_packed(Engine& eng, Rng& rng, const Ac17MasterKey& msk, const std::vector<std::string>& policies, PolicyLanguage lang, size_t n,
+                      const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  StageTimer tm("ac17::kp_keygen_packed");
+  Engine::ArenaScope arena(eng);
+  eng.scrub_when_done();          // master-key-derived scalars pass through the staging buffers
+  if (msk.a.size() != 2 || msk.b.size() != 2 || msk.g_k.size() != 3) throw RabeError("malformed Ac17MasterKey: a, b must have 2 and g_k 3 elements");
+  if (n && (!item_policy || !out_off)) throw RabeError("kp_keygen_packed: null input");
+  std::vector<KpPolicy> kps;
+  std::vector<RecordLayout> layouts(policies.size());
+  for (size_t p_ = 0; p_ < policies.size(); p_++) {
+    kps.push_back(kp_policy(policies[p_], lang));
+    RecordLayout& L = layouts[p_];
+    const AbePolicy& msp = kps.back().msp;
+    policy_header(L, policies[p_], lang);
+    L.u32(3);
+    L.src(0, 0, 384);
+    L.u32((uint32_t)msp.m.size());
+    for (size_t r = 0; r < msp.m.size(); r++) { L.str(msp.pi[r]); L.u32(3); L.src(1, (uint32_t)(192 * r), 192); }
+    L.u32(0);                                   // k_p: empty for a KP key
+  }
+  if (!record_offsets("kp_keygen_packed", "item_policy", n, item_policy, policies.size(), [&](size_t i) { return layouts[item_policy[i]].bytes(); }, nullptr,
+                      out_buf, out_cap, out_off)) return false;
+  if (!n) return true;
+  std::vector<uint32_t> row_off(n + 1, 0), draw_off(n + 1, 0);
+  for (size_t i = 0; i < n; i++) {
+    const AbePolicy& msp = kps[item_policy[i]].msp;
+    row_off[i + 1] = row_off[i] + (uint32_t)msp.m.size();
+    draw_off[i + 1] = draw_off[i] + 2 + (uint32_t)(msp.m[0].size() - 1) + (uint32_t)msp.m.size();
+  }
+  const size_t total_rows = row_off[n];
+  std::vector<Fr> draws(draw_off[n] + 1);
+  draw_items(rng, n, 1024, 256, [&](Rng& r, size_t i) { for (uint32_t d = draw_off[i]; d < draw_off[i + 1]; d++) draws[d] = r.next_fr(); });
+  tm.lap("policies + draws");
+  Fr a_inv[2] = {must_inv(msk.a[0]), must_inv(msk.a[1])};
+  uint8_t* h_scal = eng.pinned(0, total_rows * 96 + n * 96 + 32);          // row scalars | br
+  uint8_t* h_br = h_scal + total_rows * 96;
+  uint8_t* h_add = eng.pinned(1, total_rows * 192 + 4);                     // +/- g_k[t] per row element, the point at infinity where nothing is added
+  G1 neg_gk[3];
+  {
+    std::vector<G1> ng = eng.g1_mul(msk.g_k, std::vector<Fr>(3, fr_neg(fr_one())));
+    for (int t = 0; t < 3; t++) neg_gk[t] = ng[t];
+  }
+  parallel_for(n, [&](size_t i) {
+    const KpPolicy& kp = kps[item_policy[i]];
+    const size_t cols = kp.msp.m[0].size(), rows = kp.msp.m.size();
+    const Fr* d = draws.data() + draw_off[i];
+    std::vector<Fr> scal(3 * rows);
+    Fr br[3];
+    kp_keygen_scalars(msk, kp, a_inv, d[0], d[1], d + 2, d + 2 + (cols - 1), scal.data(), br);
+    memcpy(h_scal + 96 * (size_t)row_off[i], scal.data(), 96 * rows);
+    memcpy(h_br + 96 * i, br, 96);
+    uint8_t* ad = h_add + 192 * (size_t)row_off[i];
+    for (size_t r = 0; r < rows; r++)
+      for (int t = 0; t < 3; t++) {
+        const int8_t c = kp.msp.m[r][0];
+        if (c == 0) memset(ad + 192 * r + 64 * t, 0, 64);
+        else memcpy(ad + 192 * r + 64 * t, (c == 1 ? msk.g_k[t] : neg_gk[t]).data(), 64);
+      }
+  });
+  tm.lap("scalars");
+  rhip_g1_table* gt = nullptr;
+  rhip_g2_table* ht = nullptr;
+  msk_tables(eng, msk, &gt, &ht);
+  rhip_ctx* cx = eng.ctx();
+  DBuf d_scal(&eng, total_rows * 96 + n * 96), d_add(&eng, total_rows * 192 + 4), d_pts(&eng, total_rows * 192 + 4), d_k(&eng, total_rows * 192 + 4),
+      d_k0(&eng, n * 384);
+  eng.check(rhip_upload_async(cx, d_scal.ptr(), h_scal, total_rows * 96 + n * 96), "upload");
+  eng.check(rhip_upload_async(cx, d_add.ptr(), h_add, total_rows * 192), "upload");
+  eng.check(rhip_g1_table_mul(cx, gt, 3 * total_rows, d_scal.as<rhip_fr>(), d_pts.as<rhip_g1>()), "rhip_g1_table_mul");
+  eng.check(rhip_g1_add(cx, 3 * total_rows, d_pts.as<rhip_g1>(), d_add.as<rhip_g1>(), d_k.as<rhip_g1>()), "rhip_g1_add");
+  eng.check(rhip_g2_table_mul(cx, ht, 3 * n, (const rhip_fr*)(d_scal.as<uint8_t>() + total_rows * 96), d_k0.as<rhip_g2>()), "rhip_g2_table_mul");
+  std::vector<uint64_t> src_off(2 * n);
+  for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * i; src_off[n + i] = 192ull * row_off[i]; }
+  emit_plain_records(eng, layouts, n, item_policy, {d_k0.ptr(), d_k.ptr()}, src_off, out_off, out_buf);
+  tm.lap("device: fixed-base multiplications, records; one copy out");
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------- packed batches
+// The same two functions with packed input and output (no per-item objects on either side of the C ABI): n ciphertexts are
+// one blob of canonical records (the byte form of rabe_obj_serialize for Ac17CpCiphertext) with an offset array.  Everything
+// per item that is not group arithmetic -- record assembly, KDF, AES-GCM, parsing, pruning -- runs on all host cores; the
+// group arithmetic is one launch set; PCIe copies go through pinned staging buffers.
+// parse + MSP + Fr table of a policy text, cached across calls (a server encrypts under the same few policies again and again)
+struct EncPolicy { AbePolicy msp; std::vector<Fr> tab; size_t fixed_bytes; };
+static std::shared_ptr<const EncPolicy> enc_policy(const std::string& pol, PolicyLanguage language) {
+  static std::mutex mu;
+  static std::map<std::pair<int, std::string>, std::shared_ptr<const EncPolicy>> cache;
+  const auto key = std::make_pair((int)language, pol);
+  {
+    std::lock_guard<std::mutex> g(mu);
+    auto it = cache.find(key);
+    if (it != cache.end()) return it->second;
+  }
+  auto e = std::make_shared<EncPolicy>();
+  e->msp = calculate_msp(parse_or_error(pol, language));
+  e->tab = policy_table(e->msp);
+  e->fixed_bytes = 4 + pol.size() + 1 + 4 + 3 * 128 + 4 + 384 + 4;      // record size without the sealed plaintext
+  for (const auto& name : e->msp.pi) e->fixed_bytes += 4 + name.size() + 4 + 3 * 64;
+  std::lock_guard<std::mutex> g(mu);
+  if (cache.size() >= 1024) cache.clear();
+  cache[key] = e;
+  return e;
+}
+// out_buf / out_cap: caller-allocated (reusable) output; out_off: n + 1 caller-allocated entries, always filled.  Returns false
+// -- before any randomness is drawn or work is done -- when out_cap < out_off[n], the size the records need.
+// KP-ABE's encrypt (:556-616) is the same arithmetic with a table of plain label hashes: rows = the attribute list, no MSP columns.  The
+// record differs only in its head (the attribute strings instead of policy text + language).
+static std::shared_ptr<const EncPolicy> enc_attr_set(const std::vector<std::string>& attrs) {
+  auto e = std::make_shared<EncPolicy>();
+  e->msp.pi = attrs;
+  e->msp.m.assign(attrs.size(), std::vector<int8_t>{0});
+  for (const auto& a : attrs)
+    for (int l = 0; l < 3; l++)
+      for (int t = 0; t < 2; t++) e->tab.push_back(sha3_hash_fr(a + std::to_string(l) + std::to_string(t)));
+  e->fixed_bytes = 4 + 4 + 3 * 128 + 4 + 384 + 4;
+  for (const auto& a : attrs) e->fixed_bytes += (4 + a.size()) + (4 + a.size() + 4 + 3 * 64);
+  return e;
+}
+static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::shared_ptr<const EncPolicy>>& pols,
+                                const std::vector<std::string>* policies /* CP: the texts; KP: nullptr */, PolicyLanguage language, size_t n,
+                                const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off,
+                                uint8_t* key_buf = nullptr /* encaps: no plaintexts, no sealing; 32 bytes of content key per item */);
+bool cp_encrypt_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                       const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  std::vector<std::shared_ptr<const EncPolicy>> pols;
+  for (const auto& pol : policies) pols.push_back(enc_policy(pol, language));
+  return encrypt_packed_core(eng, rng, pk, pols, &policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off);
+}
+// Key encapsulation (include/rabe_host.h: rabe_ac17_cp_encaps_packed): cp_encrypt_packed's records with a sealed part of length zero and,
+// per item, the content key SHA3-256(bytes(msg)) instead of a payload sealed under it.  Draws: cp_encrypt_packed's without the nonce.
+bool cp_encaps_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
+                      const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  if (n && !key_buf) throw RabeError("cp_encaps_packed: null input");
+  if (!n) { out_off[0] = 0; return true; }
+  std::vector<std::shared_ptr<const EncPolicy>> pols;
+  for (const auto& pol : policies) pols.push_back(enc_policy(pol, language));
+  return encrypt_packed_core(eng, rng, pk, pols, &policies, language, n, item_policy, nullptr, nullptr, out_buf, out_cap, out_off, key_buf);
+}
+// n calls of ac17::kp_encrypt: item i is encrypted under the attribute list sets[item_set[i]]; records = Ac17KpCiphertext
+bool kp_encrypt_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
+                       const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  std::vector<std::shared_ptr<const EncPolicy>> pols;
+  for (const auto& a : sets) pols.push_back(enc_attr_set(a));
+  return encrypt_packed_core(eng, rng, pk, pols, nullptr, PolicyLanguage::JsonPolicy, n, item_set, pt_blob, pt_off, out_buf, out_cap, out_off);
+}
+// Key encapsulation over the KP pair (include/rabe_host.h: rabe_ac17_kp_encaps_packed): kp_encrypt_packed's records with a sealed part of length
+// zero and the content keys, as cp_encaps_packed
+bool kp_encaps_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
+                      uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  if (n && !key_buf) throw RabeError("kp_encaps_packed: null input");
+  if (!n) { out_off[0] = 0; return true; }
+  std::vector<std::shared_ptr<const EncPolicy>> pols;
+  for (const auto& a : sets) pols.push_back(enc_attr_set(a));
+  return encrypt_packed_core(eng, rng, pk, pols, nullptr, PolicyLanguage::JsonPolicy, n, item_set, nullptr, nullptr, out_buf, out_cap, out_off, key_buf);
+}
+static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::shared_ptr<const EncPolicy>>& pols,
+                                const std::vector<std::string>* policies, PolicyLanguage language, size_t n,
+                                const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off,
+                                uint8_t* key_buf) {
+  const bool kem = key_buf != nullptr;
+  StageTimer tm(kem ? (policies ? "ac17::cp_encaps_packed" : "ac17::kp_encaps_packed") : policies ? "ac17::cp_encrypt_packed" : "ac17::kp_encrypt_packed");
+  Engine::ArenaScope arena(eng);
+  if (pk.h_a.size() != 3 || pk.e_gh_ka.size() != 2) throw RabeError("malformed Ac17PublicKey");
+  std::vector<uint32_t> a_off{0};
+  std::vector<Fr> A;
+  for (const auto& e : pols) {
+    A.insert(A.end(), e->tab.begin(), e->tab.end());
+    a_off.push_back(a_off.back() + (uint32_t)e->msp.m.size());
+  }
+  if (!record_offsets("encrypt_packed", "item_policy", n, item_policy, pols.size(), [&](size_t i) { return pols[item_policy[i]]->fixed_bytes; },
+                      kem ? nullptr : pt_off, out_buf, out_cap, out_off)) return false;
+  tm.lap("policies");
+  // randomness in the reference's per-call draw order: s0, s1, msg, nonce -- item after item (encaps: no nonce)
+  uint8_t* h_s = eng.pinned(0, n * (64 + 32));
+  uint8_t* h_rho = h_s + n * 64;
+  std::vector<std::array<uint8_t, 12>> nonces(n);
+  draw_items(rng, n, 1024, 256, [&](Rng& r, size_t i) {
+    Fr s0 = r.next_fr(), s1 = r.next_fr(), rho = r.next_fr();
+    memcpy(h_s + 64 * i, s0.l, 32);
+    memcpy(h_s + 64 * i + 32, s1.l, 32);
+    memcpy(h_rho + 32 * i, rho.l, 32);
+    if (!kem) r.fill(nonces[i].data(), 12);
+  });
+  std::vector<uint32_t> item_a_off(n), row_off(n + 1, 0);
+  for (size_t i = 0; i < n; i++) {
+    item_a_off[i] = a_off[item_policy[i]];
+    row_off[i + 1] = row_off[i] + (uint32_t)pols[item_policy[i]]->msp.m.size();
+  }
+  const size_t total_rows = row_off[n];
+  tm.lap("draws");
+  rhip_ac17_pk* dpk = eng.ac17_pk(pk.g, pk.h_a, pk.e_gh_ka);
+  rhip_gt_table* egt = eng.gt_generator_table();
+  auto fA = flatten_fr(A);
+  DBuf dA(&eng, fA.data(), fA.size()), dio(&eng, item_a_off.data(), n * 4), ds(&eng, n * 64), drho(&eng, n * 32),
+      dm(&eng, n * 384), dc0(&eng, n * 3 * 128), dc(&eng, total_rows * 3 * 64 + 4), dcp(&eng, n * 384);
+  rhip_ctx* cx = eng.ctx();
+  eng.check(rhip_upload_async(cx, ds.ptr(), h_s, n * 64), "upload");
+  eng.check(rhip_upload_async(cx, drho.ptr(), h_rho, n * 32), "upload");
+  // records and sealing on the device (records.h): per policy a template of the literal bytes with the elements dropped in
+  std::vector<RecordLayout> layouts(pols.size());
+  for (size_t p_ = 0; p_ < pols.size(); p_++) {
+    RecordLayout& L = layouts[p_];
+    const AbePolicy& msp = pols[p_]->msp;
+    if (policies) {                               // Ac17CpCiphertext: policy text + language
+      policy_header(L, (*policies)[p_], language);
+    } else {                                      // Ac17KpCiphertext: the attribute strings
+      L.u32((uint32_t)msp.pi.size());
+      for (const auto& a : msp.pi) L.str(a);
+    }
+    L.u32(3);
+    L.src(0, 0, 384);
+    L.u32((uint32_t)msp.m.size());
+    for (size_t r = 0; r < msp.m.size(); r++) {
+      L.str(msp.pi[r]);
+      L.u32(3);
+      L.src(1, (uint32_t)(192 * r), 192);
+    }
+    L.src(2, 0, 384);
+    if (L.bytes() + 4 != pols[p_]->fixed_bytes) throw RabeError("ac17 encrypt_packed: record layout and size disagree");
+    if (kem) L.u32(0);                            // encaps: the template ends in the length field of an empty sealed part, no sealed source
+  }
+  // The batch can go through the device in PARTS of >= 16 384 items, a part's records copied out (10.4 KB per item at 50 rows, 15 ms per
+  // 65 536 items) on the side stream while the next part's group arithmetic runs; randomness was drawn above for the whole batch, item
+  // after item, so the bytes do not depend on the cut (tests/test_gpu_packed.py).  OFF by default (RABE_AC17_ENC_PARTS=4 turns it on):
+  // measured no faster -- 37.2 against 36.9 ms at 65 536 items -- because the runtime's D2H copy of such a block is a blit kernel that
+  // covers the chip: k_table_pow_gt of the next part takes 5.3 instead of 1.3 ms under it.
+  static const size_t max_parts = [] { const char* e = getenv("RABE_AC17_ENC_PARTS"); const long v = e ? atol(e) : 1; return (size_t)(v > 0 ? v : 1); }();
+  const size_t parts = kem ? 1 : std::max<size_t>(1, std::min<size_t>(max_parts, n / 16384));
+  std::vector<PendingCopy> pending(parts);
+  if (parts > 1) eng.pinned_reserve((size_t)out_off[n] + parts * ((size_t)8 << 20) + 300 * n);          // staging of every part + their parameter packs: no growth inside the loop
+  // every part's row offsets (relative to the part's first row), uploaded once and asynchronously: nothing inside the loop may wait for
+  // the stream, or the host would queue part k + 1 only after part k has finished
+  std::vector<uint32_t> ro_all(n + parts);
+  std::vector<size_t> ro_at(parts);
+  for (size_t part = 0, at = 0; part < parts; part++) {
+    const size_t lo = n * part / parts, hi = n * (part + 1) / parts;
+    ro_at[part] = at;
+    for (size_t i = lo; i <= hi; i++) ro_all[at++] = row_off[i] - row_off[lo];
+  }
+  uint8_t* const h_ro = eng.pinned_bump(ro_all.size() * 4);
+  memcpy(h_ro, ro_all.data(), ro_all.size() * 4);
+  DBuf d_ro_all(&eng, ro_all.size() * 4);
+  eng.check(rhip_upload_async(cx, d_ro_all.ptr(), h_ro, ro_all.size() * 4), "upload");
+  for (size_t part = 0; part < parts; part++) {
+    const size_t lo = n * part / parts, hi = n * (part + 1) / parts, np = hi - lo;
+    const uint32_t* const ro = ro_all.data() + ro_at[part];
+    const uint32_t* const dro_p = d_ro_all.as<uint32_t>() + ro_at[part];
+    const size_t rows_p = ro[np];
+    rhip_g1* const dc_p = (rhip_g1*)(dc.as<uint8_t>() + 192ull * row_off[lo]);
+    eng.check(rhip_gt_table_pow(cx, egt, np, drho.as<rhip_fr>() + lo, dm.as<rhip_gt>() + lo), "rhip_gt_table_pow");
+    eng.check(rhip_ac17_cp_encrypt_batch(cx, dpk, np, dA.as<rhip_fr>(), dio.as<uint32_t>() + lo, dro_p, rows_p, ds.as<rhip_fr>() + 2 * lo,
+                                         dm.as<rhip_gt>() + lo, dc0.as<rhip_g2>() + 3 * lo, dc_p, dcp.as<rhip_gt>() + lo), "rhip_ac17_cp_encrypt_batch");
+    std::vector<uint64_t> src_off(3 * np);
+    for (size_t i = 0; i < np; i++) { src_off[i] = 384ull * i; src_off[np + i] = 192ull * ro[i]; src_off[2 * np + i] = 384ull * i; }
+    if (kem) {          // one part: headers from the template alone, keys straight out of the msg array -- no seal kernel is launched
+      DBuf d_keys(&eng, n * 32 + 4);
+      eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
+      eng.check(rhip_gt_kdf_batch(cx, n, dm.as<rhip_gt>(), nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
+      emit_plain_records(eng, layouts, n, item_policy, {dc0.ptr(), (const void*)dc_p, dcp.ptr()}, src_off, out_off, out_buf);
+      if (n) eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
+      continue;
+    }
+    emit_sealed_records(eng, layouts, np, item_policy + lo, {dc0.as<uint8_t>() + 384ull * lo, (const void*)dc_p, dcp.as<uint8_t>() + 384ull * lo}, src_off,
+                        dm.as<uint8_t>() + 384ull * lo, (const uint8_t*)nonces.data() + 12 * lo, pt_blob, pt_off + lo, out_off + lo, out_buf,
+                        parts > 1 ? &pending[part] : nullptr);
+  }
+  for (auto& pc : pending) pc.wait(eng);
+  tm.lap(kem ? "device: group arithmetic, headers, keys; two copies out" : "device: group arithmetic, records, sealing; copies out beside the next part");
+  return true;
+}
+
+static void* make_ac17_sk_lines(Engine& eng, const void* arg) {
+  const std::string& k0 = *(const std::string*)arg;
+  DBuf d(&eng, k0.data(), k0.size());
+  rhip_ac17_sk_lines* lines = nullptr;
+  eng.check(rhip_ac17_sk_prepare(eng.ctx(), 1, d.as<rhip_g2>(), &lines), "rhip_ac17_sk_prepare");
+  return lines;
+}
+static void destroy_ac17_sk_lines(void* h) { rhip_ac17_sk_lines_destroy((rhip_ac17_sk_lines*)h); }
+// status[i]: 0 ok, -1 the key does not satisfy the policy / malformed record / authentication failure (errors[i] says which).
+// pt_buf / pt_cap: caller-allocated; a capacity of ct_off[n] bytes always suffices (a plaintext is 28 bytes shorter than its sealed
+// form).  Returns false, before any work, when pt_cap is smaller than that.
+//
+// The records come from outside: the offsets are validated against ct_len before anything is read (monotone, inside the blob -- an
+// item whose own bounds are bad fails alone), and unless `trusted` is set every decoded element goes through one batched membership
+// pass on the GPU (coordinates < p, rows on the G1 curve, c_0 in the r-torsion of the twist, c_p in the order-r subgroup of Fq12:
+// what rabe-bn's decoding establishes, FieldError::NotMember) -- the Gt arithmetic downstream (cyclotomic squarings, conjugate as
+// inverse) is only valid inside the subgroup.  `trusted` is for ciphertexts this process produced itself.
+// KP-ABE's decrypt (:625-675) is the same product of pairings with the roles of the two sides' names swapped: the policy is the KEY's, the
+// attribute list the ciphertext's (its record starts with the attribute strings instead of policy text + language); k_p is absent.
+// plans of the packed decrypt, kept across calls: one bucket per key fingerprint (attributes or policy + row names), inside it one plan
+// per policy text.  A bucket that has grown past its cap is REPLACED (calls that still hold the old one finish on it).
+struct Ac17PolPlan {
+  std::string err; PrunedList lst; std::vector<uint32_t> sk_sel;
+  std::mutex mu; std::atomic<bool> have_rows{false}; std::vector<std::string> row_names; std::vector<uint32_t> ct_sel;
+  // the name-matching loop of ac17/mod.rs:403-408 as an index list
+  void select(const std::vector<Name>& names, std::vector<uint32_t>* out) const {
+    for (const auto& cur : lst)
+      for (uint32_t r = 0; r < names.size(); r++) if (same(names[r], cur.first)) out->push_back(r);
+  }
+  // The first record seen with this plan defines its row names and ct_sel (under mu, once; read-only from then on).  Does a record with
+  // these names have that layout -- may it use ct_sel?  Any other record selects on its own.
+  bool shares_layout(const std::vector<Name>& names) {
+    if (!have_rows.load(std::memory_order_acquire)) {
+      std::lock_guard<std::mutex> g(mu);
+      if (!have_rows.load(std::memory_order_relaxed)) {
+        for (const Name& nm : names) row_names.emplace_back(nm.first, nm.second);
+        select(names, &ct_sel);
+        have_rows.store(true, std::memory_order_release);
+      }
+    }
+    if (row_names.size() != names.size()) return false;
+    for (size_t r = 0; r < names.size(); r++) if (!same(names[r], row_names[r])) return false;
+    return true;
+  }
+};
+struct Ac17PlanBucket { PlanCache<Ac17PolPlan> plans; };
+struct Ac17PlanCache {
+  static std::shared_ptr<Ac17PlanBucket> get(const std::string& fingerprint) {
+    static std::mutex mu;
+    static std::unordered_map<std::string, std::shared_ptr<Ac17PlanBucket>> m;
+    std::lock_guard<std::mutex> g(mu);
+    if (m.size() > 64) m.clear();                                     // keys come and go: bounded
+    auto& b = m[fingerprint];
+    if (!b || b->plans.size() > 4096) b = std::make_shared<Ac17PlanBucket>();       // policies come and go as well
+    return b;
+  }
+};
+struct DecKey {
+  const Ac17SecretKey& sk;
+  const std::vector<std::string>* cp_attrs;      // CP: the key's attributes; the policy comes with every ciphertext
+  const PolicyRef* kp_policy;                    // KP: the key's policy; the attributes come with every ciphertext
+};
+// The plan of one key text: the verdict for this key, the pruned list and the key-side selection.  CP: `text` is a record's policy.  KP:
+// `text` is a record's head as the reader accepted it -- u32 count, then (u32 length, bytes) per attribute -- and kp_tree the key's parsed policy.
+static void make_plan(Ac17PolPlan& pl, const std::string& text, PolicyLanguage lang, const DecKey& key, const PolicyNode* kp_tree) {
+  if (kp_tree) {
+    std::vector<std::string> attrs;
+    Cursor c{(const uint8_t*)text.data(), (const uint8_t*)text.data() + text.size()};
+    for (uint32_t k = 0, cnt = c.u32(); k < cnt; k++) { const Name a = c.str(); attrs.emplace_back(a.first, a.second); }
+    if (!traverse_policy(attrs, *kp_tree)) throw RabeError("Error in kp_decrypt: attributes in ct do not match policy in sk.");
+    if (!calc_pruned(attrs, *kp_tree, &pl.lst)) throw RabeError("Error in kp_decrypt: pruned attributes in sk do not match policy in ct.");
+  } else {
+    PolicyNode tree = parse_or_error(text, lang);
+    if (!traverse_policy(*key.cp_attrs, tree)) throw RabeError("Error in cp_decrypt: attributes in SK do not match policy in CT.");
+    if (!calc_pruned(*key.cp_attrs, tree, &pl.lst)) throw RabeError("Error: attributes in sk do not match policy in ct.");
+  }
+  for (const auto& cur : pl.lst)
+    for (size_t r = 0; r < key.sk.k.size(); r++) if (key.sk.k[r].first == cur.first) pl.sk_sel.push_back((uint32_t)r);
+}
+static bool decrypt_packed_core(Engine& eng, const DecKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                                int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors,
+                                uint8_t* key_buf = nullptr /* decaps: keys instead of plaintexts; pt_buf / pt_cap / pt_off unused */);
+bool cp_decrypt_packed(Engine& eng, const Ac17CpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                       int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
+  if (sk.sk.k_p.size() != 3) throw RabeError("malformed Ac17CpSecretKey");
+  return decrypt_packed_core(eng, DecKey{sk.sk, &sk.attr, nullptr}, n, ct_blob, ct_len, ct_off, trusted, status, pt_buf, pt_cap, pt_off, errors);
+}
+// Key decapsulation (include/rabe_host.h: rabe_ac17_cp_decaps_packed): cp_decrypt_packed up to the final Gt, then the KDF behind the verdict
+// mask (records.h: derive_keys) instead of gather + open.  The sealed part of a record is skipped by its length field and never read.
+void cp_decaps_packed(Engine& eng, const Ac17CpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                      int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
+  if (sk.sk.k_p.size() != 3) throw RabeError("malformed Ac17CpSecretKey");
+  if (n && (!status || !key_buf)) throw RabeError("cp_decaps_packed: null input");
+  uint8_t none = 0;          // n = 0: nothing is written
+  decrypt_packed_core(eng, DecKey{sk.sk, &sk.attr, nullptr}, n, ct_blob, ct_len, ct_off, trusted, status, nullptr, 0, nullptr, errors, key_buf ? key_buf : &none);
+}
+bool kp_decrypt_packed(Engine& eng, const Ac17KpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                       int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
+  if (!(sk.sk.k_p.empty() || sk.sk.k_p.size() == 3)) throw RabeError("malformed Ac17KpSecretKey");
+  return decrypt_packed_core(eng, DecKey{sk.sk, nullptr, &sk.policy}, n, ct_blob, ct_len, ct_off, trusted, status, pt_buf, pt_cap, pt_off, errors);
+}
+// Key decapsulation over the KP pair (include/rabe_host.h: rabe_ac17_kp_decaps_packed), as cp_decaps_packed: kp_decrypt_packed up to the final Gt
+void kp_decaps_packed(Engine& eng, const Ac17KpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                      int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
+  if (!(sk.sk.k_p.empty() || sk.sk.k_p.size() == 3)) throw RabeError("malformed Ac17KpSecretKey");
+  if (n && (!status || !key_buf)) throw RabeError("kp_decaps_packed: null input");
+  uint8_t none = 0;          // n = 0: nothing is written
+  decrypt_packed_core(eng, DecKey{sk.sk, nullptr, &sk.policy}, n, ct_blob, ct_len, ct_off, trusted, status, nullptr, 0, nullptr, errors, key_buf ? key_buf : &none);
+}
+static const char* const C0_NOT_MEMBER = "deserialize: c_0 element is not a member of G2 (FieldError::NotMember)";
+static bool decrypt_packed_core(Engine& eng, const DecKey& key, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                                int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors, uint8_t* key_buf) {
+  const bool kp = key.kp_policy != nullptr, kem = key_buf != nullptr;
+  const Ac17SecretKey& core = key.sk;
+  StageTimer tm(kem ? (kp ? "ac17::kp_decaps_packed" : "ac17::cp_decaps_packed") : kp ? "ac17::kp_decrypt_packed" : "ac17::cp_decrypt_packed");
+  Engine::ArenaScope arena(eng);
+  errors->assign(n, "");
+  if (!ct_off || (n && !ct_blob)) throw RabeError("cp_decrypt_packed: null input");
+  // ---- bounds first: everything below trusts [ct_off[i], ct_off[i+1]) to lie inside the blob
+  const uint64_t span = check_offsets(n, ct_off, ct_len, errors);
+  if (!kem && (!pt_buf || pt_cap < span)) return false;
+  // ---- the key
+  if (core.k_0.size() != 3) throw RabeError("malformed AC17 secret key");
+  for (const auto& row : core.k) if (row.second.size() != 3) throw RabeError("malformed AC17 secret key: a row does not have 3 elements");
+  PolicyNode kp_tree;                            // KP: the key's policy, parsed once (a policy that does not parse fails the call like kp_decrypt)
+  if (kp) kp_tree = parse_or_error(key.kp_policy->first, key.kp_policy->second);
+  // ---- parse + plan.  Per distinct policy text (items of a batch repeat a few): the verdict for this key, the key-side selection and -- for
+  // the row layout the first item with that policy shows -- the ciphertext-side selection.  The plans are a pure function of (key attributes /
+  // key policy, key row names, policy text): they are kept ACROSS calls (Ac17PlanCache above) -- a queue batch of a few dozen requests spent
+  // 1.5 of its 6 ms re-parsing and re-pruning the same sixteen policies.
+  std::string fp(kp ? "K" : "C");
+  if (kp) { fp += key.kp_policy->first; fp.push_back((char)('0' + (int)key.kp_policy->second)); }
+  else for (const auto& a : *key.cp_attrs) { fp += a; fp.push_back('\x1f'); }
+  fp.push_back('\x1e');
+  for (const auto& row : core.k) { fp += row.first; fp.push_back('\x1f'); }
+  const std::shared_ptr<Ac17PlanBucket> bucket = Ac17PlanCache::get(fp);          // holds every plan the items below point to
+  BlobGather gather(eng, ct_blob, ct_len);          // the blob starts for the device now, beside the parsing below (records.h)
+  struct Item { View rec; Ac17PolPlan* plan = nullptr; bool shared = false; std::vector<uint32_t> own_sel;
+                const std::vector<uint32_t>& ct_sel() const { return shared ? plan->ct_sel : own_sel; } };
+  std::vector<Item> v(n);
+  const auto plan_for_key = [&](Ac17PolPlan& pl, const std::string& text, PolicyLanguage l) { make_plan(pl, text, l, key, kp ? &kp_tree : nullptr); };
+  for_each_record(n, errors, [&](size_t i) {
+    static thread_local std::vector<Name> names;      // per-thread scratch: no allocation per item
+    Item& it = v[i];
+    read_record(ct_blob + ct_off[i], ct_blob + ct_off[i + 1], kp, names, &it.rec);
+    const PolicyLanguage lang = it.rec.human ? PolicyLanguage::HumanPolicy : PolicyLanguage::JsonPolicy;
+    it.plan = bucket->plans.get_kept((const char*)it.rec.key, it.rec.key_len, lang, plan_for_key);          // `bucket` keeps it alive
+    if (!it.plan->err.empty()) throw RabeError(it.plan->err);
+    it.shared = it.plan->shares_layout(names);
+    if (!it.shared) it.plan->select(names, &it.own_sel);
+  });
+  tm.lap("parse + plan");
+  std::vector<size_t> live;
+  for (size_t i = 0; i < n; i++) if ((*errors)[i].empty()) live.push_back(i);
+  const size_t m = live.size();
+  // ---- selection lists: offsets first (a scan), then the lists copied into place on all cores (65 536 items x ~30 entries x 2: 6 ms when
+  // serial), straight into pinned staging (65 536 items: 2 x 8 MB), and uploaded from there.  Two plain index lists without weights: not a
+  // `Selection`, which is serial and shaped for (record row, key row, z) entries (docs/tried.md).
+  std::vector<uint32_t> ct_row_off(m + 1, 0), ct_sel_off(m + 1, 0), sk_sel_off(m + 1, 0);
+  for (size_t j = 0; j < m; j++) {
+    const Item& w = v[live[j]];
+    ct_row_off[j + 1] = ct_row_off[j] + w.rec.rows;
+    ct_sel_off[j + 1] = ct_sel_off[j] + (uint32_t)w.ct_sel().size();
+    sk_sel_off[j + 1] = sk_sel_off[j] + (uint32_t)w.plan->sk_sel.size();
+  }
+  const size_t n_ct_sel = ct_sel_off[m], n_sk_sel = sk_sel_off[m];
+  uint32_t* const ct_sel = (uint32_t*)eng.pinned_bump((n_ct_sel + n_sk_sel + 2) * 4);
+  uint32_t* const sk_sel = ct_sel + n_ct_sel + 1;
+  {
+    const size_t per = 1024, blocks = (m + per - 1) / per;
+    parallel_for(blocks, [&](size_t b) {
+      for (size_t j = b * per; j < m && j < (b + 1) * per; j++) {
+        const Item& w = v[live[j]];
+        const std::vector<uint32_t>&cs = w.ct_sel(), &ss = w.plan->sk_sel;
+        if (!cs.empty()) memcpy(ct_sel + ct_sel_off[j], cs.data(), cs.size() * 4);
+        if (!ss.empty()) memcpy(sk_sel + sk_sel_off[j], ss.data(), ss.size() * 4);
+      }
+    });
+  }
+  // uploaded at once: a later take from the same pinned block may move the block (Engine::pinned_bump waits for the stream first)
+  DBuf d_sel(&eng, (n_ct_sel + n_sk_sel + 2) * 4);
+  eng.check(rhip_upload_async(eng.ctx(), d_sel.ptr(), ct_sel, (n_ct_sel + n_sk_sel + 2) * 4), "upload (selection lists)");
+  const uint32_t* const d_ct_sel = d_sel.as<uint32_t>();
+  const uint32_t* const d_sk_sel = d_ct_sel + n_ct_sel + 1;
+  if (!m) {
+    if (kem) { for (size_t i = 0; i < n; i++) status[i] = -1; if (n) memset(key_buf, 0, n * 32); return true; }
+    pt_off[0] = 0;
+    for (size_t i = 0; i < n; i++) { pt_off[i + 1] = 0; status[i] = -1; }
+    return true;
+  }
+  const size_t total_rows = ct_row_off[m];
+  rhip_ctx* cx = eng.ctx();
+  // ---- shapes: the elements are gathered out of the device copy of the blob.  Records on their plan's shared layout share one part list,
+  // keyed by the plan; any other record brings its own.  Sharing needs no comparison of offsets: one plan means equal key text (CP: the
+  // policy text, behind it ONE language byte whatever its value; KP: the whole attribute head), so c_0 starts at the same offset, and the
+  // shared layout means the same number of rows with equal names, which fixes every later offset of the skeleton up to and including c_p.
+  std::vector<uint64_t> sealed_off(m);
+  std::vector<uint32_t> sealed_len(m);
+  for (size_t j = 0; j < m; j++) {
+    const Item& w = v[live[j]];
+    const uint8_t* rec = ct_blob + ct_off[live[j]];
+    sealed_off[j] = (uint64_t)(w.rec.sealed - ct_blob);
+    sealed_len[j] = w.rec.sealed_len;
+    gather_record(gather, ct_off[live[j]], w.shared ? w.plan : nullptr, [&](std::vector<RecordLayout::Part>& parts) {
+      parts.push_back({(uint32_t)(w.rec.c0 - rec), 384, 0, 0});
+      for (uint32_t r = 0; r < w.rec.rows; r++) parts.push_back({(uint32_t)(w.rec.row_ptr[r] - rec), 192, 1, 192 * r});
+      parts.push_back({(uint32_t)(w.rec.cp - rec), 384, 2, 0});
+    });
+  }
+  // ---- buffers
+  std::vector<uint8_t> k0 = flatten(core.k_0), kp_bytes = core.k_p.size() == 3 ? flatten(core.k_p) : std::vector<uint8_t>(3 * 64, 0), kk;   // KP: prod_h starts from G1::zero()
+  for (const auto& row : core.k) for (const auto& x : row.second) kk.insert(kk.end(), x.begin(), x.end());
+  if (kk.empty()) kk.assign(64, 0);
+  std::vector<uint32_t> sk_row_off{0, (uint32_t)core.k.size()}, sk_idx(m, 0);
+  DBuf d1(&eng, m * 384), d2(&eng, total_rows * 192 + 4), d4(&eng, m * 384), dout(&eng, m * 384);
+  std::vector<uint64_t> dst_off(3 * m);
+  for (size_t j = 0; j < m; j++) { dst_off[j] = 384ull * j; dst_off[m + j] = 192ull * ct_row_off[j]; dst_off[2 * m + j] = 384ull * j; }
+  std::vector<uint32_t> seg(m + 1);          // c_0: three elements per item
+  for (size_t j = 0; j <= m; j++) seg[j] = (uint32_t)j;
+  ParamPack pp(eng);
+  const size_t h3 = pp.add(ct_row_off), h6 = pp.add(kk), h7 = pp.add(sk_row_off), h8 = pp.add(kp_bytes), h9 = pp.add(sk_idx),
+               h11 = pp.add(ct_sel_off), h13 = pp.add(sk_sel_off), h_seg = trusted ? 0 : pp.add(seg);
+  pp.upload();
+  tm.lap("selection tables");
+  gather.run({d1.ptr(), d2.ptr(), d4.ptr()}, dst_off);
+  const uint32_t* d3 = pp.dev<uint32_t>(h3);
+  // ---- checks: decoding checks over the gathered elements, on the side context beside the decrypt kernels; a non-member fails its item only
+  // (the batch still runs: the kernels terminate on any input, the item's result is discarded below).  mc's checks: 0 rows, 1 c_p, and
+  // without walk verdicts 2 = c_0 stand-alone, segmented like the rows -- an item's verdict is the AND of its three elements' on either path.
+  // c_0's segment offsets (item j = elements 3 j .. 3 j + 2) went up with the call's parameter pack: `pp`, declared before `ws`, outlives
+  // the walk's late verdicts, and MemberChecks' side context waits for everything queued before it, the pack's upload included.  WalkScope
+  // owns the checks and the walk; its d_g2 is not needed here -- c_0 is d1, which lives as long as the call.
+  WalkScope ws;
+  if (!trusted) {
+    ws.mc.reset(new MemberChecks(eng));
+    ws.mc->add(1, d2.ptr(), 3 * total_rows, d3, m, 3);
+    ws.mc->add(3, d4.ptr(), m);
+    // c_0: the decrypt walks all three elements of every ciphertext -- their subgroup membership comes out of its Miller loops
+    if (walk_checks()) ws.walked.reset(new WalkedG2(eng, *ws.mc, d1.ptr(), 3 * m, pp.dev<uint32_t>(h_seg), seg, 3));
+    else { ws.k_alone = ws.mc->add_count(); ws.mc->add(2, d1.ptr(), 3 * m, pp.dev<uint32_t>(h_seg), m, 3); }
+  }
+  // ---- launch.  The key's prepared k_0 lines are a function of the key alone: kept across calls (a server decrypts with the same key again and again)
+  std::string k0_key((const char*)k0.data(), k0.size());
+  rhip_ac17_sk_lines* lines = (rhip_ac17_sk_lines*)eng.aux("ac17_sk_lines", k0_key, make_ac17_sk_lines, &k0_key, destroy_ac17_sk_lines, 4);
+  if (ws.walked) ws.walked->arm();
+  eng.check(rhip_ac17_cp_decrypt_batch_prepared(cx, m, d1.as<rhip_g2>(), d2.as<rhip_g1>(), d3, d4.as<rhip_gt>(), lines, pp.dev<rhip_g1>(h6),
+                                                pp.dev<uint32_t>(h7), pp.dev<rhip_g1>(h8), pp.dev<uint32_t>(h9), d_ct_sel,
+                                                pp.dev<uint32_t>(h11), d_sk_sel, pp.dev<uint32_t>(h13), dout.as<rhip_gt>()),
+            "rhip_ac17_cp_decrypt_batch_prepared");
+  // ---- verdicts, in the decoder's order: c_0, rows, c_p
+  if (ws.mc) {
+    ws.mc->collect();
+    ws.fail(live, {ws.k_alone}, C0_NOT_MEMBER, errors);
+    ws.fail(live, {0}, "deserialize: a row element is not a point of G1 (FieldError::NotMember)", errors);
+    ws.fail(live, {1}, "deserialize: c_p is not a member of Gt (FieldError::NotMember)", errors);
+  }
+  // ---- ending
+  if (kem) {          // every verdict first (there is no open to queue behind the pairings), then the KDF behind their mask: 32 n bytes come back
+    ws.fail_walked(live, C0_NOT_MEMBER, errors);
+    derive_keys(eng, n, live, dout.ptr(), status, key_buf, *errors);
+    tm.lap(trusted ? "device: gather, pairings, keys" : "device: gather, pairings, keys; membership beside");
+    return true;
+  }
+  // KDF + AES-GCM open on the device: the decrypted Gt never leaves HBM; plaintext bytes come back in one copy
+  open_sealed_records(eng, n, live, dout.ptr(), gather.dev_blob(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
+  ws.retract(live, C0_NOT_MEMBER, status, pt_buf, pt_off, errors);          // read AFTER the open was queued behind the pairings (records.h: retract_item)
+  tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
+  return true;
+}
 }  // namespace ac17
 
 // ================================================================================================================= BSW
@@ -575,7 +1103,7 @@ void destroy_gen_tables(void* h) {
 // computed once per call), D_j.g1 = g1*r_j, D_j.g2 = g2*(r + h(j) r_j) -- three window-table launches for the whole batch.
 bool keygen_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const CpAbeMasterKey& msk, const std::vector<std::vector<std::string>>& sets, size_t n,
                    const uint32_t* item_set, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  Timer tm("bsw::keygen_packed");
+  StageTimer tm("bsw::keygen_packed");
   Engine::ArenaScope arena(eng);
   eng.scrub_when_done();          // master-key-derived scalars pass through the staging buffers
   if (n && (!item_set || !out_off)) throw RabeError("bsw::keygen_packed: null input");
@@ -670,7 +1198,7 @@ void destroy_f_table(void* h) { rhip_g2_table_destroy((rhip_g2_table*)h); }
 }  // namespace
 bool delegate_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const CpAbeSecretKey& sk, const std::vector<std::vector<std::string>>& subsets, size_t n,
                      const uint32_t* item_subset, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  Timer tm("bsw::delegate_packed");
+  StageTimer tm("bsw::delegate_packed");
   Engine::ArenaScope arena(eng);
   eng.scrub_when_done();          // the key's elements pass through the staging buffers
   if (n && (!item_subset || !out_off)) throw RabeError("bsw::delegate_packed: null input");
@@ -758,7 +1286,7 @@ static bool encrypt_core(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const 
                          const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off,
                          uint8_t* key_buf) {
   const bool kem = key_buf != nullptr;
-  Timer tm(kem ? "bsw::encaps_packed" : "bsw::encrypt_packed");
+  StageTimer tm(kem ? "bsw::encaps_packed" : "bsw::encrypt_packed");
   Engine::ArenaScope arena(eng);
   ShareTrees st;
   for (const auto& p : policies) st.add(p, language);
@@ -850,7 +1378,7 @@ bool encaps_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const std::v
 static bool decrypt_core(Engine& eng, const CpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                          int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors, uint8_t* key_buf) {
   const bool kem = key_buf != nullptr;
-  Timer tm(kem ? "bsw::decaps_packed" : "bsw::decrypt_packed");
+  StageTimer tm(kem ? "bsw::decaps_packed" : "bsw::decrypt_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
   if (!ct_off || (n && !ct_blob)) throw RabeError("bsw::decrypt_packed: null input");
@@ -1080,7 +1608,7 @@ void* make_enc_tables(Engine& eng, const void* arg) {
 // sealed plaintext.  Every element is a fixed-base multiple of a public-key element: window-table launches for the whole batch.
 bool encrypt_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
                     const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  Timer tm("lsw::encrypt_packed");
+  StageTimer tm("lsw::encrypt_packed");
   Engine::ArenaScope arena(eng);
   if (n && (!item_set || !pt_off || !out_off)) throw RabeError("lsw::encrypt_packed: null input");
   std::vector<size_t> fixed(sets.size());
@@ -1183,7 +1711,7 @@ bool encrypt_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::
 // e5 is two walks on one accumulator and a row's three conversions share one inversion.  e1 and e2 keep their table calls.  No AES kernel.
 bool encaps_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
                    uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
-  Timer tm("lsw::encaps_packed");
+  StageTimer tm("lsw::encaps_packed");
   Engine::ArenaScope arena(eng);
   if (n && (!item_set || !key_buf)) throw RabeError("lsw::encaps_packed: null input");
   if (!out_off) throw RabeError("lsw::encaps_packed: null input");
@@ -1273,7 +1801,7 @@ bool encaps_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::v
 // d3..d5 the identity for positive leaves and d1, d2 the identity for negative ones ("!x", :137-146: rhip_lsw_keygen_batch_signed).
 bool keygen_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const KpAbeMasterKey& msk, const std::vector<std::string>& policies,
                    PolicyLanguage language, size_t n, const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  Timer tm("lsw::keygen_packed");
+  StageTimer tm("lsw::keygen_packed");
   Engine::ArenaScope arena(eng);
   eng.scrub_when_done();          // master-key-derived scalars pass through the staging buffers
   ShareTrees st;
@@ -1358,7 +1886,7 @@ bool keygen_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const KpAbeM
 // (:249-263).  A pruned negative attribute (the reference's TODO branch, :265-278) fails the item here: the object API reproduces it.
 bool decrypt_packed(Engine& eng, const KpAbeCiphertext& ct, size_t n, const uint8_t* sk_blob, size_t sk_len, const uint64_t* sk_off, bool trusted,
                     int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
-  Timer tm("lsw::decrypt_packed");
+  StageTimer tm("lsw::decrypt_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
   if (!sk_off || (n && !sk_blob)) throw RabeError("lsw::decrypt_packed: null input");
@@ -1515,7 +2043,7 @@ void* make_sk_d2_lines(Engine& eng, const void* arg) {          // arg: d2 of ev
 static bool decrypt_one_sk_core(Engine& eng, const KpAbeSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                                 int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors, uint8_t* key_buf) {
   const bool kem = key_buf != nullptr;
-  Timer tm(kem ? "lsw::decaps_packed" : "lsw::decrypt_one_sk_packed");
+  StageTimer tm(kem ? "lsw::decaps_packed" : "lsw::decrypt_one_sk_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
   if (!ct_off || (!kem && !pt_off) || (n && !ct_blob)) throw RabeError("lsw::decrypt_one_sk_packed: null input");
@@ -1710,7 +2238,7 @@ static bool encrypt_core(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const s
                          PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf,
                          size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
   const bool kem = key_buf != nullptr;
-  Timer tm(kem ? "aw11::encaps_packed" : "aw11::encrypt_packed");
+  StageTimer tm(kem ? "aw11::encaps_packed" : "aw11::encrypt_packed");
   Engine::ArenaScope arena(eng);
   PkArg arg{&gk, {}};
   std::string key((const char*)gk.g1.data(), 64);
@@ -1834,7 +2362,7 @@ void destroy_g1_table(void* h) { rhip_g1_table_destroy((rhip_g1_table*)h); }
 // unwrap panic (:213); an empty gid or list its RabeError.
 bool keygen_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11MasterKey& msk, const std::vector<std::string>& gids,
                    const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  Timer tm("aw11::keygen_packed");
+  StageTimer tm("aw11::keygen_packed");
   Engine::ArenaScope arena(eng);
   eng.scrub_when_done();          // master-key-derived scalars pass through the staging buffers
   if (n && (!item_set || !out_off)) throw RabeError("aw11::keygen_packed: null input");
@@ -1906,7 +2434,7 @@ bool keygen_packed(Engine& eng, const Aw11GlobalKey& gk, const Aw11MasterKey& ms
 static bool decrypt_core(Engine& eng, const Aw11GlobalKey& gk, const Aw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
                          bool trusted, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors, uint8_t* key_buf) {
   const bool kem = key_buf != nullptr;
-  Timer tm(kem ? "aw11::decaps_packed" : "aw11::decrypt_packed");
+  StageTimer tm(kem ? "aw11::decaps_packed" : "aw11::decrypt_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
   if (!ct_off || (n && !ct_blob)) throw RabeError("aw11::decrypt_packed: null input");
@@ -2101,7 +2629,7 @@ static bool encrypt_core(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const 
                          const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off,
                          uint8_t* key_buf) {
   const bool kem = key_buf != nullptr;
-  Timer tm(kem ? "ghw11::encaps_packed" : "ghw11::encrypt_packed");
+  StageTimer tm(kem ? "ghw11::encaps_packed" : "ghw11::encrypt_packed");
   Engine::ArenaScope arena(eng);
   ShareTrees st;
   for (const auto& p : policies) st.add(p, language);
@@ -2195,7 +2723,7 @@ bool encaps_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::v
 // record, c or t not in Gt (unless trusted), a tag that does not verify (a wrong rk, for one).
 bool decrypt_out_packed(Engine& eng, const Ghw11RetrieveKey& rk, size_t n, const uint8_t* tct, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
                         bool trusted, int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
-  Timer tm("ghw11::decrypt_out_packed");
+  StageTimer tm("ghw11::decrypt_out_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
   if (!ct_off || !pt_off || (n && (!ct_blob || !tct || !status))) throw RabeError("ghw11::decrypt_out_packed: null input");
@@ -2377,7 +2905,7 @@ rhip_g2_lines* key_lines(Engine& eng, const char* aux_name, const G2& k, const G
 // Every G2 argument is the key's: the batch replays prepared lines (kept across calls) and does no G2 arithmetic.
 bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                       int32_t* status, uint8_t* out_buf, size_t out_cap, std::vector<std::string>* errors) {
-  Timer tm("ghw11::transform_packed");
+  StageTimer tm("ghw11::transform_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
   if (!ct_off || (n && !ct_blob) || !status) throw RabeError("ghw11::transform_packed: null input");
@@ -2463,7 +2991,7 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
 static bool decrypt_core(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                          int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors, uint8_t* key_buf) {
   const bool kem = key_buf != nullptr;
-  Timer tm(kem ? "ghw11::decaps_packed" : "ghw11::decrypt_packed");
+  StageTimer tm(kem ? "ghw11::decaps_packed" : "ghw11::decrypt_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
   if (!ct_off || (!kem && !pt_off) || (n && (!ct_blob || !status))) throw RabeError("ghw11::decrypt_packed: null input");
@@ -2566,7 +3094,7 @@ void decaps_packed(Engine& eng, const Ghw11SecretKey& sk, size_t n, const uint8_
 // c or t not in Gt unless trusted -- with trusted a non-member's key is unspecified (the power's split assumes the order-r subgroup).
 void decaps_out_packed(Engine& eng, const Ghw11RetrieveKey& rk, size_t n, const uint8_t* tct, bool trusted, int32_t* status, uint8_t* key_buf,
                        std::vector<std::string>* errors) {
-  Timer tm("ghw11::decaps_out_packed");
+  StageTimer tm("ghw11::decaps_out_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
   if (n && (!tct || !status || !key_buf)) throw RabeError("ghw11::decaps_out_packed: null input");
@@ -2626,7 +3154,7 @@ void decaps_out_packed(Engine& eng, const Ghw11RetrieveKey& rk, size_t n, const 
 // g2_a (k_ghw11_keygen_rows; tables built once per key pair and kept), records written on the device from one template per list.
 bool keygen_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw11MasterKey& msk, const std::vector<std::vector<std::string>>& sets, size_t n,
                    const uint32_t* item_set, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  Timer tm("ghw11::keygen_packed");
+  StageTimer tm("ghw11::keygen_packed");
   Engine::ArenaScope arena(eng);
   eng.scrub_when_done();          // the keys' r pass through the staging buffers
   if (!out_off || (n && !item_set)) throw RabeError("ghw11::keygen_packed: null input");
@@ -2687,7 +3215,7 @@ bool keygen_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw11M
 // split of z^-1 per item, one joint chain per row); tk record = the sk record with every element replaced, rk = z.
 bool tkgen_packed(Engine& eng, Rng& rng, size_t n, const uint8_t* sk_blob, size_t sk_len, const uint64_t* sk_off, bool trusted, int32_t* status,
                   uint8_t* tk_buf, size_t tk_cap, uint64_t* tk_off, uint8_t* rk_buf, std::vector<std::string>* errors) {
-  Timer tm("ghw11::tkgen_packed");
+  StageTimer tm("ghw11::tkgen_packed");
   Engine::ArenaScope arena(eng);
   eng.scrub_when_done();          // z and z^-1 (the retrieve keys) pass through the staging buffers
   errors->assign(n, "");
@@ -2808,7 +3336,7 @@ bool tkgen_packed(Engine& eng, Rng& rng, size_t n, const uint8_t* sk_blob, size_
 bool provision_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw11MasterKey& msk, const std::vector<std::vector<std::string>>& sets,
                       size_t n, const uint32_t* item_set, uint8_t* sk_buf, size_t sk_cap, uint64_t* sk_off, uint8_t* tk_buf, size_t tk_cap,
                       uint64_t* tk_off, uint8_t* rk_buf) {
-  Timer tm("ghw11::provision_packed");
+  StageTimer tm("ghw11::provision_packed");
   Engine::ArenaScope arena(eng);
   eng.scrub_when_done();          // r, z, z^-1 and r z^-1 pass through the staging buffers
   const bool want_sk = sk_off != nullptr;
@@ -2933,7 +3461,7 @@ void destroy_pk(void* h) { rhip_dnf_pk_destroy((rhip_dnf_pk*)h); }
 bool encrypt_packed(Engine& eng, Rng& rng, const DnfScheme& sc, const G1& p1, const G2& p2, const std::vector<DnfKey>& keys,
                     const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
                     const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  Timer tm(sc.timer);
+  StageTimer tm(sc.timer);
   Engine::ArenaScope arena(eng);
   Engine::Busy working(eng);          // a term set evicted by a later policy of this call lives until the call is done
   const size_t P = policies.size(), n_gt = sc.n_gt;
@@ -3068,7 +3596,7 @@ void destroy_keys(void* h) { rhip_dnf_keys_destroy((rhip_dnf_keys*)h); }
 // source of their own, one layout per distinct name length.
 bool keygen_packed(Engine& eng, Rng& rng, const char* what, const G1& p1, const G1& g1, const G2& p2, const G2& g2, const G1& a1, const G2& a2,
                    const std::vector<std::string>& names, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  Timer tm(what);
+  StageTimer tm(what);
   Engine::ArenaScope arena(eng);
   eng.scrub_when_done();          // the keys' r_u pass through the staging buffers
   const size_t n = names.size();
@@ -3130,7 +3658,7 @@ bool keygen_packed(Engine& eng, Rng& rng, const char* what, const G1& p1, const 
 bool request_sk_packed(Engine& eng, const char* what, const std::string& authority, const Fr& secret, const std::vector<std::vector<std::string>>& sets,
                        size_t n, const uint32_t* item_set, const uint8_t* blob, size_t blob_len, const uint64_t* in_off, bool trusted, int32_t* status,
                        uint8_t* out_buf, size_t out_cap, uint64_t* out_off, std::vector<std::string>* errors) {
-  Timer tm(what);
+  StageTimer tm(what);
   Engine::ArenaScope arena(eng);
   eng.scrub_when_done();          // the attribute exponents pass through the staging buffers
   errors->assign(n, "");

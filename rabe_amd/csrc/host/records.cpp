@@ -207,14 +207,14 @@ BlobGather::~BlobGather() {
   delete up_;
 }
 int BlobGather::find(const void* key) const {
-  for (const auto& k : keys_) if (k.first == key) return (int)k.second;
-  return -1;
+  const auto it = keys_.find(key);
+  return it == keys_.end() ? -1 : (int)it->second;
 }
 uint32_t BlobGather::add_shape(const void* key, std::vector<RecordLayout::Part> parts) {
   const uint32_t id = (uint32_t)shape_off_.size() - 1;
   for (const auto& pt : parts) { part_src_.push_back(pt.rec_off); part_dst_.push_back(pt.part_off); part_len_.push_back(pt.len); part_k_.push_back(pt.k); }
   shape_off_.push_back((uint32_t)part_src_.size());
-  if (key) keys_.push_back({key, id});
+  if (key) keys_.emplace(key, id);
   return id;
 }
 void BlobGather::run(const std::vector<void*>& dst, const std::vector<uint64_t>& dst_item_off) {

@@ -10,6 +10,7 @@
 #include <string.h>
 #include <memory>
 #include <string>
+#include <unordered_map>
 #include <vector>
 #include "common.h"
 
@@ -120,7 +121,7 @@ class BlobGather {
   DBuf d_blob_;
   struct Up;
   Up* up_;
-  std::vector<std::pair<const void*, uint32_t>> keys_;
+  std::unordered_map<const void*, uint32_t> keys_;          // a batch may bring thousands of shared shapes: one lookup per record
   std::vector<uint32_t> shape_off_{0}, part_src_, part_dst_, part_len_, part_k_, item_shape_;
   std::vector<uint64_t> rec_off_;
   std::unique_ptr<ParamPack> pp_;          // the gather's tables: alive as long as the kernel may read them

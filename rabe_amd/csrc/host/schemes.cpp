@@ -5,7 +5,6 @@
 #include "records.h"
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <deque>
 #include <memory>
@@ -13,7 +12,6 @@
 #include <functional>
 #include <future>
 #include <mutex>
-#include <shared_mutex>
 #include <thread>
 #include <unordered_map>
 
@@ -641,7 +639,7 @@ static std::vector<G1> g1_add(Engine& e, const std::vector<G1>& a, const std::ve
   e.check(rhip_g1_add(e.ctx(), n, da.as<rhip_g1>(), db.as<rhip_g1>(), out.as<rhip_g1>()), "rhip_g1_add");
   return fetch<64>(out, n);
 }
-static Fr must_inv(const Fr& a) {
+Fr must_inv(const Fr& a) {
   Fr o;
   if (!fr_inv(a, &o)) throw std::runtime_error("called `Option::unwrap()` on a `None` value (Fr::inverse of zero)");
   return o;
@@ -664,19 +662,6 @@ static Bytes open_or_error(const Gt& msg, const Bytes& ct) {               // de
   return out;
 }
 
-// RABE_HOST_TIMING=1: stage timings of the batch entry points on stderr (development aid)
-struct StageTimer {
-  bool on;
-  const char* what;
-  std::chrono::steady_clock::time_point t0;
-  explicit StageTimer(const char* w) : on(getenv("RABE_HOST_TIMING") != nullptr), what(w), t0(std::chrono::steady_clock::now()) {}
-  void lap(const char* stage) {
-    if (!on) return;
-    auto t1 = std::chrono::steady_clock::now();
-    fprintf(stderr, "[host-timing] %s: %s %.1f ms\n", what, stage, std::chrono::duration<double, std::milli>(t1 - t0).count());
-    t0 = t1;
-  }
-};
 // ---- batched decryption tail shared by bsw / lsw / aw11: item i yields
 //   lead_i * prod_j gbase_ij^gexp_ij * FE( prod_j ML(scal_ij * base_ij, q_ij) )
 // with ONE g1_mul, ONE pairing-product launch (one final exponentiation per item) and ONE gt_pow for the whole batch.
@@ -996,7 +981,7 @@ Ac17CpSecretKey cp_keygen(Engine& eng, Rng& rng, const Ac17MasterKey& msk, const
 }
 
 // per-policy Fr table A[row][l][t] (SURVEY.md Appendix B.3 = ac17/mod.rs:305-348 with the hashes pre-combined)
-static std::vector<Fr> policy_table(const AbePolicy& msp) {
+std::vector<Fr> policy_table(const AbePolicy& msp) {
   const size_t cols = msp.m.empty() ? 0 : msp.m[0].size();
   std::vector<Fr> colh(cols * 6);
   for (size_t j = 0; j < cols; j++)
@@ -1214,582 +1199,11 @@ Bytes cp_decrypt(Engine& eng, const Ac17CpSecretKey& sk, const Ac17CpCiphertext&
   return open_or_error(cp_decrypt_gt(eng, sk, ct), ct.ct.ct);
 }
 
-// ---------------------------------------------------------------------------------------------- packed batches
-// The same two functions with packed input and output (no per-item objects on either side of the C ABI): n ciphertexts are
-// one blob of canonical records (the byte form of rabe_obj_serialize for Ac17CpCiphertext) with an offset array.  Everything
-// per item that is not group arithmetic -- record assembly, KDF, AES-GCM, parsing, pruning -- runs on all host cores; the
-// group arithmetic is one launch set; PCIe copies go through pinned staging buffers.
-static inline void put_u32(uint8_t* p, uint32_t v) { for (int i = 0; i < 4; i++) p[i] = (uint8_t)(v >> (8 * i)); }
-static inline uint32_t get_u32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-// parse + MSP + Fr table of a policy text, cached across calls (a server encrypts under the same few policies again and again)
-struct EncPolicy { AbePolicy msp; std::vector<Fr> tab; size_t fixed_bytes; };
-static std::shared_ptr<const EncPolicy> enc_policy(const std::string& pol, PolicyLanguage language) {
-  static std::mutex mu;
-  static std::map<std::pair<int, std::string>, std::shared_ptr<const EncPolicy>> cache;
-  const auto key = std::make_pair((int)language, pol);
-  {
-    std::lock_guard<std::mutex> g(mu);
-    auto it = cache.find(key);
-    if (it != cache.end()) return it->second;
-  }
-  auto e = std::make_shared<EncPolicy>();
-  e->msp = calculate_msp(parse_or_error(pol, language));
-  e->tab = policy_table(e->msp);
-  e->fixed_bytes = 4 + pol.size() + 1 + 4 + 3 * 128 + 4 + 384 + 4;      // record size without the sealed plaintext
-  for (const auto& name : e->msp.pi) e->fixed_bytes += 4 + name.size() + 4 + 3 * 64;
-  std::lock_guard<std::mutex> g(mu);
-  if (cache.size() >= 1024) cache.clear();
-  cache[key] = e;
-  return e;
-}
-// out_buf / out_cap: caller-allocated (reusable) output; out_off: n + 1 caller-allocated entries, always filled.  Returns false
-// -- before any randomness is drawn or work is done -- when out_cap < out_off[n], the size the records need.
-// KP-ABE's encrypt (:556-616) is the same arithmetic with a table of plain label hashes: rows = the attribute list, no MSP columns.  The
-// record differs only in its head (the attribute strings instead of policy text + language).
-static std::shared_ptr<const EncPolicy> enc_attr_set(const std::vector<std::string>& attrs) {
-  auto e = std::make_shared<EncPolicy>();
-  e->msp.pi = attrs;
-  e->msp.m.assign(attrs.size(), std::vector<int8_t>{0});
-  for (const auto& a : attrs)
-    for (int l = 0; l < 3; l++)
-      for (int t = 0; t < 2; t++) e->tab.push_back(sha3_hash_fr(a + std::to_string(l) + std::to_string(t)));
-  e->fixed_bytes = 4 + 4 + 3 * 128 + 4 + 384 + 4;
-  for (const auto& a : attrs) e->fixed_bytes += (4 + a.size()) + (4 + a.size() + 4 + 3 * 64);
-  return e;
-}
-static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::shared_ptr<const EncPolicy>>& pols,
-                                const std::vector<std::string>* policies /* CP: the texts; KP: nullptr */, PolicyLanguage language, size_t n,
-                                const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off,
-                                uint8_t* key_buf = nullptr /* encaps: no plaintexts, no sealing; 32 bytes of content key per item */);
-bool cp_encrypt_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
-                       const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  std::vector<std::shared_ptr<const EncPolicy>> pols;
-  for (const auto& pol : policies) pols.push_back(enc_policy(pol, language));
-  return encrypt_packed_core(eng, rng, pk, pols, &policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off);
-}
-// Key encapsulation (include/rabe_host.h: rabe_ac17_cp_encaps_packed): cp_encrypt_packed's records with a sealed part of length zero and,
-// per item, the content key SHA3-256(bytes(msg)) instead of a payload sealed under it.  Draws: cp_encrypt_packed's without the nonce.
-bool cp_encaps_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
-                      const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
-  if (n && !key_buf) throw RabeError("cp_encaps_packed: null input");
-  if (!n) { out_off[0] = 0; return true; }
-  std::vector<std::shared_ptr<const EncPolicy>> pols;
-  for (const auto& pol : policies) pols.push_back(enc_policy(pol, language));
-  return encrypt_packed_core(eng, rng, pk, pols, &policies, language, n, item_policy, nullptr, nullptr, out_buf, out_cap, out_off, key_buf);
-}
-// n calls of ac17::kp_encrypt: item i is encrypted under the attribute list sets[item_set[i]]; records = Ac17KpCiphertext
-bool kp_encrypt_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
-                       const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  std::vector<std::shared_ptr<const EncPolicy>> pols;
-  for (const auto& a : sets) pols.push_back(enc_attr_set(a));
-  return encrypt_packed_core(eng, rng, pk, pols, nullptr, PolicyLanguage::JsonPolicy, n, item_set, pt_blob, pt_off, out_buf, out_cap, out_off);
-}
-// Key encapsulation over the KP pair (include/rabe_host.h: rabe_ac17_kp_encaps_packed): kp_encrypt_packed's records with a sealed part of length
-// zero and the content keys, as cp_encaps_packed
-bool kp_encaps_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
-                      uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
-  if (n && !key_buf) throw RabeError("kp_encaps_packed: null input");
-  if (!n) { out_off[0] = 0; return true; }
-  std::vector<std::shared_ptr<const EncPolicy>> pols;
-  for (const auto& a : sets) pols.push_back(enc_attr_set(a));
-  return encrypt_packed_core(eng, rng, pk, pols, nullptr, PolicyLanguage::JsonPolicy, n, item_set, nullptr, nullptr, out_buf, out_cap, out_off, key_buf);
-}
-static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::shared_ptr<const EncPolicy>>& pols,
-                                const std::vector<std::string>* policies, PolicyLanguage language, size_t n,
-                                const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off,
-                                uint8_t* key_buf) {
-  const bool kem = key_buf != nullptr;
-  StageTimer tm(kem ? (policies ? "ac17::cp_encaps_packed" : "ac17::kp_encaps_packed") : policies ? "ac17::cp_encrypt_packed" : "ac17::kp_encrypt_packed");
-  Engine::ArenaScope arena(eng);
-  if (pk.h_a.size() != 3 || pk.e_gh_ka.size() != 2) throw RabeError("malformed Ac17PublicKey");
-  std::vector<uint32_t> a_off{0};
-  std::vector<Fr> A;
-  for (const auto& e : pols) {
-    A.insert(A.end(), e->tab.begin(), e->tab.end());
-    a_off.push_back(a_off.back() + (uint32_t)e->msp.m.size());
-  }
-  if (!record_offsets("encrypt_packed", "item_policy", n, item_policy, pols.size(), [&](size_t i) { return pols[item_policy[i]]->fixed_bytes; },
-                      kem ? nullptr : pt_off, out_buf, out_cap, out_off)) return false;
-  tm.lap("policies");
-  // randomness in the reference's per-call draw order: s0, s1, msg, nonce -- item after item (encaps: no nonce)
-  uint8_t* h_s = eng.pinned(0, n * (64 + 32));
-  uint8_t* h_rho = h_s + n * 64;
-  std::vector<std::array<uint8_t, 12>> nonces(n);
-  draw_items(rng, n, 1024, 256, [&](Rng& r, size_t i) {
-    Fr s0 = r.next_fr(), s1 = r.next_fr(), rho = r.next_fr();
-    memcpy(h_s + 64 * i, s0.l, 32);
-    memcpy(h_s + 64 * i + 32, s1.l, 32);
-    memcpy(h_rho + 32 * i, rho.l, 32);
-    if (!kem) r.fill(nonces[i].data(), 12);
-  });
-  std::vector<uint32_t> item_a_off(n), row_off(n + 1, 0);
-  for (size_t i = 0; i < n; i++) {
-    item_a_off[i] = a_off[item_policy[i]];
-    row_off[i + 1] = row_off[i] + (uint32_t)pols[item_policy[i]]->msp.m.size();
-  }
-  const size_t total_rows = row_off[n];
-  tm.lap("draws");
-  rhip_ac17_pk* dpk = eng.ac17_pk(pk.g, pk.h_a, pk.e_gh_ka);
-  rhip_gt_table* egt = eng.gt_generator_table();
-  auto fA = flatten_fr(A);
-  DBuf dA(&eng, fA.data(), fA.size()), dio(&eng, item_a_off.data(), n * 4), ds(&eng, n * 64), drho(&eng, n * 32),
-      dm(&eng, n * 384), dc0(&eng, n * 3 * 128), dc(&eng, total_rows * 3 * 64 + 4), dcp(&eng, n * 384);
-  rhip_ctx* cx = eng.ctx();
-  eng.check(rhip_upload_async(cx, ds.ptr(), h_s, n * 64), "upload");
-  eng.check(rhip_upload_async(cx, drho.ptr(), h_rho, n * 32), "upload");
-  // records and sealing on the device (records.h): per policy a template of the literal bytes with the elements dropped in
-  std::vector<RecordLayout> layouts(pols.size());
-  for (size_t p_ = 0; p_ < pols.size(); p_++) {
-    RecordLayout& L = layouts[p_];
-    const AbePolicy& msp = pols[p_]->msp;
-    if (policies) {                               // Ac17CpCiphertext: policy text + language
-      policy_header(L, (*policies)[p_], language);
-    } else {                                      // Ac17KpCiphertext: the attribute strings
-      L.u32((uint32_t)msp.pi.size());
-      for (const auto& a : msp.pi) L.str(a);
-    }
-    L.u32(3);
-    L.src(0, 0, 384);
-    L.u32((uint32_t)msp.m.size());
-    for (size_t r = 0; r < msp.m.size(); r++) {
-      L.str(msp.pi[r]);
-      L.u32(3);
-      L.src(1, (uint32_t)(192 * r), 192);
-    }
-    L.src(2, 0, 384);
-    if (L.bytes() + 4 != pols[p_]->fixed_bytes) throw RabeError("ac17 encrypt_packed: record layout and size disagree");
-    if (kem) L.u32(0);                            // encaps: the template ends in the length field of an empty sealed part, no sealed source
-  }
-  // The batch can go through the device in PARTS of >= 16 384 items, a part's records copied out (10.4 KB per item at 50 rows, 15 ms per
-  // 65 536 items) on the side stream while the next part's group arithmetic runs; randomness was drawn above for the whole batch, item
-  // after item, so the bytes do not depend on the cut (tests/test_gpu_packed.py).  OFF by default (RABE_AC17_ENC_PARTS=4 turns it on):
-  // measured no faster -- 37.2 against 36.9 ms at 65 536 items -- because the runtime's D2H copy of such a block is a blit kernel that
-  // covers the chip: k_table_pow_gt of the next part takes 5.3 instead of 1.3 ms under it.
-  static const size_t max_parts = [] { const char* e = getenv("RABE_AC17_ENC_PARTS"); const long v = e ? atol(e) : 1; return (size_t)(v > 0 ? v : 1); }();
-  const size_t parts = kem ? 1 : std::max<size_t>(1, std::min<size_t>(max_parts, n / 16384));
-  std::vector<PendingCopy> pending(parts);
-  if (parts > 1) eng.pinned_reserve((size_t)out_off[n] + parts * ((size_t)8 << 20) + 300 * n);          // staging of every part + their parameter packs: no growth inside the loop
-  // every part's row offsets (relative to the part's first row), uploaded once and asynchronously: nothing inside the loop may wait for
-  // the stream, or the host would queue part k + 1 only after part k has finished
-  std::vector<uint32_t> ro_all(n + parts);
-  std::vector<size_t> ro_at(parts);
-  for (size_t part = 0, at = 0; part < parts; part++) {
-    const size_t lo = n * part / parts, hi = n * (part + 1) / parts;
-    ro_at[part] = at;
-    for (size_t i = lo; i <= hi; i++) ro_all[at++] = row_off[i] - row_off[lo];
-  }
-  uint8_t* const h_ro = eng.pinned_bump(ro_all.size() * 4);
-  memcpy(h_ro, ro_all.data(), ro_all.size() * 4);
-  DBuf d_ro_all(&eng, ro_all.size() * 4);
-  eng.check(rhip_upload_async(cx, d_ro_all.ptr(), h_ro, ro_all.size() * 4), "upload");
-  for (size_t part = 0; part < parts; part++) {
-    const size_t lo = n * part / parts, hi = n * (part + 1) / parts, np = hi - lo;
-    const uint32_t* const ro = ro_all.data() + ro_at[part];
-    const uint32_t* const dro_p = d_ro_all.as<uint32_t>() + ro_at[part];
-    const size_t rows_p = ro[np];
-    rhip_g1* const dc_p = (rhip_g1*)(dc.as<uint8_t>() + 192ull * row_off[lo]);
-    eng.check(rhip_gt_table_pow(cx, egt, np, drho.as<rhip_fr>() + lo, dm.as<rhip_gt>() + lo), "rhip_gt_table_pow");
-    eng.check(rhip_ac17_cp_encrypt_batch(cx, dpk, np, dA.as<rhip_fr>(), dio.as<uint32_t>() + lo, dro_p, rows_p, ds.as<rhip_fr>() + 2 * lo,
-                                         dm.as<rhip_gt>() + lo, dc0.as<rhip_g2>() + 3 * lo, dc_p, dcp.as<rhip_gt>() + lo), "rhip_ac17_cp_encrypt_batch");
-    std::vector<uint64_t> src_off(3 * np);
-    for (size_t i = 0; i < np; i++) { src_off[i] = 384ull * i; src_off[np + i] = 192ull * ro[i]; src_off[2 * np + i] = 384ull * i; }
-    if (kem) {          // one part: headers from the template alone, keys straight out of the msg array -- no seal kernel is launched
-      DBuf d_keys(&eng, n * 32 + 4);
-      eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
-      eng.check(rhip_gt_kdf_batch(cx, n, dm.as<rhip_gt>(), nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
-      emit_plain_records(eng, layouts, n, item_policy, {dc0.ptr(), (const void*)dc_p, dcp.ptr()}, src_off, out_off, out_buf);
-      if (n) eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
-      continue;
-    }
-    emit_sealed_records(eng, layouts, np, item_policy + lo, {dc0.as<uint8_t>() + 384ull * lo, (const void*)dc_p, dcp.as<uint8_t>() + 384ull * lo}, src_off,
-                        dm.as<uint8_t>() + 384ull * lo, (const uint8_t*)nonces.data() + 12 * lo, pt_blob, pt_off + lo, out_off + lo, out_buf,
-                        parts > 1 ? &pending[part] : nullptr);
-  }
-  for (auto& pc : pending) pc.wait(eng);
-  tm.lap(kem ? "device: group arithmetic, headers, keys; two copies out" : "device: group arithmetic, records, sealing; copies out beside the next part");
-  return true;
-}
-
-static void* make_ac17_sk_lines(Engine& eng, const void* arg) {
-  const std::string& k0 = *(const std::string*)arg;
-  DBuf d(&eng, k0.data(), k0.size());
-  rhip_ac17_sk_lines* lines = nullptr;
-  eng.check(rhip_ac17_sk_prepare(eng.ctx(), 1, d.as<rhip_g2>(), &lines), "rhip_ac17_sk_prepare");
-  return lines;
-}
-static void destroy_ac17_sk_lines(void* h) { rhip_ac17_sk_lines_destroy((rhip_ac17_sk_lines*)h); }
-// status[i]: 0 ok, -1 the key does not satisfy the policy / malformed record / authentication failure (errors[i] says which).
-// pt_buf / pt_cap: caller-allocated; a capacity of ct_off[n] bytes always suffices (a plaintext is 28 bytes shorter than its sealed
-// form).  Returns false, before any work, when pt_cap is smaller than that.
-//
-// The records come from outside: the offsets are validated against ct_len before anything is read (monotone, inside the blob -- an
-// item whose own bounds are bad fails alone), and unless `trusted` is set every decoded element goes through one batched membership
-// pass on the GPU (coordinates < p, rows on the G1 curve, c_0 in the r-torsion of the twist, c_p in the order-r subgroup of Fq12:
-// what rabe-bn's decoding establishes, FieldError::NotMember) -- the Gt arithmetic downstream (cyclotomic squarings, conjugate as
-// inverse) is only valid inside the subgroup.  `trusted` is for ciphertexts this process produced itself.
-// KP-ABE's decrypt (:625-675) is the same product of pairings with the roles of the two sides' names swapped: the policy is the KEY's, the
-// attribute list the ciphertext's (its record starts with the attribute strings instead of policy text + language); k_p is absent.
-// plans of the packed decrypt, kept across calls: one bucket per key fingerprint (attributes or policy + row names), inside it one plan
-// per policy text.  A bucket that has grown past its cap is REPLACED (calls that still hold the old one finish on it).
-struct Ac17PolPlan {
-  std::string text; PolicyLanguage lang; std::string err; PrunedList lst; std::vector<uint32_t> sk_sel;
-  std::mutex mu; std::atomic<bool> have_rows{false}; std::vector<std::string> row_names; std::vector<uint32_t> ct_sel;
-};
-struct Ac17PlanBucket {
-  std::unordered_map<uint64_t, std::vector<std::shared_ptr<Ac17PolPlan>>> plans;
-  std::shared_mutex mu;
-  std::atomic<size_t> n{0};
-};
-struct Ac17PlanCache {
-  static std::shared_ptr<Ac17PlanBucket> get(const std::string& fingerprint) {
-    static std::mutex mu;
-    static std::unordered_map<std::string, std::shared_ptr<Ac17PlanBucket>> m;
-    std::lock_guard<std::mutex> g(mu);
-    if (m.size() > 64) m.clear();                                     // keys come and go: bounded
-    auto& b = m[fingerprint];
-    if (!b || b->n.load() > 4096) b = std::make_shared<Ac17PlanBucket>();       // policies come and go as well
-    return b;
-  }
-};
-struct DecKey {
-  const Ac17SecretKey& sk;
-  const std::vector<std::string>* cp_attrs;      // CP: the key's attributes; the policy comes with every ciphertext
-  const PolicyRef* kp_policy;                    // KP: the key's policy; the attributes come with every ciphertext
-};
-static bool decrypt_packed_core(Engine& eng, const DecKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                                int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors,
-                                uint8_t* key_buf = nullptr /* decaps: keys instead of plaintexts; pt_buf / pt_cap / pt_off unused */);
-bool cp_decrypt_packed(Engine& eng, const Ac17CpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                       int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
-  if (sk.sk.k_p.size() != 3) throw RabeError("malformed Ac17CpSecretKey");
-  return decrypt_packed_core(eng, DecKey{sk.sk, &sk.attr, nullptr}, n, ct_blob, ct_len, ct_off, trusted, status, pt_buf, pt_cap, pt_off, errors);
-}
-// Key decapsulation (include/rabe_host.h: rabe_ac17_cp_decaps_packed): cp_decrypt_packed up to the final Gt, then the KDF behind the verdict
-// mask (records.h: derive_keys) instead of gather + open.  The sealed part of a record is skipped by its length field and never read.
-void cp_decaps_packed(Engine& eng, const Ac17CpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                      int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
-  if (sk.sk.k_p.size() != 3) throw RabeError("malformed Ac17CpSecretKey");
-  if (n && (!status || !key_buf)) throw RabeError("cp_decaps_packed: null input");
-  uint8_t none = 0;          // n = 0: nothing is written
-  decrypt_packed_core(eng, DecKey{sk.sk, &sk.attr, nullptr}, n, ct_blob, ct_len, ct_off, trusted, status, nullptr, 0, nullptr, errors, key_buf ? key_buf : &none);
-}
-bool kp_decrypt_packed(Engine& eng, const Ac17KpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                       int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors) {
-  if (!(sk.sk.k_p.empty() || sk.sk.k_p.size() == 3)) throw RabeError("malformed Ac17KpSecretKey");
-  return decrypt_packed_core(eng, DecKey{sk.sk, nullptr, &sk.policy}, n, ct_blob, ct_len, ct_off, trusted, status, pt_buf, pt_cap, pt_off, errors);
-}
-// Key decapsulation over the KP pair (include/rabe_host.h: rabe_ac17_kp_decaps_packed), as cp_decaps_packed: kp_decrypt_packed up to the final Gt
-void kp_decaps_packed(Engine& eng, const Ac17KpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                      int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
-  if (!(sk.sk.k_p.empty() || sk.sk.k_p.size() == 3)) throw RabeError("malformed Ac17KpSecretKey");
-  if (n && (!status || !key_buf)) throw RabeError("kp_decaps_packed: null input");
-  uint8_t none = 0;          // n = 0: nothing is written
-  decrypt_packed_core(eng, DecKey{sk.sk, nullptr, &sk.policy}, n, ct_blob, ct_len, ct_off, trusted, status, nullptr, 0, nullptr, errors, key_buf ? key_buf : &none);
-}
-static bool decrypt_packed_core(Engine& eng, const DecKey& key, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                                int32_t* status, uint8_t* pt_buf, size_t pt_cap, uint64_t* pt_off, std::vector<std::string>* errors, uint8_t* key_buf) {
-  const bool kp = key.kp_policy != nullptr, kem = key_buf != nullptr;
-  const Ac17SecretKey& core = key.sk;
-  StageTimer tm(kem ? (kp ? "ac17::kp_decaps_packed" : "ac17::cp_decaps_packed") : kp ? "ac17::kp_decrypt_packed" : "ac17::cp_decrypt_packed");
-  Engine::ArenaScope arena(eng);
-  errors->assign(n, "");
-  if (!ct_off || (n && !ct_blob)) throw RabeError("cp_decrypt_packed: null input");
-  // bounds first: everything below trusts [ct_off[i], ct_off[i+1]) to lie inside the blob
-  uint64_t span = 0;
-  for (size_t i = 0; i < n; i++) {
-    if (ct_off[i] > ct_off[i + 1] || ct_off[i + 1] > ct_len) (*errors)[i] = "deserialize: record offsets are not monotone inside the blob";
-    else span += ct_off[i + 1] - ct_off[i];
-  }
-  if (!kem && (!pt_buf || pt_cap < span)) return false;
-  if (core.k_0.size() != 3) throw RabeError("malformed AC17 secret key");
-  for (const auto& row : core.k) if (row.second.size() != 3) throw RabeError("malformed AC17 secret key: a row does not have 3 elements");
-  PolicyNode kp_tree;                            // KP: the key's policy, parsed once (a policy that does not parse fails the call like kp_decrypt)
-  if (kp) kp_tree = parse_or_error(key.kp_policy->first, key.kp_policy->second);
-  // per distinct policy text (items of a batch repeat a few): the tree, the verdict for this key, the key-side selection and --
-  // for the row layout the first item with that policy shows -- the ciphertext-side selection.  The plans are a pure function of
-  // (key attributes / key policy, key row names, policy text): they are kept ACROSS calls (Ac17PlanCache above) -- a queue batch of a few
-  // dozen requests spent 1.5 of its 6 ms re-parsing and re-pruning the same sixteen policies.
-  typedef Ac17PolPlan PolPlan;
-  std::string fp(kp ? "K" : "C");
-  if (kp) { fp += key.kp_policy->first; fp.push_back((char)('0' + (int)key.kp_policy->second)); }
-  else for (const auto& a : *key.cp_attrs) { fp += a; fp.push_back('\x1f'); }
-  fp.push_back('\x1e');
-  for (const auto& row : core.k) { fp += row.first; fp.push_back('\x1f'); }
-  const std::shared_ptr<Ac17PlanBucket> bucket_owner = Ac17PlanCache::get(fp);
-  auto& plans = bucket_owner->plans;
-  std::shared_mutex& plans_mu = bucket_owner->mu;
-  // what a plan's shared row layout looks like in THIS call's gather (filled after the parse, serially)
-  struct PlanShape { int shape = -1; uint32_t e_c0 = 0, e_row0 = 0, e_cp = 0, e_rows = 0; };
-  std::unordered_map<const PolPlan*, PlanShape> shapes;
-  auto plan_of = [&](const uint8_t* txt, size_t len, PolicyLanguage lang) -> PolPlan* {
-    uint64_t h = 1469598103934665603ull ^ (uint64_t)lang;
-    for (size_t i = 0; i + 8 <= len; i += 8) { uint64_t w; memcpy(&w, txt + i, 8); h = (h ^ w) * 1099511628211ull; }
-    for (size_t i = len & ~(size_t)7; i < len; i++) h = (h ^ txt[i]) * 1099511628211ull;
-    {
-      std::shared_lock<std::shared_mutex> g(plans_mu);          // the common case: the policy has been seen, readers do not serialise
-      auto it = plans.find(h);
-      if (it != plans.end())
-        for (auto& e : it->second) if (e->lang == lang && e->text.size() == len && memcmp(e->text.data(), txt, len) == 0) return e.get();
-    }
-    std::unique_lock<std::shared_mutex> g(plans_mu);
-    auto& bucket = plans[h];
-    for (auto& e : bucket) if (e->lang == lang && e->text.size() == len && memcmp(e->text.data(), txt, len) == 0) return e.get();
-    auto e = std::make_shared<PolPlan>();
-    e->text.assign((const char*)txt, len);
-    e->lang = lang;
-    try {
-      if (kp) {                                  // e->text = the record's head: u32 count, then (u32 length, bytes) per attribute
-        std::vector<std::string> attrs;
-        const uint8_t* q = (const uint8_t*)e->text.data();
-        const uint32_t cnt = get_u32(q); q += 4;
-        for (uint32_t k = 0; k < cnt; k++) { const uint32_t l = get_u32(q); q += 4; attrs.emplace_back((const char*)q, l); q += l; }
-        if (!traverse_policy(attrs, kp_tree)) throw RabeError("Error in kp_decrypt: attributes in ct do not match policy in sk.");
-        if (!calc_pruned(attrs, kp_tree, &e->lst)) throw RabeError("Error in kp_decrypt: pruned attributes in sk do not match policy in ct.");
-      } else {
-        PolicyNode tree = parse_or_error(e->text, lang);
-        if (!traverse_policy(*key.cp_attrs, tree)) throw RabeError("Error in cp_decrypt: attributes in SK do not match policy in CT.");
-        if (!calc_pruned(*key.cp_attrs, tree, &e->lst)) throw RabeError("Error: attributes in sk do not match policy in ct.");
-      }
-      for (const auto& cur : e->lst)
-        for (size_t r = 0; r < core.k.size(); r++) if (core.k[r].first == cur.first) e->sk_sel.push_back((uint32_t)r);
-    } catch (const std::exception& ex) {
-      e->err = ex.what();
-      if (e->err.empty()) e->err = "policy error";
-    }
-    bucket.push_back(e);
-    bucket_owner->n++;
-    return e.get();
-  };
-  BlobGather gather(eng, ct_blob, ct_len);          // the blob starts for the device now, beside the parsing below (records.h)
-  struct View { const uint8_t* c0; const uint8_t* cp; const uint8_t* sealed; uint32_t sealed_len; uint32_t rows; const uint8_t* first_row;
-                std::vector<const uint8_t*> row_ptr; const std::vector<uint32_t>* ct_sel; const std::vector<uint32_t>* sk_sel;
-                std::vector<uint32_t> own_sel; PolPlan* plan = nullptr; };
-  std::vector<View> v(n);
-  parallel_for(n, [&](size_t i) {
-    if (!(*errors)[i].empty()) return;
-    try {
-      const uint8_t* p = ct_blob + ct_off[i];
-      const uint8_t* end = ct_blob + ct_off[i + 1];
-      auto need = [&](size_t k) { if ((size_t)(end - p) < k) throw RabeError("deserialize: truncated input"); };
-      const uint8_t* pol;                         // what the plan is keyed by: CP the policy text, KP the whole attribute head
-      uint32_t pl;
-      PolicyLanguage lang = PolicyLanguage::JsonPolicy;
-      if (kp) {
-        pol = p;
-        need(4); const uint32_t cnt = get_u32(p); p += 4;
-        if ((size_t)cnt * 4 > (size_t)(end - p)) throw RabeError("deserialize: truncated input");
-        for (uint32_t k = 0; k < cnt; k++) { need(4); const uint32_t l = get_u32(p); p += 4; need(l); p += l; }
-        pl = (uint32_t)(p - pol);
-      } else {
-        need(4); pl = get_u32(p); p += 4;
-        need((size_t)pl + 1);
-        pol = p; p += pl;
-        lang = *p++ ? PolicyLanguage::HumanPolicy : PolicyLanguage::JsonPolicy;
-      }
-      need(4 + 384); if (get_u32(p) != 3) throw RabeError("deserialize: c_0 does not have 3 elements"); p += 4;
-      v[i].c0 = p; p += 384;
-      need(4); const uint32_t rows = get_u32(p); p += 4;
-      if ((size_t)rows * 200 > (size_t)(end - p)) throw RabeError("deserialize: truncated input");
-      v[i].rows = rows;
-      v[i].row_ptr.resize(rows);
-      static thread_local std::vector<std::pair<const char*, uint32_t>> names;      // per-thread scratch: no allocation per item
-      names.resize(rows);
-      for (uint32_t r = 0; r < rows; r++) {
-        need(4); const uint32_t nl = get_u32(p); p += 4;
-        need((size_t)nl + 4 + 192);
-        names[r] = {(const char*)p, nl}; p += nl;
-        if (get_u32(p) != 3) throw RabeError("deserialize: an AC17 row does not have 3 elements"); p += 4;
-        v[i].row_ptr[r] = p; p += 192;
-      }
-      need(384 + 4); v[i].cp = p; p += 384;
-      v[i].sealed_len = get_u32(p); p += 4;
-      need(v[i].sealed_len);
-      v[i].sealed = p;
-      PolPlan* pp = plan_of(pol, pl, lang);
-      if (!pp->err.empty()) throw RabeError(pp->err);
-      v[i].sk_sel = &pp->sk_sel;
-      v[i].plan = pp;
-      auto select = [&](std::vector<uint32_t>* out) {          // the name-matching loop of ac17/mod.rs:403-408 as an index list
-        for (const auto& cur : pp->lst)
-          for (uint32_t r = 0; r < rows; r++)
-            if (names[r].second == cur.first.size() && memcmp(names[r].first, cur.first.data(), cur.first.size()) == 0) out->push_back(r);
-      };
-      bool shared = false;
-      if (!pp->have_rows.load(std::memory_order_acquire)) {
-        std::lock_guard<std::mutex> g(pp->mu);
-        if (!pp->have_rows.load(std::memory_order_relaxed)) {
-          for (uint32_t r = 0; r < rows; r++) pp->row_names.emplace_back(names[r].first, names[r].second);
-          select(&pp->ct_sel);
-          pp->have_rows.store(true, std::memory_order_release);
-        }
-      }
-      if (pp->row_names.size() == rows) {          // read-only from here on
-        shared = true;
-        for (uint32_t r = 0; r < rows && shared; r++)
-          shared = pp->row_names[r].size() == names[r].second && memcmp(pp->row_names[r].data(), names[r].first, names[r].second) == 0;
-      }
-      if (shared) v[i].ct_sel = &pp->ct_sel;
-      else { select(&v[i].own_sel); v[i].ct_sel = &v[i].own_sel; }
-    } catch (const std::exception& ex) {
-      (*errors)[i] = ex.what();
-      if ((*errors)[i].empty()) (*errors)[i] = "malformed record";
-    }
-  });
-  tm.lap("parse + plan");
-  std::vector<size_t> live;
-  for (size_t i = 0; i < n; i++) if ((*errors)[i].empty()) live.push_back(i);
-  const size_t m = live.size();
-  // offsets first (a scan), then the selection lists copied into place on all cores (65 536 items x ~30 entries x 2: 6 ms when serial)
-  std::vector<uint32_t> ct_row_off(m + 1, 0), ct_sel_off(m + 1, 0), sk_sel_off(m + 1, 0);
-  for (size_t j = 0; j < m; j++) {
-    const View& w = v[live[j]];
-    ct_row_off[j + 1] = ct_row_off[j] + w.rows;
-    ct_sel_off[j + 1] = ct_sel_off[j] + (uint32_t)w.ct_sel->size();
-    sk_sel_off[j + 1] = sk_sel_off[j] + (uint32_t)w.sk_sel->size();
-  }
-  // the lists themselves are written straight into pinned staging (65 536 items: 2 x 8 MB) and uploaded from there
-  const size_t n_ct_sel = ct_sel_off[m], n_sk_sel = sk_sel_off[m];
-  uint32_t* const ct_sel = (uint32_t*)eng.pinned_bump((n_ct_sel + n_sk_sel + 2) * 4);
-  uint32_t* const sk_sel = ct_sel + n_ct_sel + 1;
-  {
-    const size_t per = 1024, blocks = (m + per - 1) / per;
-    parallel_for(blocks, [&](size_t b) {
-      for (size_t j = b * per; j < m && j < (b + 1) * per; j++) {
-        const View& w = v[live[j]];
-        if (!w.ct_sel->empty()) memcpy(ct_sel + ct_sel_off[j], w.ct_sel->data(), w.ct_sel->size() * 4);
-        if (!w.sk_sel->empty()) memcpy(sk_sel + sk_sel_off[j], w.sk_sel->data(), w.sk_sel->size() * 4);
-      }
-    });
-  }
-  // uploaded at once: a later take from the same pinned block may move the block (Engine::pinned_bump waits for the stream first)
-  DBuf d_sel(&eng, (n_ct_sel + n_sk_sel + 2) * 4);
-  eng.check(rhip_upload_async(eng.ctx(), d_sel.ptr(), ct_sel, (n_ct_sel + n_sk_sel + 2) * 4), "upload (selection lists)");
-  const uint32_t* const d_ct_sel = d_sel.as<uint32_t>();
-  const uint32_t* const d_sk_sel = d_ct_sel + n_ct_sel + 1;
-  if (!m) {
-    if (kem) { for (size_t i = 0; i < n; i++) status[i] = -1; if (n) memset(key_buf, 0, n * 32); return true; }
-    pt_off[0] = 0;
-    for (size_t i = 0; i < n; i++) { pt_off[i + 1] = 0; status[i] = -1; }
-    return true;
-  }
-  const size_t total_rows = ct_row_off[m];
-  rhip_ctx* cx = eng.ctx();
-  // The elements are gathered out of the device copy of the blob.  Items that share a policy and its row names share one part list --
-  // their records have the same skeleton, hence the same relative offsets (checked on the ends); any other item brings its own.
-  std::vector<uint64_t> sealed_off(m);
-  std::vector<uint32_t> sealed_len(m);
-  auto parts_of = [&](const View& w, const uint8_t* rec) {
-    std::vector<RecordLayout::Part> parts;
-    parts.push_back({(uint32_t)(w.c0 - rec), 384, 0, 0});
-    for (uint32_t r = 0; r < w.rows; r++) parts.push_back({(uint32_t)(w.row_ptr[r] - rec), 192, 1, 192 * r});
-    parts.push_back({(uint32_t)(w.cp - rec), 384, 2, 0});
-    return parts;
-  };
-  for (size_t j = 0; j < m; j++) {
-    const View& w = v[live[j]];
-    const uint8_t* rec = ct_blob + ct_off[live[j]];
-    sealed_off[j] = (uint64_t)(w.sealed - ct_blob);
-    sealed_len[j] = w.sealed_len;
-    const uint32_t e_c0 = (uint32_t)(w.c0 - rec), e_row0 = w.rows ? (uint32_t)(w.row_ptr[0] - rec) : 0u, e_cp = (uint32_t)(w.cp - rec);
-    int shape = -1;
-    if (w.ct_sel != &w.own_sel) {                 // the plan's shared row layout: its shape is remembered in the plan itself
-      PlanShape& ps = shapes[w.plan];
-      if (ps.shape < 0) {
-        ps.shape = (int)gather.add_shape(nullptr, parts_of(w, rec));
-        ps.e_c0 = e_c0; ps.e_row0 = e_row0; ps.e_cp = e_cp; ps.e_rows = w.rows;
-      }
-      if (ps.e_c0 == e_c0 && ps.e_row0 == e_row0 && ps.e_cp == e_cp && ps.e_rows == w.rows) shape = ps.shape;
-    }
-    if (shape < 0) shape = (int)gather.add_shape(nullptr, parts_of(w, rec));
-    gather.item(ct_off[live[j]], (uint32_t)shape);
-  }
-  std::vector<uint8_t> k0 = flatten(core.k_0), kp_bytes = core.k_p.size() == 3 ? flatten(core.k_p) : std::vector<uint8_t>(3 * 64, 0), kk;   // KP: prod_h starts from G1::zero()
-  for (const auto& row : core.k) for (const auto& x : row.second) kk.insert(kk.end(), x.begin(), x.end());
-  if (kk.empty()) kk.assign(64, 0);
-  std::vector<uint32_t> sk_row_off{0, (uint32_t)core.k.size()}, sk_idx(m, 0);
-  DBuf d1(&eng, m * 384), d2(&eng, total_rows * 192 + 4), d4(&eng, m * 384), dout(&eng, m * 384);
-  std::vector<uint64_t> dst_off(3 * m);
-  for (size_t j = 0; j < m; j++) { dst_off[j] = 384ull * j; dst_off[m + j] = 192ull * ct_row_off[j]; dst_off[2 * m + j] = 384ull * j; }
-  ParamPack pp(eng);
-  const size_t h3 = pp.add(ct_row_off), h6 = pp.add(kk), h7 = pp.add(sk_row_off), h8 = pp.add(kp_bytes), h9 = pp.add(sk_idx),
-               h11 = pp.add(ct_sel_off), h13 = pp.add(sk_sel_off);
-  pp.upload();
-
-  tm.lap("selection tables");
-  gather.run({d1.ptr(), d2.ptr(), d4.ptr()}, dst_off);
-  const uint32_t* d3 = pp.dev<uint32_t>(h3);
-  // decoding checks over the gathered elements, on the side context beside the decrypt kernels; a non-member fails its item only (the
-  // batch still runs: the kernels terminate on any input, the item's result is discarded below)
-  std::unique_ptr<MemberChecks> mc;
-  std::unique_ptr<WalkedG2> walked;
-  DBuf seg_keep;
-  if (!trusted) {
-    mc.reset(new MemberChecks(eng));
-    mc->add(1, d2.ptr(), 3 * total_rows, d3, m, 3);
-    mc->add(3, d4.ptr(), m);
-    // c_0: the decrypt walks all three elements of every ciphertext -- their subgroup membership comes out of its Miller loops
-    if (walk_checks()) {
-      std::vector<uint32_t> seg(m + 1);
-      for (size_t j = 0; j <= m; j++) seg[j] = (uint32_t)j;
-      DBuf d_seg(&eng, (m + 1) * 4);
-      uint8_t* const hs = eng.pinned_bump((m + 1) * 4);
-      memcpy(hs, seg.data(), (m + 1) * 4);
-      eng.check(rhip_upload_async(cx, d_seg.ptr(), hs, (m + 1) * 4), "upload");
-      eng.check(rhip_ctx_wait_for(mc->ctx(), cx), "rhip_ctx_wait_for");
-      seg_keep = std::move(d_seg);
-      walked.reset(new WalkedG2(eng, *mc, d1.ptr(), 3 * m, seg_keep.as<uint32_t>(), seg, 3));
-    } else {
-      mc->add(2, d1.ptr(), 3 * m);
-    }
-  }
-  // the key's prepared k_0 lines are a function of the key alone: kept across calls (a server decrypts with the same key again and again)
-  std::string k0_key((const char*)k0.data(), k0.size());
-  rhip_ac17_sk_lines* lines = (rhip_ac17_sk_lines*)eng.aux("ac17_sk_lines", k0_key, make_ac17_sk_lines, &k0_key, destroy_ac17_sk_lines, 4);
-  if (walked) walked->arm();
-  eng.check(rhip_ac17_cp_decrypt_batch_prepared(cx, m, d1.as<rhip_g2>(), d2.as<rhip_g1>(), d3, d4.as<rhip_gt>(), lines, pp.dev<rhip_g1>(h6),
-                                                pp.dev<uint32_t>(h7), pp.dev<rhip_g1>(h8), pp.dev<uint32_t>(h9), d_ct_sel,
-                                                pp.dev<uint32_t>(h11), d_sk_sel, pp.dev<uint32_t>(h13), dout.as<rhip_gt>()),
-            "rhip_ac17_cp_decrypt_batch_prepared");
-  if (mc) {
-    mc->collect();
-    const auto &ok_rows = mc->ok(0), &ok_cp = mc->ok(1);
-    std::vector<uint8_t> ok_c0(m, 1);
-    if (!walked) { const auto& e = mc->ok(2); for (size_t j = 0; j < m; j++) for (int t = 0; t < 3; t++) if (!e[3 * j + t]) ok_c0[j] = 0; }
-    for (size_t j = 0; j < m; j++) {
-      const char* bad = !ok_c0[j] ? "deserialize: c_0 element is not a member of G2 (FieldError::NotMember)" : nullptr;
-      if (!bad && !ok_rows[j]) bad = "deserialize: a row element is not a point of G1 (FieldError::NotMember)";
-      if (!bad && !ok_cp[j]) bad = "deserialize: c_p is not a member of Gt (FieldError::NotMember)";
-      if (bad) (*errors)[live[j]] = bad;
-    }
-  }
-  if (kem) {          // every verdict first (there is no open to queue behind the pairings), then the KDF behind their mask: 32 n bytes come back
-    if (walked) {
-      std::vector<uint8_t> ok_c0;
-      walked->finish(&ok_c0);
-      for (size_t j = 0; j < m; j++) if (!ok_c0[j]) (*errors)[live[j]] = "deserialize: c_0 element is not a member of G2 (FieldError::NotMember)";
-    }
-    derive_keys(eng, n, live, dout.ptr(), status, key_buf, *errors);
-    tm.lap(trusted ? "device: gather, pairings, keys" : "device: gather, pairings, keys; membership beside");
-    return true;
-  }
-  // KDF + AES-GCM open on the device: the decrypted Gt never leaves HBM; plaintext bytes come back in one copy
-  open_sealed_records(eng, n, live, dout.ptr(), gather.dev_blob(), sealed_off, sealed_len, status, pt_buf, pt_off, errors);
-  if (walked) {          // the walk's verdicts are read AFTER the open was queued behind the pairings (records.h: retract_item)
-    std::vector<uint8_t> ok_c0;
-    walked->finish(&ok_c0);
-    for (size_t j = 0; j < m; j++)
-      if (!ok_c0[j]) retract_item(live[j], "deserialize: c_0 element is not a member of G2 (FieldError::NotMember)", status, pt_buf, pt_off, errors);
-  }
-  tm.lap(trusted ? "device: gather, pairings, open" : "device: gather, pairings, open; membership beside");
-  return true;
-}
-
 // ---------------------------------------------------------------------------------------------- KP-ABE
 // The Fr half of kp_keygen (:455-538) for one key: 3 scalars per MSP row (multiples of g), in row order, and br = (b0 r0, b1 r1, r0 + r1)
 // (multiples of h).  `hashes`: the label hashes of a policy -- rows h(pi_i || l || t) then columns h("0" || j || l || t), l major -- which do
 // not depend on the key.
-struct KpPolicy { AbePolicy msp; std::vector<Fr> row_h /*[rows][t][l]*/, col_h /*[cols][t][l], j = 0 unused*/; };
-static KpPolicy kp_policy(const std::string& policy, PolicyLanguage lang) {
+KpPolicy kp_policy(const std::string& policy, PolicyLanguage lang) {
   KpPolicy kp;
   kp.msp = calculate_msp(parse_or_error(policy, lang));
   const size_t cols = kp.msp.m[0].size(), rows = kp.msp.m.size();
@@ -1803,7 +1217,7 @@ static KpPolicy kp_policy(const std::string& policy, PolicyLanguage lang) {
       for (int l = 0; l < 3; l++) kp.row_h[(i * 2 + t) * 3 + l] = sha3_hash_fr(kp.msp.pi[i] + std::to_string(l) + std::to_string(t));
   return kp;
 }
-static void kp_keygen_scalars(const Ac17MasterKey& msk, const KpPolicy& kp, const Fr a_inv[2], const Fr& r0, const Fr& r1, const Fr* sigma_prime,
+void kp_keygen_scalars(const Ac17MasterKey& msk, const KpPolicy& kp, const Fr a_inv[2], const Fr& r0, const Fr& r1, const Fr* sigma_prime,
                               const Fr* sigma, Fr* scal /*[3 rows]*/, Fr br[3]) {
   const AbePolicy& msp = kp.msp;
   const size_t cols = msp.m[0].size(), rows = msp.m.size();
@@ -1873,88 +1287,6 @@ Ac17KpSecretKey kp_keygen(Engine& eng, Rng& rng, const Ac17MasterKey& msk, const
   for (size_t i = 0; i < rows; i++) out.sk.k.push_back({msp.pi[i], {pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]}});
   return out;
 }
-// n calls of ac17::kp_keygen (:439-547) under one master key: item i's policy = policies[item_policy[i]].  Draw order per item as above.
-// The Fr half runs on all host cores; the group half is ONE fixed-base launch per group (window tables of msk.g / msk.h, kept across
-// calls), one batched addition for the rows whose first MSP column is +/-1 (+/- g_k), and the records are written on the device.
-// Record = Ac17KpSecretKey: policy text, language, k_0 (3 G2), rows (name, 3 G1), an empty k_p.  Buffers as cp_keygen_packed.
-bool kp_keygen_packed(Engine& eng, Rng& rng, const Ac17MasterKey& msk, const std::vector<std::string>& policies, PolicyLanguage lang, size_t n,
-                      const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  StageTimer tm("ac17::kp_keygen_packed");
-  Engine::ArenaScope arena(eng);
-  eng.scrub_when_done();          // master-key-derived scalars pass through the staging buffers
-  if (msk.a.size() != 2 || msk.b.size() != 2 || msk.g_k.size() != 3) throw RabeError("malformed Ac17MasterKey: a, b must have 2 and g_k 3 elements");
-  if (n && (!item_policy || !out_off)) throw RabeError("kp_keygen_packed: null input");
-  std::vector<KpPolicy> kps;
-  std::vector<RecordLayout> layouts(policies.size());
-  for (size_t p_ = 0; p_ < policies.size(); p_++) {
-    kps.push_back(kp_policy(policies[p_], lang));
-    RecordLayout& L = layouts[p_];
-    const AbePolicy& msp = kps.back().msp;
-    policy_header(L, policies[p_], lang);
-    L.u32(3);
-    L.src(0, 0, 384);
-    L.u32((uint32_t)msp.m.size());
-    for (size_t r = 0; r < msp.m.size(); r++) { L.str(msp.pi[r]); L.u32(3); L.src(1, (uint32_t)(192 * r), 192); }
-    L.u32(0);                                   // k_p: empty for a KP key
-  }
-  if (!record_offsets("kp_keygen_packed", "item_policy", n, item_policy, policies.size(), [&](size_t i) { return layouts[item_policy[i]].bytes(); }, nullptr,
-                      out_buf, out_cap, out_off)) return false;
-  if (!n) return true;
-  std::vector<uint32_t> row_off(n + 1, 0), draw_off(n + 1, 0);
-  for (size_t i = 0; i < n; i++) {
-    const AbePolicy& msp = kps[item_policy[i]].msp;
-    row_off[i + 1] = row_off[i] + (uint32_t)msp.m.size();
-    draw_off[i + 1] = draw_off[i] + 2 + (uint32_t)(msp.m[0].size() - 1) + (uint32_t)msp.m.size();
-  }
-  const size_t total_rows = row_off[n];
-  std::vector<Fr> draws(draw_off[n] + 1);
-  draw_items(rng, n, 1024, 256, [&](Rng& r, size_t i) { for (uint32_t d = draw_off[i]; d < draw_off[i + 1]; d++) draws[d] = r.next_fr(); });
-  tm.lap("policies + draws");
-  Fr a_inv[2] = {must_inv(msk.a[0]), must_inv(msk.a[1])};
-  uint8_t* h_scal = eng.pinned(0, total_rows * 96 + n * 96 + 32);          // row scalars | br
-  uint8_t* h_br = h_scal + total_rows * 96;
-  uint8_t* h_add = eng.pinned(1, total_rows * 192 + 4);                     // +/- g_k[t] per row element, the point at infinity where nothing is added
-  G1 neg_gk[3];
-  {
-    std::vector<G1> ng = eng.g1_mul(msk.g_k, std::vector<Fr>(3, fr_neg(fr_one())));
-    for (int t = 0; t < 3; t++) neg_gk[t] = ng[t];
-  }
-  parallel_for(n, [&](size_t i) {
-    const KpPolicy& kp = kps[item_policy[i]];
-    const size_t cols = kp.msp.m[0].size(), rows = kp.msp.m.size();
-    const Fr* d = draws.data() + draw_off[i];
-    std::vector<Fr> scal(3 * rows);
-    Fr br[3];
-    kp_keygen_scalars(msk, kp, a_inv, d[0], d[1], d + 2, d + 2 + (cols - 1), scal.data(), br);
-    memcpy(h_scal + 96 * (size_t)row_off[i], scal.data(), 96 * rows);
-    memcpy(h_br + 96 * i, br, 96);
-    uint8_t* ad = h_add + 192 * (size_t)row_off[i];
-    for (size_t r = 0; r < rows; r++)
-      for (int t = 0; t < 3; t++) {
-        const int8_t c = kp.msp.m[r][0];
-        if (c == 0) memset(ad + 192 * r + 64 * t, 0, 64);
-        else memcpy(ad + 192 * r + 64 * t, (c == 1 ? msk.g_k[t] : neg_gk[t]).data(), 64);
-      }
-  });
-  tm.lap("scalars");
-  rhip_g1_table* gt = nullptr;
-  rhip_g2_table* ht = nullptr;
-  msk_tables(eng, msk, &gt, &ht);
-  rhip_ctx* cx = eng.ctx();
-  DBuf d_scal(&eng, total_rows * 96 + n * 96), d_add(&eng, total_rows * 192 + 4), d_pts(&eng, total_rows * 192 + 4), d_k(&eng, total_rows * 192 + 4),
-      d_k0(&eng, n * 384);
-  eng.check(rhip_upload_async(cx, d_scal.ptr(), h_scal, total_rows * 96 + n * 96), "upload");
-  eng.check(rhip_upload_async(cx, d_add.ptr(), h_add, total_rows * 192), "upload");
-  eng.check(rhip_g1_table_mul(cx, gt, 3 * total_rows, d_scal.as<rhip_fr>(), d_pts.as<rhip_g1>()), "rhip_g1_table_mul");
-  eng.check(rhip_g1_add(cx, 3 * total_rows, d_pts.as<rhip_g1>(), d_add.as<rhip_g1>(), d_k.as<rhip_g1>()), "rhip_g1_add");
-  eng.check(rhip_g2_table_mul(cx, ht, 3 * n, (const rhip_fr*)(d_scal.as<uint8_t>() + total_rows * 96), d_k0.as<rhip_g2>()), "rhip_g2_table_mul");
-  std::vector<uint64_t> src_off(2 * n);
-  for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * i; src_off[n + i] = 192ull * row_off[i]; }
-  emit_plain_records(eng, layouts, n, item_policy, {d_k0.ptr(), d_k.ptr()}, src_off, out_off, out_buf);
-  tm.lap("device: fixed-base multiplications, records; one copy out");
-  return true;
-}
-
 std::vector<Ac17KpCiphertext> kp_encrypt_batch(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::vector<std::string>>& attribute_sets,
                                                const std::vector<Bytes>& datas) {   // :556-616, n times
   if (attribute_sets.size() != datas.size()) throw RabeError("kp_encrypt_batch: attribute sets / datas length mismatch");

@@ -11,7 +11,9 @@
 #pragma once
 #include "common.h"
 
-namespace rabe { namespace schemes {
+namespace rabe {
+Fr must_inv(const Fr& a);          // schemes.cpp (internal): the reference's `.inverse().unwrap()`
+namespace schemes {
 
 typedef std::pair<std::string, PolicyLanguage> PolicyRef;
 // per item of a *_decrypt_batch: ok flag + plaintext or error text (a non-matching key fails its item, not the batch)
@@ -41,7 +43,7 @@ void msk_tables(Engine& eng, const Ac17MasterKey& msk, rhip_g1_table** g, rhip_g
 // n keys under one master key in one call (packed.cpp): item i gets the attribute list sets[item_set[i]]; records = Ac17CpSecretKey
 bool cp_keygen_packed(Engine& eng, Rng& rng, const Ac17MasterKey& msk, const std::vector<std::vector<std::string>>& sets, size_t n,
                       const uint32_t* item_set, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
-// packed forms: n ciphertexts = one blob of canonical records + offsets (schemes.cpp: "packed batches")
+// packed forms: n ciphertexts = one blob of canonical records + offsets (packed.cpp: "packed batches")
 bool cp_encrypt_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
                        const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
 bool cp_decrypt_packed(Engine& eng, const Ac17CpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
@@ -67,7 +69,7 @@ Bytes kp_decrypt(Engine& eng, const Ac17KpSecretKey& sk, const Ac17KpCiphertext&
 Gt kp_decrypt_gt(Engine& eng, const Ac17KpSecretKey& sk, const Ac17KpCiphertext& ct);
 std::vector<Ac17KpCiphertext> kp_encrypt_batch(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::vector<std::string>>& attribute_sets,
                                                const std::vector<Bytes>& datas);
-// packed forms of the KP pair (schemes.cpp: the CP entry points with the record head and the roles of the names swapped)
+// packed forms of the KP pair (packed.cpp: the CP entry points with the record head and the roles of the names swapped)
 bool kp_encrypt_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
                        const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
 bool kp_decrypt_packed(Engine& eng, const Ac17KpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
@@ -78,6 +80,12 @@ bool kp_encaps_packed(Engine& eng, Rng& rng, const Ac17PublicKey& pk, const std:
 void kp_decaps_packed(Engine& eng, const Ac17KpSecretKey& sk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                       int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors);
 std::vector<DecryptResult> kp_decrypt_batch(Engine& eng, const std::vector<const Ac17KpSecretKey*>& sks, const std::vector<const Ac17KpCiphertext*>& cts);
+// ---- internal: defined in schemes.cpp, used by the packed forms in packed.cpp as well; no part of the scheme API
+std::vector<Fr> policy_table(const host::AbePolicy& msp);          // per-policy Fr table A[row][l][t] of the encrypt row kernel
+struct KpPolicy { host::AbePolicy msp; std::vector<Fr> row_h /*[rows][t][l]*/, col_h /*[cols][t][l], j = 0 unused*/; };
+KpPolicy kp_policy(const std::string& policy, PolicyLanguage lang);
+void kp_keygen_scalars(const Ac17MasterKey& msk, const KpPolicy& kp, const Fr a_inv[2], const Fr& r0, const Fr& r1, const Fr* sigma_prime,
+                       const Fr* sigma, Fr* scal /*[3 rows]*/, Fr br[3]);
 }  // namespace ac17
 
 namespace bsw {
