@@ -634,6 +634,23 @@ int32_t rhip_dnf_encrypt_batch(rhip_ctx* ctx, const rhip_dnf_pk* pk, size_t n_se
                                const uint32_t* dev_row_term /*[n_rows]*/, const uint32_t* dev_row_item /*[n_rows]*/, const rhip_fr* dev_r /*[n_rows]*/,
                                const rhip_gt* dev_msg /*[n_gt][n_items]*/, rhip_gt* dev_gt /*[n_rows][n_gt]*/, rhip_g1* dev_g1 /*[n_rows][2]*/,
                                rhip_g2* dev_g2 /*[n_rows][2]*/);
+/* BDABE / MKE08 decrypt (bdabe/mod.rs:377-380, mke08/mod.rs:385-388) of n_items ciphertext conjunctions under ONE user key, in the four-pair
+ * form: with S1 = sum au1_k and S2 = sum au2_k over the conjunction's attribute keys (sums of the KEY's elements: fixed per distinct
+ * conjunction, a CLASS, stated by the caller)
+ *   out[i] = lead[i] * e(e2, S2) * e(S1, e3) * e(-e4, u2) * e(-u1, e5)          (MKE08: lead = j1 j2; e2 .. e5 = j3 .. j6)
+ * which is the element the per-attribute form prod_k e(e2, au2_k) ... gives (rhip_pairing_jobs as the host's plan_term fills it).  Four Miller
+ * loops per item whatever the conjunction's length: pairs 0 and 2 replay prepared lines -- key_lines = rhip_g2_lines_prepare over
+ * [sk.u2, S2_0, S2_1, ...], block 0 the user key's u2 and block 1 + c the S2 of class c -- and pairs 1 and 3 walk the item's own e3 and e5,
+ * whose membership verdicts rhip_ctx_collect_walk_verdicts hands out.  dev_class_skip[c]: bit 0 = S1 of the class is the identity, bit 1 =
+ * S2 is (dev_class_s1[c] is not read then); a pair with an argument at infinity -- those two, a ciphertext element, u1 or u2 -- contributes 1.
+ * dev_item_class[i] < n_classes (an item that names no class has all four pairs skipped).  One gather kernel (k_dnf_dec_pairs: uniform pair
+ * map, four pairs per item, no scalar multiplication), then the Miller dispatch and the final exponentiation of every multi-pairing launch.
+ * dev_lead may be NULL (no leading factor) or dev_out (in place). */
+int32_t rhip_dnf_decrypt_batch_one_uk(rhip_ctx* ctx, size_t n_items, size_t n_classes, const uint32_t* dev_item_class /*[n_items]*/,
+                                      const rhip_g1* dev_class_s1 /*[n_classes]*/, const uint8_t* dev_class_skip /*[n_classes]: bit 0 S1 = O, bit 1 S2 = O*/,
+                                      const rhip_g1* dev_neg_u1 /*[1]*/, const rhip_g2_lines* key_lines /* block 0: sk.u2, block 1 + c: S2 of class c */,
+                                      const rhip_g1* dev_ct_g1 /*[n_items][2]: e2, e4*/, const rhip_g2* dev_ct_g2 /*[n_items][2]: e3, e5*/,
+                                      const rhip_gt* dev_lead /*[n_items]*/, rhip_gt* dev_out /*[n_items]*/);
 
 /* ---- Level B: AW11 multi-authority CP-ABE (src/schemes/aw11/mod.rs) -----------------------------------------------
  * rhip_aw11_pk: gk (g1, g2), the constant e(g1, g2) and, for each of the n_attrs attributes of the authorities in play,

@@ -51,7 +51,8 @@ int32_t rabe_host_create(int32_t device, rabe_host** out);
  *   the AW11 KEM: rabe_aw11_encaps_packed, rabe_aw11_decaps_packed;
  *   the GHW11 service: rabe_ghw11_encrypt_packed, rabe_ghw11_transform_packed, rabe_ghw11_decrypt_out_packed, rabe_ghw11_decrypt_packed,
  *     rabe_ghw11_keygen_packed, rabe_ghw11_provision_packed;
- *   the DNF schemes' encrypt: rabe_bdabe_encrypt_packed, rabe_mke08_encrypt_packed.
+ *   the DNF schemes' encrypt: rabe_bdabe_encrypt_packed, rabe_mke08_encrypt_packed;
+ *   the DNF schemes' KEM: rabe_bdabe_kem_encaps, rabe_bdabe_kem_decaps, rabe_mke08_kem_encaps, rabe_mke08_kem_decaps.
  * Each cuts its n_items into one contiguous block per device (sizes differ by at most one, blocks in device order; fewer items than
  * devices: one item each for the first), runs every block on its own host thread with its engine's device current (each device builds its
  * replica of a key's window tables / prepared lines on first use and keeps it), and the records / plaintexts / fixed-size slots (the
@@ -574,6 +575,37 @@ int32_t rabe_mke08_encrypt_packed(rabe_host* h, const void* pk, const void* cons
                                   const char* const* policies, size_t n_policies, int32_t language, size_t n_items,
                                   const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off,
                                   uint8_t* ct_buf, size_t ct_cap, uint64_t* ct_off);
+/* Key encapsulation for bdabe / mke08: everything said at rabe_ac17_cp_{encaps,decaps}_packed about the format, the key (SHA3-256(bytes(Gt))),
+ * the failure of an item alone (status -1, 32 zero bytes, the first error's text), the bounds and the scrubbed staging, with BdabeCiphertext /
+ * Mke08Ciphertext records and rabe_{bdabe,mke08}_decrypt_gt as the definition of X.  Compositions: the reference has neither function.  (The
+ * names do not end in _packed: the table of rabe_*_packed symbols is a recorded contract; the calls are packed calls in every other respect.)
+ * ENCAPS: arguments of rabe_{bdabe,mke08}_encrypt_packed minus the payloads, plus key_buf.  Header i is the record encrypt_packed writes for the
+ *   same draws with a sealed part of length zero; key i = SHA3-256(bytes(msg_i)) (MKE08: msg = msg1 * msg2, the element encrypt_packed seals
+ *   under).  DRAW ORDER: encrypt_packed's minus the AES nonce -- BDABE a, b, the r_j; MKE08 a, b, c, the r_j.  Call-level errors, hdr_off and
+ *   the return of 1 on a short buffer (nothing drawn) are encrypt_packed's.  The launch set is rhip_dnf_encrypt_batch; no AES kernel is launched.
+ * DECAPS: ONE user key against n_items records; headers and full records are both valid input, the sealed part is skipped by its length field,
+ *   neither read nor authenticated.  Item verdicts are those of rabe_{bdabe,mke08}_decrypt_packed's decoding (bounds, a malformed record,
+ *   trailing bytes; unless RABE_PACKED_TRUSTED a non-member among ANY decoded element of the record, the conjunctions that are not chosen
+ *   included) and of the reference's traverse_policy ("attributes in sk do not match policy in ct").  ONE DIFFERENCE from decrypt_gt: a record
+ *   whose policy text the key satisfies but none of whose conjunction lists it does fails with a message of its own -- decrypt_gt returns
+ *   Gt::one() there, which the AES layer of a decrypt then rejects; a KEM has no such layer and must not hand out the KDF of one.
+ *   The chosen conjunction is the first in record order whose names the key holds; its attribute list as stated (order and repetitions
+ *   included) is its CLASS.  Per class S1 = sum au1, S2 = sum au2 over the first key row of each name, on the device; per call one set of
+ *   prepared lines over [sk.u2, S2 of every class]; then FOUR Miller loops per item whatever the conjunction's length
+ *   (rhip_dnf_decrypt_batch_one_uk: e(e2, S2) and e(-e4, u2) on prepared lines, e(S1, e3) and e(-u1, e5) walked, their walks giving the
+ *   membership verdicts of e3 and e5) where rabe_*_decrypt_packed runs m + 3, the KDF behind the verdict mask and one download of
+ *   32 n_items bytes.  No Gt element crosses PCIe.
+ * Both calls are cut over a device group (encaps like encrypt_packed; decaps block by block, each engine with its own lines). */
+int32_t rabe_bdabe_kem_encaps(rabe_host* h, const void* pk, const void* const* attr_pks, size_t n_pks, const char* const* policies, size_t n_policies,
+                              int32_t language, size_t n_items, const uint32_t* item_policy /*[n_items]*/, uint8_t* hdr_buf, size_t hdr_cap,
+                              uint64_t* hdr_off /*[n_items+1]*/, uint8_t* key_buf /*32 n_items*/);
+int32_t rabe_bdabe_kem_decaps(rabe_host* h, const void* uk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off /*[n_items+1]*/,
+                              uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* key_buf /*32 n_items*/);
+int32_t rabe_mke08_kem_encaps(rabe_host* h, const void* pk, const void* const* attr_pks, size_t n_pks, const char* const* policies, size_t n_policies,
+                              int32_t language, size_t n_items, const uint32_t* item_policy /*[n_items]*/, uint8_t* hdr_buf, size_t hdr_cap,
+                              uint64_t* hdr_off /*[n_items+1]*/, uint8_t* key_buf /*32 n_items*/);
+int32_t rabe_mke08_kem_decaps(rabe_host* h, const void* uk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off /*[n_items+1]*/,
+                              uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* key_buf /*32 n_items*/);
 /* Bulk key issuing of the two schemes (conventions of rabe_ghw11_keygen_packed / rabe_ghw11_tkgen_packed).
  * keygen_packed: n_items calls of keygen (bdabe/mod.rs:201-222, mke08/mod.rs:185-206) under one authority key (MKE08: the master key), item i
  * for the user names[i].  Record i = rabe_obj_serialize's bytes of the user key with an empty sk_a: sk.u1 | sk.u2 | name | pk.u1 | pk.u2 | u32 0.

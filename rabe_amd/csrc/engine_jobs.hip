@@ -2277,6 +2277,58 @@ extern "C" int32_t rhip_dnf_encrypt_batch(rhip_ctx* ctx, const rhip_dnf_pk* pk, 
   return RHIP_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ BDABE / MKE08 decrypt under one user key
+// bdabe::decrypt :377-380 / mke08::decrypt :385-388 in the four-pair form (include/rabe_hip.h: rhip_dnf_decrypt_batch_one_uk): item i owns
+//   4i     : P =  e2,          Q = S2 of the item's class   (prepared lines, block 1 + class)
+//   4i + 1 : P =  S1[class],   Q = e3                       (walked)
+//   4i + 2 : P = -e4,          Q = sk.u2                    (prepared lines, block 0)
+//   4i + 3 : P = -u1,          Q = e5                       (walked)
+// The uniform pair map with ppi = 4: a wave holds pair j of 64 neighbouring items, so its lanes take one branch and read neighbouring elements
+// of one array (e2 / e4 at a stride of two G1, e3 / e5 at a stride of two G2; S1 and -u1 are one or a few addresses for the whole wave).
+// Wire form -> affine Montgomery, the negation a field negation of y: no scalar, no NAF chain, hence no inversion and no LDS.
+__global__ void __launch_bounds__(RB_PAIRS_BLOCK, RB_MIN_WAVES) k_dnf_dec_pairs(size_t n_items, size_t n_classes, const uint32_t* item_class, const rhip_g1* class_s1,
+                                                                                const uint8_t* class_skip, const rhip_g1* neg_u1, const uint8_t* line_inf,
+                                                                                const rhip_g1* ct_g1, const rhip_g2* ct_g2, G1M* P, G2M* Q, uint32_t* qref) {
+  size_t t, item;
+  bool active;
+  pair_lane((size_t)blockIdx.x * blockDim.x + threadIdx.x, n_items, n_items * 4, (const uint32_t*)nullptr, 4, (const uint32_t*)nullptr, &t, &item, &active);
+  if (!active) return;
+  const uint32_t j = (uint32_t)(t & 3);
+  const uint32_t c = item_class[item];
+  if (c >= n_classes) { qref[t] = RHIP_Q_SKIP; return; }
+  if ((j & 1) == 0) {          // a ciphertext G1 element against prepared lines of the key
+    G1Aff p = load_g1(ct_g1[2 * item + (j >> 1)].l);
+    const uint32_t line = j ? 0u : 1u + c;
+    const bool skip = aff_is_inf(p) || line_inf[line] || (!j && (class_skip[c] & 2));
+    if (j) p.y = neg(p.y);
+    if (!skip) st_g1_q(P + t, p);
+    qref[t] = skip ? RHIP_Q_SKIP : line;
+    return;
+  }
+  // a G1 element of the key against a walked ciphertext G2 element
+  const bool key_inf = j == 1 && (class_skip[c] & 1);
+  const G1Aff p = key_inf ? aff_inf<Fp>() : load_g1((j == 1 ? class_s1 + c : neg_u1)->l);
+  const G2Aff q = load_g2(ct_g2[2 * item + (j >> 1)].l);
+  const bool skip = aff_is_inf(p) || aff_is_inf(q);
+  if (!skip) { st_g1_q(P + t, p); st_g2_q(Q + t, q); }
+  qref[t] = skip ? RHIP_Q_SKIP : RHIP_Q_WALK;
+}
+extern "C" int32_t rhip_dnf_decrypt_batch_one_uk(rhip_ctx* ctx, size_t n_items, size_t n_classes, const uint32_t* item_class, const rhip_g1* class_s1,
+                                                 const uint8_t* class_skip, const rhip_g1* neg_u1, const rhip_g2_lines* key_lines, const rhip_g1* ct_g1,
+                                                 const rhip_g2* ct_g2, const rhip_gt* lead, rhip_gt* out) {
+  NEED(ctx);
+  if (!n_items) return RHIP_OK;
+  if (!n_classes || !item_class || !class_s1 || !class_skip || !neg_u1 || !key_lines || key_lines->n < n_classes + 1 || !ct_g1 || !ct_g2 || !out ||
+      n_items >= ((size_t)1 << 30) || n_classes >= ((size_t)1 << 30))
+    return RHIP_ERR_ARG;
+  PairLists pl;
+  RC_TRY(alloc_pair_lists(ctx, n_items * 4, &pl));
+  KLAUNCH(ctx, "k_dnf_dec_pairs", k_dnf_dec_pairs, dim3(blocks_for(pair_lanes(n_items, n_items * 4, 4), RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items,
+          n_classes, item_class, class_s1, class_skip, neg_u1, (const uint8_t*)key_lines->q_inf, ct_g1, ct_g2, pl.P, pl.Q, pl.qref);
+  // every item owns four pairs: the fixed Miller geometry, as the AC17 decrypt on shared accumulators passes its six
+  return run_pair_lists(ctx, n_items, (const uint32_t*)nullptr, 4, 0, pl, (const LineM*)key_lines->lines, key_lines->lines29, lead, out);
+}
+
 // ------------------------------------------------------------------------------------------------ membership of decoded elements
 // What a decoder has to establish before an untrusted key / ciphertext reaches the pairing kernels (rabe-bn's decoding
 // raises FieldError::NotMember, src/error.rs:66): G1 has cofactor 1 (on-curve is enough: rhip_g1_on_curve); the twist has

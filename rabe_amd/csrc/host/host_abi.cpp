@@ -1807,6 +1807,33 @@ int32_t rabe_mke08_encrypt_packed(rabe_host* h, const void* pk, const void* cons
       [](auto&&... a) { return mke08::encrypt_packed(a...); });
   GUARD_END(h)
 }
+// key encapsulation over the DNF pair.  Encaps is cut over a device group where rabe_{bdabe,mke08}_encrypt_packed are cut; decaps block by block
+// through decaps_shape (every engine sums its own classes and prepares its own lines) -- rabe_{bdabe,mke08}_decrypt_packed stay on devices[0]
+#define DNF_KEM(SCHEME, PK, APK, UK)                                                                                                        \
+  int32_t rabe_##SCHEME##_kem_encaps(rabe_host* h, const void* pk, const void* const* attr_pks, size_t n_pks, const char* const* policies,  \
+                                     size_t n_policies, int32_t language, size_t n_items, const uint32_t* item_policy, uint8_t* hdr_buf,    \
+                                     size_t hdr_cap, uint64_t* hdr_off, uint8_t* key_buf) {                                                 \
+    GUARD_BEGIN                                                                                                                             \
+    require(item_policy && hdr_off, #SCHEME "::encaps_packed: null input");                                                                 \
+    const auto v = key_ptrs<SCHEME::APK>(attr_pks, n_pks);                                                                                  \
+    const auto& key = *(const SCHEME::PK*)pk;                                                                                               \
+    const auto pols = strs(policies, n_policies);                                                                                           \
+    const auto lang = lang_of(language);                                                                                                    \
+    return produce_shape(h, h->engines_if(key_buf != nullptr), CHUNK_DNF, n_items, item_policy, nullptr, hdr_buf, hdr_cap, hdr_off, key_buf, \
+                         [&](const ProduceBlock& b) { return SCHEME::encaps_packed(b.eng, b.rng, key, v, pols, lang, b.n, b.item, b.out, b.cap, b.off, b.keys); }); \
+    GUARD_END(h)                                                                                                                            \
+  }                                                                                                                                         \
+  int32_t rabe_##SCHEME##_kem_decaps(rabe_host* h, const void* uk, size_t n_items, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, \
+                                     uint32_t flags, int32_t* status, uint8_t* key_buf) {                                                   \
+    GUARD_BEGIN                                                                                                                             \
+    const auto& key = *(const SCHEME::UK*)uk;                                                                                               \
+    return decaps_shape(h, h->engines_if(ct_off && status && key_buf), CHUNK_DNF, n_items, ct_off, status, key_buf, [&](const DecapsBlock& b) { \
+      SCHEME::decaps_packed(b.eng, key, b.n, ct_blob, ct_len, b.in_off, trusted_of(flags), b.status, b.keys, b.errors);                     \
+    });                                                                                                                                     \
+    GUARD_END(h)                                                                                                                            \
+  }
+DNF_KEM(bdabe, BdabePublicKey, BdabePublicAttributeKey, BdabeUserKey)
+DNF_KEM(mke08, Mke08PublicKey, Mke08PublicAttributeKey, Mke08UserKey)
 int32_t rabe_bdabe_keygen_packed(rabe_host* h, const void* pk, const void* ska, const char* const* names, size_t n_items, uint8_t* uk_buf, size_t uk_cap,
                                  uint64_t* uk_off) {
   GUARD_BEGIN

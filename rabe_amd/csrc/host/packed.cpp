@@ -3,7 +3,7 @@
 // instead of the per-object pairing jobs.  In file order: AC17 bulk keygen (CP, KP) / encrypt / decrypt (CP and KP: one body each); BSW keygen /
 // delegate / encrypt / decrypt; LSW encrypt / keygen / decrypt (n keys, one ciphertext) / decrypt (n ciphertexts, one key); AW11 encrypt /
 // keygen / decrypt; GHW11 encrypt / decrypt_out / transform / decrypt / keygen / tkgen / provision; BDABE and MKE08 (one body, dnfabe) encrypt /
-// keygen / secret attribute keys.  The key-encapsulation forms (rabe_{ac17_cp,ac17_kp,bsw,...}_{encaps,decaps}_packed) are a mode of the encrypt /
+// keygen / secret attribute keys / decaps.  The key-encapsulation forms (rabe_{ac17_cp,ac17_kp,bsw,...}_{encaps,decaps}_packed) are a mode of the encrypt /
 // decrypt bodies: same caches, plans and launch sets, another ending.
 // What stays on the host is what the reference does with strings and bytes: policy parsing, flattening the tree into the index tables the
 // share kernels walk, traverse / calc_pruned / calc_coefficients per distinct policy, the selection tables, record layouts.  Records are the
@@ -3410,6 +3410,7 @@ namespace {
 struct DnfKey { const std::string* attr; const G1* g1; const G2* g2; const Gt* gt[2]; };
 struct DnfScheme {
   const char* timer;               // "bdabe::encrypt_packed"
+  const char* kem_timer;           // "bdabe::encaps_packed"
   const char* terms_kind;          // cache of the term tables (Engine::aux)
   const char* not_dnf;             // the object API's message for a policy that is not in DNF
   uint32_t n_gt;
@@ -3458,10 +3459,14 @@ void destroy_pk(void* h) { rhip_dnf_pk_destroy((rhip_dnf_pk*)h); }
 // msg1 msg2 = gen^(ab(1+c))), one r_j per DNF term in json_to_dnf's order, the AES nonce.  Per distinct policy: parse, DNF check,
 // json_to_dnf against the names of attr_pks, term tables (folded once, cached).  One row per (item, term) on the device
 // (rhip_dnf_encrypt_batch); records assembled and sealed there (records.h).
+// key_buf != nullptr is the key encapsulation (include/rabe_host.h: rabe_{bdabe,mke08}_kem_encaps): no plaintexts, no nonce draw, records that end
+// in the length field of an empty sealed part, and per item the content key SHA3-256(bytes(msg)) -- of the element the data would be sealed
+// under -- instead of a payload.  Call-level errors keep encrypt_packed's texts.
 bool encrypt_packed(Engine& eng, Rng& rng, const DnfScheme& sc, const G1& p1, const G2& p2, const std::vector<DnfKey>& keys,
                     const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
-                    const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  StageTimer tm(sc.timer);
+                    const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf = nullptr) {
+  const bool kem = key_buf != nullptr;
+  StageTimer tm(kem ? sc.kem_timer : sc.timer);
   Engine::ArenaScope arena(eng);
   Engine::Busy working(eng);          // a term set evicted by a later policy of this call lives until the call is done
   const size_t P = policies.size(), n_gt = sc.n_gt;
@@ -3492,9 +3497,10 @@ bool encrypt_packed(Engine& eng, Rng& rng, const DnfScheme& sc, const G1& p1, co
       L.src(1, (uint32_t)(128 * y + 64), 64);
       L.src(2, (uint32_t)(256 * y + 128), 128);
     }
+    if (kem) L.u32(0);          // the length field of an empty sealed part; no sealed source
   }
-  if (!record_offsets(sc.timer, "item_policy", n, item_policy, P, [&](size_t i) { return layouts[item_policy[i]].bytes() + 4; }, pt_off, out_buf, out_cap,
-                      out_off)) return false;
+  if (!record_offsets(sc.timer, "item_policy", n, item_policy, P, [&](size_t i) { return layouts[item_policy[i]].bytes() + (kem ? 0 : 4); },
+                      kem ? nullptr : pt_off, out_buf, out_cap, out_off)) return false;
   if (!n) return true;
   std::vector<uint32_t> row_off(n + 1, 0);
   for (size_t i = 0; i < n; i++) row_off[i + 1] = row_off[i] + (uint32_t)terms[item_policy[i]].size();
@@ -3556,7 +3562,7 @@ bool encrypt_packed(Engine& eng, Rng& rng, const DnfScheme& sc, const G1& p1, co
       memcpy(h_in + 32 * (2 * n + i), msg.l, 32);
     }
     for (uint32_t y = row_off[i]; y < row_off[i + 1]; y++) { const Fr rj = r.next_fr(); memcpy(h_r + 32 * (size_t)y, rj.l, 32); }
-    r.fill(nonces[i].data(), 12);
+    if (!kem) r.fill(nonces[i].data(), 12);
   });
   tm.lap("draws");
   rhip_ctx* cx = eng.ctx();
@@ -3572,6 +3578,15 @@ bool encrypt_packed(Engine& eng, Rng& rng, const DnfScheme& sc, const G1& p1, co
   // records and sealing on the device (records.h); the data is sealed under msg (BDABE) / msg1 msg2 (MKE08)
   std::vector<uint64_t> src_off(3 * n);
   for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * n_gt * row_off[i]; src_off[n + i] = 128ull * row_off[i]; src_off[2 * n + i] = 256ull * row_off[i]; }
+  if (kem) {          // headers from the template alone, keys straight out of the msg array: no seal kernel is launched
+    DBuf d_keys(&eng, n * 32 + 4);
+    eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
+    eng.check(rhip_gt_kdf_batch(cx, n, d_msg.as<rhip_gt>() + (n_exp - 1) * n, nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
+    emit_plain_records(eng, layouts, n, item_policy, {d_gt.ptr(), d_g1.ptr(), d_g2.ptr()}, src_off, out_off, out_buf);
+    eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
+    tm.lap("device: group arithmetic, headers, keys; two copies out");
+    return true;
+  }
   emit_sealed_records(eng, layouts, n, item_policy, {d_gt.ptr(), d_g1.ptr(), d_g2.ptr()}, src_off, d_msg.as<rhip_gt>() + (n_exp - 1) * n,
                       (const uint8_t*)nonces.data(), pt_blob, pt_off, out_off, out_buf);
   tm.lap("device: group arithmetic, records, sealing; one copy out");
@@ -3795,17 +3810,284 @@ bool request_sk_packed(Engine& eng, const char* what, const std::string& authori
   for (size_t i = 0; i < n; i++) status[i] = (*errors)[i].empty() ? 0 : -1;
   return true;
 }
+
+// ------------------------------------------------------------------------------------------------ BDABE / MKE08 key decapsulation
+// n calls of bdabe::decrypt (bdabe/mod.rs:367-399) / mke08::decrypt (mke08/mod.rs:343-380) up to the Gt, with ONE user key against n records
+// (include/rabe_host.h: rabe_{bdabe,mke08}_kem_decaps), then the KDF behind the verdict mask.  Record = policy, language, conjunction count, per
+// conjunction (name count, names, n_gt Gt, G1, G2, G1, G2), sealed length, sealed bytes (skipped, never read).  Three caches of the call:
+//   policies  by (language, text): parse + traverse_policy against the key's attribute names -- the reference's first verdict;
+//   classes   by the bytes of ONE conjunction's name list as the record states it: is_satisfiable and, name by name, the FIRST key row (find());
+//   skeletons by (policy length, the name lists of all conjunctions): the first satisfiable conjunction and its class -- records of one skeleton
+//             have every element at the same offset, so they also share their gather shape.
+// Per class S1 = sum au1, S2 = sum au2 in list order on the device (rounds of rhip_g1_add / rhip_g2_add over the classes that still have a
+// term: classes are numbered by falling length, so a round is a prefix), one rhip_g2_lines_prepare over [u2, S2 of every class], then
+// rhip_dnf_decrypt_batch_one_uk: four Miller loops per item.  Untrusted input: every element of every conjunction is gathered a second time into
+// whole-record arrays for the decoder's checks (curve, Gt membership, G2 subgroup -- the chosen conjunction's two G2 elements out of their own
+// walks); the pairings read the chosen conjunction's copy.
+struct DnfUserRow { const std::string* attr; const G1* g1; const G2* g2; };
+struct DnfDecScheme {
+  const char* timer;               // "bdabe::decaps_packed"
+  const char* no_match;            // the object API's message where traverse_policy fails
+  uint32_t n_gt;
+};
+void decaps_packed(Engine& eng, const DnfDecScheme& sc, const G1& u1, const G2& u2, const std::vector<DnfUserRow>& rows, size_t n, const uint8_t* ct_blob,
+                   size_t ct_len, const uint64_t* ct_off, bool trusted, int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
+  StageTimer tm(sc.timer);
+  Engine::ArenaScope arena(eng);
+  errors->assign(n, "");
+  if (!ct_off || (n && (!ct_blob || !status || !key_buf))) throw RabeError(std::string(sc.timer) + ": null input");
+  if (!n) return;
+  (void)check_offsets(n, ct_off, ct_len, errors);
+  BlobGather gather(eng, ct_blob, ct_len);          // the blob starts for the device now, beside the parsing below (records.h)
+  const size_t n_gt = sc.n_gt, conj_bytes = 384 * n_gt + 384;
+  std::vector<std::string> key_names;
+  for (const auto& r : rows) key_names.push_back(*r.attr);
+  struct PolPlan { std::string err; };
+  struct ClassPlan { std::string err; bool sat = true; std::vector<uint32_t> key_row; uint32_t id = 0xFFFFFFFFu; };
+  struct SkelPlan { std::string err; uint32_t chosen = 0, n_conj = 0; std::shared_ptr<ClassPlan> cls; };
+  PlanCache<PolPlan> pols;
+  PlanCache<ClassPlan> classes;          // keyed on bytes, like the skeletons: the language is no part of those keys
+  PlanCache<SkelPlan> skels;
+  auto make_pol = [&](PolPlan&, const std::string& text, PolicyLanguage lang) {
+    if (!traverse_policy(key_names, parse_or_error(text, lang))) throw RabeError(sc.no_match);
+  };
+  auto make_class = [&](ClassPlan& c, const std::string& names, PolicyLanguage) {          // names: u32 count, then (u32 length, bytes) per name
+    for (size_t at = 4; at < names.size();) {
+      const uint32_t l = get_u32((const uint8_t*)names.data() + at);
+      size_t k = 0;
+      while (k < rows.size() && !(rows[k].attr->size() == l && memcmp(rows[k].attr->data(), names.data() + at + 4, l) == 0)) k++;
+      if (k == rows.size()) { c.sat = false; c.key_row.clear(); return; }
+      c.key_row.push_back((uint32_t)k);
+      at += 4 + (size_t)l;
+    }
+  };
+  auto make_skel = [&](SkelPlan& s, const std::string& key, PolicyLanguage) {          // key: u32 policy length, u32 conjunctions, their name lists
+    const uint8_t* p = (const uint8_t*)key.data() + 4;
+    s.n_conj = get_u32(p);
+    p += 4;
+    for (uint32_t y = 0; y < s.n_conj; y++) {
+      const uint8_t* first = p;
+      const uint32_t na = get_u32(p);
+      p += 4;
+      for (uint32_t k = 0; k < na; k++) p += 4 + (size_t)get_u32(p);
+      auto c = classes.get((const char*)first, (size_t)(p - first), PolicyLanguage::JsonPolicy, make_class);
+      if (!c->sat) continue;
+      s.chosen = y;
+      s.cls = c;
+      return;
+    }
+    throw RabeError(std::string(sc.timer) + ": the key satisfies the record's policy but none of its conjunction lists (decrypt_gt returns Gt::one() there)");
+  };
+  struct View { std::shared_ptr<SkelPlan> skel; uint32_t first_conj = 0; };          // first_conj: offset of the first conjunction in the record
+  std::vector<View> v(n);
+  for_each_record(n, errors, [&](size_t i) {
+    const uint8_t* rec = ct_blob + ct_off[i];
+    Cursor r{rec, ct_blob + ct_off[i + 1]};
+    const auto text = r.str();
+    const PolicyLanguage lang = *r.raw(1) ? PolicyLanguage::HumanPolicy : PolicyLanguage::JsonPolicy;
+    static thread_local std::string key;          // per-thread scratch: no allocation per record once it has grown
+    key.assign(8, '\0');
+    put_u32((uint8_t*)&key[0], text.second);
+    const uint32_t n_conj = r.u32();
+    if ((size_t)n_conj * (4 + conj_bytes) > (size_t)(r.end - r.p)) throw_truncated();          // before anything is sized by it
+    put_u32((uint8_t*)&key[4], n_conj);
+    v[i].first_conj = (uint32_t)(r.p - rec);
+    for (uint32_t y = 0; y < n_conj; y++) {
+      const uint8_t* first = r.p;
+      const uint32_t na = r.u32();
+      if ((size_t)na * 4 > (size_t)(r.end - r.p)) throw_truncated();
+      for (uint32_t k = 0; k < na; k++) (void)r.str();
+      key.append((const char*)first, (size_t)(r.p - first));
+      (void)r.raw(conj_bytes);
+    }
+    (void)r.raw(r.u32());          // the sealed part: skipped by its length field
+    if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
+    auto pl = pols.get(text.first, text.second, lang, make_pol);
+    if (!pl->err.empty()) throw RabeError(pl->err);
+    auto sk = skels.get(key.data(), key.size(), PolicyLanguage::JsonPolicy, make_skel);
+    if (!sk->err.empty()) throw RabeError(sk->err);
+    v[i].skel = sk;
+  });
+  tm.lap("parse + plan");
+  // ---- live items, their rows (one per conjunction of the record) and the classes they name, numbered by falling length
+  std::vector<size_t> live;
+  std::vector<uint32_t> row_off{0};
+  std::vector<ClassPlan*> cls;
+  for (size_t i = 0; i < n; i++) {
+    if (!(*errors)[i].empty()) continue;
+    live.push_back(i);
+    row_off.push_back(row_off.back() + v[i].skel->n_conj);
+    ClassPlan* c = v[i].skel->cls.get();
+    if (c->id == 0xFFFFFFFFu) { c->id = 0; cls.push_back(c); }
+  }
+  const size_t m = live.size(), total = row_off[m], n_classes = cls.size();
+  if (!m) {
+    for (size_t i = 0; i < n; i++) status[i] = -1;
+    memset(key_buf, 0, n * 32);
+    return;
+  }
+  std::stable_sort(cls.begin(), cls.end(), [](const ClassPlan* a, const ClassPlan* b) { return a->key_row.size() > b->key_row.size(); });
+  for (size_t c = 0; c < n_classes; c++) cls[c]->id = (uint32_t)c;
+  rhip_ctx* cx = eng.ctx();
+  // ---- S1, S2 per class: the first terms from the host, then one round of additions per further term over the classes that have one
+  const size_t longest = cls[0]->key_row.size();
+  std::vector<uint8_t> h_s1(n_classes * 64, 0), h_q((1 + n_classes) * 128, 0), b1, b2;
+  std::vector<uint8_t> skip(n_classes, 0);
+  memcpy(h_q.data(), u2.data(), 128);
+  std::vector<size_t> round_n;
+  for (size_t c = 0; c < n_classes; c++) {
+    if (cls[c]->key_row.empty()) { skip[c] = 3; continue; }          // an empty conjunction: both sums are the identity
+    const DnfUserRow& k = rows[cls[c]->key_row[0]];
+    memcpy(h_s1.data() + 64 * c, k.g1->data(), 64);
+    memcpy(h_q.data() + 128 * (1 + c), k.g2->data(), 128);
+  }
+  for (size_t r = 1; r < longest; r++) {
+    size_t k_r = 0;
+    while (k_r < n_classes && cls[k_r]->key_row.size() > r) k_r++;
+    round_n.push_back(k_r);
+    for (size_t c = 0; c < k_r; c++) {
+      const DnfUserRow& k = rows[cls[c]->key_row[r]];
+      b1.insert(b1.end(), k.g1->begin(), k.g1->end());
+      b2.insert(b2.end(), k.g2->begin(), k.g2->end());
+    }
+  }
+  eng.scrub_session_when_done();          // the key's elements and their sums pass through the arena
+  DBuf d_s1 = up_bytes(eng, h_s1), d_q = up_bytes(eng, h_q), d_b1 = up_bytes(eng, b1.empty() ? std::vector<uint8_t>(64, 0) : b1),
+       d_b2 = up_bytes(eng, b2.empty() ? std::vector<uint8_t>(128, 0) : b2);
+  {
+    size_t at = 0;
+    for (size_t k_r : round_n) {
+      eng.check(rhip_g1_add(cx, k_r, d_s1.as<rhip_g1>(), d_b1.as<rhip_g1>() + at, d_s1.as<rhip_g1>()), "rhip_g1_add");
+      eng.check(rhip_g2_add(cx, k_r, d_q.as<rhip_g2>() + 1, d_b2.as<rhip_g2>() + at, d_q.as<rhip_g2>() + 1), "rhip_g2_add");
+      at += k_r;
+    }
+  }
+  if (longest > 1) {          // a sum may be the identity (key rows that cancel): the skip bits are read off the sums themselves
+    eng.check(rhip_download(cx, h_s1.data(), d_s1.ptr(), h_s1.size()), "download (S1)");
+    eng.check(rhip_download(cx, h_q.data(), d_q.ptr(), h_q.size()), "download (S2)");
+  }
+  auto all_zero = [](const uint8_t* p, size_t k) { for (size_t i = 0; i < k; i++) if (p[i]) return false; return true; };
+  for (size_t c = 0; c < n_classes; c++)
+    skip[c] |= (all_zero(h_s1.data() + 64 * c, 64) ? 1 : 0) | (all_zero(h_q.data() + 128 * (1 + c), 128) ? 2 : 0);
+  std::unique_ptr<rhip_g2_lines, void (*)(rhip_g2_lines*)> lines(nullptr, rhip_g2_lines_destroy);
+  {
+    rhip_g2_lines* l = nullptr;
+    eng.check(rhip_g2_lines_prepare(cx, 1 + n_classes, d_q.as<rhip_g2>(), &l), "rhip_g2_lines_prepare");
+    lines.reset(l);
+  }
+  DBuf d_u1 = up_bytes(eng, std::vector<uint8_t>(u1.begin(), u1.end())), d_nu1(&eng, 64), d_skip = up_bytes(eng, skip);
+  eng.check(rhip_g1_neg(cx, 1, d_u1.as<rhip_g1>(), d_nu1.as<rhip_g1>()), "rhip_g1_neg");
+  tm.lap("classes: sums, lines");
+  // ---- shapes: destinations 0 / 1 the chosen conjunction's Gt element(s), 2 its (e2, e4), 3 its (e3, e5); untrusted input also 4 / 5 / 6:
+  // every conjunction's Gt, G1 and G2 elements, for the decoder's checks
+  std::vector<uint32_t> item_class(m), walked_idx, walked_off{0};
+  const size_t n_dst = trusted ? 4 : 7;
+  std::vector<uint64_t> dst_off(n_dst * m);
+  for (size_t j = 0; j < m; j++) {
+    const View& w = v[live[j]];
+    const SkelPlan& s = *w.skel;
+    item_class[j] = s.cls->id;
+    dst_off[j] = dst_off[m + j] = 384ull * j;
+    dst_off[2 * m + j] = 128ull * j;
+    dst_off[3 * m + j] = 256ull * j;
+    if (!trusted) {
+      dst_off[4 * m + j] = 384ull * n_gt * row_off[j];
+      dst_off[5 * m + j] = 128ull * row_off[j];
+      dst_off[6 * m + j] = 256ull * row_off[j];
+      walked_idx.push_back(2 * (row_off[j] + s.chosen));
+      walked_idx.push_back(2 * (row_off[j] + s.chosen) + 1);
+      walked_off.push_back((uint32_t)walked_idx.size());
+    }
+    gather_record(gather, ct_off[live[j]], &s, [&](std::vector<RecordLayout::Part>& parts) {
+      const uint8_t* rec = ct_blob + ct_off[live[j]];
+      Cursor r{rec + w.first_conj, ct_blob + ct_off[live[j] + 1]};
+      for (uint32_t y = 0; y < s.n_conj; y++) {
+        const uint32_t na = r.u32();
+        for (uint32_t k = 0; k < na; k++) (void)r.str();
+        const uint32_t at = (uint32_t)(r.raw(conj_bytes) - rec), g = at + (uint32_t)(384 * n_gt);          // Gt element(s) | G1 G2 G1 G2
+        if (y == s.chosen) {
+          for (uint32_t t = 0; t < n_gt; t++) parts.push_back({at + 384 * t, 384, t, 0});
+          parts.push_back({g, 64, 2, 0});
+          parts.push_back({g + 64, 128, 3, 0});
+          parts.push_back({g + 192, 64, 2, 64});
+          parts.push_back({g + 256, 128, 3, 128});
+        }
+        if (trusted) continue;
+        parts.push_back({at, (uint32_t)(384 * n_gt), 4, (uint32_t)(384 * n_gt * y)});
+        parts.push_back({g, 64, 5, 128 * y});
+        parts.push_back({g + 64, 128, 6, 256 * y});
+        parts.push_back({g + 192, 64, 5, 128 * y + 64});
+        parts.push_back({g + 256, 128, 6, 256 * y + 128});
+      }
+    });
+  }
+  tm.lap("shapes");
+  DBuf d_class = up32(eng, item_class), d_row_off = up32(eng, row_off), d_j1(&eng, m * 384), d_j2(&eng, n_gt == 2 ? m * 384 : 4), d_g1(&eng, m * 128),
+       d_g2(&eng, m * 256), d_out(&eng, m * 384 + 4), d_all_gt(&eng, trusted ? 4 : total * 384 * n_gt + 4), d_all_g1(&eng, trusted ? 4 : total * 128 + 4);
+  WalkScope ws;
+  ws.d_g2 = DBuf(&eng, trusted ? 4 : total * 256 + 4);
+  std::vector<void*> dst{d_j1.ptr(), d_j2.ptr(), d_g1.ptr(), d_g2.ptr()};
+  if (!trusted) { dst.push_back(d_all_gt.ptr()); dst.push_back(d_all_g1.ptr()); dst.push_back(ws.d_g2.ptr()); }
+  gather.run(dst, dst_off);
+  if (!trusted) {
+    ws.mc.reset(new MemberChecks(eng));
+    ws.mc->add(1, d_all_g1.ptr(), total * 2, d_row_off.as<uint32_t>(), m, 2);
+    ws.mc->add(3, d_all_gt.ptr(), total * n_gt, d_row_off.as<uint32_t>(), m, (uint32_t)n_gt);
+    // e3 and e5 of the chosen conjunction are the two walking arguments of an item: their membership comes out of the decrypt's own Miller
+    // loops; the G2 elements of the other conjunctions, and those of an item with a skipped pair, get the stand-alone test (common.h: WalkedG2)
+    if (walk_checks()) ws.walked.reset(new WalkedG2(eng, *ws.mc, ws.d_g2.ptr(), total * 2, d_row_off.as<uint32_t>(), row_off, 2, &walked_idx, &walked_off));
+    else { ws.k_alone = ws.mc->add_count(); ws.mc->add(2, ws.d_g2.ptr(), total * 2, d_row_off.as<uint32_t>(), m, 2); }
+  }
+  if (n_gt == 2) eng.check(rhip_gt_mul(cx, m, d_j1.as<rhip_gt>(), d_j2.as<rhip_gt>(), d_j1.as<rhip_gt>()), "rhip_gt_mul");          // MKE08: the lead is j1 j2
+  if (ws.walked) ws.walked->arm();
+  eng.check(rhip_dnf_decrypt_batch_one_uk(cx, m, n_classes, d_class.as<uint32_t>(), d_s1.as<rhip_g1>(), d_skip.as<uint8_t>(), d_nu1.as<rhip_g1>(), lines.get(),
+                                          d_g1.as<rhip_g1>(), d_g2.as<rhip_g2>(), d_j1.as<rhip_gt>(), d_out.as<rhip_gt>()),
+            "rhip_dnf_decrypt_batch_one_uk");
+  static const char* const G2_NOT_MEMBER = "deserialize: a G2 element is not a group member (FieldError::NotMember)";
+  if (ws.mc) {
+    ws.mc->collect();
+    ws.fail(live, {0}, "deserialize: a G1 element is not a group member (FieldError::NotMember)", errors);
+    ws.fail(live, {ws.k_alone}, G2_NOT_MEMBER, errors);
+    ws.fail(live, {1}, "deserialize: a Gt element is not a group member (FieldError::NotMember)", errors);
+  }
+  ws.fail_walked(live, G2_NOT_MEMBER, errors);          // every verdict first: there is no open to queue behind the pairings
+  derive_keys(eng, n, live, d_out.ptr(), status, key_buf, *errors);
+  tm.lap(trusted ? "device: gather, pairings, keys" : "device: gather, pairings, keys; membership beside");
+}
 }  // namespace
 }  // namespace dnfabe
 
 namespace bdabe {
+static bool encrypt_core(Engine& eng, Rng& rng, const BdabePublicKey& pk, const std::vector<const BdabePublicAttributeKey*>& attr_pks,
+                         const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
+                         const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  static const dnfabe::DnfScheme sc{"bdabe::encrypt_packed", "bdabe::encaps_packed", "bdabe_terms", "Error in bdabe/encrypt: Policy not in DNF.", 1};
+  std::vector<dnfabe::DnfKey> keys;
+  for (const auto* k : attr_pks) keys.push_back({&k->attr, &k->a1, &k->a2, {&k->a3, nullptr}});
+  return dnfabe::encrypt_packed(eng, rng, sc, pk.p1, pk.p2, keys, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off, key_buf);
+}
 bool encrypt_packed(Engine& eng, Rng& rng, const BdabePublicKey& pk, const std::vector<const BdabePublicAttributeKey*>& attr_pks,
                     const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
                     const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  static const dnfabe::DnfScheme sc{"bdabe::encrypt_packed", "bdabe_terms", "Error in bdabe/encrypt: Policy not in DNF.", 1};
-  std::vector<dnfabe::DnfKey> keys;
-  for (const auto* k : attr_pks) keys.push_back({&k->attr, &k->a1, &k->a2, {&k->a3, nullptr}});
-  return dnfabe::encrypt_packed(eng, rng, sc, pk.p1, pk.p2, keys, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off);
+  return encrypt_core(eng, rng, pk, attr_pks, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off, nullptr);
+}
+// n key encapsulations (include/rabe_host.h: rabe_bdabe_kem_encaps): header i is the BdabeCiphertext record encrypt_packed writes for the same draws
+// with a sealed part of length zero, key_buf + 32 i = SHA3-256(bytes(msg_i)).  Draw order: encrypt_packed's minus the nonce.
+bool encaps_packed(Engine& eng, Rng& rng, const BdabePublicKey& pk, const std::vector<const BdabePublicAttributeKey*>& attr_pks,
+                   const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap,
+                   uint64_t* out_off, uint8_t* key_buf) {
+  if (n && !key_buf) throw RabeError("bdabe::encaps_packed: null input");
+  if (!n) { out_off[0] = 0; return true; }
+  return encrypt_core(eng, rng, pk, attr_pks, policies, language, n, item_policy, nullptr, nullptr, out_buf, out_cap, out_off, key_buf);
+}
+// n key decapsulations under ONE user key (include/rabe_host.h: rabe_bdabe_kem_decaps): key_buf + 32 i = SHA3-256(bytes(Gt)) of what decrypt_gt
+// returns for record i; input may be headers or full records
+void decaps_packed(Engine& eng, const BdabeUserKey& uk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                   int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
+  static const dnfabe::DnfDecScheme sc{"bdabe::decaps_packed", "Error in bdabe/decrypt: attributes in sk do not match policy in ct.", 1};
+  std::vector<dnfabe::DnfUserRow> rows;
+  for (const auto& k : uk.sk_a) rows.push_back({&k.attr, &k.au1, &k.au2});
+  dnfabe::decaps_packed(eng, sc, uk.sk.u1, uk.sk.u2, rows, n, ct_blob, ct_len, ct_off, trusted, status, key_buf, errors);
 }
 bool keygen_packed(Engine& eng, Rng& rng, const BdabePublicKey& pk, const BdabeSecretAuthorityKey& ska, const std::vector<std::string>& names,
                    uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
@@ -3820,13 +4102,33 @@ bool request_attribute_sk_packed(Engine& eng, const BdabeSecretAuthorityKey& ska
 }  // namespace bdabe
 
 namespace mke08 {
+static bool encrypt_core(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const std::vector<const Mke08PublicAttributeKey*>& attr_pks,
+                         const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
+                         const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  static const dnfabe::DnfScheme sc{"mke08::encrypt_packed", "mke08::encaps_packed", "mke08_terms", "Error in mke08/encrypt: policy is not in dnf", 2};
+  std::vector<dnfabe::DnfKey> keys;
+  for (const auto* k : attr_pks) keys.push_back({&k->attr, &k->g1, &k->g2, {&k->gt1, &k->gt2}});
+  return dnfabe::encrypt_packed(eng, rng, sc, pk.p1, pk.p2, keys, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off, key_buf);
+}
 bool encrypt_packed(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const std::vector<const Mke08PublicAttributeKey*>& attr_pks,
                     const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
                     const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  static const dnfabe::DnfScheme sc{"mke08::encrypt_packed", "mke08_terms", "Error in mke08/encrypt: policy is not in dnf", 2};
-  std::vector<dnfabe::DnfKey> keys;
-  for (const auto* k : attr_pks) keys.push_back({&k->attr, &k->g1, &k->g2, {&k->gt1, &k->gt2}});
-  return dnfabe::encrypt_packed(eng, rng, sc, pk.p1, pk.p2, keys, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off);
+  return encrypt_core(eng, rng, pk, attr_pks, policies, language, n, item_policy, pt_blob, pt_off, out_buf, out_cap, out_off, nullptr);
+}
+// the key encapsulation pair, as bdabe's: the key is the KDF of msg1 * msg2, the element encrypt_packed seals under
+bool encaps_packed(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const std::vector<const Mke08PublicAttributeKey*>& attr_pks,
+                   const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap,
+                   uint64_t* out_off, uint8_t* key_buf) {
+  if (n && !key_buf) throw RabeError("mke08::encaps_packed: null input");
+  if (!n) { out_off[0] = 0; return true; }
+  return encrypt_core(eng, rng, pk, attr_pks, policies, language, n, item_policy, nullptr, nullptr, out_buf, out_cap, out_off, key_buf);
+}
+void decaps_packed(Engine& eng, const Mke08UserKey& uk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                   int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors) {
+  static const dnfabe::DnfDecScheme sc{"mke08::decaps_packed", "Error in mke08/decrypt: attributes in sk do not match policy in ct.", 2};
+  std::vector<dnfabe::DnfUserRow> rows;
+  for (const auto& k : uk.sk_a) rows.push_back({&k.attr, &k.g1, &k.g2});
+  dnfabe::decaps_packed(eng, sc, uk.sk.g1, uk.sk.g2, rows, n, ct_blob, ct_len, ct_off, trusted, status, key_buf, errors);
 }
 bool keygen_packed(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const Mke08MasterKey& msk, const std::vector<std::string>& names, uint8_t* out_buf,
                    size_t out_cap, uint64_t* out_off) {

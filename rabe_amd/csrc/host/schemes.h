@@ -310,6 +310,13 @@ std::vector<DecryptResult> decrypt_batch(Engine& eng, const std::vector<const Bd
 bool encrypt_packed(Engine& eng, Rng& rng, const BdabePublicKey& pk, const std::vector<const BdabePublicAttributeKey*>& attr_pks,
                     const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
                     const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
+// the key encapsulation pair (packed.cpp; include/rabe_host.h: rabe_bdabe_kem_encaps / _decaps): encrypt_packed's headers with SHA3-256(bytes(msg))
+// per item; ONE user key against n records in the four-pair form of decrypt (rhip_dnf_decrypt_batch_one_uk), keys behind the verdict mask
+bool encaps_packed(Engine& eng, Rng& rng, const BdabePublicKey& pk, const std::vector<const BdabePublicAttributeKey*>& attr_pks,
+                   const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap,
+                   uint64_t* out_off, uint8_t* key_buf);
+void decaps_packed(Engine& eng, const BdabeUserKey& uk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                   int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors);
 // bulk key issuing (packed.cpp).  keygen_packed: n calls of keygen under one authority key, records = BdabeUserKey with an empty sk_a (false =
 // out_cap too small, nothing drawn).  request_attribute_sk_packed: for every BdabePublicUserKey record (name | u1 | u2) of an untrusted blob the
 // secret attribute keys of the list sets[item_set[i]]; records = u32 count + rows (attribute, au1, au2), the sk_a tail of the user-key record
@@ -346,6 +353,12 @@ std::vector<DecryptResult> decrypt_batch(Engine& eng, const std::vector<const Mk
 bool encrypt_packed(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const std::vector<const Mke08PublicAttributeKey*>& attr_pks,
                     const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, const uint8_t* pt_blob,
                     const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);
+// the key encapsulation pair (packed.cpp), as bdabe's; the key is the KDF of msg1 * msg2
+bool encaps_packed(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const std::vector<const Mke08PublicAttributeKey*>& attr_pks,
+                   const std::vector<std::string>& policies, PolicyLanguage language, size_t n, const uint32_t* item_policy, uint8_t* out_buf, size_t out_cap,
+                   uint64_t* out_off, uint8_t* key_buf);
+void decaps_packed(Engine& eng, const Mke08UserKey& uk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                   int32_t* status, uint8_t* key_buf, std::vector<std::string>* errors);
 // bulk key issuing (packed.cpp): as bdabe's, under the master key (keygen) and an authority's r (request_authority_sk)
 bool keygen_packed(Engine& eng, Rng& rng, const Mke08PublicKey& pk, const Mke08MasterKey& msk, const std::vector<std::string>& names, uint8_t* out_buf,
                    size_t out_cap, uint64_t* out_off);

@@ -712,6 +712,14 @@ def lsw_decrypt_one_sk_dev(eng, n_items, max_pairs, total_pairs, n_sel, d_pair_o
                                                      _p(sk_d2_lines), _p(d_out)))
 
 
+def dnf_decrypt_one_uk_dev(eng, n_items, n_classes, d_item_class, d_class_s1, d_class_skip, d_neg_u1, key_lines, d_ct_g1, d_ct_g2, d_lead, d_out):
+    """BDABE / MKE08 decrypt under ONE user key in the four-pair form (rhip_dnf_decrypt_batch_one_uk): out[i] = lead[i] * e(e2, S2) * e(S1, e3) *
+    e(-e4, u2) * e(-u1, e5).  key_lines: G2Lines over [sk.u2, S2 of class 0, S2 of class 1, ...]; d_ct_g1 = (e2, e4) and d_ct_g2 = (e3, e5) per
+    item; d_class_skip[c]: bit 0 S1 = O, bit 1 S2 = O"""
+    eng._check(eng.lib.rhip_dnf_decrypt_batch_one_uk(eng.ctx, _sz(n_items), _sz(n_classes), _p(d_item_class), _p(d_class_s1), _p(d_class_skip), _p(d_neg_u1),
+                                                     _p(key_lines), _p(d_ct_g1), _p(d_ct_g2), _p(d_lead), _p(d_out)))
+
+
 def lsw_encrypt_rows_dev(eng, g1_tbl, g1_b_tbl, g1_b2_tbl, h_b_tbl, n_items, total_rows, d_item_row_off, d_item_hash_off, d_hash, d_secret, d_sx,
                          d_out):
     """rhip_lsw_encrypt_rows: the attribute rows of n_items lsw::encrypt calls, one lane per row (k_lsw_enc_rows).  The four tables are

@@ -70,6 +70,23 @@ def encrypt_packed(host, pk, attr_pks, policies, item_policy, pt_blob, pt_off, l
                           (_as_u8(pt_blob), np.ascontiguousarray(pt_off, dtype=np.uint64)), out)
 
 
+# ---- key encapsulation (rabe_mke08_kem_encaps / rabe_mke08_kem_decaps): the packed pair without payloads
+def encaps_packed(host, pk, attr_pks, policies, item_policy, language=JSON_POLICY, out=None):
+    """n headers (Mke08Ciphertext records with an empty sealed part: encrypt_packed's for the same draws minus the nonce) + n 32-byte content
+    keys SHA3-256(bytes(msg1 * msg2)).  Returns (hdr_blob view, hdr_off uint64 [n+1], keys uint8 [n, 32])."""
+    from ..hostlib import packed_encaps
+    arr = (ctypes.c_void_p * max(1, len(attr_pks)))(*[p.ptr for p in attr_pks])
+    return packed_encaps(host, "rabe_mke08_kem_encaps", (pk.ptr, arr, ctypes.c_size_t(len(attr_pks))), policies, item_policy, language, out)
+
+
+def decaps_packed(host, uk, ct_blob, ct_off, trusted=False):
+    """the content keys of n records (headers or full ciphertexts) under one user key: key i = SHA3-256(bytes(decrypt_gt(uk, record i))), from
+    four Miller loops per item whatever the conjunction's length.  Returns (keys uint8 [n, 32], status int32 [n]); a failed item has status -1
+    and 32 zero bytes.  The sealed parts are neither read nor authenticated."""
+    from ..hostlib import packed_decaps
+    return packed_decaps(host, "rabe_mke08_kem_decaps", (uk.ptr,), ct_blob, ct_off, trusted)
+
+
 def keygen_packed(host, pk, msk, names, out=None):
     """one user key per name under the master key (rabe_mke08_keygen_packed).  Returns (uk_blob: numpy uint8 view of the Mke08UserKey
     records with an empty sk_a, uk_off: numpy uint64 [n+1])."""
