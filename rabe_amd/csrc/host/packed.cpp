@@ -12,8 +12,9 @@
 // parse + plan, lists, shapes, buffers, checks, launch, verdicts -- over check_offsets / Cursor / same (ac17_record.h, with AC17's record reader)
 // and the helpers of the anonymous namespace below: PlanCache, for_each_record, Selection, WalkScope, gather_record.  AC17 differs in two
 // places: its plans are kept ACROSS calls (Ac17PlanCache: a PlanCache per key fingerprint), and its selection is two plain index lists copied
-// on all cores instead of a Selection.  The issuers size their output with record_offsets (records.h), and the four that walk share trees (bsw /
-// ghw11 / aw11 encrypt, lsw keygen) keep them in a ShareTrees.
+// on all cores instead of a Selection.  The issuers size their output with record_offsets, say where an item's parts lie with a RecordSources
+// (record_layout.h) and the encrypts end in finish_encrypt (records.h); the four that walk share trees (bsw / ghw11 / aw11 encrypt, lsw keygen)
+// keep them in a ShareTrees.
 #include "schemes.h"
 #include "records.h"
 #include "ac17_record.h"
@@ -587,9 +588,7 @@ bool kp_keygen_packed(Engine& eng, Rng& rng, const Ac17MasterKey& msk, const std
   eng.check(rhip_g1_table_mul(cx, gt, 3 * total_rows, d_scal.as<rhip_fr>(), d_pts.as<rhip_g1>()), "rhip_g1_table_mul");
   eng.check(rhip_g1_add(cx, 3 * total_rows, d_pts.as<rhip_g1>(), d_add.as<rhip_g1>(), d_k.as<rhip_g1>()), "rhip_g1_add");
   eng.check(rhip_g2_table_mul(cx, ht, 3 * n, (const rhip_fr*)(d_scal.as<uint8_t>() + total_rows * 96), d_k0.as<rhip_g2>()), "rhip_g2_table_mul");
-  std::vector<uint64_t> src_off(2 * n);
-  for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * i; src_off[n + i] = 192ull * row_off[i]; }
-  emit_plain_records(eng, layouts, n, item_policy, {d_k0.ptr(), d_k.ptr()}, src_off, out_off, out_buf);
+  emit_plain_records(eng, layouts, n, item_policy, RecordSources(n).by_item(d_k0.ptr(), 384).by_rows(d_k.ptr(), 192, row_off), out_off, out_buf);
   tm.lap("device: fixed-base multiplications, records; one copy out");
   return true;
 }
@@ -735,8 +734,7 @@ static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, 
       L.src(1, (uint32_t)(192 * r), 192);
     }
     L.src(2, 0, 384);
-    if (L.bytes() + 4 != pols[p_]->fixed_bytes) throw RabeError("ac17 encrypt_packed: record layout and size disagree");
-    if (kem) L.u32(0);                            // encaps: the template ends in the length field of an empty sealed part, no sealed source
+    if (close_ciphertext(L, kem) != pols[p_]->fixed_bytes) throw RabeError("ac17 encrypt_packed: record layout and size disagree");
   }
   // The batch can go through the device in PARTS of >= 16 384 items, a part's records copied out (10.4 KB per item at 50 rows, 15 ms per
   // 65 536 items) on the side stream while the next part's group arithmetic runs; randomness was drawn above for the whole batch, item
@@ -769,19 +767,11 @@ static bool encrypt_packed_core(Engine& eng, Rng& rng, const Ac17PublicKey& pk, 
     eng.check(rhip_gt_table_pow(cx, egt, np, drho.as<rhip_fr>() + lo, dm.as<rhip_gt>() + lo), "rhip_gt_table_pow");
     eng.check(rhip_ac17_cp_encrypt_batch(cx, dpk, np, dA.as<rhip_fr>(), dio.as<uint32_t>() + lo, dro_p, rows_p, ds.as<rhip_fr>() + 2 * lo,
                                          dm.as<rhip_gt>() + lo, dc0.as<rhip_g2>() + 3 * lo, dc_p, dcp.as<rhip_gt>() + lo), "rhip_ac17_cp_encrypt_batch");
-    std::vector<uint64_t> src_off(3 * np);
-    for (size_t i = 0; i < np; i++) { src_off[i] = 384ull * i; src_off[np + i] = 192ull * ro[i]; src_off[2 * np + i] = 384ull * i; }
-    if (kem) {          // one part: headers from the template alone, keys straight out of the msg array -- no seal kernel is launched
-      DBuf d_keys(&eng, n * 32 + 4);
-      eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
-      eng.check(rhip_gt_kdf_batch(cx, n, dm.as<rhip_gt>(), nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
-      emit_plain_records(eng, layouts, n, item_policy, {dc0.ptr(), (const void*)dc_p, dcp.ptr()}, src_off, out_off, out_buf);
-      if (n) eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
-      continue;
-    }
-    emit_sealed_records(eng, layouts, np, item_policy + lo, {dc0.as<uint8_t>() + 384ull * lo, (const void*)dc_p, dcp.as<uint8_t>() + 384ull * lo}, src_off,
-                        dm.as<uint8_t>() + 384ull * lo, (const uint8_t*)nonces.data() + 12 * lo, pt_blob, pt_off + lo, out_off + lo, out_buf,
-                        parts > 1 ? &pending[part] : nullptr);
+    // the part's sources: base pointers shifted to its first item, row offsets relative to its first row.  An encaps is one part (lo = 0)
+    RecordSources src(np);
+    src.by_item(dc0.as<uint8_t>() + 384ull * lo, 384).by_rows(dc_p, 192, ro, np + 1).by_item(dcp.as<uint8_t>() + 384ull * lo, 384);
+    finish_encrypt(eng, nullptr, layouts, np, item_policy + lo, src, dm.as<uint8_t>() + 384ull * lo, (const uint8_t*)nonces.data() + 12 * lo, pt_blob,
+                   kem ? nullptr : pt_off + lo, out_off + lo, out_buf, key_buf, parts > 1 ? &pending[part] : nullptr);
   }
   for (auto& pc : pending) pc.wait(eng);
   tm.lap(kem ? "device: group arithmetic, headers, keys; two copies out" : "device: group arithmetic, records, sealing; copies out beside the next part");
@@ -1270,9 +1260,8 @@ bool delegate_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const CpAb
   eng.check(rhip_g1_add(cx, total, (const rhip_g1*)(old + n * 128), d_m1.as<rhip_g1>(), d_g1.as<rhip_g1>()), "rhip_g1_add");
   eng.check(rhip_g2_table_mul(cx, tb->g2, total, kr + n + total, d_m2.as<rhip_g2>()), "rhip_g2_table_mul");
   eng.check(rhip_g2_add(cx, total, (const rhip_g2*)(old + n * 128 + total * 64), d_m2.as<rhip_g2>(), d_g2.as<rhip_g2>()), "rhip_g2_add");
-  std::vector<uint64_t> src_off(3 * n);
-  for (size_t i = 0; i < n; i++) { src_off[i] = 128ull * i; src_off[n + i] = 64ull * row_off[i]; src_off[2 * n + i] = 128ull * row_off[i]; }
-  emit_plain_records(eng, layouts, n, item_subset, {d_d.ptr(), d_g1.ptr(), d_g2.ptr()}, src_off, out_off, out_buf);
+  emit_plain_records(eng, layouts, n, item_subset, RecordSources(n).by_item(d_d.ptr(), 128).by_rows(d_g1.ptr(), 64, row_off).by_rows(d_g2.ptr(), 128, row_off),
+                     out_off, out_buf);
   tm.lap("device: fixed-base multiplications, additions, records; one copy out");
   return true;
 }
@@ -1291,9 +1280,23 @@ static bool encrypt_core(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const 
   ShareTrees st;
   for (const auto& p : policies) st.add(p, language);
   const auto& pols = st.pols;
+  // records and sealing on the device (records.h); a record's size is its layout's
   std::vector<size_t> fixed(policies.size());
-  for (size_t p = 0; p < policies.size(); p++)
-    fixed[p] = 4 + policies[p].size() + 1 + 64 + 384 + 4 + pols[p]->leaf_name.size() * (4 + 64 + 128) + pols[p]->names_bytes + 4;
+  std::vector<RecordLayout> layouts(policies.size());
+  for (size_t p_ = 0; p_ < policies.size(); p_++) {
+    RecordLayout& L = layouts[p_];
+    const FlatPolicy& f = *pols[p_];
+    policy_header(L, policies[p_], language);
+    L.src(0, 0, 64);
+    L.src(1, 0, 384);
+    L.u32((uint32_t)f.leaf_name.size());
+    for (size_t y = 0; y < f.leaf_name.size(); y++) {
+      L.str(f.leaf_name_col[y]);
+      L.src(2, (uint32_t)(64 * y), 64);
+      L.src(3, (uint32_t)(128 * y), 128);
+    }
+    fixed[p_] = close_ciphertext(L, kem);
+  }
   if (!record_offsets("bsw::encrypt_packed", "item_policy", n, item_policy, policies.size(), fixed, kem ? nullptr : pt_off, out_buf, out_cap, out_off)) return false;
   st.place(n, item_policy, 1);
   const std::vector<uint32_t>&leaf_off = st.leaf_off, &coef_off = st.coef_off;
@@ -1325,37 +1328,9 @@ static bool encrypt_core(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const 
                                    st.d_leaf_off, st.d_tree_leaf, st.d_tree_gate, st.d_path_off, st.d_path_gate, st.d_path_x, st.d_gate_k, st.d_gate_coef_off, st.d_leaf_hash,
                                    dsec, dsec + 2 * n, st.d_coef_off, d_msg.as<rhip_gt>(), d_c.as<rhip_g1>(), d_cp.as<rhip_gt>(), d_g1.as<rhip_g1>(),
                                    d_g2.as<rhip_g2>()), "rhip_bsw_encrypt_batch");
-  // records and sealing on the device (records.h)
-  std::vector<RecordLayout> layouts(policies.size());
-  for (size_t p_ = 0; p_ < policies.size(); p_++) {
-    RecordLayout& L = layouts[p_];
-    const FlatPolicy& f = *pols[p_];
-    policy_header(L, policies[p_], language);
-    L.src(0, 0, 64);
-    L.src(1, 0, 384);
-    L.u32((uint32_t)f.leaf_name.size());
-    for (size_t y = 0; y < f.leaf_name.size(); y++) {
-      L.str(f.leaf_name_col[y]);
-      L.src(2, (uint32_t)(64 * y), 64);
-      L.src(3, (uint32_t)(128 * y), 128);
-    }
-    if (L.bytes() + 4 != fixed[p_]) throw RabeError("bsw::encrypt_packed: record layout and size disagree");
-    if (kem) L.u32(0);          // the length field of an empty sealed part; no sealed source
-  }
-  std::vector<uint64_t> src_off(4 * n);
-  for (size_t i = 0; i < n; i++) { src_off[i] = 64ull * i; src_off[n + i] = 384ull * i; src_off[2 * n + i] = 64ull * leaf_off[i]; src_off[3 * n + i] = 128ull * leaf_off[i]; }
-  if (kem) {          // headers from the template alone, keys straight out of the msg array: no seal kernel is launched
-    DBuf d_keys(&eng, n * 32 + 4);
-    eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
-    eng.check(rhip_gt_kdf_batch(cx, n, d_msg.as<rhip_gt>(), nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
-    emit_plain_records(eng, layouts, n, item_policy, {d_c.ptr(), d_cp.ptr(), d_g1.ptr(), d_g2.ptr()}, src_off, out_off, out_buf);
-    if (n) eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
-    tm.lap("device: group arithmetic, headers, keys; two copies out");
-    return true;
-  }
-  emit_sealed_records(eng, layouts, n, item_policy, {d_c.ptr(), d_cp.ptr(), d_g1.ptr(), d_g2.ptr()}, src_off, d_msg.ptr(), (const uint8_t*)nonces.data(),
-                      pt_blob, pt_off, out_off, out_buf);
-  tm.lap("device: group arithmetic, records, sealing; one copy out");
+  RecordSources src(n);
+  src.by_item(d_c.ptr(), 64).by_item(d_cp.ptr(), 384).by_rows(d_g1.ptr(), 64, leaf_off).by_rows(d_g2.ptr(), 128, leaf_off);
+  finish_encrypt(eng, &tm, layouts, n, item_policy, src, d_msg.ptr(), (const uint8_t*)nonces.data(), pt_blob, pt_off, out_off, out_buf, key_buf);
   return true;
 }
 bool encrypt_packed(Engine& eng, Rng& rng, const CpAbePublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
@@ -1602,154 +1577,112 @@ void* make_enc_tables(Engine& eng, const void* arg) {
   return t;
 }
 }  // namespace
-// n calls of lsw::encrypt (lsw/mod.rs:180-219): item i under the attribute list sets[item_set[i]].  Draw order per item: secret (:188), one
-// sx per attribute (:196-200, with the reference's index quirk: sx[0] loses sx[i], not the new element), the message exponent, the nonce.
-// Record = KpAbeCiphertext: e1 = e_gg_alpha^secret * msg, e2 = g2*secret, rows (name, g1*(h(a) secret), g1_b*sx_i, g1_b2*(sx_i h(a)) + h_b*sx_i),
-// sealed plaintext.  Every element is a fixed-base multiple of a public-key element: window-table launches for the whole batch.
-bool encrypt_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
-                    const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  StageTimer tm("lsw::encrypt_packed");
-  Engine::ArenaScope arena(eng);
-  if (n && (!item_set || !pt_off || !out_off)) throw RabeError("lsw::encrypt_packed: null input");
-  std::vector<size_t> fixed(sets.size());
-  std::vector<std::vector<Fr>> hashes(sets.size());
-  for (size_t s = 0; s < sets.size(); s++) {
-    if (sets[s].empty()) throw RabeError("attributes or data empty");
-    fixed[s] = 384 + 128 + 4 + 4;
-    for (const auto& a : sets[s]) { fixed[s] += 4 + a.size() + 3 * 64; hashes[s].push_back(sha3_hash_fr(a)); }
-  }
-  // the first bad item decides the message: an empty payload counts up to the first index out of range, which record_offsets reports
-  for (size_t i = 0; i < n && item_set[i] < sets.size(); i++) if (pt_off[i + 1] <= pt_off[i]) throw RabeError("attributes or data empty");
-  if (!record_offsets("lsw::encrypt_packed", "item_set", n, item_set, sets.size(), fixed, pt_off, out_buf, out_cap, out_off)) return false;
-  if (!n) return true;
-  std::vector<size_t> row_off(n + 1, 0);
-  for (size_t i = 0; i < n; i++) row_off[i + 1] = row_off[i] + sets[item_set[i]].size();
-  const size_t total = row_off[n];
-  // scalars: per item secret | msg exponent; per row h*secret | sx_i | sx_i*h
-  uint8_t* h_k = eng.pinned(0, (2 * n + 3 * total) * 32 + 32);
-  uint8_t* h_sec = h_k;
-  uint8_t* h_rho = h_sec + n * 32;
-  uint8_t* h_a = h_rho + n * 32;
-  uint8_t* h_b = h_a + total * 32;
-  uint8_t* h_c = h_b + total * 32;
-  std::vector<std::array<uint8_t, 12>> nonces(n);
-  draw_items(rng, n, [&](Rng& r, size_t i) {
-    const Fr secret = r.next_fr();
-    const auto& hs = hashes[item_set[i]];
-    std::vector<Fr> sx{secret};
-    for (size_t y = 0; y < hs.size(); y++) {
-      sx.push_back(r.next_fr());
-      sx[0] = fr_sub(sx[0], sx[y]);                 // :197-200 as it is written
-    }
-    for (size_t y = 0; y < hs.size(); y++) {
-      const Fr a = fr_mul(hs[y], secret), c = fr_mul(sx[y], hs[y]);
-      memcpy(h_a + 32 * (row_off[i] + y), a.l, 32);
-      memcpy(h_b + 32 * (row_off[i] + y), sx[y].l, 32);
-      memcpy(h_c + 32 * (row_off[i] + y), c.l, 32);
-    }
-    const Fr rho = r.next_fr();
-    memcpy(h_sec + 32 * i, secret.l, 32);
-    memcpy(h_rho + 32 * i, rho.l, 32);
-    r.fill(nonces[i].data(), 12);
-  });
-  tm.lap("draws + scalars");
-  const EncTables* tb;
-  {
-    std::string key((const char*)pk.g1.data(), 64);
-    key.append((const char*)pk.g2.data(), 128).append((const char*)pk.g1_b.data(), 64).append((const char*)pk.g1_b2.data(), 64).append((const char*)pk.h_b.data(), 64);
-    key.append((const char*)pk.e_gg_alpha.data(), 384);
-    tb = (const EncTables*)eng.aux("lsw_enc_tables", key, make_enc_tables, &pk, destroy_enc_tables, 2);
-  }
-  rhip_gt_table* gen = eng.gt_generator_table();
+// The rows of the ciphertexts, two ways.  Both read the call's scalar block d_k (per item secret | msg exponent, then what the draw loop stored
+// per row) and leave the sources of the three row elements in `src`.  heads() uploads d_k and queues msg, e1 and e2: a stage calls it once it
+// has its buffers, so that the fused stage's small blocking uploads go before anything is queued, not behind it.
+namespace {
+// encrypt: the host stored h*secret | sx | sx*h per row; four table walks and an addition write e3, e4, e5 as three arrays of 64-byte rows
+void rows_by_tables(Engine& eng, const EncTables* tb, size_t n, size_t total, const DBuf& d_k, const std::vector<uint32_t>& row_off,
+                    const std::function<void()>& heads, std::vector<DBuf>& keep, RecordSources& src) {
   rhip_ctx* cx = eng.ctx();
-  DBuf d_k(&eng, (2 * n + 3 * total) * 32 + 4), d_msg(&eng, n * 384), d_pw(&eng, n * 384), d_e1(&eng, n * 384), d_e2(&eng, n * 128), d_r1(&eng, total * 64 + 4),
-      d_r2(&eng, total * 64 + 4), d_t1(&eng, total * 64 + 4), d_t2(&eng, total * 64 + 4), d_r3(&eng, total * 64 + 4);
-  eng.check(rhip_upload_async(cx, d_k.ptr(), h_k, (2 * n + 3 * total) * 32), "upload");
-  const rhip_fr* k_sec = d_k.as<rhip_fr>();
-  const rhip_fr* k_rho = k_sec + n;
-  const rhip_fr* k_a = k_rho + n;
+  const rhip_fr* k_a = d_k.as<rhip_fr>() + 2 * n;
   const rhip_fr* k_b = k_a + total;
   const rhip_fr* k_c = k_b + total;
-  eng.check(rhip_gt_table_pow(cx, gen, n, k_rho, d_msg.as<rhip_gt>()), "rhip_gt_table_pow");                 // rng.gen::<Gt>() = e(g1, g2)^rho
-  eng.check(rhip_gt_table_pow(cx, tb->egg, n, k_sec, d_pw.as<rhip_gt>()), "rhip_gt_table_pow");
-  eng.check(rhip_gt_mul(cx, n, d_pw.as<rhip_gt>(), d_msg.as<rhip_gt>(), d_e1.as<rhip_gt>()), "rhip_gt_mul");
-  eng.check(rhip_g2_table_mul(cx, tb->g2, n, k_sec, d_e2.as<rhip_g2>()), "rhip_g2_table_mul");
+  DBuf d_r1(&eng, total * 64 + 4), d_r2(&eng, total * 64 + 4), d_t1(&eng, total * 64 + 4), d_t2(&eng, total * 64 + 4), d_r3(&eng, total * 64 + 4);
+  heads();
   eng.check(rhip_g1_table_mul(cx, tb->g1, total, k_a, d_r1.as<rhip_g1>()), "rhip_g1_table_mul");
   eng.check(rhip_g1_table_mul(cx, tb->g1_b, total, k_b, d_r2.as<rhip_g1>()), "rhip_g1_table_mul");
   eng.check(rhip_g1_table_mul(cx, tb->g1_b2, total, k_c, d_t1.as<rhip_g1>()), "rhip_g1_table_mul");
   eng.check(rhip_g1_table_mul(cx, tb->h_b, total, k_b, d_t2.as<rhip_g1>()), "rhip_g1_table_mul");
   eng.check(rhip_g1_add(cx, total, d_t1.as<rhip_g1>(), d_t2.as<rhip_g1>(), d_r3.as<rhip_g1>()), "rhip_g1_add");
-  // records and sealing on the device (records.h); layout = attribute set
-  std::vector<RecordLayout> layouts(sets.size());
-  for (size_t p_ = 0; p_ < sets.size(); p_++) {
-    RecordLayout& L = layouts[p_];
-    L.src(0, 0, 384);
-    L.src(1, 0, 128);
-    L.u32((uint32_t)sets[p_].size());
-    for (size_t y = 0; y < sets[p_].size(); y++) {
-      L.str(sets[p_][y]);
-      L.src(2, (uint32_t)(64 * y), 64);
-      L.src(3, (uint32_t)(64 * y), 64);
-      L.src(4, (uint32_t)(64 * y), 64);
-    }
-  }
-  std::vector<uint64_t> src_off(5 * n);
-  for (size_t i = 0; i < n; i++) {
-    src_off[i] = 384ull * i; src_off[n + i] = 128ull * i;
-    src_off[2 * n + i] = src_off[3 * n + i] = src_off[4 * n + i] = 64ull * row_off[i];
-  }
-  emit_sealed_records(eng, layouts, n, item_set, {d_e1.ptr(), d_e2.ptr(), d_r1.ptr(), d_r2.ptr(), d_r3.ptr()}, src_off, d_msg.ptr(),
-                      (const uint8_t*)nonces.data(), pt_blob, pt_off, out_off, out_buf);
-  tm.lap("device: group arithmetic, records, sealing; one copy out");
-  return true;
+  src.by_rows(d_r1.ptr(), 64, row_off).by_rows(d_r2.ptr(), 64, row_off).by_rows(d_r3.ptr(), 64, row_off);
+  for (DBuf* d : {&d_r1, &d_r2, &d_t1, &d_t2, &d_r3}) keep.push_back(std::move(*d));
 }
+// encaps: the host stored sx alone; one lane per row (k_lsw_enc_rows) forms h secret and sx h on the device from one hash per (list, position),
+// takes e5 as two walks on one accumulator and shares one inversion among a row's three conversions: one array of 192-byte rows
+void rows_fused(Engine& eng, const EncTables* tb, size_t n, size_t total, const DBuf& d_k, const std::vector<uint32_t>& row_off,
+                const std::vector<uint32_t>& hash_off, const std::vector<Fr>& hashes, const std::function<void()>& heads, std::vector<DBuf>& keep,
+                RecordSources& src) {
+  DBuf d_rows(&eng, total * 192 + 4), d_row_off = up32(eng, row_off), d_hash_off = up32(eng, hash_off), d_hash = up_bytes(eng, flatten_fr(hashes));
+  const rhip_fr* k_sec = d_k.as<rhip_fr>();
+  heads();
+  eng.check(rhip_lsw_encrypt_rows(eng.ctx(), tb->g1, tb->g1_b, tb->g1_b2, tb->h_b, n, total, d_row_off.as<uint32_t>(), d_hash_off.as<uint32_t>(),
+                                  d_hash.as<rhip_fr>(), k_sec, k_sec + 2 * n, d_rows.as<rhip_g1>()), "rhip_lsw_encrypt_rows");
+  src.by_rows(d_rows.ptr(), 192, row_off);
+  for (DBuf* d : {&d_rows, &d_row_off, &d_hash_off, &d_hash}) keep.push_back(std::move(*d));
+}
+}  // namespace
 
-// n key encapsulations (include/rabe_host.h: rabe_lsw_encaps_packed): record i is the KpAbeCiphertext header encrypt_packed writes for the same
-// draws with a sealed part of length zero, key_buf + 32 i = SHA3-256(bytes(msg_i)).  Draw order per item: encrypt_packed's without the nonce --
-// secret, one sx per attribute (the same index quirk), the message exponent.  The rows are one lane each (k_lsw_enc_rows): the host uploads
-// sx as it computes it (32 bytes per row), one secret per item and one hash per (list, position); h secret and sx h are formed on the device,
-// e5 is two walks on one accumulator and a row's three conversions share one inversion.  e1 and e2 keep their table calls.  No AES kernel.
-bool encaps_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
-                   uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
-  StageTimer tm("lsw::encaps_packed");
+// n calls of lsw::encrypt (lsw/mod.rs:180-219): item i under the attribute list sets[item_set[i]].  Draw order per item: secret (:188), one
+// sx per attribute (:196-200, with the reference's index quirk: sx[0] loses sx[i], not the new element), the message exponent, the nonce.
+// Record = KpAbeCiphertext: e1 = e_gg_alpha^secret * msg, e2 = g2*secret, rows (name, g1*(h(a) secret), g1_b*sx_i, g1_b2*(sx_i h(a)) + h_b*sx_i),
+// sealed plaintext.  Every element is a fixed-base multiple of a public-key element: window-table launches for the whole batch.
+// key_buf != nullptr is the key encapsulation (encaps_packed below): no plaintexts, no nonce draw, records that end in the length field of an
+// empty sealed part, per item the content key SHA3-256(bytes(msg)) -- and the rows from the fused kernel (rows_fused), which writes the
+// three elements of a row side by side: the kem flag forks what the draw loop stores, the row stage and with it the row source, nothing else.
+static bool encrypt_core(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
+                         const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  const bool kem = key_buf != nullptr;
+  const char* const what = kem ? "lsw::encaps_packed" : "lsw::encrypt_packed";
+  StageTimer tm(what);
   Engine::ArenaScope arena(eng);
-  if (n && (!item_set || !key_buf)) throw RabeError("lsw::encaps_packed: null input");
-  if (!out_off) throw RabeError("lsw::encaps_packed: null input");
   std::vector<size_t> fixed(sets.size());
   std::vector<uint32_t> set_hash_off(sets.size() + 1, 0);
   std::vector<Fr> hashes;
+  std::vector<RecordLayout> layouts(sets.size());          // layout = attribute set; a record's size is its layout's
   for (size_t s = 0; s < sets.size(); s++) {
     if (sets[s].empty()) throw RabeError("attributes or data empty");
-    fixed[s] = 384 + 128 + 4 + 4;
-    for (const auto& a : sets[s]) { fixed[s] += 4 + a.size() + 3 * 64; hashes.push_back(sha3_hash_fr(a)); }
+    RecordLayout& L = layouts[s];
+    L.src(0, 0, 384);
+    L.src(1, 0, 128);
+    L.u32((uint32_t)sets[s].size());
+    for (size_t y = 0; y < sets[s].size(); y++) {
+      hashes.push_back(sha3_hash_fr(sets[s][y]));
+      L.str(sets[s][y]);
+      if (kem) L.src(2, (uint32_t)(192 * y), 192);
+      else for (uint32_t k = 2; k < 5; k++) L.src(k, (uint32_t)(64 * y), 64);
+    }
     set_hash_off[s + 1] = (uint32_t)hashes.size();
+    fixed[s] = close_ciphertext(L, kem);
   }
-  if (!record_offsets("lsw::encaps_packed", "item_set", n, item_set, sets.size(), fixed, nullptr, out_buf, out_cap, out_off)) return false;
+  // the first bad item decides the message: an empty payload counts up to the first index out of range, which record_offsets reports
+  if (!kem) for (size_t i = 0; i < n && item_set[i] < sets.size(); i++) if (pt_off[i + 1] <= pt_off[i]) throw RabeError("attributes or data empty");
+  if (!record_offsets(what, "item_set", n, item_set, sets.size(), fixed, pt_off, out_buf, out_cap, out_off)) return false;
   if (!n) return true;
   std::vector<uint32_t> row_off(n + 1, 0), hash_off(n);
   for (size_t i = 0; i < n; i++) {
     row_off[i + 1] = row_off[i] + (uint32_t)sets[item_set[i]].size();
     hash_off[i] = set_hash_off[item_set[i]];
   }
-  const size_t total = row_off[n];
-  eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
-  // scalars: per item secret | msg exponent; per row sx
-  uint8_t* h_k = eng.pinned(0, (2 * n + total) * 32 + 32);
+  const size_t total = row_off[n], per_row = kem ? 1 : 3;
+  // scalars: per item secret | msg exponent; per row sx (encaps), or h*secret | sx_i | sx_i*h as three arrays (encrypt)
+  const size_t k_bytes = (2 * n + per_row * total) * 32;
+  uint8_t* h_k = eng.pinned(0, k_bytes + 32);
   uint8_t* h_sec = h_k;
   uint8_t* h_rho = h_sec + n * 32;
-  uint8_t* h_sx = h_rho + n * 32;
+  uint8_t* h_row = h_rho + n * 32;
+  std::vector<std::array<uint8_t, 12>> nonces(n);
   draw_items(rng, n, [&](Rng& r, size_t i) {
     const Fr secret = r.next_fr();
+    const Fr* hs = hashes.data() + hash_off[i];
     const size_t rows = row_off[i + 1] - row_off[i];
     std::vector<Fr> sx{secret};
     for (size_t y = 0; y < rows; y++) {
       sx.push_back(r.next_fr());
       sx[0] = fr_sub(sx[0], sx[y]);                 // :197-200 as it is written
     }
-    for (size_t y = 0; y < rows; y++) memcpy(h_sx + 32 * (row_off[i] + y), sx[y].l, 32);
+    for (size_t y = 0; y < rows; y++) {
+      uint8_t* at = h_row + 32 * (row_off[i] + y);
+      if (kem) { memcpy(at, sx[y].l, 32); continue; }
+      const Fr a = fr_mul(hs[y], secret), c = fr_mul(sx[y], hs[y]);
+      memcpy(at, a.l, 32);
+      memcpy(at + 32 * total, sx[y].l, 32);
+      memcpy(at + 64 * total, c.l, 32);
+    }
     const Fr rho = r.next_fr();
     memcpy(h_sec + 32 * i, secret.l, 32);
     memcpy(h_rho + 32 * i, rho.l, 32);
+    if (!kem) r.fill(nonces[i].data(), 12);
   });
   tm.lap("draws + scalars");
   const EncTables* tb;
@@ -1761,39 +1694,37 @@ bool encaps_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::v
   }
   rhip_gt_table* gen = eng.gt_generator_table();
   rhip_ctx* cx = eng.ctx();
-  DBuf d_k(&eng, (2 * n + total) * 32 + 4), d_msg(&eng, n * 384), d_pw(&eng, n * 384), d_e1(&eng, n * 384), d_e2(&eng, n * 128), d_rows(&eng, total * 192 + 4),
-      d_keys(&eng, n * 32 + 4), d_row_off = up32(eng, row_off), d_hash_off = up32(eng, hash_off), d_hash = up_bytes(eng, flatten_fr(hashes));
-  eng.check(rhip_upload_async(cx, d_k.ptr(), h_k, (2 * n + total) * 32), "upload");
-  const rhip_fr* k_sec = d_k.as<rhip_fr>();
-  const rhip_fr* k_rho = k_sec + n;
-  const rhip_fr* k_sx = k_rho + n;
-  eng.check(rhip_gt_table_pow(cx, gen, n, k_rho, d_msg.as<rhip_gt>()), "rhip_gt_table_pow");                 // rng.gen::<Gt>() = e(g1, g2)^rho
-  eng.check(rhip_gt_table_pow(cx, tb->egg, n, k_sec, d_pw.as<rhip_gt>()), "rhip_gt_table_pow");
-  eng.check(rhip_gt_mul(cx, n, d_pw.as<rhip_gt>(), d_msg.as<rhip_gt>(), d_e1.as<rhip_gt>()), "rhip_gt_mul");
-  eng.check(rhip_g2_table_mul(cx, tb->g2, n, k_sec, d_e2.as<rhip_g2>()), "rhip_g2_table_mul");
-  eng.check(rhip_lsw_encrypt_rows(cx, tb->g1, tb->g1_b, tb->g1_b2, tb->h_b, n, total, d_row_off.as<uint32_t>(), d_hash_off.as<uint32_t>(), d_hash.as<rhip_fr>(),
-                                  k_sec, k_sx, d_rows.as<rhip_g1>()), "rhip_lsw_encrypt_rows");
-  // headers from the template alone (records.h), keys straight out of the msg array: no seal kernel is launched
-  std::vector<RecordLayout> layouts(sets.size());
-  for (size_t p_ = 0; p_ < sets.size(); p_++) {
-    RecordLayout& L = layouts[p_];
-    L.src(0, 0, 384);
-    L.src(1, 0, 128);
-    L.u32((uint32_t)sets[p_].size());
-    for (size_t y = 0; y < sets[p_].size(); y++) {
-      L.str(sets[p_][y]);
-      L.src(2, (uint32_t)(192 * y), 192);
-    }
-    if (L.bytes() + 4 != fixed[p_]) throw RabeError("lsw::encaps_packed: record layout and size disagree");
-    L.u32(0);          // the length field of an empty sealed part; no sealed source
-  }
-  std::vector<uint64_t> src_off(3 * n);
-  for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * i; src_off[n + i] = 128ull * i; src_off[2 * n + i] = 192ull * row_off[i]; }
-  eng.check(rhip_gt_kdf_batch(cx, n, d_msg.as<rhip_gt>(), nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
-  emit_plain_records(eng, layouts, n, item_set, {d_e1.ptr(), d_e2.ptr(), d_rows.ptr()}, src_off, out_off, out_buf);
-  eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
-  tm.lap("device: group arithmetic, headers, keys; two copies out");
+  DBuf d_k(&eng, k_bytes + 4), d_msg(&eng, n * 384), d_pw(&eng, n * 384), d_e1(&eng, n * 384), d_e2(&eng, n * 128);
+  const auto heads = [&] {
+    eng.check(rhip_upload_async(cx, d_k.ptr(), h_k, k_bytes), "upload");
+    const rhip_fr* k_sec = d_k.as<rhip_fr>();
+    const rhip_fr* k_rho = k_sec + n;
+    eng.check(rhip_gt_table_pow(cx, gen, n, k_rho, d_msg.as<rhip_gt>()), "rhip_gt_table_pow");                 // rng.gen::<Gt>() = e(g1, g2)^rho
+    eng.check(rhip_gt_table_pow(cx, tb->egg, n, k_sec, d_pw.as<rhip_gt>()), "rhip_gt_table_pow");
+    eng.check(rhip_gt_mul(cx, n, d_pw.as<rhip_gt>(), d_msg.as<rhip_gt>(), d_e1.as<rhip_gt>()), "rhip_gt_mul");
+    eng.check(rhip_g2_table_mul(cx, tb->g2, n, k_sec, d_e2.as<rhip_g2>()), "rhip_g2_table_mul");
+  };
+  RecordSources src(n);
+  src.by_item(d_e1.ptr(), 384).by_item(d_e2.ptr(), 128);
+  std::vector<DBuf> d_rows;
+  if (kem) rows_fused(eng, tb, n, total, d_k, row_off, hash_off, hashes, heads, d_rows, src);
+  else rows_by_tables(eng, tb, n, total, d_k, row_off, heads, d_rows, src);
+  finish_encrypt(eng, &tm, layouts, n, item_set, src, d_msg.ptr(), (const uint8_t*)nonces.data(), pt_blob, pt_off, out_off, out_buf, key_buf);
   return true;
+}
+bool encrypt_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
+                    const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
+  if (n && (!item_set || !pt_off || !out_off)) throw RabeError("lsw::encrypt_packed: null input");
+  return encrypt_core(eng, rng, pk, sets, n, item_set, pt_blob, pt_off, out_buf, out_cap, out_off, nullptr);
+}
+// n key encapsulations (include/rabe_host.h: rabe_lsw_encaps_packed): record i is the KpAbeCiphertext header encrypt_packed writes for the same
+// draws with a sealed part of length zero, key_buf + 32 i = SHA3-256(bytes(msg_i)).  Draw order per item: encrypt_packed's without the nonce.
+// e1 and e2 keep their table calls.  No AES kernel.
+bool encaps_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const std::vector<std::vector<std::string>>& sets, size_t n, const uint32_t* item_set,
+                   uint8_t* out_buf, size_t out_cap, uint64_t* out_off, uint8_t* key_buf) {
+  if (n && (!item_set || !key_buf)) throw RabeError("lsw::encaps_packed: null input");
+  if (!out_off) throw RabeError("lsw::encaps_packed: null input");
+  return encrypt_core(eng, rng, pk, sets, n, item_set, nullptr, nullptr, out_buf, out_cap, out_off, key_buf);
 }
 
 // n calls of lsw::keygen (lsw/mod.rs:121-170).  Draw order per item: the gate coefficients of gen_shares_policy(alpha1), then one
@@ -1867,15 +1798,10 @@ bool keygen_packed(Engine& eng, Rng& rng, const KpAbePublicKey& pk, const KpAbeM
       else { const uint8_t zeros[192] = {0}; L.lit(zeros, 192); }
     }
   }
-  std::vector<const void*> srcs{d_d1.ptr(), d_d2.ptr()};
-  std::vector<uint64_t> src_off((any_negative ? 5 : 2) * n);
-  for (size_t i = 0; i < n; i++) { src_off[i] = 64ull * leaf_off[i]; src_off[n + i] = 128ull * leaf_off[i]; }
-  if (any_negative) {
-    const uint8_t* d3 = d_d345.as<uint8_t>();
-    srcs.push_back(d3); srcs.push_back(d3 + total * 64); srcs.push_back(d3 + 2 * total * 64);
-    for (size_t i = 0; i < n; i++) src_off[2 * n + i] = src_off[3 * n + i] = src_off[4 * n + i] = 64ull * leaf_off[i];
-  }
-  emit_plain_records(eng, layouts, n, item_policy, srcs, src_off, out_off, out_buf);
+  RecordSources src(n);
+  src.by_rows(d_d1.ptr(), 64, leaf_off).by_rows(d_d2.ptr(), 128, leaf_off);
+  if (any_negative) for (size_t k = 0; k < 3; k++) src.by_rows(d_d345.as<uint8_t>() + k * total * 64, 64, leaf_off);
+  emit_plain_records(eng, layouts, n, item_policy, src, out_off, out_buf);
   tm.lap("device: shares, fixed-base multiplications, records; one copy out");
   return true;
 }
@@ -2246,22 +2172,28 @@ static bool encrypt_core(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const s
   for (const auto* pk : pks) for (const auto& t : pk->attr) { arg.attrs.push_back(&t); key.append((const char*)t.egg_alpha.data(), 384).append((const char*)t.g2_y.data(), 128); }
   if (arg.attrs.empty()) throw RabeError("aw11::encrypt_packed: no authority attributes");
   ShareTrees st;
-  std::vector<std::vector<std::string>> row_name(policies.size());
   std::vector<uint32_t> leaf_attr;
   std::vector<size_t> fixed(policies.size());
+  std::vector<RecordLayout> layouts(policies.size());          // records and sealing on the device (records.h); a record's size is its layout's
   for (size_t p = 0; p < policies.size(); p++) {
     const FlatPolicy& f = st.add(policies[p], language);
     (void)calculate_msp(f.tree);                           // built and unused in the reference (:253-255) -- but it must not panic
-    fixed[p] = 4 + policies[p].size() + 1 + 384 + 4 + 4;
-    for (const auto& nc : f.leaf_name_col) {
-      const std::string up = upper(nc), want = remove_index(up);
+    RecordLayout& L = layouts[p];
+    policy_header(L, policies[p], language);
+    L.src(0, 0, 384);
+    L.u32((uint32_t)f.leaf_name_col.size());
+    for (uint32_t y = 0; y < f.leaf_name_col.size(); y++) {
+      const std::string up = upper(f.leaf_name_col[y]), want = remove_index(up);
       size_t a = 0;
       while (a < arg.attrs.size() && arg.attrs[a]->name != want) a++;
       if (a == arg.attrs.size()) throw RabeError("aw11::encrypt_packed: attribute " + want + " is in no authority key (rabe_aw11_encrypt drops such rows like the reference)");
       leaf_attr.push_back((uint32_t)a);
-      row_name[p].push_back(up);
-      fixed[p] += 4 + up.size() + 384 + 128 + 128;
+      L.str(up);
+      L.src(1, 384 * y, 384);
+      L.src(2, 128 * y, 128);
+      L.src(3, 128 * y, 128);
     }
+    fixed[p] = close_ciphertext(L, kem);
   }
   if (!record_offsets("aw11::encrypt_packed", "item_policy", n, item_policy, policies.size(), fixed, kem ? nullptr : pt_off, out_buf, out_cap, out_off)) return false;
   st.place(n, item_policy, 2);          // the s-shares' coefficients, then the 0-shares'
@@ -2297,38 +2229,9 @@ static bool encrypt_core(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const s
                                     st.d_leaf_off, st.d_tree_leaf, st.d_tree_gate, d_nc.as<uint32_t>(), st.d_path_off, st.d_path_gate, st.d_path_x, st.d_gate_k, st.d_gate_coef_off,
                                     d_leaf_attr.as<uint32_t>(), din, din + 2 * n, st.d_coef_off, din + 2 * n + total_coef, d_msg.as<rhip_gt>(), d_c0.as<rhip_gt>(),
                                     d_c1.as<rhip_gt>(), d_c2.as<rhip_g2>(), d_c3.as<rhip_g2>()), "rhip_aw11_encrypt_batch");
-  // records and sealing on the device (records.h)
-  std::vector<RecordLayout> layouts(policies.size());
-  for (size_t p_ = 0; p_ < policies.size(); p_++) {
-    RecordLayout& L = layouts[p_];
-    policy_header(L, policies[p_], language);
-    L.src(0, 0, 384);
-    L.u32((uint32_t)row_name[p_].size());
-    for (size_t y = 0; y < row_name[p_].size(); y++) {
-      L.str(row_name[p_][y]);
-      L.src(1, (uint32_t)(384 * y), 384);
-      L.src(2, (uint32_t)(128 * y), 128);
-      L.src(3, (uint32_t)(128 * y), 128);
-    }
-    if (kem) {
-      if (L.bytes() + 4 != fixed[p_]) throw RabeError("aw11::encaps_packed: record layout and size disagree");
-      L.u32(0);          // the length field of an empty sealed part; no sealed source
-    }
-  }
-  std::vector<uint64_t> src_off(4 * n);
-  for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * i; src_off[n + i] = 384ull * row_off[i]; src_off[2 * n + i] = src_off[3 * n + i] = 128ull * row_off[i]; }
-  if (kem) {          // headers from the template alone, keys straight out of the msg array: no seal kernel is launched
-    DBuf d_keys(&eng, n * 32 + 4);
-    eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
-    eng.check(rhip_gt_kdf_batch(cx, n, d_msg.as<rhip_gt>(), nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
-    emit_plain_records(eng, layouts, n, item_policy, {d_c0.ptr(), d_c1.ptr(), d_c2.ptr(), d_c3.ptr()}, src_off, out_off, out_buf);
-    if (n) eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
-    tm.lap("device: group arithmetic, headers, keys; two copies out");
-    return true;
-  }
-  emit_sealed_records(eng, layouts, n, item_policy, {d_c0.ptr(), d_c1.ptr(), d_c2.ptr(), d_c3.ptr()}, src_off, d_msg.ptr(), (const uint8_t*)nonces.data(),
-                      pt_blob, pt_off, out_off, out_buf);
-  tm.lap("device: group arithmetic, records, sealing; one copy out");
+  RecordSources src(n);
+  src.by_item(d_c0.ptr(), 384).by_rows(d_c1.ptr(), 384, row_off).by_rows(d_c2.ptr(), 128, row_off).by_rows(d_c3.ptr(), 128, row_off);
+  finish_encrypt(eng, &tm, layouts, n, item_policy, src, d_msg.ptr(), (const uint8_t*)nonces.data(), pt_blob, pt_off, out_off, out_buf, key_buf);
   return true;
 }
 bool encrypt_packed(Engine& eng, Rng& rng, const Aw11GlobalKey& gk, const std::vector<const Aw11PublicKey*>& pks, const std::vector<std::string>& policies,
@@ -2634,9 +2537,22 @@ static bool encrypt_core(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const 
   ShareTrees st;
   for (const auto& p : policies) st.add(p, language);
   const auto& pols = st.pols;
+  // records and sealing on the device (records.h); a record's size is its layout's
   std::vector<size_t> fixed(policies.size());
-  for (size_t p = 0; p < policies.size(); p++)
-    fixed[p] = 4 + policies[p].size() + 1 + 384 + 64 + 4 + pols[p]->leaf_name.size() * (4 + 64 + 64) + pols[p]->names_bytes + 4;
+  std::vector<RecordLayout> layouts(policies.size());
+  for (size_t p_ = 0; p_ < policies.size(); p_++) {
+    RecordLayout& L = layouts[p_];
+    const FlatPolicy& f = *pols[p_];
+    policy_header(L, policies[p_], language);
+    L.src(0, 0, 384);
+    L.src(1, 0, 64);
+    L.u32((uint32_t)f.leaf_name.size());
+    for (size_t y = 0; y < f.leaf_name.size(); y++) {
+      L.str(f.leaf_name_col[y]);
+      L.src(2, (uint32_t)(128 * y), 128);          // C | D, adjacent in the row kernel's output as in the record
+    }
+    fixed[p_] = close_ciphertext(L, kem);
+  }
   if (!record_offsets("ghw11::encrypt_packed", "item_policy", n, item_policy, policies.size(), fixed, kem ? nullptr : pt_off, out_buf, out_cap, out_off)) return false;
   st.place(n, item_policy, 1);
   const std::vector<uint32_t>&leaf_off = st.leaf_off, &coef_off = st.coef_off;
@@ -2671,36 +2587,9 @@ static bool encrypt_core(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const 
                                      st.d_leaf_off, st.d_tree_leaf, st.d_tree_gate, st.d_path_off, st.d_path_gate, st.d_path_x, st.d_gate_k, st.d_gate_coef_off, st.d_leaf_hash,
                                      dsec, dsec + 2 * n, st.d_coef_off, dsec + 2 * n + total_coef, d_msg.as<rhip_gt>(), d_c.as<rhip_gt>(), d_c1.as<rhip_g1>(),
                                      d_cd.as<rhip_g1>()), "rhip_ghw11_encrypt_batch");
-  // records and sealing on the device (records.h)
-  std::vector<RecordLayout> layouts(policies.size());
-  for (size_t p_ = 0; p_ < policies.size(); p_++) {
-    RecordLayout& L = layouts[p_];
-    const FlatPolicy& f = *pols[p_];
-    policy_header(L, policies[p_], language);
-    L.src(0, 0, 384);
-    L.src(1, 0, 64);
-    L.u32((uint32_t)f.leaf_name.size());
-    for (size_t y = 0; y < f.leaf_name.size(); y++) {
-      L.str(f.leaf_name_col[y]);
-      L.src(2, (uint32_t)(128 * y), 128);          // C | D, adjacent in the row kernel's output as in the record
-    }
-    if (L.bytes() + 4 != fixed[p_]) throw RabeError("ghw11::encrypt_packed: record layout and size disagree");
-    if (kem) L.u32(0);          // the length field of an empty sealed part; no sealed source
-  }
-  std::vector<uint64_t> src_off(3 * n);
-  for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * i; src_off[n + i] = 64ull * i; src_off[2 * n + i] = 128ull * leaf_off[i]; }
-  if (kem) {          // headers from the template alone, keys straight out of the msg array: no seal kernel is launched
-    DBuf d_keys(&eng, n * 32 + 4);
-    eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
-    eng.check(rhip_gt_kdf_batch(cx, n, d_msg.as<rhip_gt>(), nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
-    emit_plain_records(eng, layouts, n, item_policy, {d_c.ptr(), d_c1.ptr(), d_cd.ptr()}, src_off, out_off, out_buf);
-    if (n) eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
-    tm.lap("device: group arithmetic, headers, keys; two copies out");
-    return true;
-  }
-  emit_sealed_records(eng, layouts, n, item_policy, {d_c.ptr(), d_c1.ptr(), d_cd.ptr()}, src_off, d_msg.ptr(), (const uint8_t*)nonces.data(),
-                      pt_blob, pt_off, out_off, out_buf);
-  tm.lap("device: group arithmetic, records, sealing; one copy out");
+  RecordSources src(n);
+  src.by_item(d_c.ptr(), 384).by_item(d_c1.ptr(), 64).by_rows(d_cd.ptr(), 128, leaf_off);
+  finish_encrypt(eng, &tm, layouts, n, item_policy, src, d_msg.ptr(), (const uint8_t*)nonces.data(), pt_blob, pt_off, out_off, out_buf, key_buf);
   return true;
 }
 bool encrypt_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
@@ -3200,9 +3089,7 @@ bool keygen_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw11M
     for (size_t y = 0; y < sets[s].size(); y++) { L.str(sets[s][y]); L.src(0, (uint32_t)(128 * (2 + y)), 128); }
     if (L.bytes() != fixed[s]) throw RabeError("ghw11::keygen_packed: record layout and size disagree");
   }
-  std::vector<uint64_t> src_off(n);
-  for (size_t i = 0; i < n; i++) src_off[i] = 128ull * row_off[i];
-  emit_plain_records(eng, layouts, n, item_set, {d_out.ptr()}, src_off, out_off, out_buf);
+  emit_plain_records(eng, layouts, n, item_set, RecordSources(n).by_rows(d_out.ptr(), 128, row_off), out_off, out_buf);
   tm.lap("device: rows, records; one copy out");
   return true;
 }
@@ -3389,14 +3276,12 @@ bool provision_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const Ghw
     for (size_t y = 0; y < sets[s].size(); y++) { L.str(sets[s][y]); L.src(0, (uint32_t)(128 * (2 + y)), 128); }
     if (L.bytes() != fixed[s]) throw RabeError("ghw11::provision_packed: record layout and size disagree");
   }
-  std::vector<uint64_t> src_off(n);
-  for (size_t i = 0; i < n; i++) src_off[i] = 128ull * row_off[i];
   eng.check(rhip_sync(cx), "rhip_sync");
   for (size_t i = 0; i < n; i++)
     if (get_u32(h_flags + 4 * i)) throw std::runtime_error("called `Option::unwrap()` on a `None` value (Fr::inverse of zero)");
   tm.lap("device: scalars, rows");
-  if (want_sk) emit_plain_records(eng, layouts, n, item_set, {d_sk.ptr()}, src_off, sk_off, sk_buf);
-  emit_plain_records(eng, layouts, n, item_set, {d_tk.ptr()}, src_off, tk_off, tk_buf);
+  if (want_sk) emit_plain_records(eng, layouts, n, item_set, RecordSources(n).by_rows(d_sk.ptr(), 128, row_off), sk_off, sk_buf);
+  emit_plain_records(eng, layouts, n, item_set, RecordSources(n).by_rows(d_tk.ptr(), 128, row_off), tk_off, tk_buf);
   memcpy(rk_buf, h_rz + n * 32, n * 32);
   tm.lap("device: records; copies out");
   return true;
@@ -3474,6 +3359,7 @@ bool encrypt_packed(Engine& eng, Rng& rng, const DnfScheme& sc, const G1& p1, co
   for (const auto& k : keys) names.push_back(*k.attr);
   std::vector<std::vector<DnfTerm>> terms(P);
   std::vector<RecordLayout> layouts(P);
+  std::vector<size_t> fixed(P);
   for (size_t p = 0; p < P; p++) {
     PolicyNode tree;
     try {
@@ -3497,10 +3383,9 @@ bool encrypt_packed(Engine& eng, Rng& rng, const DnfScheme& sc, const G1& p1, co
       L.src(1, (uint32_t)(128 * y + 64), 64);
       L.src(2, (uint32_t)(256 * y + 128), 128);
     }
-    if (kem) L.u32(0);          // the length field of an empty sealed part; no sealed source
+    fixed[p] = close_ciphertext(L, kem);
   }
-  if (!record_offsets(sc.timer, "item_policy", n, item_policy, P, [&](size_t i) { return layouts[item_policy[i]].bytes() + (kem ? 0 : 4); },
-                      kem ? nullptr : pt_off, out_buf, out_cap, out_off)) return false;
+  if (!record_offsets(sc.timer, "item_policy", n, item_policy, P, fixed, kem ? nullptr : pt_off, out_buf, out_cap, out_off)) return false;
   if (!n) return true;
   std::vector<uint32_t> row_off(n + 1, 0);
   for (size_t i = 0; i < n; i++) row_off[i + 1] = row_off[i] + (uint32_t)terms[item_policy[i]].size();
@@ -3576,20 +3461,10 @@ bool encrypt_packed(Engine& eng, Rng& rng, const DnfScheme& sc, const G1& p1, co
   eng.check(rhip_dnf_encrypt_batch(cx, dpk, sets.size(), sets.data(), n, rows, d_rt.as<uint32_t>(), d_ri.as<uint32_t>(), d_in.as<rhip_fr>() + n_exp * n,
                                    d_msg.as<rhip_gt>(), d_gt.as<rhip_gt>(), d_g1.as<rhip_g1>(), d_g2.as<rhip_g2>()), "rhip_dnf_encrypt_batch");
   // records and sealing on the device (records.h); the data is sealed under msg (BDABE) / msg1 msg2 (MKE08)
-  std::vector<uint64_t> src_off(3 * n);
-  for (size_t i = 0; i < n; i++) { src_off[i] = 384ull * n_gt * row_off[i]; src_off[n + i] = 128ull * row_off[i]; src_off[2 * n + i] = 256ull * row_off[i]; }
-  if (kem) {          // headers from the template alone, keys straight out of the msg array: no seal kernel is launched
-    DBuf d_keys(&eng, n * 32 + 4);
-    eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
-    eng.check(rhip_gt_kdf_batch(cx, n, d_msg.as<rhip_gt>() + (n_exp - 1) * n, nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
-    emit_plain_records(eng, layouts, n, item_policy, {d_gt.ptr(), d_g1.ptr(), d_g2.ptr()}, src_off, out_off, out_buf);
-    eng.check(rhip_download(cx, key_buf, d_keys.ptr(), n * 32), "download (keys)");
-    tm.lap("device: group arithmetic, headers, keys; two copies out");
-    return true;
-  }
-  emit_sealed_records(eng, layouts, n, item_policy, {d_gt.ptr(), d_g1.ptr(), d_g2.ptr()}, src_off, d_msg.as<rhip_gt>() + (n_exp - 1) * n,
-                      (const uint8_t*)nonces.data(), pt_blob, pt_off, out_off, out_buf);
-  tm.lap("device: group arithmetic, records, sealing; one copy out");
+  RecordSources src(n);
+  src.by_rows(d_gt.ptr(), 384 * n_gt, row_off).by_rows(d_g1.ptr(), 128, row_off).by_rows(d_g2.ptr(), 256, row_off);
+  finish_encrypt(eng, &tm, layouts, n, item_policy, src, d_msg.as<rhip_gt>() + (n_exp - 1) * n, (const uint8_t*)nonces.data(), pt_blob, pt_off, out_off, out_buf,
+                 key_buf);
   return true;
 }
 
@@ -3657,9 +3532,8 @@ bool keygen_packed(Engine& eng, Rng& rng, const char* what, const G1& p1, const 
   DBuf d_r(&eng, n * 32), d_g1(&eng, n * 128 + 4), d_g2(&eng, n * 256 + 4), d_names = up_bytes(eng, name_bytes);
   eng.check(rhip_upload_async(cx, d_r.ptr(), h_r, n * 32), "upload");
   eng.check(rhip_dnf_keygen_batch(cx, keys, n, d_r.as<rhip_fr>(), d_g1.as<rhip_g1>(), d_g2.as<rhip_g2>()), "rhip_dnf_keygen_batch");
-  std::vector<uint64_t> src_off(3 * n);
-  for (size_t i = 0; i < n; i++) { src_off[i] = 128ull * i; src_off[n + i] = 256ull * i; src_off[2 * n + i] = name_off[i]; }
-  emit_plain_records(eng, layouts, n, item_layout.data(), {d_g1.ptr(), d_g2.ptr(), d_names.ptr()}, src_off, out_off, out_buf);
+  emit_plain_records(eng, layouts, n, item_layout.data(), RecordSources(n).by_item(d_g1.ptr(), 128).by_item(d_g2.ptr(), 256).at_bytes(d_names.ptr(), name_off),
+                     out_off, out_buf);
   tm.lap("device: rows, records; one copy out");
   return true;
 }
@@ -3802,8 +3676,8 @@ bool request_sk_packed(Engine& eng, const char* what, const std::string& authori
     }
     out_off[n] = at;
     rec_off.push_back(at);
-    off1.insert(off1.end(), off2.begin(), off2.end());
-    emit_plain_records(eng, layouts, lay.size(), lay.data(), {d_a1.ptr(), d_a2.ptr()}, off1, rec_off.data(), out_buf);
+    emit_plain_records(eng, layouts, lay.size(), lay.data(), RecordSources(lay.size()).at_bytes(d_a1.ptr(), off1).at_bytes(d_a2.ptr(), off2), rec_off.data(),
+                       out_buf);
     if (lay.empty()) eng.check(rhip_sync(cx), "rhip_sync");
     tm.lap(trusted ? "device: rows, records; one copy out" : "device: rows, records, membership beside; one copy out");
   }

@@ -61,36 +61,60 @@ void sym_shape(const std::vector<uint32_t>& len, std::vector<uint32_t>* blk_off,
   }
 }
 
-void emit_sealed_records(Engine& eng, const std::vector<RecordLayout>& layouts, size_t n, const uint32_t* item_layout,
-                         const std::vector<const void*>& dev_src, const std::vector<uint64_t>& src_item_off, const void* d_msg,
-                         const uint8_t* nonces, const uint8_t* pt_blob, const uint64_t* pt_off, const uint64_t* out_off, uint8_t* out_buf,
+// What the two record writers share.  The constructor puts the layouts' maps back to back, checks that record i is its layout's bytes and
+// tail(i, where those end) more, and makes the tables of rhip_assemble_records the first six of pp, in this order; the writer adds its own,
+// uploads pp and allocates; launch() takes the device pointer that out_off is relative to.
+namespace {
+struct Assembly {
+  ParamPack& pp;
+  const size_t n, n_src;
+  size_t h_out_off, h_layout, h_loff, h_map, h_src, h_sio;
+  template <class TAIL>
+  Assembly(const std::string& who, ParamPack& pp_, const std::vector<RecordLayout>& layouts, size_t n_, const uint32_t* item_layout, const RecordSources& src,
+           const uint64_t* out_off, TAIL tail) : pp(pp_), n(n_), n_src(src.dev_src.size()) {
+    if (src.n != n || src.item_off.size() != n_src * n) throw RabeError(who + ": src_item_off has the wrong size");
+    std::vector<uint32_t> layout_off{0}, map;
+    for (const auto& l : layouts) {
+      map.insert(map.end(), l.map.begin(), l.map.end());
+      layout_off.push_back((uint32_t)map.size());
+    }
+    for (size_t i = 0; i < n; i++) {
+      const uint64_t end = out_off[i] + layouts[item_layout[i]].bytes();
+      if (end + tail(i, end) != out_off[i + 1]) throw RabeError(who + ": record sizes do not add up");
+    }
+    h_out_off = pp.add(out_off, n * 8); h_layout = pp.add(item_layout, n * 4); h_loff = pp.add(layout_off); h_map = pp.add(map);
+    h_src = pp.add(src.dev_src); h_sio = pp.add(src.item_off);
+  }
+  void launch(Engine& eng, uint8_t* d_out) const {
+    eng.check(rhip_assemble_records(eng.ctx(), n, d_out, pp.dev<uint64_t>(h_out_off), pp.dev<uint32_t>(h_layout), pp.dev<uint32_t>(h_loff),
+                                    pp.dev<uint32_t>(h_map), (uint32_t)n_src, pp.dev<const uint8_t*>(h_src), pp.dev<uint64_t>(h_sio)),
+              "rhip_assemble_records");
+  }
+};
+}  // namespace
+
+void emit_sealed_records(Engine& eng, const std::vector<RecordLayout>& layouts, size_t n, const uint32_t* item_layout, const RecordSources& src,
+                         const void* d_msg, const uint8_t* nonces, const uint8_t* pt_blob, const uint64_t* pt_off, const uint64_t* out_off, uint8_t* out_buf,
                          PendingCopy* defer) {
   if (!n) return;
   TailTimer tm(eng, "emit_sealed_records");
   tm.lap("kernels queued before the tail");
-  const size_t n_src = dev_src.size();
-  if (src_item_off.size() != n_src * n) throw RabeError("emit_sealed_records: src_item_off has the wrong size");
-  std::vector<uint32_t> layout_off{0}, map;
-  for (const auto& l : layouts) {
-    map.insert(map.end(), l.map.begin(), l.map.end());
-    layout_off.push_back((uint32_t)map.size());
-  }
+  auto pp_owner = std::make_shared<ParamPack>(eng);
+  ParamPack& pp = *pp_owner;
   std::vector<uint32_t> len(n), blk_off, seg_off;
   std::vector<uint64_t> sealed_off(n);
-  for (size_t i = 0; i < n; i++) {
+  // behind the layout's bytes: the u32 length of the sealed part, then nonce, ciphertext and tag
+  const Assembly as("emit_sealed_records", pp, layouts, n, item_layout, src, out_off, [&](size_t i, uint64_t end) -> uint64_t {
     const uint64_t l = pt_off[i + 1] - pt_off[i];
     if (l > 0xFFFFFF00ull) throw RabeError("packed call: a plaintext of 4 GB or more");
     len[i] = (uint32_t)l;
-    sealed_off[i] = out_off[i] + layouts[item_layout[i]].bytes() + 4;
-    if (sealed_off[i] + l + 28 != out_off[i + 1]) throw RabeError("emit_sealed_records: record sizes do not add up");
-  }
+    sealed_off[i] = end + 4;
+    return 4 + l + 28;
+  });
   sym_shape(len, &blk_off, &seg_off);
   rhip_ctx* cx = eng.ctx();
-  auto pp_owner = std::make_shared<ParamPack>(eng);
-  ParamPack& pp = *pp_owner;
-  const size_t h_out_off = pp.add(out_off, n * 8), h_layout = pp.add(item_layout, n * 4), h_loff = pp.add(layout_off), h_map = pp.add(map),
-               h_src = pp.add(dev_src), h_sio = pp.add(src_item_off), h_nonce = pp.add(nonces, n * 12), h_pt_off = pp.add(pt_off, n * 8),
-               h_soff = pp.add(sealed_off), h_len = pp.add(len), h_blk = pp.add(blk_off), h_seg = pp.add(seg_off);
+  const size_t h_nonce = pp.add(nonces, n * 12), h_pt_off = pp.add(pt_off, n * 8), h_soff = pp.add(sealed_off), h_len = pp.add(len), h_blk = pp.add(blk_off),
+               h_seg = pp.add(seg_off);
   const uint64_t pt_bytes = pt_off[n] - pt_off[0];
   const bool small_pt = pt_bytes <= (8u << 20);
   const size_t h_pt = small_pt ? pp.add(pt_blob + pt_off[0], (size_t)pt_bytes) : 0;
@@ -110,9 +134,7 @@ void emit_sealed_records(Engine& eng, const std::vector<RecordLayout>& layouts, 
   const size_t out_bytes = (size_t)(out_off[n] - out_off[0]);
   DBuf d_out_buf(&eng, out_bytes ? out_bytes : 4), d_ws(&eng, rhip_seal_workspace_bytes(n, seg_off[n]));
   uint8_t* const d_out = d_out_buf.as<uint8_t>() - out_off[0];
-  eng.check(rhip_assemble_records(cx, n, d_out, pp.dev<uint64_t>(h_out_off), pp.dev<uint32_t>(h_layout), pp.dev<uint32_t>(h_loff),
-                                  pp.dev<uint32_t>(h_map), (uint32_t)n_src, pp.dev<const uint8_t*>(h_src), pp.dev<uint64_t>(h_sio)),
-            "rhip_assemble_records");
+  as.launch(eng, d_out);
   tm.lap("rhip_assemble_records");
   // pt_off is relative to pt_blob; the device copy starts at pt_off[0]
   eng.scrub_session_when_done();          // Gt session keys, AES key schedules and the encryption scalars do not outlive the call
@@ -169,28 +191,31 @@ PendingCopy::~PendingCopy() {          // a caller that unwinds without wait(): 
   if (eng) { eng->pinned_hold(-1); eng = nullptr; }
 }
 
-void emit_plain_records(Engine& eng, const std::vector<RecordLayout>& layouts, size_t n, const uint32_t* item_layout,
-                        const std::vector<const void*>& dev_src, const std::vector<uint64_t>& src_item_off, const uint64_t* out_off, uint8_t* out_buf) {
+void emit_plain_records(Engine& eng, const std::vector<RecordLayout>& layouts, size_t n, const uint32_t* item_layout, const RecordSources& src,
+                        const uint64_t* out_off, uint8_t* out_buf) {
   if (!n) return;
-  const size_t n_src = dev_src.size();
-  if (src_item_off.size() != n_src * n) throw RabeError("emit_plain_records: src_item_off has the wrong size");
-  std::vector<uint32_t> layout_off{0}, map;
-  for (const auto& l : layouts) {
-    map.insert(map.end(), l.map.begin(), l.map.end());
-    layout_off.push_back((uint32_t)map.size());
-  }
-  for (size_t i = 0; i < n; i++)
-    if (out_off[i] + layouts[item_layout[i]].bytes() != out_off[i + 1]) throw RabeError("emit_plain_records: record sizes do not add up");
-  rhip_ctx* cx = eng.ctx();
   ParamPack pp(eng);
-  const size_t h_out_off = pp.add(out_off, n * 8), h_layout = pp.add(item_layout, n * 4), h_loff = pp.add(layout_off), h_map = pp.add(map),
-               h_src = pp.add(dev_src), h_sio = pp.add(src_item_off);
+  const Assembly as("emit_plain_records", pp, layouts, n, item_layout, src, out_off, [](size_t, uint64_t) -> uint64_t { return 0; });
   pp.upload();
   DBuf d_out(&eng, (size_t)out_off[n]);
-  eng.check(rhip_assemble_records(cx, n, d_out.as<uint8_t>(), pp.dev<uint64_t>(h_out_off), pp.dev<uint32_t>(h_layout), pp.dev<uint32_t>(h_loff),
-                                  pp.dev<uint32_t>(h_map), (uint32_t)n_src, pp.dev<const uint8_t*>(h_src), pp.dev<uint64_t>(h_sio)),
-            "rhip_assemble_records");
-  eng.check(rhip_download(cx, out_buf + out_off[0], d_out.as<uint8_t>() + out_off[0], (size_t)(out_off[n] - out_off[0])), "download (records)");
+  as.launch(eng, d_out.as<uint8_t>());
+  eng.check(rhip_download(eng.ctx(), out_buf + out_off[0], d_out.as<uint8_t>() + out_off[0], (size_t)(out_off[n] - out_off[0])), "download (records)");
+}
+
+void finish_encrypt(Engine& eng, StageTimer* tm, const std::vector<RecordLayout>& layouts, size_t n, const uint32_t* item_layout, const RecordSources& src,
+                    const void* d_msg, const uint8_t* nonces, const uint8_t* pt_blob, const uint64_t* pt_off, const uint64_t* out_off, uint8_t* out_buf,
+                    uint8_t* key_buf, PendingCopy* defer) {
+  if (key_buf) {          // headers from the template alone, keys straight out of the msg array: no seal kernel is launched
+    DBuf d_keys(&eng, n * 32 + 4);
+    eng.scrub_session_when_done();          // msg, the keys and the encryption scalars do not outlive the call
+    eng.check(rhip_gt_kdf_batch(eng.ctx(), n, (const rhip_gt*)d_msg, nullptr, d_keys.as<uint8_t>()), "rhip_gt_kdf_batch");
+    emit_plain_records(eng, layouts, n, item_layout, src, out_off, out_buf);
+    if (n) eng.check(rhip_download(eng.ctx(), key_buf, d_keys.ptr(), n * 32), "download (keys)");
+    if (tm) tm->lap("device: group arithmetic, headers, keys; two copies out");
+    return;
+  }
+  emit_sealed_records(eng, layouts, n, item_layout, src, d_msg, nonces, pt_blob, pt_off, out_off, out_buf, defer);
+  if (tm) tm->lap("device: group arithmetic, records, sealing; one copy out");
 }
 
 struct BlobGather::Up { std::future<int32_t> f; };

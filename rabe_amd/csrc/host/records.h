@@ -13,50 +13,14 @@
 #include <unordered_map>
 #include <vector>
 #include "common.h"
+#include "record_layout.h"
 
 namespace rabe { namespace schemes {
-
-// the fixed part of one record shape (everything but the sealed plaintext and its u32 length): byte b is a literal or byte `o` of
-// the item's part in source k (include/rabe_hip.h: rhip_assemble_records)
-struct RecordLayout {
-  std::vector<uint32_t> map;
-  struct Part { uint32_t rec_off, len, k, part_off; };
-  std::vector<Part> parts;
-  void lit(const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; for (size_t i = 0; i < n; i++) map.push_back(0xFF000000u | b[i]); }
-  void u8(uint8_t v) { map.push_back(0xFF000000u | v); }
-  void u32(uint32_t v) { for (int i = 0; i < 4; i++) map.push_back(0xFF000000u | ((v >> (8 * i)) & 0xFFu)); }
-  void str(const std::string& s) { u32((uint32_t)s.size()); lit(s.data(), s.size()); }
-  void src(uint32_t k, uint32_t off, uint32_t len) {
-    parts.push_back({(uint32_t)map.size(), len, k, off});
-    for (uint32_t i = 0; i < len; i++) map.push_back((k << 24) | (off + i));
-  }
-  size_t bytes() const { return map.size(); }
-};
 
 // the head of a record that starts with its policy: the text, then the language as one byte
 inline void policy_header(RecordLayout& L, const std::string& text, PolicyLanguage language) {
   L.str(text);
   L.u8(language == PolicyLanguage::HumanPolicy ? 1 : 0);
-}
-
-// Sizing of an issuing call (n records out, item i of kind idx[i] < n_kinds).  check_index throws "<what>: <index_name> out of range";
-// record_offsets calls it, then fills out_off[0 .. n]: record i takes fixed(i) bytes -- or fixed[idx[i]], for a table by kind -- and, where
-// pt_off is given, its sealed plaintext (the payload + 28 bytes of nonce and tag).  Returns whether out_buf is there and holds out_off[n]
-// bytes.  Nothing is drawn or written before a caller has seen the answer; what a caller does at n == 0 is its own line.
-inline void check_index(const std::string& what, const char* index_name, size_t n, const uint32_t* idx, size_t n_kinds) {
-  for (size_t i = 0; i < n; i++) if (idx[i] >= n_kinds) throw RabeError(what + ": " + index_name + " out of range");
-}
-template <class FIXED>
-bool record_offsets(const std::string& what, const char* index_name, size_t n, const uint32_t* idx, size_t n_kinds, FIXED fixed, const uint64_t* pt_off,
-                    const uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  check_index(what, index_name, n, idx, n_kinds);
-  out_off[0] = 0;
-  for (size_t i = 0; i < n; i++) out_off[i + 1] = out_off[i] + fixed(i) + (pt_off ? (pt_off[i + 1] - pt_off[i]) + 28 : 0);
-  return out_buf && out_cap >= out_off[n];
-}
-inline bool record_offsets(const std::string& what, const char* index_name, size_t n, const uint32_t* idx, size_t n_kinds, const std::vector<size_t>& fixed,
-                           const uint64_t* pt_off, const uint8_t* out_buf, size_t out_cap, uint64_t* out_off) {
-  return record_offsets(what, index_name, n, idx, n_kinds, [&](size_t i) { return fixed[idx[i]]; }, pt_off, out_buf, out_cap, out_off);
 }
 
 // many small host arrays -> one staging area -> ONE upload; device pointers by handle afterwards
@@ -76,12 +40,14 @@ class ParamPack {
 // prefix sums of the 16-byte blocks and 64-block GHASH segments of plaintexts of these lengths (rabe_hip.h, Level S)
 void sym_shape(const std::vector<uint32_t>& len, std::vector<uint32_t>* blk_off, std::vector<uint32_t>* seg_off);
 
-// Tail of a packed encrypt.  layouts[l]: the record shape of layout l; item i has layout item_layout[i], its record starts at
-// out_off[i] and is layouts[l].bytes() + 4 + (plaintext length + 28) bytes long.  dev_src[k] / src_item_off[k * n + i]: where item i's
-// part in source k starts (device).  d_msg: the n Gt messages (device).  Writes the n finished records to out_buf.
-// With `defer`, the copy of the finished records into out_buf is handed to a helper thread on the lane's SIDE stream (it starts when the
-// kernels queued so far are done) and the call returns at once: a caller that cuts its batch into parts launches the next part's group
-// arithmetic beside it (PendingCopy::wait before the buffers are read; the parts of one call share one ArenaScope).
+// The record writers.  layouts[l]: the record shape of layout l; item i has layout item_layout[i] and its record starts at out_off[i];
+// src (record_layout.h: RecordSources) says where item i's part in every source starts on the device.  The n finished records go to
+// out_buf in one copy.
+//
+// emit_sealed_records: a record is layouts[l].bytes() + 4 + (plaintext length + 28) bytes long; d_msg: the n Gt messages (device) that key
+// the seal (rhip_seal_batch).  With `defer`, the copy of the finished records into out_buf is handed to a helper thread on the lane's SIDE
+// stream (it starts when the kernels queued so far are done) and the call returns at once: a caller that cuts its batch into parts launches
+// the next part's group arithmetic beside it (PendingCopy::wait before the buffers are read; the parts of one call share one ArenaScope).
 struct PendingCopy {
   DBuf d_out;
   // everything the queued assemble / seal kernels still read when emit_sealed_records returns early: the parameter pack, a large
@@ -93,15 +59,24 @@ struct PendingCopy {
   void wait(Engine& eng);
   ~PendingCopy();
 };
-void emit_sealed_records(Engine& eng, const std::vector<RecordLayout>& layouts, size_t n, const uint32_t* item_layout,
-                         const std::vector<const void*>& dev_src, const std::vector<uint64_t>& src_item_off, const void* d_msg,
-                         const uint8_t* nonces /*[n][12]*/, const uint8_t* pt_blob, const uint64_t* pt_off /*[n+1]*/,
+void emit_sealed_records(Engine& eng, const std::vector<RecordLayout>& layouts, size_t n, const uint32_t* item_layout, const RecordSources& src,
+                         const void* d_msg, const uint8_t* nonces /*[n][12]*/, const uint8_t* pt_blob, const uint64_t* pt_off /*[n+1]*/,
                          const uint64_t* out_off /*[n+1]*/, uint8_t* out_buf, PendingCopy* defer = nullptr);
 
-// The same without a sealed part (bulk key issuing): a record is exactly its layout's bytes.
-void emit_plain_records(Engine& eng, const std::vector<RecordLayout>& layouts, size_t n, const uint32_t* item_layout,
-                        const std::vector<const void*>& dev_src, const std::vector<uint64_t>& src_item_off, const uint64_t* out_off /*[n+1]*/,
-                        uint8_t* out_buf);
+// The same without a sealed part (bulk key issuing, KEM headers): a record is exactly its layout's bytes.
+void emit_plain_records(Engine& eng, const std::vector<RecordLayout>& layouts, size_t n, const uint32_t* item_layout, const RecordSources& src,
+                        const uint64_t* out_off /*[n+1]*/, uint8_t* out_buf);
+
+// The ONE end of a packed encrypt, after the group arithmetic is queued; d_msg keys it.
+//   key_buf == nullptr   the payloads are sealed under d_msg and the records written: emit_sealed_records
+//   key_buf != nullptr   key encapsulation (layouts closed by close_ciphertext(L, true)): the key buffer in the call's arena, the session
+//                        scrub flag (msg, the keys and the encryption scalars do not outlive the call), the KDF straight out of d_msg
+//                        (rhip_gt_kdf_batch: no seal kernel is launched), the headers from the templates alone, the key download --
+//                        two copies out
+// tm, where given, gets the lap of the device stage; a caller that cuts its batch into parts passes none, and a `defer` per part.
+void finish_encrypt(Engine& eng, StageTimer* tm, const std::vector<RecordLayout>& layouts, size_t n, const uint32_t* item_layout, const RecordSources& src,
+                    const void* d_msg, const uint8_t* nonces /*[n][12]*/, const uint8_t* pt_blob, const uint64_t* pt_off /*[n+1]*/,
+                    const uint64_t* out_off /*[n+1]*/, uint8_t* out_buf, uint8_t* key_buf /*[n][32]*/, PendingCopy* defer = nullptr);
 
 // Head of a packed decrypt: the caller's blob goes to the device as it is -- the copy starts at construction, on a helper thread, so it
 // runs beside the host's parsing of the records -- and the elements are gathered out of it there (rhip_gather_parts).  A SHAPE is the part
