@@ -214,6 +214,96 @@ class Engine:
         raw = self.download(out, n_rows * G1)
         return [raw[i * G1:(i + 1) * G1] for i in range(n_rows)]
 
+    def _mul_rows_at(self, g, elem, points, row_src, item_row_off, scalars, row_dst, out_rows, fill):
+        what = "%s_mul_rows_at" % g
+        n_rows, n_items = len(row_src), len(scalars)
+        out_rows = n_rows if out_rows is None else out_rows
+        if len(row_dst) != n_rows:
+            raise ValueError("%s: row_src and row_dst must hold one entry per row" % what)
+        if len(item_row_off) != n_items + 1 or item_row_off[0] != 0 or item_row_off[-1] != n_rows:
+            raise ValueError("%s: item_row_off must run from 0 to len(row_src) in len(scalars) + 1 entries" % what)
+        if any(item_row_off[i] > item_row_off[i + 1] for i in range(n_items)):
+            raise ValueError("%s: item_row_off must not decrease" % what)
+        if any(not 0 <= s < len(points) for s in row_src):
+            raise ValueError("%s: row_src must index into points" % what)
+        if any(not 0 <= d < out_rows for d in row_dst):
+            raise ValueError("%s: row_dst must index into the out_rows output elements" % what)
+        dp, dk, doff = self.upload(b"".join(points)), self.upload(b"".join(scalars)), self.upload_u32(item_row_off)
+        dsrc, ddst = self.upload_u32(row_src), self.upload_u32(row_dst)
+        out = self.alloc(out_rows * elem) if fill is None else self.upload(bytes([fill]) * (out_rows * elem))
+        self._check(getattr(self.lib, "rhip_" + what)(self.ctx, ctypes.c_size_t(n_rows), doff.ptr, dp.ptr, dsrc.ptr, ctypes.c_size_t(n_items), dk.ptr,
+                                                      ddst.ptr, out.ptr))
+        raw = self.download(out, out_rows * elem)
+        return [raw[i * elem:(i + 1) * elem] for i in range(out_rows)]
+
+    def g2_mul_rows_at(self, points, row_src, item_row_off, scalars, row_dst, out_rows=None, fill=None):
+        """out[row_dst[t]] = scalars[i] * points[row_src[t]] for the rows t of item i (rhip_g2_mul_rows_at); the rows are len(row_src), the
+        points may be fewer.  Returns the out_rows (default: the rows) output elements; with `fill` the output buffer starts as that repeated
+        byte, so a slot no row was written to shows it."""
+        return self._mul_rows_at("g2", G2, points, row_src, item_row_off, scalars, row_dst, out_rows, fill)
+
+    def g1_mul_rows_at(self, points, row_src, item_row_off, scalars, row_dst, out_rows=None, fill=None):
+        """out[row_dst[t]] = scalars[i] * points[row_src[t]] for the rows t of item i (rhip_g1_mul_rows_at), as g2_mul_rows_at"""
+        return self._mul_rows_at("g1", G1, points, row_src, item_row_off, scalars, row_dst, out_rows, fill)
+
+    def _upload_ptrs(self, bufs):
+        import array
+        return self.upload(array.array("Q", [b.ptr.value or 0 for b in bufs]).tobytes())
+
+    def assemble_records(self, out_size, out_off, layout, layout_off, map_words, sources, src_item_off, fill=None):
+        """rhip_assemble_records on host bytes: byte b of record i (at out_off[i] of an output of out_size bytes) = map word
+        map_words[layout_off[layout[i]] + b], 0xFF0000vv the literal vv, k << 24 | o byte o of sources[k] from src_item_off[k * n + i] on.
+        The array of source pointers is made here.  Returns the output bytes (started as the repeated byte `fill`, if given)."""
+        import array
+        n, n_src = len(out_off), len(sources)
+        if len(layout) != n or len(src_item_off) != n_src * n:
+            raise ValueError("assemble_records: one layout index per record and one source offset per (source, record)")
+        if any(not 0 <= l < len(layout_off) - 1 for l in layout) or any(not 0 <= o <= len(map_words) for o in layout_off):
+            raise ValueError("assemble_records: layout / layout_off out of range")
+        for i in range(n):
+            m0, m1 = layout_off[layout[i]], layout_off[layout[i] + 1]
+            if m1 < m0 or out_off[i] < 0 or out_off[i] + (m1 - m0) > out_size:
+                raise ValueError("assemble_records: record %d does not lie inside the output" % i)
+            for v in map_words[m0:m1]:
+                k = v >> 24
+                if k != 0xFF and (k >= n_src or not 0 <= src_item_off[k * n + i] + (v & 0xFFFFFF) < len(sources[k])):
+                    raise ValueError("assemble_records: record %d reads outside source %d" % (i, k))
+        up = {}
+        for s in sources:          # one object named twice is uploaded once
+            if id(s) not in up:
+                up[id(s)] = self.upload(s)
+        dsrc = [up[id(s)] for s in sources]
+        out =self.alloc(out_size) if fill is None else self.upload(bytes([fill]) * out_size)
+        doo, dsio, dptr = self.upload(array.array("Q", out_off).tobytes()), self.upload(array.array("Q", src_item_off).tobytes()), self._upload_ptrs(dsrc)
+        dl, dlo, dmap = self.upload_u32(layout), self.upload_u32(layout_off), self.upload_u32(map_words)
+        self._check(self.lib.rhip_assemble_records(self.ctx, ctypes.c_size_t(n), out.ptr, doo.ptr, dl.ptr, dlo.ptr, dmap.ptr, ctypes.c_uint32(n_src),
+                                                   dptr.ptr, dsio.ptr))
+        return self.download(out, out_size)
+
+    def gather_parts(self, blob, rec_off, layout, layout_off, part_src, part_dst, part_len, part_k, dst_sizes, dst_item_off, fill=None):
+        """rhip_gather_parts on host bytes: part p of layout[i] (the parts layout_off[l] .. layout_off[l + 1]) copies part_len[p] bytes from
+        blob[rec_off[i] + part_src[p]] to destination part_k[p] at dst_item_off[k * n + i] + part_dst[p].  The destinations (dst_sizes bytes
+        each, started as the repeated byte `fill`, if given) and the array of their pointers are made here.  Returns the destinations."""
+        import array
+        n, n_dst, n_parts = len(rec_off), len(dst_sizes), len(part_k)
+        if len(layout) != n or len(dst_item_off) != n_dst * n or not len(part_src) == len(part_dst) == len(part_len) == n_parts:
+            raise ValueError("gather_parts: one layout index per record, one offset per (destination, record), four entries per part")
+        if any(not 0 <= l < len(layout_off) - 1 for l in layout) or any(not 0 <= o <= n_parts for o in layout_off) or \
+                any(not 0 <= k < n_dst for k in part_k):
+            raise ValueError("gather_parts: layout / layout_off / part_k out of range")
+        for i in range(n):
+            for p in range(layout_off[layout[i]], layout_off[layout[i] + 1]):
+                s, d = rec_off[i] + part_src[p], dst_item_off[part_k[p] * n + i] + part_dst[p]
+                if part_len[p] < 0 or min(s, d) < 0 or s + part_len[p] > len(blob) or d + part_len[p] > dst_sizes[part_k[p]]:
+                    raise ValueError("gather_parts: part %d of record %d leaves the blob or its destination" % (p, i))
+        ddst = [self.alloc(s) if fill is None else self.upload(bytes([fill]) * s) for s in dst_sizes]
+        dblob, dro, ddio = self.upload(blob), self.upload(array.array("Q", rec_off).tobytes()), self.upload(array.array("Q", dst_item_off).tobytes())
+        dl, dlo, dptr = self.upload_u32(layout), self.upload_u32(layout_off), self._upload_ptrs(ddst)
+        dps, dpd, dpl, dpk = self.upload_u32(part_src), self.upload_u32(part_dst), self.upload_u32(part_len), self.upload_u32(part_k)
+        self._check(self.lib.rhip_gather_parts(self.ctx, ctypes.c_size_t(n), dblob.ptr, dro.ptr, dl.ptr, dlo.ptr, dps.ptr, dpd.ptr, dpl.ptr, dpk.ptr,
+                                               dptr.ptr, ddio.ptr))
+        return [self.download(d, s) for d, s in zip(ddst, dst_sizes)]
+
     def _ghw11_rows_in(self, what, item_row_off, item_hash_off, hashes, per_item):
         n_items = len(item_hash_off)
         if len(item_row_off) != n_items + 1 or item_row_off[0] != 0 or any(len(x) != n_items for x in per_item):
