@@ -665,6 +665,9 @@ typedef struct rhip_aw11_pk rhip_aw11_pk;
 int32_t rhip_aw11_pk_create(rhip_ctx* ctx, const rhip_g1* host_g1, const rhip_g2* host_g2, size_t n_attrs,
                             const rhip_gt* host_egg_alpha /*[n_attrs]*/, const rhip_g2* host_g2_y /*[n_attrs]*/, rhip_aw11_pk** out);
 void rhip_aw11_pk_destroy(rhip_aw11_pk* pk);
+/* The form the per-attribute tables of a handle took (read-only; the fallbacks above are silent otherwise): 0 plain 8-bit windows, 1 16-bit
+ * windows per attribute, 9 ... 14 signed windows of that width. */
+int32_t rhip_aw11_pk_table_form(const rhip_aw11_pk* pk, int32_t* form);
 /* Group arithmetic of n_items calls of aw11::encrypt (aw11/mod.rs:241-289).  Explicit randomness per item, in the
  * reference's draw order: s (:257), the gate coefficients of the s-shares then of the 0-shares (item_n_coef[i] each,
  * consecutive in dev_coef from item_coef_off[i]; :259-260), the Gt `msg` (:262), and one r_x per row (dev_rand, :267).

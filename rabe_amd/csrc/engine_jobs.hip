@@ -1811,6 +1811,12 @@ extern "C" int32_t rhip_aw11_pk_create(rhip_ctx* ctx, const rhip_g1* g1, const r
   *out = pk;
   return RHIP_OK;
 }
+// which per-attribute tables the handle got (the attr_w16 argument of k_aw11_enc_c1): 0 plain 8-bit, 1 16-bit, 9 ... 14 signed of that width
+extern "C" int32_t rhip_aw11_pk_table_form(const rhip_aw11_pk* pk, int32_t* form) {
+  if (!pk || !form) return RHIP_ERR_ARG;
+  *form = pk->attr_gt16 ? 1 : pk->attr_gt_s ? pk->s_bits : 0;
+  return RHIP_OK;
+}
 // one lane per (item, leaf row): lambda_x = share of s, omega_x = share of 0 (second coefficient set follows the first in
 // the item's draw list, aw11/mod.rs:259-260)
 __global__ void __launch_bounds__(256, RB_MIN_WAVES) k_aw11_enc_scalars(size_t n_items, size_t total_rows, const uint32_t* item_row_off,

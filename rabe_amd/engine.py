@@ -825,6 +825,12 @@ class Aw11Pk:
         eng._check(eng.lib.rhip_aw11_pk_create(eng.ctx, bytes(g1), bytes(g2), _sz(len(egg_alpha)), b"".join(egg_alpha), b"".join(g2_y),
                                                ctypes.byref(self.h)))
 
+    def table_form(self):
+        """rhip_aw11_pk_table_form: 0 plain 8-bit per-attribute tables, 1 16-bit ones, 9 ... 14 signed windows of that width"""
+        form = ctypes.c_int32(-1)
+        self.eng._check(self.eng.lib.rhip_aw11_pk_table_form(self.h, ctypes.byref(form)))
+        return form.value
+
     def destroy(self):
         if self.h:
             self.eng.lib.rhip_aw11_pk_destroy(self.h)
