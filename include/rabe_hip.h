@@ -384,6 +384,9 @@ int32_t rhip_ac17_cp_decrypt_batch_prepared(rhip_ctx* ctx, size_t n_items,
 typedef struct rhip_g2_lines rhip_g2_lines;
 int32_t rhip_g2_lines_prepare(rhip_ctx* ctx, size_t n, const rhip_g2* dev_q, rhip_g2_lines** out);
 void rhip_g2_lines_destroy(rhip_g2_lines* p);
+/* device memory the handle holds, in bytes: the line triples, the reduced-radix copy the contexts that run those kernels keep beside
+ * them, one flag per point */
+size_t rhip_g2_lines_bytes(const rhip_g2_lines* p);
 
 /* ---- Level B: BSW CP-ABE (src/schemes/bsw/mod.rs) ---------------------------------------------------------------
  * Flattened policy trees (the host has parsed the policy text; everything below is numbers).  The leaves of a policy
@@ -546,6 +549,22 @@ int32_t rhip_ghw11_transform_batch(rhip_ctx* ctx, size_t n_items, size_t max_pai
                                    const uint32_t* dev_sel_ct_row, const uint32_t* dev_sel_tk_attr, const rhip_fr* dev_sel_coeff,
                                    const rhip_g1* dev_ct_c1 /*[n_items]*/, const rhip_g1* dev_ct_c /*[rows]: ci*/, const rhip_g1* dev_ct_d /*[rows]: di*/,
                                    const uint32_t* dev_ct_row_off /*[n_items+1]*/, const rhip_g2_lines* tk_lines, rhip_gt* dev_out /*[n_items]*/);
+/* The same batch under MANY transform keys -- a proxy's mixed queue, item i served under its own user's key.  store_lines = ONE
+ * rhip_g2_lines_prepare over the elements of all keys, key after key, each in the order k_z, l_z, k_x[0], k_x[1], ...;
+ * dev_item_line_base[i] = the index, in that array, of the k_z of item i's key, so the item's pairs replay the blocks base, base + 1 and
+ * base + 2 + sel_tk_attr[e].  The other arguments are rhip_ghw11_transform_batch's, and out[i] is what that call returns for item i under
+ * its key's own handle, bit for bit: only the gather kernel differs (k_ghw11_pairs_keyed), the sum, the Miller loops and the final
+ * exponentiation are the same launches.  dev_item_ok (may be NULL: every item is served): an item with dev_item_ok[i] = 0 contributes no
+ * pair and its output is zeros -- what a caller that zeroed dev_out finds there (the launch set ends by writing them); its arrays are
+ * still read, so they must be valid.  A pair whose block index lies beyond the handle's count is skipped, never read.  RHIP_ERR_ARG: a
+ * handle of 2^32 - 2 or more elements (the two largest 32-bit values mark skipped and walking pairs). */
+int32_t rhip_ghw11_transform_batch_keyed(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel,
+                                         const uint32_t* dev_pair_off /*[n_items+1]*/, const uint32_t* dev_sel_start /*[n_items]*/,
+                                         const uint32_t* dev_sel_ct_row, const uint32_t* dev_sel_tk_attr, const rhip_fr* dev_sel_coeff,
+                                         const rhip_g1* dev_ct_c1 /*[n_items]*/, const rhip_g1* dev_ct_c /*[rows]: ci*/, const rhip_g1* dev_ct_d /*[rows]: di*/,
+                                         const uint32_t* dev_ct_row_off /*[n_items+1]*/, const uint32_t* dev_item_line_base /*[n_items]*/,
+                                         const uint32_t* dev_item_ok /*[n_items], may be NULL*/, const rhip_g2_lines* store_lines,
+                                         rhip_gt* dev_out /*[n_items]*/);
 /* ghw11 decrypt for the HOLDER of the secret key (no proxy): arguments of rhip_ghw11_transform_batch with sk_lines = rhip_g2_lines_prepare over
  * k, l, k_x[0], k_x[1], ... of the Ghw11SecretKey (a transform key has that layout), plus c of every item.
  *   msg[i] = c[i] * t_1[i]^-1,  t_1 = the transform's expression on the secret key's own elements

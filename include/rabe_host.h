@@ -25,6 +25,7 @@ enum {   /* object kinds for rabe_obj_free / rabe_obj_serialize / rabe_obj_deser
   RABE_LSW_PK = 20, RABE_LSW_MSK = 21, RABE_LSW_SK = 22, RABE_LSW_CT = 23,
   RABE_AW11_GK = 30, RABE_AW11_PK = 31, RABE_AW11_MSK = 32, RABE_AW11_SK = 33, RABE_AW11_CT = 34,
   RABE_GHW11_PK = 40, RABE_GHW11_MSK = 41, RABE_GHW11_SK = 42, RABE_GHW11_TK = 43, RABE_GHW11_RK = 44, RABE_GHW11_CT = 45, RABE_GHW11_TCT = 46,
+  RABE_GHW11_TK_STORE = 47,   /* rabe_ghw11_tk_store_create's handle: rabe_obj_free only, no byte form */
   /* bdabe / mke08: public key, master key, secret AUTHORITY key, user key (with its attribute keys), public attribute key, ciphertext */
   RABE_BDABE_PK = 50, RABE_BDABE_MSK = 51, RABE_BDABE_SKA = 52, RABE_BDABE_UK = 53, RABE_BDABE_PKA = 54, RABE_BDABE_CT = 55,
   RABE_MKE08_PK = 60, RABE_MKE08_MSK = 61, RABE_MKE08_SKA = 62, RABE_MKE08_UK = 63, RABE_MKE08_PKA = 64, RABE_MKE08_CT = 65
@@ -50,7 +51,7 @@ int32_t rabe_host_create(int32_t device, rabe_host** out);
  *   the key-policy KEMs: rabe_ac17_kp_encaps_packed, rabe_ac17_kp_decaps_packed, rabe_lsw_decaps_packed;
  *   the AW11 KEM: rabe_aw11_encaps_packed, rabe_aw11_decaps_packed;
  *   the GHW11 service: rabe_ghw11_encrypt_packed, rabe_ghw11_transform_packed, rabe_ghw11_decrypt_out_packed, rabe_ghw11_decrypt_packed,
- *     rabe_ghw11_keygen_packed, rabe_ghw11_provision_packed;
+ *     rabe_ghw11_keygen_packed, rabe_ghw11_provision_packed, rabe_ghw11_transform_keyed (rabe_ghw11_tk_store_create itself runs on devices[0]);
  *   the DNF schemes' encrypt: rabe_bdabe_encrypt_packed, rabe_mke08_encrypt_packed;
  *   the DNF schemes' KEM: rabe_bdabe_kem_encaps, rabe_bdabe_kem_decaps, rabe_mke08_kem_encaps, rabe_mke08_kem_decaps.
  * Each cuts its n_items into one contiguous block per device (sizes differ by at most one, blocks in device order; fewer items than
@@ -426,6 +427,31 @@ int32_t rabe_ghw11_encrypt_packed(rabe_host* h, const void* pk, const char* cons
  * part) pass through this call as full records do, with the same 768-byte output. */
 int32_t rabe_ghw11_transform_packed(rabe_host* h, const void* tk, size_t n_items, const uint8_t* ct_blob, size_t ct_len,
                                     const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/, uint8_t* tct_buf, size_t tct_cap);
+/* ---- the proxy's call for a MIXED queue: a device-resident store of many users' transform keys, and a batch in which item i belongs to
+ * user item_key[i].  (rabe_ghw11_transform_packed serves a batch under ONE key: a queue sorted by user becomes one small launch set per user.)
+ * STORE: tk_blob (+ n_keys + 1 offsets, tk_len) holds Ghw11TransformKey records exactly as rabe_ghw11_tkgen_packed / rabe_ghw11_provision_packed
+ *   write them.  The blob is UNTRUSTED, with the conventions of rabe_ghw11_tkgen_packed: nothing outside [0, tk_len) is read, a record has to end
+ *   where its offsets say, and unless RABE_PACKED_TRUSTED every G2 element goes through the batched membership pass.  A bad key fails alone:
+ *   key_status[u] = -1 (0 otherwise), the first error in rabe_host_last_error, and every item that later names it fails.  The elements of all
+ *   keys go to the device once and ONE set of prepared lines is made over them (16.9 KB per element for the line triples plus the reduced-radix
+ *   copy; rabe_ghw11_tk_store_bytes reports what the store holds on all devices).  The store is immutable; it may be used by any number of
+ *   calls on the host that made it.  Free it with rabe_obj_free(RABE_GHW11_TK_STORE, store) BEFORE rabe_host_destroy: the device memory is
+ *   released at once when the host is idle, and after the calls that may still use it have ended otherwise.
+ * TRANSFORM: DEFINITION -- tct_buf + 768 i and status[i] are what rabe_ghw11_transform_packed writes for record i ALONE under key item_key[i],
+ *   byte for byte; the bounds, the membership checks (unless RABE_PACKED_TRUSTED), the error texts and the pass-through of the headers
+ *   rabe_ghw11_encaps_packed writes are that call's.  An item_key out of range, or one that names a failed key, fails that item only: status -1
+ *   and 768 zero bytes.  Returns 1, with nothing written, when tct_cap < 768 n_items.  No randomness is drawn.  The selection plan of a policy
+ *   text is made once per distinct attribute-name list among the keys the batch names, not once per key.  On the device the batch is ONE launch
+ *   set whatever the number of keys (rhip_ghw11_transform_batch_keyed: a line base per item into the store's lines).  Under a device group the
+ *   items are cut as rabe_ghw11_transform_packed cuts them; every engine prepares its replica of the store's lines on first use and keeps it
+ *   until the store is freed.  The store prepares ONE replica at a time: in the first call on a group the engines' preparations run one
+ *   after the other (the other blocks wait), and rabe_ghw11_tk_store_bytes waits for a preparation in progress. */
+int32_t rabe_ghw11_tk_store_create(rabe_host* h, size_t n_keys, const uint8_t* tk_blob, size_t tk_len, const uint64_t* tk_off /*[n_keys+1]*/,
+                                   uint32_t flags, int32_t* key_status /*[n_keys]*/, void** store);
+uint64_t rabe_ghw11_tk_store_bytes(const void* store);
+int32_t rabe_ghw11_transform_keyed(rabe_host* h, const void* store, size_t n_items, const uint32_t* item_key /*[n_items]*/, const uint8_t* ct_blob,
+                                   size_t ct_len, const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/,
+                                   uint8_t* tct_buf, size_t tct_cap);
 /* Bulk key issuing (conventions of rabe_bsw_keygen_packed): n_items calls of ghw11::keygen (ghw11/mod.rs:123-152) under one master key, item i
  * with the attribute list item_set[i]; records = Ghw11SecretKey (k, l, rows (name, k_x)), written on the device.  Draw order: one r per item, in
  * item order.  Every element is a fixed-base multiple (L = g2 * r, K = g2_alpha + g2_a * r, K_x = g2 * (h(x) r)): one lane per element over window

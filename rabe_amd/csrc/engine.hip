@@ -1726,6 +1726,15 @@ extern "C" int32_t rhip_g2_lines_prepare(rhip_ctx* ctx, size_t n, const rhip_g2*
   *out = p;
   return RHIP_OK;
 }
+extern "C" size_t rhip_g2_lines_bytes(const rhip_g2_lines* p) {          // what the allocations above are, as the runtime holds them
+  size_t total = 0;
+  if (p)
+    for (void* a : {(void*)p->lines, (void*)p->q_inf, p->lines29}) {
+      size_t sz = 0;
+      if (a && hipMemPtrGetInfo(a, &sz) == hipSuccess) total += sz;
+    }
+  return total;
+}
 extern "C" void rhip_ac17_sk_lines_destroy(rhip_ac17_sk_lines* p) {
   if (!p) return;
   (void)hipFree(p->lines);

@@ -1581,14 +1581,61 @@ __global__ void __launch_bounds__(RB_PAIRS_BLOCK, 2) k_ghw11_pairs(size_t n_item
   if (j < m) st_g1_q(terms + (t - 2 * item), load_g1(ct_c[row].l));
   qref[t] = (p_inf || line_inf[line]) ? RHIP_Q_SKIP : line;
 }
-// the launches of transform (inv = false: out = t) and of the key holder's decrypt (inv = true: out = lead * t^-1)
+// The gather of k_ghw11_pairs<false> for a batch served under MANY transform keys (rhip_ghw11_transform_batch_keyed): the prepared lines of all
+// keys lie end to end in one handle, key after key in the order k_z, l_z, k_x[0], ..., and item_line_base[item] is the block of the item's
+// key's k_z -- so line = base + {0, 1, 2 + attr}, and the l_z pair reads line_inf[base + 1].  An item whose item_ok is 0, or whose line lies
+// beyond the handle's n_lines, gets RHIP_Q_SKIP on all its pairs (k_msm_finish_g1 never turns a skip back into a pair); its arrays are read
+// like any other item's.  A kernel of its own: the two instantiations above are compiled as before.
+__global__ void __launch_bounds__(RB_PAIRS_BLOCK, 2) k_ghw11_pairs_keyed(size_t n_items, size_t total_pairs, const uint32_t* pair_off, uint32_t ppi, const uint32_t* tile_off, const uint32_t* sel_start,
+                                                                        const uint32_t* sel_ct_row, const uint32_t* sel_tk_attr, const rhip_fr* sel_coeff,
+                                                                        const rhip_g1* ct_c1, const rhip_g1* ct_c, const rhip_g1* ct_d, const uint32_t* ct_row_off,
+                                                                        const uint32_t* item_line_base, const uint32_t* item_ok, uint32_t n_lines,
+                                                                        const uint8_t* line_inf, G1M* P, uint32_t* qref, G1M* terms) {
+  __shared__ uint32_t lds[2 * 8 * RB_PAIRS_BLOCK];
+  size_t t, item;
+  bool active;
+  pair_lane((size_t)blockIdx.x * blockDim.x + threadIdx.x, n_items, total_pairs, pair_off, ppi, tile_off, &t, &item, &active);
+  const uint32_t j = (uint32_t)(t - pair_off[item]);
+  const uint32_t m = pair_off[item + 1] - pair_off[item] - 2;
+  G1Aff base = aff_inf<Fp>();
+  uint32_t k[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t row = 0, line = 1;
+  if (j < m) {
+    const uint32_t e = sel_start[item] + j;
+    row = ct_row_off[item] + sel_ct_row[e];
+    base = load_g1(ct_d[row].l);
+    ld_scalar(k, sel_coeff + e);
+    line = 2 + sel_tk_attr[e];
+  } else if (j == m) {
+    base = load_g1(ct_c1[item].l);
+    line = 0;
+  }
+  const uint64_t at = (uint64_t)item_line_base[item] + line;
+  bool p_inf;
+  scale_and_store(lds, active && j <= m, base, k, j < m, P + t, &p_inf);
+  if (!active) return;
+  const bool dead = (item_ok && !item_ok[item]) || at >= n_lines;
+  if (j > m) { qref[t] = (dead || line_inf[at]) ? RHIP_Q_SKIP : (uint32_t)at; return; }          // P comes from k_msm_finish_g1 (which may turn the pair into a skip)
+  if (j < m) st_g1_q(terms + (t - 2 * item), load_g1(ct_c[row].l));
+  qref[t] = (dead || p_inf || line_inf[at]) ? RHIP_Q_SKIP : (uint32_t)at;
+}
+// lane = 16 bytes of an output: zeros over the outputs of the items whose item_ok is 0 (their pairs were all skipped, so the final exponentiation
+// left the unit there; a failed item's slot holds zeros, as the caller's buffer did before the call)
+__global__ void __launch_bounds__(256) k_zero_failed_gt(size_t n_quads, const uint32_t* item_ok, uint4* out) {
+  const size_t v = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < n_quads && !item_ok[v / (sizeof(rhip_gt) / 16)]) out[v] = make_uint4(0, 0, 0, 0);
+}
+// the launches of transform (inv = false: out = t) and of the key holder's decrypt (inv = true: out = lead * t^-1);
+// item_line_base != nullptr: the transform under many keys (tk_lines = the lines of all of them, item_ok may be null)
 static int32_t ghw11_pairs_batch(rhip_ctx* ctx, bool inv, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
                                  const uint32_t* sel_start, const uint32_t* sel_ct_row, const uint32_t* sel_tk_attr, const rhip_fr* sel_coeff,
                                  const rhip_g1* ct_c1, const rhip_g1* ct_c, const rhip_g1* ct_d, const uint32_t* ct_row_off,
-                                 const rhip_g2_lines* tk_lines, const rhip_gt* lead, rhip_gt* out) {
+                                 const rhip_g2_lines* tk_lines, const rhip_gt* lead, rhip_gt* out, const uint32_t* item_line_base = nullptr,
+                                 const uint32_t* item_ok = nullptr) {
   NEED(ctx);
   if (!n_items) return RHIP_OK;
   if (!total_pairs || !pair_off || !tk_lines || max_pairs < 2 || total_pairs < 2 * n_items) return RHIP_ERR_ARG;
+  if (item_line_base && tk_lines->n >= RHIP_Q_SKIP) return RHIP_ERR_ARG;          // a line block's number must not read as a sentinel
   PairLists pl;
   int32_t rc = alloc_pair_lists(ctx, total_pairs, &pl);
   if (rc) return rc;
@@ -1602,7 +1649,11 @@ static int32_t ghw11_pairs_batch(rhip_ctx* ctx, bool inv, size_t n_items, size_t
   size_t g_lanes = 0;
   const uint32_t* tile_off = nullptr;
   if ((rc = gather_lanes(ctx, n_items, max_pairs, total_pairs, pair_off, ppi, &tile_off, &g_lanes)) != RHIP_OK) return rc;
-  if (inv)
+  if (item_line_base)
+    KLAUNCH(ctx, "k_ghw11_pairs_keyed", k_ghw11_pairs_keyed, dim3(blocks_for(g_lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items,
+            total_pairs, pair_off, ppi, tile_off, sel_start, sel_ct_row, sel_tk_attr, sel_coeff, ct_c1, ct_c, ct_d, ct_row_off, item_line_base, item_ok,
+            (uint32_t)tk_lines->n, (const uint8_t*)tk_lines->q_inf, pl.P, pl.qref, (G1M*)sum.terms);
+  else if (inv)
     KLAUNCH(ctx, "k_ghw11_pairs_inv", k_ghw11_pairs<true>, dim3(blocks_for(g_lanes, RB_PAIRS_BLOCK)), dim3(RB_PAIRS_BLOCK), 0, ctx->stream, n_items,
             total_pairs, pair_off, ppi, tile_off, sel_start, sel_ct_row, sel_tk_attr, sel_coeff, ct_c1, ct_c, ct_d, ct_row_off, (const uint8_t*)tk_lines->q_inf, pl.P,
             pl.qref, (G1M*)sum.terms);
@@ -1613,7 +1664,11 @@ static int32_t ghw11_pairs_batch(rhip_ctx* ctx, bool inv, size_t n_items, size_t
   // the sum's sign is the masks' orientation: flipped (sum_e (-w_e) C_e) for t, as they are (sum_e w_e C_e) for t^-1
   RC_TRY(sum.partial_g1((const uint32_t*)sum.off, sel_start, inv ? 0 : 1));
   RC_TRY(sum.finish_g1(pair_off, pl));
-  return run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, (const LineM*)tk_lines->lines, tk_lines->lines29, lead, out);
+  RC_TRY(run_pair_lists(ctx, n_items, pair_off, max_pairs, total_pairs, pl, (const LineM*)tk_lines->lines, tk_lines->lines29, lead, out));
+  if (item_ok)
+    KLAUNCH(ctx, "k_zero_failed_gt", k_zero_failed_gt, dim3(blocks_for(n_items * (sizeof(rhip_gt) / 16), 256)), dim3(256), 0, ctx->stream, n_items * (sizeof(rhip_gt) / 16),
+            item_ok, (uint4*)out);
+  return RHIP_OK;
 }
 extern "C" int32_t rhip_ghw11_transform_batch(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
                                               const uint32_t* sel_start, const uint32_t* sel_ct_row, const uint32_t* sel_tk_attr, const rhip_fr* sel_coeff,
@@ -1621,6 +1676,16 @@ extern "C" int32_t rhip_ghw11_transform_batch(rhip_ctx* ctx, size_t n_items, siz
                                               const rhip_g2_lines* tk_lines, rhip_gt* out) {
   return ghw11_pairs_batch(ctx, false, n_items, max_pairs, total_pairs, n_sel, pair_off, sel_start, sel_ct_row, sel_tk_attr, sel_coeff, ct_c1, ct_c, ct_d, ct_row_off,
                            tk_lines, (const rhip_gt*)nullptr, out);
+}
+// the same under MANY transform keys: one handle over the elements of all keys, a line base per item (k_ghw11_pairs_keyed); everything
+// behind the gather -- the sum stage, the Miller dispatch, the final exponentiation -- is the launch set above
+extern "C" int32_t rhip_ghw11_transform_batch_keyed(rhip_ctx* ctx, size_t n_items, size_t max_pairs, size_t total_pairs, size_t n_sel, const uint32_t* pair_off,
+                                                    const uint32_t* sel_start, const uint32_t* sel_ct_row, const uint32_t* sel_tk_attr, const rhip_fr* sel_coeff,
+                                                    const rhip_g1* ct_c1, const rhip_g1* ct_c, const rhip_g1* ct_d, const uint32_t* ct_row_off,
+                                                    const uint32_t* item_line_base, const uint32_t* item_ok, const rhip_g2_lines* store_lines, rhip_gt* out) {
+  if (n_items && !item_line_base) return RHIP_ERR_ARG;
+  return ghw11_pairs_batch(ctx, false, n_items, max_pairs, total_pairs, n_sel, pair_off, sel_start, sel_ct_row, sel_tk_attr, sel_coeff, ct_c1, ct_c, ct_d, ct_row_off,
+                           store_lines, (const rhip_gt*)nullptr, out, item_line_base, item_ok);
 }
 // ghw11 decrypt for the holder of the secret key: decrypt_out(transform(ct, tk), rk) for ANY z of tkgen is c * t_1^-1 with t_1 = transform's
 // expression on the secret key's own (k, l, k_x) -- the blinding cancels (ghw11/mod.rs:252-282, :302).  sk_lines: prepared lines of k, l, k_x[0], ...

@@ -255,6 +255,9 @@ class Engine {
   // device-side key handles of the packed entry points (rhip_bsw_pk, rhip_lsw_pk, rhip_aw11_pk), cached by the key's bytes and
   // destroyed with the engine; at most `cap` entries per kind live at a time
   void* aux(const std::string& kind, const std::string& key, void* (*make)(Engine&, const void*), const void* arg, void (*destroy)(void*), size_t cap = 4);
+  // a device handle that lives OUTSIDE the caches above (a key store's prepared lines: its owner frees it) goes the way an evicted one
+  // does: destroyed now when no Busy scope is alive, parked until the scopes that may hold it have ended otherwise
+  void release(void* h, void (*destroy)(void*));
 
  private:
   struct Lane {

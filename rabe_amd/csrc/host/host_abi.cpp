@@ -1121,6 +1121,7 @@ void rabe_obj_free(int32_t kind, void* o) {
     case RABE_GHW11_RK: delete (ghw11::Ghw11RetrieveKey*)o; break;
     case RABE_GHW11_CT: delete (ghw11::Ghw11Ciphertext*)o; break;
     case RABE_GHW11_TCT: delete (ghw11::Ghw11TransformCiphertext*)o; break;
+    case RABE_GHW11_TK_STORE: delete (ghw11::TkStore*)o; break;          // its device handles: Engine::release, the parked handles' rule
     default: break;
   }
 }
@@ -1993,6 +1994,36 @@ int32_t rabe_ghw11_transform_packed(rabe_host* h, const void* tk, size_t n_items
     const bool whole = hi - lo == n_items;          // the uncut call judges the caller's own capacity
     return ghw11::transform_packed(eng, key, hi - lo, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted_of(flags), status ? status + lo : nullptr,
                                    tct_buf ? tct_buf + TCT * lo : nullptr, whole ? tct_cap : TCT * (hi - lo), errs);
+  }, &errors))
+    return 1;
+  first_error(h, errors);
+  return 0;
+  GUARD_END(h)
+}
+// ---- ghw11: a proxy's device-resident key store and the transform of a mixed queue against it
+int32_t rabe_ghw11_tk_store_create(rabe_host* h, size_t n_keys, const uint8_t* tk_blob, size_t tk_len, const uint64_t* tk_off, uint32_t flags, int32_t* key_status,
+                                   void** store) {
+  GUARD_BEGIN
+  if (!store) throw RabeError("ghw11::tk_store_create: null input");
+  std::vector<std::string> errors;
+  *store = ghw11::tk_store_create(h->eng, n_keys, tk_blob, tk_len, tk_off, trusted_of(flags), key_status, &errors).release();
+  first_error(h, errors);
+  return 0;
+  GUARD_END(h)
+}
+uint64_t rabe_ghw11_tk_store_bytes(const void* store) { return store ? ((ghw11::TkStore*)store)->device_bytes() : 0; }
+int32_t rabe_ghw11_transform_keyed(rabe_host* h, const void* store, size_t n_items, const uint32_t* item_key, const uint8_t* ct_blob, size_t ct_len,
+                                   const uint64_t* ct_off, uint32_t flags, int32_t* status, uint8_t* tct_buf, size_t tct_cap) {
+  GUARD_BEGIN
+  if (!store) throw RabeError("ghw11::transform_keyed: null input");
+  std::vector<std::string> errors;
+  auto& keys = *(ghw11::TkStore*)store;
+  // cut as rabe_ghw11_transform_packed is: block [lo, hi) reads item_key + lo and writes its slots and verdicts in place
+  const bool room = tct_buf && tct_cap >= n_items * TCT;
+  if (!pipeline::for_blocks(h->engines_if(ct_off && status && item_key && room), n_items, pipeline::GROUP_ONLY, [&](Engine& eng, size_t lo, size_t hi, std::vector<std::string>* errs) {
+    const bool whole = hi - lo == n_items;
+    return ghw11::transform_keyed(eng, keys, hi - lo, item_key ? item_key + lo : nullptr, ct_blob, ct_len, ct_off ? ct_off + lo : nullptr, trusted_of(flags),
+                                  status ? status + lo : nullptr, tct_buf ? tct_buf + TCT * lo : nullptr, whole ? tct_cap : TCT * (hi - lo), errs);
   }, &errors))
     return 1;
   first_error(h, errors);

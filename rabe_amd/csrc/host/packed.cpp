@@ -2709,15 +2709,21 @@ struct CtBatch {
   // with_sealed = false: the sealed data stays with the client (transform); true: it is kept, and the record has to end with it, as
   // decrypt_out_packed demands of the same record -- checked last, after everything the transform would have refused
   void parse(const std::vector<Ghw11Attribute>& key_attr, size_t n, const uint8_t* ct_blob, const uint64_t* ct_off, bool with_sealed,
-             std::vector<std::string>* errors);
+             std::vector<std::string>* errors) {
+    std::vector<std::vector<std::string>> one(1);
+    for (const auto& a : key_attr) one[0].push_back(a.string);
+    parse(one, nullptr, n, ct_blob, ct_off, with_sealed, errors);
+  }
+  // the records of a mixed queue: record i against the attribute names lists[item_list[i]] (item_list == nullptr: every record against
+  // lists[0]).  One plan per pair of a list and a policy text -- a PlanCache per list, so keys that carry the same names share their plans.
+  void parse(const std::vector<std::vector<std::string>>& lists, const uint32_t* item_list, size_t n, const uint8_t* ct_blob, const uint64_t* ct_off,
+             bool with_sealed, std::vector<std::string>* errors);
   void select(size_t n, const std::vector<std::string>& errors);
 };
-void CtBatch::parse(const std::vector<Ghw11Attribute>& key_attr, size_t n, const uint8_t* ct_blob, const uint64_t* ct_off, bool with_sealed,
-                    std::vector<std::string>* errors) {
-  std::vector<std::string> attr;
-  for (const auto& a : key_attr) attr.push_back(a.string);
-  PlanCache<CtPlan> plans;
-  auto make_plan = [&](CtPlan& pl, const std::string& text, PolicyLanguage lang) {
+void CtBatch::parse(const std::vector<std::vector<std::string>>& lists, const uint32_t* item_list, size_t n, const uint8_t* ct_blob, const uint64_t* ct_off,
+                    bool with_sealed, std::vector<std::string>* errors) {
+  std::unique_ptr<PlanCache<CtPlan>[]> plans(new PlanCache<CtPlan>[lists.size()]);
+  auto make_plan = [](const std::vector<std::string>& attr, CtPlan& pl, const std::string& text, PolicyLanguage lang) {
     pl.flat = flat_policy(text, lang);
     const auto& names = pl.flat->leaf_name_col;
     if (!traverse_policy(attr, pl.flat->tree)) throw RabeError("Error: attributes in tk do not match policy in ct.");
@@ -2725,9 +2731,9 @@ void CtBatch::parse(const std::vector<Ghw11Attribute>& key_attr, size_t n, const
     if (!calc_pruned(attr, pl.flat->tree, &list)) throw RabeError("Error in Ghw11/decrypt: attributes in sk do not match policy in ct.");
     for (const auto& cur : list) {
       size_t a = 0, co = 0;
-      while (a < key_attr.size() && key_attr[a].string != cur.first) a++;
+      while (a < attr.size() && attr[a] != cur.first) a++;
       while (co < names.size() && names[co] != cur.second) co++;
-      if (a == key_attr.size() || co == names.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
+      if (a == attr.size() || co == names.size()) throw std::runtime_error("called `Option::unwrap()` on a `None` value");
       pl.ent.push_back({cur.second, (uint32_t)a, pl.flat->leaf_coeff[co], (uint32_t)co});
     }
   };
@@ -2749,7 +2755,9 @@ void CtBatch::parse(const std::vector<Ghw11Attribute>& key_attr, size_t n, const
     const uint32_t dl = r.u32();
     const uint8_t* data = r.raw(dl);                   // transform: the sealed data stays with the client (decrypt_out)
     if (with_sealed) { sealed[i].len = dl; sealed[i].p = data; parsed[i] = 1; }
-    auto pl = plans.get(pol.first, pol.second, lang, make_plan);
+    const std::vector<std::string>& attr = lists[item_list ? item_list[i] : 0];
+    auto pl = plans[item_list ? item_list[i] : 0].get(pol.first, pol.second, lang,
+                                                      [&](CtPlan& made, const std::string& text, PolicyLanguage l) { make_plan(attr, made, text, l); });
     if (!pl->err.empty()) throw RabeError(pl->err);
     v[i].plan = pl;
     const auto& std_names = pl->flat->leaf_name_col;
@@ -2792,16 +2800,29 @@ rhip_g2_lines* key_lines(Engine& eng, const char* aux_name, const G2& k, const G
 // Per distinct policy: traverse_policy, calc_pruned, and per pruned (name, name_col) the FIRST coefficient named name_col, the FIRST
 // key attribute named `name`, the FIRST ciphertext row named name_col (:259-281); a missing one is the reference's unwrap panic.
 // Every G2 argument is the key's: the batch replays prepared lines (kept across calls) and does no G2 arithmetic.
-bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
-                      int32_t* status, uint8_t* out_buf, size_t out_cap, std::vector<std::string>* errors) {
-  StageTimer tm("ghw11::transform_packed");
+// The body is shared with transform_keyed (a mixed queue over a TkStore, below): `store` set = item i is served under key item_key[i] of the
+// store -- its record is parsed against that key's attribute names, its pairs replay the store's lines from the key's base -- and `tk` is unused.
+static bool transform_core(Engine& eng, const Ghw11TransformKey* tk, TkStore* store, const uint32_t* item_key, size_t n, const uint8_t* ct_blob, size_t ct_len,
+                           const uint64_t* ct_off, bool trusted, int32_t* status, uint8_t* out_buf, size_t out_cap, std::vector<std::string>* errors) {
+  StageTimer tm(store ? "ghw11::transform_keyed" : "ghw11::transform_packed");
   Engine::ArenaScope arena(eng);
   errors->assign(n, "");
-  if (!ct_off || (n && !ct_blob) || !status) throw RabeError("ghw11::transform_packed: null input");
+  if (!ct_off || (n && !ct_blob) || !status || (store && n && !item_key)) throw RabeError(store ? "ghw11::transform_keyed: null input" : "ghw11::transform_packed: null input");
   if (!out_buf || out_cap < n * 768) return false;
   (void)check_offsets(n, ct_off, ct_len, errors);
   CtBatch b;
-  b.parse(tk.attr_key_z, n, ct_blob, ct_off, false, errors);
+  if (store) {
+    std::vector<uint32_t> item_list(n, 0);
+    for (size_t i = 0; i < n; i++) {
+      const uint32_t u = item_key[i];
+      if (u >= store->key_ok.size()) { if ((*errors)[i].empty()) (*errors)[i] = "ghw11::transform_keyed: item_key is out of the store's range"; }
+      else if (!store->key_ok[u]) { if ((*errors)[i].empty()) (*errors)[i] = "ghw11::transform_keyed: the item's key failed when the store was built"; }
+      else item_list[i] = store->key_list[u];
+    }
+    b.parse(store->lists, item_list.data(), n, ct_blob, ct_off, false, errors);
+  } else {
+    b.parse(tk->attr_key_z, n, ct_blob, ct_off, false, errors);
+  }
   tm.lap("parse + plan");
   b.select(n, *errors);
   const Selection& sel = b.sel;
@@ -2823,7 +2844,13 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
     });
     tm.lap("pack");
     rhip_ctx* cx = eng.ctx();
-    rhip_g2_lines* lines = key_lines(eng, "ghw11_tk_lines", tk.k_z, tk.l_z, tk.attr_key_z);
+    rhip_g2_lines* lines = store ? store->lines_on(eng) : key_lines(eng, "ghw11_tk_lines", tk->k_z, tk->l_z, tk->attr_key_z);
+    DBuf d_base;          // per live item: where its key's lines start in the store's handle
+    if (store) {
+      std::vector<uint32_t> line_base(m_items);
+      for (size_t j = 0; j < m_items; j++) line_base[j] = store->key_base[item_key[live[j]]];
+      d_base = up32(eng, line_base);
+    }
     DBuf d_c1(&eng, m_items * 64), d_c(&eng, m_items * 384), d_ci(&eng, total * 64 + 4), d_di(&eng, total * 64 + 4), d_row_off = up32(eng, sel.row_off),
         d_pair_off = up32(eng, sel.pair_off), d_sel_start = up32(eng, sel.sel_start), d_sel_ct = up32(eng, sel.sel_rec), d_sel_tk = up32(eng, sel.sel_one),
         d_sel_w = up_bytes(eng, flatten_fr(sel.sel_z)), d_out(&eng, m_items * 384);
@@ -2837,13 +2864,17 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
       mc->add(1, d_c1.ptr(), m_items); mc->add(1, d_ci.ptr(), total, d_row_off.as<uint32_t>(), m_items);
       mc->add(1, d_di.ptr(), total, d_row_off.as<uint32_t>(), m_items); mc->add(3, d_c.ptr(), m_items);
     }
-    int32_t rc = rhip_ghw11_transform_batch(cx, m_items, sel.max_pairs, sel.pair_off[m_items], sel.sel_rec.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
-                                            d_sel_ct.as<uint32_t>(), d_sel_tk.as<uint32_t>(), d_sel_w.as<rhip_fr>(), d_c1.as<rhip_g1>(), d_ci.as<rhip_g1>(),
-                                            d_di.as<rhip_g1>(), d_row_off.as<uint32_t>(), lines, d_out.as<rhip_gt>());
+    int32_t rc = store ? rhip_ghw11_transform_batch_keyed(cx, m_items, sel.max_pairs, sel.pair_off[m_items], sel.sel_rec.size(), d_pair_off.as<uint32_t>(),
+                                                          d_sel_start.as<uint32_t>(), d_sel_ct.as<uint32_t>(), d_sel_tk.as<uint32_t>(), d_sel_w.as<rhip_fr>(),
+                                                          d_c1.as<rhip_g1>(), d_ci.as<rhip_g1>(), d_di.as<rhip_g1>(), d_row_off.as<uint32_t>(),
+                                                          d_base.as<uint32_t>(), nullptr, lines, d_out.as<rhip_gt>())          // a failed key's items are not live
+                       : rhip_ghw11_transform_batch(cx, m_items, sel.max_pairs, sel.pair_off[m_items], sel.sel_rec.size(), d_pair_off.as<uint32_t>(), d_sel_start.as<uint32_t>(),
+                                                    d_sel_ct.as<uint32_t>(), d_sel_tk.as<uint32_t>(), d_sel_w.as<rhip_fr>(), d_c1.as<rhip_g1>(), d_ci.as<rhip_g1>(),
+                                                    d_di.as<rhip_g1>(), d_row_off.as<uint32_t>(), lines, d_out.as<rhip_gt>());
     h_out = h_x + m_items * 448;
     if (rc == RHIP_OK) rc = rhip_download_async(cx, h_out, d_out.ptr(), m_items * 384);
     if (rc == RHIP_OK) rc = rhip_sync(cx);
-    eng.check(rc, "rhip_ghw11_transform_batch");
+    eng.check(rc, store ? "rhip_ghw11_transform_batch_keyed" : "rhip_ghw11_transform_batch");
     if (mc) {
       mc->collect();
       const auto &ok_c1 = mc->ok(0), &ok_ci = mc->ok(1), &ok_di = mc->ok(2), &ok_c = mc->ok(3);
@@ -2863,6 +2894,108 @@ bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const 
   });
   tm.lap("assembly");
   return true;
+}
+bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
+                      int32_t* status, uint8_t* out_buf, size_t out_cap, std::vector<std::string>* errors) {
+  return transform_core(eng, &tk, nullptr, nullptr, n, ct_blob, ct_len, ct_off, trusted, status, out_buf, out_cap, errors);
+}
+bool transform_keyed(Engine& eng, TkStore& store, size_t n, const uint32_t* item_key, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
+                     bool trusted, int32_t* status, uint8_t* out_buf, size_t out_cap, std::vector<std::string>* errors) {
+  return transform_core(eng, nullptr, &store, item_key, n, ct_blob, ct_len, ct_off, trusted, status, out_buf, out_cap, errors);
+}
+
+// ---- the device-resident key store of a proxy (schemes.h: TkStore)
+rhip_g2_lines* TkStore::lines_on(Engine& eng, const void* dev_points) {
+  std::lock_guard<std::mutex> g(mu_);          // an engine's first use prepares; the others of a group wait their turn behind it
+  for (const auto& r : replicas_) if (r.first == &eng) return r.second;
+  if (points.empty()) throw RabeError("ghw11 key store: no key of the store is usable");
+  rhip_g2_lines* lines = nullptr;
+  if (dev_points) {
+    eng.check(rhip_g2_lines_prepare(eng.ctx(), points.size() / 128, (const rhip_g2*)dev_points, &lines), "rhip_g2_lines_prepare");
+  } else {
+    lines = (rhip_g2_lines*)make_tk_lines(eng, &points);
+  }
+  replicas_.push_back({&eng, lines});
+  return lines;
+}
+uint64_t TkStore::device_bytes() {
+  std::lock_guard<std::mutex> g(mu_);
+  uint64_t total = 0;
+  for (const auto& r : replicas_) total += rhip_g2_lines_bytes(r.second);
+  return total;
+}
+TkStore::~TkStore() {
+  for (const auto& r : replicas_) r.first->release(r.second, destroy_tk_lines);
+}
+// Records as tkgen_packed writes them (k_z, l_z, u32 rows, rows of (name, k_x_z)), read with its conventions: bounds, a record that has to end
+// where its offsets say, and -- unless trusted -- the batched G2 membership pass over every element, folded per key.  A key that fails keeps
+// its slot in the numbering (key_ok = 0); a non-member's elements stay in `points`, where no item reaches them.
+std::unique_ptr<TkStore> tk_store_create(Engine& eng, size_t n_keys, const uint8_t* tk_blob, size_t tk_len, const uint64_t* tk_off, bool trusted,
+                                         int32_t* key_status, std::vector<std::string>* errors) {
+  StageTimer tm("ghw11::tk_store_create");
+  Engine::ArenaScope arena(eng);
+  errors->assign(n_keys, "");
+  if (!tk_off || (n_keys && (!tk_blob || !key_status))) throw RabeError("ghw11::tk_store_create: null input");
+  (void)check_offsets(n_keys, tk_off, tk_len, errors);
+  std::vector<std::vector<std::string>> names(n_keys);
+  for_each_record(n_keys, errors, [&](size_t u) {
+    Cursor r{tk_blob + tk_off[u], tk_blob + tk_off[u + 1]};
+    (void)r.raw(256);
+    const uint32_t cnt = r.u32();
+    if ((size_t)cnt * 132 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
+    for (uint32_t y = 0; y < cnt; y++) { auto nm = r.str(); names[u].emplace_back(nm.first, nm.second); (void)r.raw(128); }
+    if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
+  });
+  tm.lap("parse");
+  std::unique_ptr<TkStore> st(new TkStore());
+  st->key_list.assign(n_keys, 0); st->key_base.assign(n_keys, 0); st->key_ok.assign(n_keys, 0);
+  std::map<std::vector<std::string>, uint32_t> list_of;
+  std::vector<size_t> live;
+  std::vector<uint32_t> row_off{0};
+  for (size_t u = 0; u < n_keys; u++) {
+    if (!(*errors)[u].empty()) continue;
+    const uint64_t next = (uint64_t)row_off.back() + 2 + names[u].size();
+    if (next >= 0xFFFFFFF0ull) throw RabeError("ghw11::tk_store_create: more than 2^32 key elements in one store");
+    auto it = list_of.find(names[u]);
+    if (it == list_of.end()) { it = list_of.insert({names[u], (uint32_t)st->lists.size()}).first; st->lists.push_back(names[u]); }
+    st->key_list[u] = it->second;
+    st->key_base[u] = row_off.back();
+    st->key_ok[u] = 1;
+    live.push_back(u);
+    row_off.push_back((uint32_t)next);
+  }
+  const size_t m = live.size(), total = row_off[m];
+  st->points.resize(total * 128);
+  parallel_for(m, [&](size_t j) {
+    const uint8_t* rec = tk_blob + tk_off[live[j]];
+    uint8_t* o = (uint8_t*)&st->points[128 * (size_t)row_off[j]];
+    memcpy(o, rec, 256);
+    const uint8_t* q = rec + 260;
+    for (uint32_t y = 2; y < row_off[j + 1] - row_off[j]; y++) {
+      q += 4 + get_u32(q);
+      memcpy(o + 128 * (size_t)y, q, 128);
+      q += 128;
+    }
+  });
+  tm.lap("pack");
+  if (m) {
+    DBuf d_p(&eng, st->points.data(), st->points.size()), d_row_off = up32(eng, row_off);
+    std::unique_ptr<MemberChecks> mc;
+    if (!trusted) {
+      mc.reset(new MemberChecks(eng));
+      mc->add(2, d_p.ptr(), total, d_row_off.as<uint32_t>(), m);
+    }
+    (void)st->lines_on(eng, d_p.ptr());          // the one preparation; returns when the lines are complete
+    if (mc) {
+      mc->collect();
+      const auto& ok = mc->ok(0);
+      for (size_t j = 0; j < m; j++)
+        if (!ok[j]) { st->key_ok[live[j]] = 0; (*errors)[live[j]] = "deserialize: a key element is not a member of G2 (FieldError::NotMember)"; }
+    }
+  }
+  for (size_t u = 0; u < n_keys; u++) key_status[u] = st->key_ok[u] ? 0 : -1;
+  tm.lap(trusted ? "device: upload, lines" : "device: upload, lines; membership beside");
+  return st;
 }
 // ghw11 for a key holder WITHOUT a proxy: n ciphertext records under ONE secret key.  By definition the plaintexts of tkgen -> transform_packed
 // -> decrypt_out_packed for any z: with k_z = k / z, l_z = l / z, k_x_z = k_x / z the transform returns t_z = t_1^(1/z), t_1 = its own

@@ -382,6 +382,10 @@ void Engine::retire(void* h, void (*destroy)(void*)) {        // mu_ held
   if (busy_ > 0) parked_.push_back(Parked{++busy_clock_, h, destroy});
   else destroy(h);
 }
+void Engine::release(void* h, void (*destroy)(void*)) {
+  std::lock_guard<std::recursive_mutex> lk(mu_);
+  retire(h, destroy);
+}
 Engine::Busy::Busy(Engine& eng) : e(eng), start(0) {
   std::lock_guard<std::recursive_mutex> lk(e.mu_);
   e.busy_++;

@@ -235,6 +235,31 @@ std::vector<Ghw11TransformCiphertext> transform_batch(Engine& eng, const std::ve
 // record (c | t) of item i, zeros where status[i] = -1.  The device-resident path: every Miller loop replays the key's prepared lines.
 bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                       int32_t* status, uint8_t* out_buf, size_t out_cap, std::vector<std::string>* errors);
+// A proxy's transform keys, resident on the device (packed.cpp; include/rabe_host.h: rabe_ghw11_tk_store_create).  Immutable once built.  The
+// G2 elements of every key whose record parsed lie in `points`, key after key in the order k_z, l_z, k_x[0], ...; key u's k_z is element
+// key_base[u], its attribute names are lists[key_list[u]] (keys with the same names share a list, and with it their selection plans), and
+// key_ok[u] = 0 marks a key that failed (a malformed record, a non-member element): every item that names it fails.  The prepared lines of
+// `points` -- ONE handle per engine -- are made by tk_store_create on its engine and by lines_on on every other engine's first use.
+struct TkStore {
+  std::vector<std::vector<std::string>> lists;
+  std::vector<uint32_t> key_list, key_base;
+  std::vector<uint8_t> key_ok;
+  std::string points;
+  rhip_g2_lines* lines_on(Engine& eng, const void* dev_points = nullptr);          // dev_points: `points` on eng's device already
+  uint64_t device_bytes();
+  ~TkStore();          // the handles go through Engine::release: free the store before the host whose engines served it
+ private:
+  std::mutex mu_;
+  std::vector<std::pair<Engine*, rhip_g2_lines*>> replicas_;
+};
+// n_keys Ghw11TransformKey records of an UNTRUSTED blob (tkgen_packed's / provision_packed's output) -> a store; key_status[u] = 0 / -1, a
+// bad key fails alone.  All elements go up once: the membership pass (unless trusted) and the one rhip_g2_lines_prepare read the same array.
+std::unique_ptr<TkStore> tk_store_create(Engine& eng, size_t n_keys, const uint8_t* tk_blob, size_t tk_len, const uint64_t* tk_off, bool trusted,
+                                         int32_t* key_status, std::vector<std::string>* errors);
+// transform_packed for a mixed queue: item i under key item_key[i] of the store -- by definition the record and verdict transform_packed
+// gives for record i alone under that key.  An item_key out of range or naming a failed key fails its item only.
+bool transform_keyed(Engine& eng, TkStore& store, size_t n, const uint32_t* item_key, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
+                     bool trusted, int32_t* status, uint8_t* out_buf, size_t out_cap, std::vector<std::string>* errors);
 // n calls of encrypt (packed.cpp): records = what rabe_obj_serialize writes for a Ghw11Ciphertext, built and sealed on the device
 bool encrypt_packed(Engine& eng, Rng& rng, const Ghw11PublicKey& pk, const std::vector<std::string>& policies, PolicyLanguage language, size_t n,
                     const uint32_t* item_policy, const uint8_t* pt_blob, const uint64_t* pt_off, uint8_t* out_buf, size_t out_cap, uint64_t* out_off);

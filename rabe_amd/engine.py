@@ -666,10 +666,32 @@ class G2Lines:
         self.h = ctypes.c_void_p()
         eng._check(eng.lib.rhip_g2_lines_prepare(eng.ctx, _sz(n), dq.ptr, ctypes.byref(self.h)))
 
+    def nbytes(self):
+        """device memory the handle holds (rhip_g2_lines_bytes)"""
+        self.eng.lib.rhip_g2_lines_bytes.restype = ctypes.c_size_t
+        return int(self.eng.lib.rhip_g2_lines_bytes(self.h))
+
     def destroy(self):
         if self.h:
             self.eng.lib.rhip_g2_lines_destroy(self.h)
             self.h = None
+
+
+def ghw11_transform_dev(eng, n_items, max_pairs, total_pairs, n_sel, d_pair_off, d_sel_start, d_sel_ct_row, d_sel_tk_attr, d_sel_coeff, d_ct_c1, d_ct_c,
+                        d_ct_d, d_ct_row_off, tk_lines, d_out):
+    """n transforms under ONE key (rhip_ghw11_transform_batch); tk_lines: G2Lines over k_z, l_z, k_x[0], ..."""
+    eng._check(eng.lib.rhip_ghw11_transform_batch(eng.ctx, _sz(n_items), _sz(max_pairs), _sz(total_pairs), _sz(n_sel), _p(d_pair_off), _p(d_sel_start),
+                                                  _p(d_sel_ct_row), _p(d_sel_tk_attr), _p(d_sel_coeff), _p(d_ct_c1), _p(d_ct_c), _p(d_ct_d),
+                                                  _p(d_ct_row_off), _p(tk_lines), _p(d_out)))
+
+
+def ghw11_transform_keyed_dev(eng, n_items, max_pairs, total_pairs, n_sel, d_pair_off, d_sel_start, d_sel_ct_row, d_sel_tk_attr, d_sel_coeff, d_ct_c1,
+                              d_ct_c, d_ct_d, d_ct_row_off, d_item_line_base, d_item_ok, store_lines, d_out):
+    """the same under MANY keys (rhip_ghw11_transform_batch_keyed): store_lines = G2Lines over the elements of all keys, key after key;
+    d_item_line_base[i] = the index of the k_z of item i's key; d_item_ok (or None): 0 = the item is skipped and its output is zeros"""
+    eng._check(eng.lib.rhip_ghw11_transform_batch_keyed(eng.ctx, _sz(n_items), _sz(max_pairs), _sz(total_pairs), _sz(n_sel), _p(d_pair_off),
+                                                        _p(d_sel_start), _p(d_sel_ct_row), _p(d_sel_tk_attr), _p(d_sel_coeff), _p(d_ct_c1), _p(d_ct_c),
+                                                        _p(d_ct_d), _p(d_ct_row_off), _p(d_item_line_base), _p(d_item_ok), _p(store_lines), _p(d_out)))
 
 
 class BswPk:

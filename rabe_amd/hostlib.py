@@ -11,6 +11,7 @@ KINDS = {"ac17_pk": 1, "ac17_msk": 2, "ac17_cp_sk": 3, "ac17_cp_ct": 4, "ac17_kp
          "lsw_pk": 20, "lsw_msk": 21, "lsw_sk": 22, "lsw_ct": 23,
          "aw11_gk": 30, "aw11_pk": 31, "aw11_msk": 32, "aw11_sk": 33, "aw11_ct": 34,
          "ghw11_pk": 40, "ghw11_msk": 41, "ghw11_sk": 42, "ghw11_tk": 43, "ghw11_rk": 44, "ghw11_ct": 45, "ghw11_tct": 46,
+         "ghw11_tk_store": 47,
          "bdabe_pk": 50, "bdabe_msk": 51, "bdabe_ska": 52, "bdabe_uk": 53, "bdabe_pka": 54, "bdabe_ct": 55,
          "mke08_pk": 60, "mke08_msk": 61, "mke08_ska": 62, "mke08_uk": 63, "mke08_pka": 64, "mke08_ct": 65}
 
@@ -116,6 +117,8 @@ class Host:
 
     def close(self):
         if self.h:
+            for store in list(getattr(self, "_stores", ())):          # device handles owned outside the engines' caches go first
+                store.free()
             self.lib.rabe_host_destroy(self.h)
             self.h = None
 

@@ -92,6 +92,68 @@ def transform_packed(host, tk, ct_blob, ct_off, trusted=False):
     return out[:n], status[:n]
 
 
+class TkStore:
+    """A proxy's transform keys, resident on the device (rabe_ghw11_tk_store_create).  key_status: numpy int32 [n_keys], -1 where a key's
+    record was refused; immutable.  free() -- or closing the host, or the garbage collector -- releases the device memory."""
+
+    def __init__(self, host, ptr, key_status):
+        import weakref
+        self.host, self.ptr, self.key_status = host, ptr, key_status
+        if not hasattr(host, "_stores"):
+            host._stores = weakref.WeakSet()
+        host._stores.add(self)
+
+    def nbytes(self):
+        """device memory held, over all engines that have prepared the store's lines (rabe_ghw11_tk_store_bytes)"""
+        self.host.lib.rabe_ghw11_tk_store_bytes.restype = ctypes.c_uint64
+        return int(self.host.lib.rabe_ghw11_tk_store_bytes(self.ptr))
+
+    def free(self):
+        if self.ptr and self.host.h:
+            from ..hostlib import KINDS
+            self.host.lib.rabe_obj_free(KINDS["ghw11_tk_store"], self.ptr)
+        self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def tk_store_create(host, tk_blob, tk_off, trusted=False):
+    """the transform keys of many users -- the Ghw11TransformKey records tkgen_packed / provision_packed write -- uploaded once, with ONE set
+    of prepared lines over all their elements (rabe_ghw11_tk_store_create).  Returns a TkStore."""
+    import numpy as np
+    from ..hostlib import PACKED_TRUSTED, _as_u8, _np_ptr
+    n = len(tk_off) - 1
+    tk = _as_u8(tk_blob)
+    to = np.ascontiguousarray(tk_off, dtype=np.uint64)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    store = ctypes.c_void_p()
+    host.call("rabe_ghw11_tk_store_create", ctypes.c_size_t(n), _np_ptr(tk), ctypes.c_size_t(tk.size), _np_ptr(to),
+              ctypes.c_uint32(PACKED_TRUSTED if trusted else 0), _np_ptr(status), ctypes.byref(store))
+    return TkStore(host, store, status[:n])
+
+
+def transform_keyed(host, store, item_key, ct_blob, ct_off, trusted=False):
+    """a mixed queue in one call (rabe_ghw11_transform_keyed): record i is transformed under key item_key[i] of the store -- by definition what
+    transform_packed gives for that record alone under that key.  Returns (tct: numpy uint8 [n, 768], status: numpy int32 [n])."""
+    import numpy as np
+    from ..hostlib import PACKED_TRUSTED, _as_u8, _np_ptr
+    n = len(ct_off) - 1
+    if len(item_key) != n:
+        raise ValueError("transform_keyed: %d item keys for %d records" % (len(item_key), n))
+    ct = _as_u8(ct_blob)
+    co = np.ascontiguousarray(ct_off, dtype=np.uint64)
+    ik = np.ascontiguousarray(item_key, dtype=np.uint32)
+    out = np.zeros((max(n, 1), 768), dtype=np.uint8)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    host.call("rabe_ghw11_transform_keyed", store.ptr, ctypes.c_size_t(n), _np_ptr(ik), _np_ptr(ct), ctypes.c_size_t(ct.size), _np_ptr(co),
+              ctypes.c_uint32(PACKED_TRUSTED if trusted else 0), _np_ptr(status), _np_ptr(out), ctypes.c_size_t(out.size))
+    return out[:n], status[:n]
+
+
 def encrypt_packed(host, pk, policies, item_policy, pt_blob, pt_off, language=JSON_POLICY, out=None):
     """n encryptions in one call (rabe_ghw11_encrypt_packed): policies are distinct texts, item_policy[i] indexes them, plaintext
     i = pt_blob[pt_off[i]:pt_off[i+1]] -> (ct_blob, ct_off), the serialized Ghw11Ciphertext records"""
