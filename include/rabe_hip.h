@@ -387,6 +387,25 @@ void rhip_g2_lines_destroy(rhip_g2_lines* p);
 /* device memory the handle holds, in bytes: the line triples, the reduced-radix copy the contexts that run those kernels keep beside
  * them, one flag per point */
 size_t rhip_g2_lines_bytes(const rhip_g2_lines* p);
+/* ---- a handle of fixed capacity, filled and emptied by ranges of blocks (a block = one point's 88 triples, its reduced-radix copy and
+ * its flag): what a key store that adds and revokes keys in place is made of.  rhip_g2_lines_reserve makes a handle with room for
+ * `capacity` points in which every block is EMPTY: zero line words in both copies and the flag of the point at infinity, so a pair that
+ * names an empty block contributes 1.  rhip_g2_lines_bytes reports the reserved size, which is that of rhip_g2_lines_prepare over
+ * `capacity` points; a handle from rhip_g2_lines_prepare is a handle of capacity n and takes the three range calls too.
+ * rhip_g2_lines_prepare_range: the lines of dev_q[0 .. n) into blocks [first, first + n) -- for points of G2 the bytes
+ *   rhip_g2_lines_prepare makes for them at blocks 0 .. n, in both copies; a block whose point is the point at infinity is left empty.
+ *   Nothing outside the range is written.
+ * rhip_g2_lines_scrub_range: blocks [first, first + n) back to empty, with a kernel of plain vector stores (key material, wiped as the
+ *   session secrets are).
+ * rhip_g2_lines_range_is_zero: *out_zero = 1 iff every line word of blocks [first, first + n) is zero in BOTH copies and every flag
+ *   says empty, 0 otherwise.
+ * All return after their device work is complete (rhip_g2_lines_prepare's rule), so the handle may be used from any context of its
+ * device afterwards; the caller lets no batch that names the range run beside a call that writes it.  first + n > capacity:
+ * RHIP_ERR_ARG, nothing is touched.  n = 0: nothing is done (*out_zero = 1). */
+int32_t rhip_g2_lines_reserve(rhip_ctx* ctx, size_t capacity, rhip_g2_lines** out);
+int32_t rhip_g2_lines_prepare_range(rhip_ctx* ctx, rhip_g2_lines* lines, size_t first, size_t n, const rhip_g2* dev_q);
+int32_t rhip_g2_lines_scrub_range(rhip_ctx* ctx, rhip_g2_lines* lines, size_t first, size_t n);
+int32_t rhip_g2_lines_range_is_zero(rhip_ctx* ctx, const rhip_g2_lines* lines, size_t first, size_t n, int32_t* out_zero);
 
 /* ---- Level B: BSW CP-ABE (src/schemes/bsw/mod.rs) ---------------------------------------------------------------
  * Flattened policy trees (the host has parsed the policy text; everything below is numbers).  The leaves of a policy

@@ -25,7 +25,7 @@ enum {   /* object kinds for rabe_obj_free / rabe_obj_serialize / rabe_obj_deser
   RABE_LSW_PK = 20, RABE_LSW_MSK = 21, RABE_LSW_SK = 22, RABE_LSW_CT = 23,
   RABE_AW11_GK = 30, RABE_AW11_PK = 31, RABE_AW11_MSK = 32, RABE_AW11_SK = 33, RABE_AW11_CT = 34,
   RABE_GHW11_PK = 40, RABE_GHW11_MSK = 41, RABE_GHW11_SK = 42, RABE_GHW11_TK = 43, RABE_GHW11_RK = 44, RABE_GHW11_CT = 45, RABE_GHW11_TCT = 46,
-  RABE_GHW11_TK_STORE = 47,   /* rabe_ghw11_tk_store_create's handle: rabe_obj_free only, no byte form */
+  RABE_GHW11_TK_STORE = 47,   /* rabe_ghw11_tk_store_create's / _open's handle: rabe_obj_free only, no byte form */
   /* bdabe / mke08: public key, master key, secret AUTHORITY key, user key (with its attribute keys), public attribute key, ciphertext */
   RABE_BDABE_PK = 50, RABE_BDABE_MSK = 51, RABE_BDABE_SKA = 52, RABE_BDABE_UK = 53, RABE_BDABE_PKA = 54, RABE_BDABE_CT = 55,
   RABE_MKE08_PK = 60, RABE_MKE08_MSK = 61, RABE_MKE08_SKA = 62, RABE_MKE08_UK = 63, RABE_MKE08_PKA = 64, RABE_MKE08_CT = 65
@@ -434,7 +434,8 @@ int32_t rabe_ghw11_transform_packed(rabe_host* h, const void* tk, size_t n_items
  *   where its offsets say, and unless RABE_PACKED_TRUSTED every G2 element goes through the batched membership pass.  A bad key fails alone:
  *   key_status[u] = -1 (0 otherwise), the first error in rabe_host_last_error, and every item that later names it fails.  The elements of all
  *   keys go to the device once and ONE set of prepared lines is made over them (16.9 KB per element for the line triples plus the reduced-radix
- *   copy; rabe_ghw11_tk_store_bytes reports what the store holds on all devices).  The store is immutable; it may be used by any number of
+ *   copy; rabe_ghw11_tk_store_bytes reports what the store holds on all devices).  The store made this way has room for exactly the blocks
+ *   of its well-formed keys; keys are added and revoked in place with the MUTABLE STORE calls below.  It may be used by any number of
  *   calls on the host that made it.  Free it with rabe_obj_free(RABE_GHW11_TK_STORE, store) BEFORE rabe_host_destroy: the device memory is
  *   released at once when the host is idle, and after the calls that may still use it have ended otherwise.
  * TRANSFORM: DEFINITION -- tct_buf + 768 i and status[i] are what rabe_ghw11_transform_packed writes for record i ALONE under key item_key[i],
@@ -445,10 +446,34 @@ int32_t rabe_ghw11_transform_packed(rabe_host* h, const void* tk, size_t n_items
  *   set whatever the number of keys (rhip_ghw11_transform_batch_keyed: a line base per item into the store's lines).  Under a device group the
  *   items are cut as rabe_ghw11_transform_packed cuts them; every engine prepares its replica of the store's lines on first use and keeps it
  *   until the store is freed.  The store prepares ONE replica at a time: in the first call on a group the engines' preparations run one
- *   after the other (the other blocks wait), and rabe_ghw11_tk_store_bytes waits for a preparation in progress. */
+ *   after the other (the other blocks wait), and rabe_ghw11_tk_store_bytes waits for a preparation in progress.  An item that names a
+ *   revoked key fails alone like one that names a failed key, with the message "transform key revoked"; it never reaches the device.
+ * MUTABLE STORE: one store for the life of the proxy.  rabe_ghw11_tk_store_open makes an empty store with room for capacity_blocks BLOCKS
+ *   (>= 1) on devices[0]; a block is one G2 element's prepared lines (29.6 KB with the reduced-radix copy), and a key of a attributes takes
+ *   a + 2 CONTIGUOUS blocks (k_z, l_z, k_x[..]), placed first-fit at the lowest address.  The capacity is fixed and nothing is compacted: a
+ *   key needs one free range of its size, whatever the free total.
+ *   rabe_ghw11_tk_store_add takes records as rabe_ghw11_tk_store_create does (untrusted blob, bounds, the membership pass unless
+ *   RABE_PACKED_TRUSTED).  A bad key fails alone: key_status[u] = -1, key_id[u] = UINT32_MAX, the first error in rabe_host_last_error, and it
+ *   holds no block.  A good key gets key_status 0 and its id in key_id[u] -- what item_key names in rabe_ghw11_transform_keyed.  Ids count up
+ *   from 0 in the order of successful addition and are never reused (a store from rabe_ghw11_tk_store_create has given its n_keys records the
+ *   ids 0 .. n_keys - 1, the failed ones included).  Returns 1 when the well-formed keys of the call do not ALL fit: nothing is added, nothing is
+ *   written to key_status or key_id, the store, its ids and its stat are unchanged.  Per call: one upload of the new elements only, one
+ *   membership pass over them only, the lines of the new ranges only (on every engine that holds a replica).
+ *   rabe_ghw11_tk_store_revoke: status[j] = 0 when key_id[j] is revoked now; -1, alone and with a message, for an id never issued, failed or
+ *   revoked already.  Before the call returns the key's blocks are overwritten with zeros on EVERY device that holds a replica, the host-side
+ *   copy of its elements and -- with its last user -- of its attribute names is wiped, and its range is free again, merged with free neighbours.
+ *   rabe_ghw11_tk_store_stat: out = live keys, capacity in blocks, blocks in use, largest free contiguous range; -1 for a null argument.
+ *   open, add and revoke are single-owner calls like every entry point that is not a _submit: no rabe_ghw11_transform_keyed on the store may
+ *   run beside them.  They return after their device work is complete.  An engine of a device group that first meets the store after a
+ *   change prepares its replica from the store as it is then; empty ranges stay reserved and empty. */
 int32_t rabe_ghw11_tk_store_create(rabe_host* h, size_t n_keys, const uint8_t* tk_blob, size_t tk_len, const uint64_t* tk_off /*[n_keys+1]*/,
                                    uint32_t flags, int32_t* key_status /*[n_keys]*/, void** store);
 uint64_t rabe_ghw11_tk_store_bytes(const void* store);
+int32_t rabe_ghw11_tk_store_open(rabe_host* h, uint64_t capacity_blocks, void** store);
+int32_t rabe_ghw11_tk_store_add(rabe_host* h, void* store, size_t n_keys, const uint8_t* tk_blob, size_t tk_len, const uint64_t* tk_off /*[n_keys+1]*/,
+                                uint32_t flags, int32_t* key_status /*[n_keys]*/, uint32_t* key_id /*[n_keys]*/);
+int32_t rabe_ghw11_tk_store_revoke(rabe_host* h, void* store, size_t n, const uint32_t* key_id, int32_t* status /*[n]*/);
+int32_t rabe_ghw11_tk_store_stat(const void* store, uint64_t out[4]);
 int32_t rabe_ghw11_transform_keyed(rabe_host* h, const void* store, size_t n_items, const uint32_t* item_key /*[n_items]*/, const uint8_t* ct_blob,
                                    size_t ct_len, const uint64_t* ct_off /*[n_items+1]*/, uint32_t flags, int32_t* status /*[n_items]*/,
                                    uint8_t* tct_buf, size_t tct_cap);

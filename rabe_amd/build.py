@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librabe_hip.so")
 OBJ = os.path.join(os.path.dirname(HERE), "build", "obj")
 SOURCES = [os.path.join(CSRC, "engine.hip"), os.path.join(CSRC, "engine_jobs.hip"), os.path.join(CSRC, "engine_coop.hip"), os.path.join(CSRC, "engine_coop_w1.hip"), os.path.join(CSRC, "engine_rr.hip"), os.path.join(CSRC, "engine_rr2.hip"), os.path.join(CSRC, "engine_sym.hip"),
-           os.path.join(CSRC, "engine_keys.hip"), os.path.join(CSRC, "engine_gtpow.hip"),
+           os.path.join(CSRC, "engine_keys.hip"), os.path.join(CSRC, "engine_gtpow.hip"), os.path.join(CSRC, "engine_lines.hip"),
            os.path.join(CSRC, "host", "schemes.cpp"),
            os.path.join(CSRC, "host", "host_abi.cpp"), os.path.join(CSRC, "host", "packed.cpp"),
            os.path.join(CSRC, "host", "pipeline.cpp"), os.path.join(CSRC, "host", "records.cpp")]

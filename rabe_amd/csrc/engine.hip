@@ -1700,6 +1700,10 @@ extern "C" int32_t rhip_ac17_sk_prepare(rhip_ctx* ctx, size_t n_sk, const rhip_g
   *out = p;
   return RHIP_OK;
 }
+int32_t rhip_launch_g2_prepare_lines(rhip_ctx* ctx, size_t n, const rhip_g2* q, void* lines, uint8_t* q_inf) {
+  KLAUNCH(ctx, "k_g2_prepare_lines", k_g2_prepare_lines, dim3(blocks_for(n, 64)), dim3(64), 0, ctx->stream, n, q, (LineM*)lines, q_inf);
+  return RHIP_OK;
+}
 // the generic form: lines of n G2 points (bsw: a key's d and d_j.g2; lsw / aw11: whatever side of a batch is fixed)
 extern "C" void rhip_g2_lines_destroy(rhip_g2_lines* p) {
   if (!p) return;

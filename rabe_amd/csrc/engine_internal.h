@@ -635,6 +635,13 @@ int32_t rhip_launch_final_exp_rr(rhip_ctx* ctx, size_t n_items, const uint32_t* 
 int32_t rhip_take_waiter(rhip_ctx* ctx, size_t blocks, uint32_t** started_out);
 // prepared line triples (LineM, 8 x 32-bit limbs) converted once into the records k_miller_multi_rr replays; *out is hipMalloc'ed
 int32_t rhip_lines_to_rr(rhip_ctx* ctx, size_t n_lines, const void* lines, void** out);
+// the same conversion into records that exist: out = the record of lines[0] inside a handle's reduced-radix copy (engine_lines.hip)
+int32_t rhip_lines_to_rr_into(rhip_ctx* ctx, size_t n_lines, const void* lines, void* out);
+// engine.hip: the launch of k_g2_prepare_lines over n points, lines and flags written from the given addresses on
+int32_t rhip_launch_g2_prepare_lines(rhip_ctx* ctx, size_t n, const rhip_g2* q, void* lines, uint8_t* q_inf);
+// 16-byte words of one line triple (LineM) and of its reduced-radix record (engine_rr.hip: RR_LINE_QUADS)
+#define RB_LINE_QUADS 12
+#define RB_LINE29_QUADS 9
 
 int32_t rhip_launch_gt_is_member_c6(rhip_ctx* ctx, size_t n, const rhip_gt* a, uint32_t* ok);
 bool rhip_use_c6_gt_pow(const rhip_ctx* ctx, size_t n_items);

@@ -505,10 +505,14 @@ __global__ void __launch_bounds__(256) k_lines_to_rr(size_t n, const LineM* in, 
   }
   o[8] = make_uint4(top[0], top[1], top[2], top[3]);
 }
+static_assert(RR_LINE_QUADS == RB_LINE29_QUADS, "engine_lines.hip addresses the records by RB_LINE29_QUADS");
+int32_t rhip_lines_to_rr_into(rhip_ctx* ctx, size_t n_lines, const void* lines, void* out) {
+  KLAUNCH(ctx, "k_lines_to_rr", k_lines_to_rr, dim3(blocks_for(n_lines, 256)), dim3(256), 0, ctx->stream, n_lines, (const LineM*)lines, (uint4*)out);
+  return RHIP_OK;
+}
 int32_t rhip_lines_to_rr(rhip_ctx* ctx, size_t n_lines, const void* lines, void** out) {
   HIP_TRY(ctx, hipMalloc(out, n_lines * RR_LINE_QUADS * sizeof(uint4)));
-  KLAUNCH(ctx, "k_lines_to_rr", k_lines_to_rr, dim3(blocks_for(n_lines, 256)), dim3(256), 0, ctx->stream, n_lines, (const LineM*)lines, (uint4*)*out);
-  return RHIP_OK;
+  return rhip_lines_to_rr_into(ctx, n_lines, lines, *out);
 }
 int32_t rhip_launch_miller_rr(rhip_ctx* ctx, size_t n_items, uint32_t L, uint32_t C, const uint32_t* pair_off, uint32_t uniform, const void* P, const void* Q,
                               const uint32_t* qref, const void* lines, const void* lines29, void* ws, size_t ws_bytes, void* mill, const MillerPlan* plan,

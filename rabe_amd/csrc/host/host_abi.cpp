@@ -2012,6 +2012,40 @@ int32_t rabe_ghw11_tk_store_create(rabe_host* h, size_t n_keys, const uint8_t* t
   GUARD_END(h)
 }
 uint64_t rabe_ghw11_tk_store_bytes(const void* store) { return store ? ((ghw11::TkStore*)store)->device_bytes() : 0; }
+// the store that lives as long as the proxy: opened empty, keys added and revoked in place -- single-owner calls on the host's own engine,
+// which apply the change to every engine's replica before they return
+int32_t rabe_ghw11_tk_store_open(rabe_host* h, uint64_t capacity_blocks, void** store) {
+  GUARD_BEGIN
+  if (!h || !store) throw RabeError("ghw11::tk_store_open: null input");
+  if (!capacity_blocks) throw RabeError("ghw11::tk_store_open: a store has at least one block");
+  *store = ghw11::tk_store_open(h->eng, capacity_blocks).release();
+  return 0;
+  GUARD_END(h)
+}
+int32_t rabe_ghw11_tk_store_add(rabe_host* h, void* store, size_t n_keys, const uint8_t* tk_blob, size_t tk_len, const uint64_t* tk_off, uint32_t flags,
+                                int32_t* key_status, uint32_t* key_id) {
+  GUARD_BEGIN
+  if (!h || !store) throw RabeError("ghw11::tk_store_add: null input");
+  std::vector<std::string> errors;
+  if (!((ghw11::TkStore*)store)->add(h->eng, n_keys, tk_blob, tk_len, tk_off, trusted_of(flags), false, key_status, key_id, &errors)) return 1;
+  first_error(h, errors);
+  return 0;
+  GUARD_END(h)
+}
+int32_t rabe_ghw11_tk_store_revoke(rabe_host* h, void* store, size_t n, const uint32_t* key_id, int32_t* status) {
+  GUARD_BEGIN
+  if (!h || !store) throw RabeError("ghw11::tk_store_revoke: null input");
+  std::vector<std::string> errors;
+  ((ghw11::TkStore*)store)->revoke(h->eng, n, key_id, status, &errors);
+  first_error(h, errors);
+  return 0;
+  GUARD_END(h)
+}
+int32_t rabe_ghw11_tk_store_stat(const void* store, uint64_t out[4]) {
+  if (!store || !out) return -1;
+  ((ghw11::TkStore*)store)->stat(out);
+  return 0;
+}
 int32_t rabe_ghw11_transform_keyed(rabe_host* h, const void* store, size_t n_items, const uint32_t* item_key, const uint8_t* ct_blob, size_t ct_len,
                                    const uint64_t* ct_off, uint32_t flags, int32_t* status, uint8_t* tct_buf, size_t tct_cap) {
   GUARD_BEGIN

@@ -2817,6 +2817,7 @@ static bool transform_core(Engine& eng, const Ghw11TransformKey* tk, TkStore* st
       const uint32_t u = item_key[i];
       if (u >= store->key_ok.size()) { if ((*errors)[i].empty()) (*errors)[i] = "ghw11::transform_keyed: item_key is out of the store's range"; }
       else if (!store->key_ok[u]) { if ((*errors)[i].empty()) (*errors)[i] = "ghw11::transform_keyed: the item's key failed when the store was built"; }
+      else if (store->key_ok[u] != 1) { if ((*errors)[i].empty()) (*errors)[i] = "ghw11::transform_keyed: transform key revoked"; }          // never live: the device does not see the item
       else item_list[i] = store->key_list[u];
     }
     b.parse(store->lists, item_list.data(), n, ct_blob, ct_off, false, errors);
@@ -2905,18 +2906,204 @@ bool transform_keyed(Engine& eng, TkStore& store, size_t n, const uint32_t* item
 }
 
 // ---- the device-resident key store of a proxy (schemes.h: TkStore)
-rhip_g2_lines* TkStore::lines_on(Engine& eng, const void* dev_points) {
+namespace {
+void wipe(std::string& s) { if (!s.empty()) explicit_bzero(&s[0], s.size()); }
+// the record of a transform key (k_z, l_z, u32 rows, rows of (name, k_x_z)) read with tkgen_packed's conventions: the names, or a throw
+void tk_record_names(const uint8_t* rec, const uint8_t* end, std::vector<std::string>* names) {
+  Cursor r{rec, end};
+  (void)r.raw(256);
+  const uint32_t cnt = r.u32();
+  if ((size_t)cnt * 132 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
+  for (uint32_t y = 0; y < cnt; y++) { auto nm = r.str(); names->emplace_back(nm.first, nm.second); (void)r.raw(128); }
+  if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
+}
+}  // namespace
+TkStore::TkStore(uint64_t capacity_blocks) : ranges(capacity_blocks) {
+  if (capacity_blocks >= 0xFFFFFFF0ull) throw RabeError("ghw11::tk_store_create: more than 2^32 key elements in one store");
+  points.assign((size_t)capacity_blocks * 128, '\0');
+}
+rhip_g2_lines* TkStore::lines_on(Engine& eng) {
   std::lock_guard<std::mutex> g(mu_);          // an engine's first use prepares; the others of a group wait their turn behind it
+  return replica_locked(eng);
+}
+rhip_g2_lines* TkStore::replica_locked(Engine& eng) {
   for (const auto& r : replicas_) if (r.first == &eng) return r.second;
   if (points.empty()) throw RabeError("ghw11 key store: no key of the store is usable");
   rhip_g2_lines* lines = nullptr;
-  if (dev_points) {
-    eng.check(rhip_g2_lines_prepare(eng.ctx(), points.size() / 128, (const rhip_g2*)dev_points, &lines), "rhip_g2_lines_prepare");
-  } else {
-    lines = (rhip_g2_lines*)make_tk_lines(eng, &points);
+  eng.check(rhip_g2_lines_reserve(eng.ctx(), ranges.capacity(), &lines), "rhip_g2_lines_reserve");
+  std::unique_ptr<rhip_g2_lines, void (*)(rhip_g2_lines*)> hold(lines, rhip_g2_lines_destroy);
+  const auto used = ranges.used_ranges();          // the store as it is NOW; empty ranges stay reserved and empty
+  if (!used.empty()) {
+    DBuf d(&eng, points.data(), points.size());
+    for (const auto& u : used)
+      eng.check(rhip_g2_lines_prepare_range(eng.ctx(), lines, (size_t)u.first, (size_t)u.second, d.as<rhip_g2>() + u.first), "rhip_g2_lines_prepare_range");
   }
-  replicas_.push_back({&eng, lines});
+  replicas_.push_back({&eng, hold.release()});
   return lines;
+}
+void TkStore::stat(uint64_t out[4]) {
+  std::lock_guard<std::mutex> g(mu_);
+  out[0] = live_keys; out[1] = ranges.capacity(); out[2] = ranges.in_use(); out[3] = ranges.largest_free();
+}
+// scrubbed on every replica before anything on the host forgets where the key was
+void TkStore::drop_key_locked(uint32_t id, uint8_t state) {
+  const size_t first = key_base[id], n = key_blocks[id];
+  for (const auto& r : replicas_) r.first->check(rhip_g2_lines_scrub_range(r.first->ctx(), r.second, first, n), "rhip_g2_lines_scrub_range");
+  explicit_bzero(&points[first * 128], n * 128);
+  if (key_ok[id] == 1) {
+    live_keys--;
+    const uint32_t li = key_list[id];
+    if (--list_refs_[li] == 0) {
+      list_of_.erase(lists[li]);
+      for (auto& name : lists[li]) wipe(name);
+      lists[li].clear();
+      list_free_.push_back(li);
+    }
+  }
+  if (!ranges.release(first, n)) throw RabeError("ghw11 key store: a key's range is not in use");
+  key_ok[id] = state;
+  key_list[id] = 0; key_base[id] = 0; key_blocks[id] = 0;
+}
+bool TkStore::add(Engine& eng, size_t n_keys, const uint8_t* tk_blob, size_t tk_len, const uint64_t* tk_off, bool trusted, bool index_ids, int32_t* key_status,
+                  uint32_t* key_id, std::vector<std::string>* errors) {
+  const char* who = index_ids ? "ghw11::tk_store_create" : "ghw11::tk_store_add";
+  StageTimer tm(who);
+  Engine::ArenaScope arena(eng);
+  errors->assign(n_keys, "");
+  if (!tk_off || (n_keys && (!tk_blob || !key_status || (!index_ids && !key_id)))) throw RabeError(std::string(who) + ": null input");
+  (void)check_offsets(n_keys, tk_off, tk_len, errors);
+  std::vector<std::vector<std::string>> names(n_keys);
+  for_each_record(n_keys, errors, [&](size_t u) { tk_record_names(tk_blob + tk_off[u], tk_blob + tk_off[u + 1], &names[u]); });
+  tm.lap("parse");
+  std::lock_guard<std::mutex> g(mu_);
+  if ((uint64_t)key_ok.size() + n_keys >= 0xFFFFFFFFull) throw RabeError(std::string(who) + ": the store has issued 2^32 key ids");
+  if (ranges.capacity()) (void)replica_locked(eng);          // the caller's engine holds a replica of the store as it is before the call
+  // every well-formed key gets its range, or none does
+  std::vector<size_t> fresh;          // the well-formed records, in order
+  std::vector<uint32_t> base, row_off{0};
+  {
+    host::BlockRanges trial = ranges;
+    for (size_t u = 0; u < n_keys; u++) {
+      if (!(*errors)[u].empty()) continue;
+      uint64_t first = 0;
+      if (!trial.alloc(2 + names[u].size(), &first)) return false;
+      fresh.push_back(u);
+      base.push_back((uint32_t)first);
+      row_off.push_back(row_off.back() + (uint32_t)(2 + names[u].size()));          // below the capacity, which is below 2^32
+    }
+    ranges = trial;
+  }
+  const size_t m = fresh.size(), total = row_off[m];
+  std::vector<uint8_t> member(m, 1);
+  std::string elems(total * 128, '\0');          // the new elements only, key after key: what goes to the device
+  parallel_for(m, [&](size_t j) {
+    const uint8_t* rec = tk_blob + tk_off[fresh[j]];
+    uint8_t* o = (uint8_t*)&elems[128 * (size_t)row_off[j]];
+    memcpy(o, rec, 256);
+    const uint8_t* q = rec + 260;
+    for (uint32_t y = 2; y < row_off[j + 1] - row_off[j]; y++) {
+      q += 4 + get_u32(q);
+      memcpy(o + 128 * (size_t)y, q, 128);
+      q += 128;
+    }
+    memcpy(&points[128 * (size_t)base[j]], o, 128 * (size_t)(row_off[j + 1] - row_off[j]));
+  });
+  tm.lap("pack");
+  // from here on the ranges are taken: a key that does not make it gives its range back (drop), whatever the reason
+  const size_t id0 = key_ok.size();
+  std::vector<uint32_t> id_of(m);
+  for (size_t j = 0; j < m; j++) {
+    id_of[j] = (uint32_t)(index_ids ? id0 + fresh[j] : id0 + j);          // provisional for add: closed up below when a key fails membership
+  }
+  const size_t slots = index_ids ? n_keys : m;
+  key_list.resize(id0 + slots, 0); key_base.resize(id0 + slots, 0); key_blocks.resize(id0 + slots, 0); key_ok.resize(id0 + slots, 0);
+  for (size_t j = 0; j < m; j++) { key_base[id_of[j]] = base[j]; key_blocks[id_of[j]] = row_off[j + 1] - row_off[j]; key_ok[id_of[j]] = 3; }          // 3: placed, not yet judged
+  auto undo = [&]() {          // an exception on the way: nothing of this call stays
+    for (size_t j = 0; j < m; j++) if (key_ok[id_of[j]] == 3) { try { drop_key_locked(id_of[j], 0); } catch (...) {} }
+    key_list.resize(id0); key_base.resize(id0); key_blocks.resize(id0); key_ok.resize(id0);
+  };
+  try {
+    if (m) {
+      // runs of keys whose ranges are adjacent, in the order of the upload: one rhip_g2_lines_prepare_range each
+      struct Run { size_t first, n, src; };
+      std::vector<Run> runs;
+      for (size_t j = 0; j < m; j++) {
+        const size_t n = row_off[j + 1] - row_off[j];
+        if (!runs.empty() && runs.back().first + runs.back().n == base[j]) runs.back().n += n;
+        else runs.push_back({base[j], n, row_off[j]});
+      }
+      DBuf d_p(&eng, elems.data(), elems.size()), d_row_off = up32(eng, row_off);
+      std::unique_ptr<MemberChecks> mc;
+      if (!trusted) {
+        mc.reset(new MemberChecks(eng));
+        mc->add(2, d_p.ptr(), total, d_row_off.as<uint32_t>(), m);
+      }
+      for (const auto& r : replicas_) {          // one replica at a time; each call returns when its range is complete
+        Engine& e = *r.first;
+        DBuf d_other;
+        if (&e != &eng) d_other = DBuf(&e, elems.data(), elems.size());
+        const rhip_g2* src = &e == &eng ? d_p.as<rhip_g2>() : d_other.as<rhip_g2>();
+        for (const auto& run : runs) e.check(rhip_g2_lines_prepare_range(e.ctx(), r.second, run.first, run.n, src + run.src), "rhip_g2_lines_prepare_range");
+      }
+      if (mc) {
+        mc->collect();
+        const auto& ok = mc->ok(0);
+        for (size_t j = 0; j < m; j++)
+          if (!ok[j]) { member[j] = 0; (*errors)[fresh[j]] = "deserialize: a key element is not a member of G2 (FieldError::NotMember)"; }
+      }
+    }
+    tm.lap(trusted ? "device: upload, lines" : "device: upload, lines; membership beside");
+    // a non-member leaves nothing behind: its blocks are scrubbed and free again
+    for (size_t j = 0; j < m; j++) if (!member[j]) drop_key_locked(id_of[j], 0);
+  } catch (...) {
+    undo();
+    wipe(elems);
+    throw;
+  }
+  wipe(elems);
+  if (!index_ids) {          // ids count the successful additions: close the numbering up over the keys that failed membership
+    size_t next = id0;
+    for (size_t j = 0; j < m; j++) {
+      if (!member[j]) continue;
+      const uint32_t from = id_of[j], to = (uint32_t)next++;
+      if (from != to) { key_base[to] = key_base[from]; key_blocks[to] = key_blocks[from]; }
+      id_of[j] = to;
+    }
+    key_list.resize(next); key_base.resize(next); key_blocks.resize(next); key_ok.resize(next);
+  }
+  for (size_t u = 0; u < n_keys; u++) { key_status[u] = -1; if (key_id) key_id[u] = 0xFFFFFFFFu; }
+  for (size_t j = 0; j < m; j++) {
+    if (!member[j]) continue;
+    const size_t u = fresh[j];
+    auto it = list_of_.find(names[u]);
+    if (it == list_of_.end()) {
+      uint32_t li;
+      if (!list_free_.empty()) { li = list_free_.back(); list_free_.pop_back(); lists[li] = names[u]; }
+      else { li = (uint32_t)lists.size(); lists.push_back(names[u]); list_refs_.push_back(0); }
+      it = list_of_.insert({names[u], li}).first;
+    }
+    list_refs_[it->second]++;
+    key_list[id_of[j]] = it->second;
+    key_ok[id_of[j]] = 1;
+    live_keys++;
+    key_status[u] = 0;
+    if (key_id) key_id[u] = id_of[j];
+  }
+  return true;
+}
+void TkStore::revoke(Engine& eng, size_t n, const uint32_t* key_id, int32_t* status, std::vector<std::string>* errors) {
+  (void)eng;
+  errors->assign(n, "");
+  if (n && (!key_id || !status)) throw RabeError("ghw11::tk_store_revoke: null input");
+  std::lock_guard<std::mutex> g(mu_);
+  for (size_t j = 0; j < n; j++) {
+    const uint32_t id = key_id[j];
+    status[j] = -1;
+    if (id >= key_ok.size()) (*errors)[j] = "ghw11::tk_store_revoke: key id was never issued";
+    else if (key_ok[id] == 0) (*errors)[j] = "ghw11::tk_store_revoke: the key failed when it was added";
+    else if (key_ok[id] != 1) (*errors)[j] = "ghw11::tk_store_revoke: transform key revoked already";
+    else { drop_key_locked(id, 2); status[j] = 0; }
+  }
 }
 uint64_t TkStore::device_bytes() {
   std::lock_guard<std::mutex> g(mu_);
@@ -2927,74 +3114,31 @@ uint64_t TkStore::device_bytes() {
 TkStore::~TkStore() {
   for (const auto& r : replicas_) r.first->release(r.second, destroy_tk_lines);
 }
-// Records as tkgen_packed writes them (k_z, l_z, u32 rows, rows of (name, k_x_z)), read with its conventions: bounds, a record that has to end
-// where its offsets say, and -- unless trusted -- the batched G2 membership pass over every element, folded per key.  A key that fails keeps
-// its slot in the numbering (key_ok = 0); a non-member's elements stay in `points`, where no item reaches them.
+std::unique_ptr<TkStore> tk_store_open(Engine& eng, uint64_t capacity_blocks) {
+  std::unique_ptr<TkStore> st(new TkStore(capacity_blocks));
+  if (capacity_blocks) (void)st->lines_on(eng);          // reserved, every block empty
+  return st;
+}
+// Records as tkgen_packed writes them, read with its conventions (TkStore::add).  The store is opened with exactly the blocks of the records
+// that parse and filled by one add: a key that fails keeps its slot in the numbering (key_ok = 0), and the blocks of a key that failed the
+// membership pass are free -- the only room such a store has until a key is revoked.
 std::unique_ptr<TkStore> tk_store_create(Engine& eng, size_t n_keys, const uint8_t* tk_blob, size_t tk_len, const uint64_t* tk_off, bool trusted,
                                          int32_t* key_status, std::vector<std::string>* errors) {
-  StageTimer tm("ghw11::tk_store_create");
-  Engine::ArenaScope arena(eng);
   errors->assign(n_keys, "");
   if (!tk_off || (n_keys && (!tk_blob || !key_status))) throw RabeError("ghw11::tk_store_create: null input");
-  (void)check_offsets(n_keys, tk_off, tk_len, errors);
-  std::vector<std::vector<std::string>> names(n_keys);
-  for_each_record(n_keys, errors, [&](size_t u) {
-    Cursor r{tk_blob + tk_off[u], tk_blob + tk_off[u + 1]};
-    (void)r.raw(256);
-    const uint32_t cnt = r.u32();
-    if ((size_t)cnt * 132 > (size_t)(r.end - r.p)) throw RabeError("deserialize: truncated input");
-    for (uint32_t y = 0; y < cnt; y++) { auto nm = r.str(); names[u].emplace_back(nm.first, nm.second); (void)r.raw(128); }
-    if (r.p != r.end) throw RabeError("deserialize: trailing bytes after the record");
+  std::vector<std::string> sizing(n_keys, "");
+  (void)check_offsets(n_keys, tk_off, tk_len, &sizing);
+  std::vector<uint64_t> blocks(n_keys, 0);
+  for_each_record(n_keys, &sizing, [&](size_t u) {
+    std::vector<std::string> names;
+    tk_record_names(tk_blob + tk_off[u], tk_blob + tk_off[u + 1], &names);
+    blocks[u] = 2 + names.size();
   });
-  tm.lap("parse");
-  std::unique_ptr<TkStore> st(new TkStore());
-  st->key_list.assign(n_keys, 0); st->key_base.assign(n_keys, 0); st->key_ok.assign(n_keys, 0);
-  std::map<std::vector<std::string>, uint32_t> list_of;
-  std::vector<size_t> live;
-  std::vector<uint32_t> row_off{0};
-  for (size_t u = 0; u < n_keys; u++) {
-    if (!(*errors)[u].empty()) continue;
-    const uint64_t next = (uint64_t)row_off.back() + 2 + names[u].size();
-    if (next >= 0xFFFFFFF0ull) throw RabeError("ghw11::tk_store_create: more than 2^32 key elements in one store");
-    auto it = list_of.find(names[u]);
-    if (it == list_of.end()) { it = list_of.insert({names[u], (uint32_t)st->lists.size()}).first; st->lists.push_back(names[u]); }
-    st->key_list[u] = it->second;
-    st->key_base[u] = row_off.back();
-    st->key_ok[u] = 1;
-    live.push_back(u);
-    row_off.push_back((uint32_t)next);
-  }
-  const size_t m = live.size(), total = row_off[m];
-  st->points.resize(total * 128);
-  parallel_for(m, [&](size_t j) {
-    const uint8_t* rec = tk_blob + tk_off[live[j]];
-    uint8_t* o = (uint8_t*)&st->points[128 * (size_t)row_off[j]];
-    memcpy(o, rec, 256);
-    const uint8_t* q = rec + 260;
-    for (uint32_t y = 2; y < row_off[j + 1] - row_off[j]; y++) {
-      q += 4 + get_u32(q);
-      memcpy(o + 128 * (size_t)y, q, 128);
-      q += 128;
-    }
-  });
-  tm.lap("pack");
-  if (m) {
-    DBuf d_p(&eng, st->points.data(), st->points.size()), d_row_off = up32(eng, row_off);
-    std::unique_ptr<MemberChecks> mc;
-    if (!trusted) {
-      mc.reset(new MemberChecks(eng));
-      mc->add(2, d_p.ptr(), total, d_row_off.as<uint32_t>(), m);
-    }
-    (void)st->lines_on(eng, d_p.ptr());          // the one preparation; returns when the lines are complete
-    if (mc) {
-      mc->collect();
-      const auto& ok = mc->ok(0);
-      for (size_t j = 0; j < m; j++)
-        if (!ok[j]) { st->key_ok[live[j]] = 0; (*errors)[live[j]] = "deserialize: a key element is not a member of G2 (FieldError::NotMember)"; }
-    }
-  }
-  for (size_t u = 0; u < n_keys; u++) key_status[u] = st->key_ok[u] ? 0 : -1;
-  tm.lap(trusted ? "device: upload, lines" : "device: upload, lines; membership beside");
+  uint64_t capacity = 0;
+  for (size_t u = 0; u < n_keys; u++) if (sizing[u].empty()) capacity += blocks[u];
+  std::unique_ptr<TkStore> st = tk_store_open(eng, capacity);
+  if (!st->add(eng, n_keys, tk_blob, tk_len, tk_off, trusted, true, key_status, nullptr, errors))
+    throw RabeError("ghw11::tk_store_create: the keys do not fit the store sized for them");
   return st;
 }
 // ghw11 for a key holder WITHOUT a proxy: n ciphertext records under ONE secret key.  By definition the plaintexts of tkgen -> transform_packed

@@ -10,6 +10,7 @@
 // where the reference draws from thread_rng(), an Rng, as its first arguments; the rest is the reference signature.
 #pragma once
 #include "common.h"
+#include "block_ranges.h"
 
 namespace rabe {
 Fr must_inv(const Fr& a);          // schemes.cpp (internal): the reference's `.inverse().unwrap()`
@@ -235,29 +236,51 @@ std::vector<Ghw11TransformCiphertext> transform_batch(Engine& eng, const std::ve
 // record (c | t) of item i, zeros where status[i] = -1.  The device-resident path: every Miller loop replays the key's prepared lines.
 bool transform_packed(Engine& eng, const Ghw11TransformKey& tk, size_t n, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off, bool trusted,
                       int32_t* status, uint8_t* out_buf, size_t out_cap, std::vector<std::string>* errors);
-// A proxy's transform keys, resident on the device (packed.cpp; include/rabe_host.h: rabe_ghw11_tk_store_create).  Immutable once built.  The
-// G2 elements of every key whose record parsed lie in `points`, key after key in the order k_z, l_z, k_x[0], ...; key u's k_z is element
-// key_base[u], its attribute names are lists[key_list[u]] (keys with the same names share a list, and with it their selection plans), and
-// key_ok[u] = 0 marks a key that failed (a malformed record, a non-member element): every item that names it fails.  The prepared lines of
-// `points` -- ONE handle per engine -- are made by tk_store_create on its engine and by lines_on on every other engine's first use.
+// A proxy's transform keys, resident on the device (packed.cpp; include/rabe_host.h: rabe_ghw11_tk_store_open / _add / _revoke / _create).  ONE
+// prepared-lines handle of fixed capacity per engine (rhip_g2_lines_reserve), addressed by BLOCK: a block is one G2 element's lines, key u
+// takes the key_blocks[u] = 2 + its attribute count contiguous blocks from key_base[u] on, in the order k_z, l_z, k_x[0], ...  `ranges` says
+// which blocks are taken (block_ranges.h: first fit at the lowest address); `points` is the host-side copy of the elements by block, zeros
+// where a range is empty, from which an engine that meets the store later prepares its replica (lines_on).  Keys are numbered by id:
+// key_ok[id] = 1 live, 0 failed (a slot only tk_store_create hands out: its ids are the blob's indices), 2 revoked; an id is never reused.
+// The attribute names of key u are lists[key_list[u]]: keys with the same names share a list, and with it their selection plans; a list
+// whose last key is revoked is wiped, and its slot is taken by the next new list.
+// add, revoke are single-owner calls: no transform runs beside them, and they return after the device work on every replica is complete.
 struct TkStore {
   std::vector<std::vector<std::string>> lists;
-  std::vector<uint32_t> key_list, key_base;
+  std::vector<uint32_t> key_list, key_base, key_blocks;
   std::vector<uint8_t> key_ok;
   std::string points;
-  rhip_g2_lines* lines_on(Engine& eng, const void* dev_points = nullptr);          // dev_points: `points` on eng's device already
+  host::BlockRanges ranges;
+  uint64_t live_keys = 0;
+  explicit TkStore(uint64_t capacity_blocks);
+  rhip_g2_lines* lines_on(Engine& eng);          // eng's replica, made on first use: reserved, then the ranges in use prepared from `points`
+  // n_keys Ghw11TransformKey records of an UNTRUSTED blob: a bad key fails alone (key_status -1, key_id UINT32_MAX), the others are placed
+  // first-fit, their elements go up once (the membership pass unless trusted and rhip_g2_lines_prepare_range per run of adjacent ranges read
+  // the same array) and every replica that exists gets them.  false, with nothing changed or written, when the well-formed keys do not all
+  // fit.  index_ids: tk_store_create's numbering -- record u gets id (ids so far) + u, a failed record's slot stays in the numbering.
+  bool add(Engine& eng, size_t n_keys, const uint8_t* tk_blob, size_t tk_len, const uint64_t* tk_off, bool trusted, bool index_ids, int32_t* key_status,
+           uint32_t* key_id, std::vector<std::string>* errors);
+  // status[j] = 0: key_id[j] is revoked now -- its blocks scrubbed on every replica, its elements and (with its last user) its name list
+  // wiped on the host, its range free and merged with free neighbours; -1 for an id never issued, failed or revoked already
+  void revoke(Engine& eng, size_t n, const uint32_t* key_id, int32_t* status, std::vector<std::string>* errors);
+  void stat(uint64_t out[4]);          // live keys, capacity in blocks, blocks in use, largest free contiguous range
   uint64_t device_bytes();
   ~TkStore();          // the handles go through Engine::release: free the store before the host whose engines served it
  private:
   std::mutex mu_;
   std::vector<std::pair<Engine*, rhip_g2_lines*>> replicas_;
+  std::map<std::vector<std::string>, uint32_t> list_of_;          // by content
+  std::vector<uint32_t> list_refs_, list_free_;
+  rhip_g2_lines* replica_locked(Engine& eng);
+  void drop_key_locked(uint32_t id, uint8_t state);          // scrub on every replica, wipe, release the range
 };
-// n_keys Ghw11TransformKey records of an UNTRUSTED blob (tkgen_packed's / provision_packed's output) -> a store; key_status[u] = 0 / -1, a
-// bad key fails alone.  All elements go up once: the membership pass (unless trusted) and the one rhip_g2_lines_prepare read the same array.
+// an empty store with room for capacity_blocks elements, its lines reserved on eng
+std::unique_ptr<TkStore> tk_store_open(Engine& eng, uint64_t capacity_blocks);
+// open(exactly the blocks of the blob's well-formed records) + add: key u of the store is record u, key_status[u] = 0 / -1
 std::unique_ptr<TkStore> tk_store_create(Engine& eng, size_t n_keys, const uint8_t* tk_blob, size_t tk_len, const uint64_t* tk_off, bool trusted,
                                          int32_t* key_status, std::vector<std::string>* errors);
 // transform_packed for a mixed queue: item i under key item_key[i] of the store -- by definition the record and verdict transform_packed
-// gives for record i alone under that key.  An item_key out of range or naming a failed key fails its item only.
+// gives for record i alone under that key.  An item_key out of range or naming a failed or revoked key fails its item only.
 bool transform_keyed(Engine& eng, TkStore& store, size_t n, const uint32_t* item_key, const uint8_t* ct_blob, size_t ct_len, const uint64_t* ct_off,
                      bool trusted, int32_t* status, uint8_t* out_buf, size_t out_cap, std::vector<std::string>* errors);
 // n calls of encrypt (packed.cpp): records = what rabe_obj_serialize writes for a Ghw11Ciphertext, built and sealed on the device

@@ -666,6 +666,29 @@ class G2Lines:
         self.h = ctypes.c_void_p()
         eng._check(eng.lib.rhip_g2_lines_prepare(eng.ctx, _sz(n), dq.ptr, ctypes.byref(self.h)))
 
+    @classmethod
+    def reserve(cls, eng, capacity):
+        """a handle with room for `capacity` points, every block empty (rhip_g2_lines_reserve)"""
+        self = cls.__new__(cls)
+        self.eng = eng
+        self.h = ctypes.c_void_p()
+        eng._check(eng.lib.rhip_g2_lines_reserve(eng.ctx, _sz(capacity), ctypes.byref(self.h)))
+        return self
+
+    def prepare_range(self, first, n, dq):
+        """the lines of the n points at dq (a device buffer, or None for n = 0) into blocks [first, first + n) (rhip_g2_lines_prepare_range)"""
+        self.eng._check(self.eng.lib.rhip_g2_lines_prepare_range(self.eng.ctx, self.h, _sz(first), _sz(n), _p(dq)))
+
+    def scrub_range(self, first, n):
+        """blocks [first, first + n) back to empty (rhip_g2_lines_scrub_range)"""
+        self.eng._check(self.eng.lib.rhip_g2_lines_scrub_range(self.eng.ctx, self.h, _sz(first), _sz(n)))
+
+    def range_is_zero(self, first, n):
+        """True iff every line word of the range is zero in both copies and every flag says empty (rhip_g2_lines_range_is_zero)"""
+        out = ctypes.c_int32(-1)
+        self.eng._check(self.eng.lib.rhip_g2_lines_range_is_zero(self.eng.ctx, self.h, _sz(first), _sz(n), ctypes.byref(out)))
+        return bool(out.value)
+
     def nbytes(self):
         """device memory the handle holds (rhip_g2_lines_bytes)"""
         self.eng.lib.rhip_g2_lines_bytes.restype = ctypes.c_size_t

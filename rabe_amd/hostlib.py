@@ -27,6 +27,14 @@ class RabePanic(Exception):
 def _lib():
     lib = load_library()
     lib.rabe_host_last_error.restype = ctypes.c_char_p
+    # the mutable GHW11 key store (include/rabe_host.h): a 64-bit capacity and bare pointers, so the prototypes are stated
+    vp, sz = ctypes.c_void_p, ctypes.c_size_t
+    lib.rabe_ghw11_tk_store_open.argtypes = [vp, ctypes.c_uint64, ctypes.POINTER(vp)]
+    lib.rabe_ghw11_tk_store_add.argtypes = [vp, vp, sz, vp, sz, vp, ctypes.c_uint32, vp, vp]
+    lib.rabe_ghw11_tk_store_revoke.argtypes = [vp, vp, sz, vp, vp]
+    lib.rabe_ghw11_tk_store_stat.argtypes = [vp, vp]
+    for fn in (lib.rabe_ghw11_tk_store_open, lib.rabe_ghw11_tk_store_add, lib.rabe_ghw11_tk_store_revoke, lib.rabe_ghw11_tk_store_stat):
+        fn.restype = ctypes.c_int32
     return lib
 
 

@@ -93,8 +93,9 @@ def transform_packed(host, tk, ct_blob, ct_off, trusted=False):
 
 
 class TkStore:
-    """A proxy's transform keys, resident on the device (rabe_ghw11_tk_store_create).  key_status: numpy int32 [n_keys], -1 where a key's
-    record was refused; immutable.  free() -- or closing the host, or the garbage collector -- releases the device memory."""
+    """A proxy's transform keys, resident on the device (rabe_ghw11_tk_store_create, or tk_store_open for an empty one).  key_status: numpy
+    int32 [n_keys] of the creating call, -1 where a key's record was refused.  add / revoke change the store in place; the calls on one store
+    run one at a time.  free() -- or closing the host, or the garbage collector -- releases the device memory."""
 
     def __init__(self, host, ptr, key_status):
         import weakref
@@ -107,6 +108,39 @@ class TkStore:
         """device memory held, over all engines that have prepared the store's lines (rabe_ghw11_tk_store_bytes)"""
         self.host.lib.rabe_ghw11_tk_store_bytes.restype = ctypes.c_uint64
         return int(self.host.lib.rabe_ghw11_tk_store_bytes(self.ptr))
+
+    def add(self, tk_blob, tk_off, trusted=False):
+        """more keys, in place (rabe_ghw11_tk_store_add): records as tk_store_create takes them.  Returns (ids: numpy uint32 [n] -- what
+        item_key names, 0xFFFFFFFF where the key was refused --, status: numpy int32 [n]), or None when the well-formed keys do not all find
+        room: nothing was added then."""
+        import numpy as np
+        from ..hostlib import PACKED_TRUSTED, _as_u8, _np_ptr
+        n = len(tk_off) - 1
+        tk = _as_u8(tk_blob)
+        to = np.ascontiguousarray(tk_off, dtype=np.uint64)
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        ids = np.zeros(max(n, 1), dtype=np.uint32)
+        if self.host.call("rabe_ghw11_tk_store_add", self.ptr, ctypes.c_size_t(n), _np_ptr(tk), ctypes.c_size_t(tk.size), _np_ptr(to),
+                          ctypes.c_uint32(PACKED_TRUSTED if trusted else 0), _np_ptr(status), _np_ptr(ids)) is None:
+            return None
+        return ids[:n], status[:n]
+
+    def revoke(self, ids):
+        """keys out, in place (rabe_ghw11_tk_store_revoke): their lines are zeroed on every device before this returns.  Returns status:
+        numpy int32 [n], -1 for an id that was never issued, failed or is revoked already."""
+        import numpy as np
+        from ..hostlib import _np_ptr
+        ki = np.ascontiguousarray(ids, dtype=np.uint32)
+        status = np.zeros(max(ki.size, 1), dtype=np.int32)
+        self.host.call("rabe_ghw11_tk_store_revoke", self.ptr, ctypes.c_size_t(ki.size), _np_ptr(ki), _np_ptr(status))
+        return status[:ki.size]
+
+    def stat(self):
+        """(live keys, capacity in blocks, blocks in use, largest free contiguous range) (rabe_ghw11_tk_store_stat)"""
+        out = (ctypes.c_uint64 * 4)()
+        if self.host.lib.rabe_ghw11_tk_store_stat(self.ptr, out) != 0:
+            raise ValueError("tk store: freed")
+        return tuple(int(v) for v in out)
 
     def free(self):
         if self.ptr and self.host.h:
@@ -134,6 +168,15 @@ def tk_store_create(host, tk_blob, tk_off, trusted=False):
     host.call("rabe_ghw11_tk_store_create", ctypes.c_size_t(n), _np_ptr(tk), ctypes.c_size_t(tk.size), _np_ptr(to),
               ctypes.c_uint32(PACKED_TRUSTED if trusted else 0), _np_ptr(status), ctypes.byref(store))
     return TkStore(host, store, status[:n])
+
+
+def tk_store_open(host, capacity_blocks):
+    """an empty store with room for capacity_blocks blocks (rabe_ghw11_tk_store_open): a key of a attributes takes a + 2 contiguous blocks.
+    Keys come and go with TkStore.add / TkStore.revoke.  Returns a TkStore."""
+    import numpy as np
+    store = ctypes.c_void_p()
+    host.call("rabe_ghw11_tk_store_open", ctypes.c_uint64(capacity_blocks), ctypes.byref(store))
+    return TkStore(host, store, np.zeros(0, dtype=np.int32))
 
 
 def transform_keyed(host, store, item_key, ct_blob, ct_off, trusted=False):
